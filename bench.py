@@ -13,7 +13,10 @@ split into contiguous row blocks (raider_amd.distributed.shard_rows), `value` = 
 the cube goes out ONCE in one packed RCCL broadcast and the only data-path collective is the MAX all-reduce of K+4 doubles
 between the two passes that keeps nParts batch-global; there is no output collective.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times --steps steps and prints the
+headline; `--full` adds what takes time or runs of its own beside it: `roofline` (HIP events around every launch, the shader clock, the
+committed counter digests), the full-scene `parity` record, `end_to_end`, `cpu_baseline`, `secondary` and, for N > 1, `parity_sample`
+and the one-GPU reference.  `--dump-outputs DIR` writes the delays of the last timed step as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -32,6 +35,26 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s HBM3E spec
 VALU_ISSUE_PEAK = 256 * 4 * 2.4e9 / 4
 FP64_VECTOR_PEAK = 256 * 4 * 16 * 2 * 2.4e9      # flop/s: 78.6 TFLOP/s fp64 vector (MI355X_MICROARCH.md), an FMA = 2 flop per lane and 4-cycle pass
 FLOP_PER_REFERENCE_SAMPLE = 110.0               # ~1.1e2 fp64 operations per (ray, sample) of the reference's algorithm
+DUMP_BYTES_MAX = 48 << 20                       # --dump-outputs: bytes of all files together (within 64 MB)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: device tensor} -> path/<name>.npy as float64 (float32 stays float32).  When the arrays together are larger
+    than DUMP_BYTES_MAX, every array keeps the same elements: a sorted sample of flat indices drawn with a fixed seed, so that two builds
+    of the project run with the same arguments write the same elements of the same inputs."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: (v if v.dtype in (torch.float32, torch.float64) else v.double()).reshape(-1) for k, v in arrays.items()}
+    total = sum(v.numel() * v.element_size() for v in arrays.values())
+    idx = {}
+    for name, v in arrays.items():
+        if total > DUMP_BYTES_MAX:
+            n = v.numel()
+            if n not in idx:
+                keep = n * (DUMP_BYTES_MAX - 4096) // total
+                idx[n] = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, keep, replace=False))).to(v.device)
+            v = v.index_select(0, idx[n])
+        np.save(os.path.join(path, f'{name}.npy'), v.cpu().numpy())
 
 
 def kernel_source_hash():
@@ -193,7 +216,16 @@ def main():
     ap.add_argument('--parity-block', type=int, default=256, help='N > 1: edge of the square block of EVERY rank\'s slab compared with the C oracle after the timed '
                                                                    'region (`parity_sample`, max over ranks; c2 / c5: that many x 64 points of the rank\'s block); 0 = skip')
     ap.add_argument('--no-one-gpu-ref', action='store_true', help='N > 1: skip the one-GPU reference run of the same job on rank 0 (`one_gpu_same_scene`, `scaling_efficiency`)')
+    ap.add_argument('--full', action='store_true', help='default workload: also measure and check everything beside the headline (roofline, parity record, '
+                                                         'end_to_end, cpu_baseline, secondary; N > 1: parity_sample, one-GPU reference); off by default.  Its timed steps run with HIP '
+                                                         'events around every launch and the clock-sample wave beside them: compare its value / ms_per_step '
+                                                         'only with other --full lines')
+    ap.add_argument('--dump-outputs', type=str, default='', metavar='DIR',
+                    help='one rank: after the timed steps write the arrays the timed path returned in its last step as DIR/<name>.npy (float64, or float32 where computed so); '
+                         f'above {DUMP_BYTES_MAX >> 20} MB in all, the same fixed seeded sample of elements of every array')
     args = ap.parse_args()
+    if args.dump_outputs and args.gpus != 1:
+        raise SystemExit('bench.py: --dump-outputs writes the outputs of a one-rank run (--gpus 1)')
     if args.scaling == 'auto':
         args.scaling = 'strong' if (args.gpus > 1 and args.rows is None) else 'weak'
     if args.scaling == 'strong' and args.rows is not None:
@@ -332,20 +364,21 @@ def main():
     torch.cuda.synchronize()
     if dist_on:
         dist.barrier()
-    # the shader clock DURING the timed steps (one sleeping wave on another stream reads the cycle and the wall counter, rdr_clock_sample_*):
-    # sized from one untimed step so that it ends inside the timed region
-    torch.cuda.synchronize()
-    tw = time.perf_counter(); step(); torch.cuda.synchronize(); tw = time.perf_counter() - tw
-    if dist_on:
-        dist.barrier()
-    ctx.set_profiling(True)                                      # HIP event pairs around every kernel launch
-    torch.cuda.synchronize()
     clock_end = None
-    if rank == 0:
-        try:
-            clock_end = ctx.clock_sample(max(0.2, 0.8 * tw * args.steps * 1e3))
-        except (RuntimeError, ValueError):       # (a diagnostic: the line is still valid without it - clock_GHz_measured: null)
-            clock_end = None
+    if args.full:
+        # the shader clock DURING the timed steps (one sleeping wave on another stream reads the cycle and the wall counter, rdr_clock_sample_*):
+        # sized from one untimed step so that it ends inside the timed region
+        torch.cuda.synchronize()
+        tw = time.perf_counter(); step(); torch.cuda.synchronize(); tw = time.perf_counter() - tw
+        if dist_on:
+            dist.barrier()
+        ctx.set_profiling(True)                                      # HIP event pairs around every kernel launch
+        torch.cuda.synchronize()
+        if rank == 0:
+            try:
+                clock_end = ctx.clock_sample(max(0.2, 0.8 * tw * args.steps * 1e3))
+            except (RuntimeError, ValueError):       # (a diagnostic: the line is still valid without it - clock_GHz_measured: null)
+                clock_end = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -353,13 +386,16 @@ def main():
     if dist_on:
         dist.barrier()
     dt = time.perf_counter() - t0
-    try:
-        clock_ghz = clock_end() if clock_end is not None else None
-    except (RuntimeError, ValueError):
-        clock_ghz = None
-    n_pre, ms_pre = ctx.profile_get(0)
-    n_march, ms_march = ctx.profile_get(1)
-    ctx.set_profiling(False)
+    if args.full:
+        try:
+            clock_ghz = clock_end() if clock_end is not None else None
+        except (RuntimeError, ValueError):
+            clock_ghz = None
+        n_pre, ms_pre = ctx.profile_get(0)
+        n_march, ms_march = ctx.profile_get(1)
+        ctx.set_profiling(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'wet': out_w, 'hydro': out_h})
     rank_s = [dt]
     if dist_on:
         rank_s = gather_rank_times(dist, dt, coll_dev, world)
@@ -375,7 +411,7 @@ def main():
     # ---- N > 1: what makes the line readable on its own (VERDICT r5 task 2) ---------------------------------------------------------------
     devices = device_identities(torch, dist, dist_on, args.backend, local, rank, world)
     parity_sample = None
-    if world > 1 and args.parity_block > 0:
+    if world > 1 and args.full and args.parity_block > 0:
         # every rank: one block at the centre of ITS slab against the C oracle driven with the all-reduced (whole-scene) partition
         min_rows = min(D.shard_rows(total_rows, world, r_)[1] for r_ in range(world)) if args.scaling == 'strong' else rows
         nb = int(min(args.parity_block, min_rows, cols))                             # the same block size on every rank
@@ -397,7 +433,7 @@ def main():
                          'what': 'GPU slab vs the C oracle (oracle/oracle_c.c) driven with the all-reduced whole-scene partition; max over ranks'}
         del cc
     one_gpu = None; eff = None
-    if world > 1 and not args.no_one_gpu_ref:
+    if world > 1 and args.full and not args.no_one_gpu_ref:
         # rank 0 ALONE (the others wait at the barrier) traces the job one GPU would have: the whole scene (strong) or one slab (weak)
         torch.cuda.synchronize(); dist.barrier()
         if rank == 0:
@@ -436,7 +472,7 @@ def main():
     # ---- end to end through the NumPy boundary (reported separately, never `value`): the same scene handed over as
     # HOST arrays - look vectors up (24 B/ray), both passes, both delays down (16 B/ray); the library pipelines the transfers
     e2e = None
-    if world == 1 and not args.no_e2e:
+    if world == 1 and args.full and not args.no_e2e:
         los_np = los_t.cpu().numpy()
         hts_h = hts_np if args.per_pixel_ht else None
         eo = (np.empty((rows, cols)), np.empty((rows, cols)))
@@ -456,38 +492,6 @@ def main():
         scene_rays = total_rows * cols                            # all ranks together
         total_rays = scene_rays * args.steps
         value = total_rays / dt
-        bytes_per_ray = 64 * S + 64                               # SURVEY.md §8(d) gather model
-        # per-STEP kernel time (a step may launch a kernel several times when the batch is marched in chunks)
-        march_ms = ms_march / args.steps
-        pre_ms = ms_pre / args.steps
-        gather_GBps = bytes_per_ray * n_rays / (march_ms * 1e-3) / 1e9
-        # SQ / HBM counters of THIS source version on THIS workload, from the tracked digest tools/profile_digest.py wrote
-        prof, prof_src = load_counters(args.cube, rows, cols)
-        wl_ok = prof is not None and prof.get('cube') == args.cube and not args.per_pixel_ht
-        km = (prof or {}).get('kernels', {}).get('march_kernel', {}) if wl_ok else {}
-        kc = (prof or {}).get('kernels', {}).get('crossings_kernel', {}) if wl_ok else {}
-        valu_rw = km.get('valu_per_raywave')                      # per 64-ray wave: independent of the number of rays
-        scene_ok = wl_ok and prof.get('hbm_scene') == [rows, cols] and world == 1
-        traffic = (km.get('hbm_read_bytes', 0) + km.get('hbm_write_bytes', 0)) if (scene_ok and 'hbm_read_bytes' in km) else None
-        step_traffic = (traffic + kc.get('hbm_read_bytes', 0) + kc.get('hbm_write_bytes', 0)) if (traffic is not None and 'hbm_read_bytes' in kc) else None
-        valu_rate = (valu_rw * (n_rays / 64.0) / (march_ms * 1e-3)) if valu_rw else None
-        compulsory = 64 + (ny * nx * nz * 8) / n_rays             # B/ray: look vector in, two delays out, the cube once
-        pr_ = 2 if args.per_pixel_ht else 0
-        ka_m, ka_c = cube.ray_kernel_attributes(1 + pr_), cube.ray_kernel_attributes(0 + pr_)      # from the loaded code object
-        frac_valu = valu_rate / VALU_ISSUE_PEAK if valu_rate else None
-        # MEASURED instruction mix of the march kernel (rocprofv3 SQ class counters, profiles/r*_instr_mix.json through the same digest): what
-        # the issued instructions were, the fp64 flops they executed, and the issue cycles they cost at the per-class rates
-        mix = km.get('instr_mix')
-        waves = n_rays / 64.0
-        executed_fp64 = (mix['fp64_flops_per_lane'] * 64.0 * waves / (march_ms * 1e-3)) if mix else None
-        class_cycles = (mix['issue_cycles_model'] * waves / (march_ms * 1e-3)) if mix else None            # SIMD cycles per second the mix needs
-        simd_cycles = 256 * 4 * 2.4e9
-        # how GOOD the kernel is, beside how busy: the reference's arithmetic (SURVEY 8d flop model: 110 fp64 flop per ray and
-        # REFERENCE sample, S of them per ray) per second of march time against the fp64 vector peak - a kernel that issues more
-        # instructions for the same rays scores lower here and the same in `frac`
-        useful_flops = FLOP_PER_REFERENCE_SAMPLE * S * n_rays / (march_ms * 1e-3)
-        parity, parity_src = load_parity('c3b' if args.per_pixel_ht else ('c3' if (rows, cols) == (4000, 4000) else 'c4' if (total_rows, cols) == (10000, 10000) else 'none'))
-        frac_hbm = (traffic / (march_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic is not None else None
         if args.per_pixel_ht:
             wl = (f'c3b (SURVEY 8d secondary workload, no reference semantics): Raytracing LOS, {total_rows}x{cols} scene on a DEM - per-pixel origin heights '
                   f'rng(2).uniform(0, 3000) m - per-pixel ECEF look vectors, synthetic ERA5-sized {args.cube} f32 cube, zref=max(z)-1, MAX_SEGMENT_LENGTH=1000; '
@@ -519,69 +523,102 @@ def main():
                        'rank_ms_per_step': [t_ / args.steps * 1e3 for t_ in rank_s],
                        'devices_visible': ndev, 'ranks_per_device': -(-world // ndev),
                        'mean_hydro_m': mean_h, 'mean_wet_m': mean_w, 'nan_fraction': nan_frac},
+        }
+        if args.full:
+            bytes_per_ray = 64 * S + 64                               # SURVEY.md §8(d) gather model
+            # per-STEP kernel time (a step may launch a kernel several times when the batch is marched in chunks)
+            march_ms = ms_march / args.steps
+            pre_ms = ms_pre / args.steps
+            gather_GBps = bytes_per_ray * n_rays / (march_ms * 1e-3) / 1e9
+            # SQ / HBM counters of THIS source version on THIS workload, from the tracked digest tools/profile_digest.py wrote
+            prof, prof_src = load_counters(args.cube, rows, cols)
+            wl_ok = prof is not None and prof.get('cube') == args.cube and not args.per_pixel_ht
+            km = (prof or {}).get('kernels', {}).get('march_kernel', {}) if wl_ok else {}
+            kc = (prof or {}).get('kernels', {}).get('crossings_kernel', {}) if wl_ok else {}
+            valu_rw = km.get('valu_per_raywave')                      # per 64-ray wave: independent of the number of rays
+            scene_ok = wl_ok and prof.get('hbm_scene') == [rows, cols] and world == 1
+            traffic = (km.get('hbm_read_bytes', 0) + km.get('hbm_write_bytes', 0)) if (scene_ok and 'hbm_read_bytes' in km) else None
+            step_traffic = (traffic + kc.get('hbm_read_bytes', 0) + kc.get('hbm_write_bytes', 0)) if (traffic is not None and 'hbm_read_bytes' in kc) else None
+            valu_rate = (valu_rw * (n_rays / 64.0) / (march_ms * 1e-3)) if valu_rw else None
+            compulsory = 64 + (ny * nx * nz * 8) / n_rays             # B/ray: look vector in, two delays out, the cube once
+            pr_ = 2 if args.per_pixel_ht else 0
+            ka_m, ka_c = cube.ray_kernel_attributes(1 + pr_), cube.ray_kernel_attributes(0 + pr_)      # from the loaded code object
+            frac_valu = valu_rate / VALU_ISSUE_PEAK if valu_rate else None
+            # MEASURED instruction mix of the march kernel (rocprofv3 SQ class counters, profiles/r*_instr_mix.json through the same digest): what
+            # the issued instructions were, the fp64 flops they executed, and the issue cycles they cost at the per-class rates
+            mix = km.get('instr_mix')
+            waves = n_rays / 64.0
+            executed_fp64 = (mix['fp64_flops_per_lane'] * 64.0 * waves / (march_ms * 1e-3)) if mix else None
+            class_cycles = (mix['issue_cycles_model'] * waves / (march_ms * 1e-3)) if mix else None            # SIMD cycles per second the mix needs
+            simd_cycles = 256 * 4 * 2.4e9
+            # how GOOD the kernel is, beside how busy: the reference's arithmetic (SURVEY 8d flop model: 110 fp64 flop per ray and
+            # REFERENCE sample, S of them per ray) per second of march time against the fp64 vector peak - a kernel that issues more
+            # instructions for the same rays scores lower here and the same in `frac`
+            useful_flops = FLOP_PER_REFERENCE_SAMPLE * S * n_rays / (march_ms * 1e-3)
+            parity, parity_src = load_parity('c3b' if args.per_pixel_ht else ('c3' if (rows, cols) == (4000, 4000) else 'c4' if (total_rows, cols) == (10000, 10000) else 'none'))
+            frac_hbm = (traffic / (march_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic is not None else None
             # The limiter the SQ counters show is fp64 vector-ALU issue, so THAT is the roofline (frac <= 1 by construction:
             # instructions actually issued / issue slots of the chip).  north_star's ">= 60 % of HBM" is not meetable at S = 178:
             # the gathers never reach HBM.  Both fractions are at the top level of this object.
-            'roofline': {'bound': 'valu_fp64_issue', 'kernel': 'march_kernel<float2,false,1,true>' if args.per_pixel_ht else 'march_kernel<float2,false,1>',
-                         'achieved': valu_rate / 1e9 if valu_rate else None, 'peak': VALU_ISSUE_PEAK / 1e9, 'unit': 'G wave64-instr/s',
-                         'frac': frac_valu, 'frac_valu': frac_valu, 'frac_hbm_measured': frac_hbm,
-                         # frac prices every VALU instruction at the fp64 rate and the 2.4 GHz data-sheet clock: it says how BUSY the issue
-                         # ports are.  useful_flops_frac (the headline for kernel quality) says how much of the chip's fp64
-                         # vector peak goes into the reference's own arithmetic; the clock the chip really ran at is beside it.
-                         # three different things: `frac` = how BUSY the issue ports are (every instruction priced at 4 cycles);
-                         # `useful_flops_frac` = the REFERENCE's arithmetic per second against the fp64 peak (a throughput-equivalent: flops the kernel
-                         # avoids still count); `executed_fp64_flops_frac` = the fp64 flops the kernel actually executed (counted by the SQ) against that
-                         # peak = its EFFICIENCY as an fp64 machine; `frac_class_priced` = issue cycles of the measured mix at the per-class rates
-                         # (fp64 + conversions 4 cycles, f32 / integer 2) over the cycles the chip had at 2.4 GHz
-                         'executed_fp64_flops_frac': (executed_fp64 / FP64_VECTOR_PEAK) if executed_fp64 else None,
-                         'executed_fp64_TFLOPs': (executed_fp64 / 1e12) if executed_fp64 else None,
-                         'frac_class_priced': (class_cycles / simd_cycles) if class_cycles else None,
-                         'valu_mix': ({k: mix[k] / mix['valu'] for k in ('fp64', 'cvt', 'int32', 'int64', 'f32', 'other')} if mix else None),
-                         'valu_mix_per_raywave': mix,
-                         'valu_mix_source': 'rocprofv3 --pmc SQ_INSTS_VALU_{FMA,ADD,MUL,TRANS}_F64 / _CVT / _INT32 / _INT64 / _{FMA,ADD,MUL,TRANS}_F32 (tools/profile_round.sh sq3-sq6)' if mix else None,
-                         'useful_flops_frac': useful_flops / FP64_VECTOR_PEAK, 'useful_TFLOPs': useful_flops / 1e12, 'fp64_vector_peak_TFLOPs': FP64_VECTOR_PEAK / 1e12,
-                         'flop_model': f'{FLOP_PER_REFERENCE_SAMPLE:.0f} fp64 flop x S = {S} reference samples per ray (SURVEY 8d)',
-                         'valu_per_reference_sample': (valu_rw / S) if valu_rw else None,
-                         'clock_GHz_measured': clock_ghz, 'clock_GHz_assumed_by_peak': 2.4,
-                         'frac_at_measured_clock': (valu_rate / (256 * 4 * clock_ghz * 1e9 / 4)) if (valu_rate and clock_ghz) else None,
-                         'useful_flops_frac_at_measured_clock': (useful_flops / (FP64_VECTOR_PEAK * clock_ghz / 2.4)) if clock_ghz else None,
-                         'traffic': traffic, 'traffic_unit': 'HBM bytes per march_kernel launch (rocprofv3 --pmc FETCH_SIZE x2 / WRITE_SIZE, separate passes)',
-                         'traffic_over_compulsory': (step_traffic / (compulsory * n_rays)) if step_traffic is not None else None,
-                         'valu_instr_per_raywave': valu_rw, 'valu_busy_frac': km.get('valu_busy_frac'),
-                         'valu_per_evaluated_sample': (valu_rw / (S - (K - 1))) if valu_rw else None,
-                         # SURVEY 8(d)'s models over the WHOLE driver-timed step (both kernels are needed to produce a ray), beside the busy-ness figure:
-                         # `frac` says how busy the issue ports are while march_kernel runs, NOT how close the step is to a hard ceiling
-                         'frac_is': 'valu_issue_busy',
-                         'survey_flops_frac_step': FLOP_PER_REFERENCE_SAMPLE * S * n_rays / (dt / args.steps) / FP64_VECTOR_PEAK,
-                         'survey_bytes_over_hbm_peak_step': bytes_per_ray * n_rays / (dt / args.steps) / (HBM_PEAK_GBS * 1e9),
-                         'survey_bytes_note': 'SURVEY 8(d) gather bytes (64 S + 64 per ray) per second of step time over the HBM peak: above 1 because the gathers are '
-                                              'cache-served (L1 / L2 / Infinity Cache) - a model rate, not a utilisation; the measured HBM fraction is hbm.step_measured_frac',
-                         'dependent_chain_note': 'figures of merit are VALU instructions and dependent-chain length PER EVALUATED SAMPLE (one sample in flight per lane, 4 waves per '
-                                                 'SIMD): round-5/6 A/Bs - 4.2 % fewer VALU bought 1.3 % (pk-diff), 6.3 % fewer (32-bit bookkeeping) bought 1-4 % box to box (LDS level records), 8.6 % fewer through LDS tiles LOST 7 % - the kernel '
-                                                 'is co-limited by the one-sample chain, so only fewer fp64-rate operations per sample or a shorter chain move it',
-                         'vgpr': ka_m['vgpr'], 'lds_bytes': ka_m['lds_static'] + ka_m['lds_dynamic'], 'scratch_bytes': ka_m['scratch'],
-                         'resources_source': 'hipFuncGetAttributes on the loaded code object + the launch\'s dynamic LDS size',
-                         'crossings': {'valu_instr_per_raywave': kc.get('valu_per_raywave'), 'valu_busy_frac': kc.get('valu_busy_frac'),
-                                       'vgpr': ka_c['vgpr'], 'lds_bytes': ka_c['lds_static'] + ka_c['lds_dynamic'], 'scratch_bytes': ka_c['scratch'],
-                                       'frac': (kc['valu_per_raywave'] * (n_rays / 64.0) / (pre_ms * 1e-3) / VALU_ISSUE_PEAK) if kc.get('valu_per_raywave') and pre_ms > 0 else None},
-                         'march_ms_per_step': march_ms, 'crossings_ms_per_step': pre_ms, 'march_launches_timed': n_march,
-                         'counters_source': prof_src if prof is not None else None, 'counters_note': None if prof is not None else prof_src,
-                         'source_hash': kernel_source_hash(), 'library_source_hash': R.load_library().rdr_source_hash().decode(),
-                         'hbm': {'peak_GBps': HBM_PEAK_GBS,
-                                 'algorithmic_bytes_per_ray': bytes_per_ray, 'compulsory_bytes_per_ray': compulsory,
-                                 'measured_GBps': (traffic / (march_ms * 1e-3) / 1e9) if traffic is not None else None,
-                                 'hbm_measured_frac': frac_hbm,
-                                 'step_traffic_bytes': step_traffic,
-                                 'step_measured_frac': (step_traffic / ((march_ms + pre_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS) if step_traffic is not None else None,
-                                 'gather_model_GBps': gather_GBps,
-                                 'gather_model_note': '(64*S+64) B/ray of SURVEY 8d x rays / march time: an ALGORITHMIC rate above the HBM peak because the '
-                                                      'gathers are L2/MALL hits - not a utilisation'}},
-        }
-        res['parity'] = ({'record': parity_src, 'rays_compared': parity.get('rays'), 'max_abs_wet_m': parity.get('max_abs_wet_m'),
-                          'max_abs_hydro_m': parity.get('max_abs_hydro_m'), 'nan_mask_mismatches': parity.get('nan_mask_mismatches'),
-                          'nparts_equal': parity.get('nparts_equal'), 'tolerance_m': parity.get('tolerance_m'), 'source_hash': parity.get('source_hash'),
-                          'what': 'every ray of this scene against the C oracle (tools/full_scene_parity.py), made with the kernels of this source hash'}
-                         if parity is not None else {'record': None, 'note': parity_src})
+            res['roofline'] = {'bound': 'valu_fp64_issue', 'kernel': 'march_kernel<float2,false,1,true>' if args.per_pixel_ht else 'march_kernel<float2,false,1>',
+                               'achieved': valu_rate / 1e9 if valu_rate else None, 'peak': VALU_ISSUE_PEAK / 1e9, 'unit': 'G wave64-instr/s',
+                               'frac': frac_valu, 'frac_valu': frac_valu, 'frac_hbm_measured': frac_hbm,
+                               # frac prices every VALU instruction at the fp64 rate and the 2.4 GHz data-sheet clock: it says how BUSY the issue
+                               # ports are.  useful_flops_frac (the headline for kernel quality) says how much of the chip's fp64
+                               # vector peak goes into the reference's own arithmetic; the clock the chip really ran at is beside it.
+                               # three different things: `frac` = how BUSY the issue ports are (every instruction priced at 4 cycles);
+                               # `useful_flops_frac` = the REFERENCE's arithmetic per second against the fp64 peak (a throughput-equivalent: flops the kernel
+                               # avoids still count); `executed_fp64_flops_frac` = the fp64 flops the kernel actually executed (counted by the SQ) against that
+                               # peak = its EFFICIENCY as an fp64 machine; `frac_class_priced` = issue cycles of the measured mix at the per-class rates
+                               # (fp64 + conversions 4 cycles, f32 / integer 2) over the cycles the chip had at 2.4 GHz
+                               'executed_fp64_flops_frac': (executed_fp64 / FP64_VECTOR_PEAK) if executed_fp64 else None,
+                               'executed_fp64_TFLOPs': (executed_fp64 / 1e12) if executed_fp64 else None,
+                               'frac_class_priced': (class_cycles / simd_cycles) if class_cycles else None,
+                               'valu_mix': ({k: mix[k] / mix['valu'] for k in ('fp64', 'cvt', 'int32', 'int64', 'f32', 'other')} if mix else None),
+                               'valu_mix_per_raywave': mix,
+                               'valu_mix_source': 'rocprofv3 --pmc SQ_INSTS_VALU_{FMA,ADD,MUL,TRANS}_F64 / _CVT / _INT32 / _INT64 / _{FMA,ADD,MUL,TRANS}_F32 (tools/profile_round.sh sq3-sq6)' if mix else None,
+                               'useful_flops_frac': useful_flops / FP64_VECTOR_PEAK, 'useful_TFLOPs': useful_flops / 1e12, 'fp64_vector_peak_TFLOPs': FP64_VECTOR_PEAK / 1e12,
+                               'flop_model': f'{FLOP_PER_REFERENCE_SAMPLE:.0f} fp64 flop x S = {S} reference samples per ray (SURVEY 8d)',
+                               'valu_per_reference_sample': (valu_rw / S) if valu_rw else None,
+                               'clock_GHz_measured': clock_ghz, 'clock_GHz_assumed_by_peak': 2.4,
+                               'frac_at_measured_clock': (valu_rate / (256 * 4 * clock_ghz * 1e9 / 4)) if (valu_rate and clock_ghz) else None,
+                               'useful_flops_frac_at_measured_clock': (useful_flops / (FP64_VECTOR_PEAK * clock_ghz / 2.4)) if clock_ghz else None,
+                               'traffic': traffic, 'traffic_unit': 'HBM bytes per march_kernel launch (rocprofv3 --pmc FETCH_SIZE x2 / WRITE_SIZE, separate passes)',
+                               'traffic_over_compulsory': (step_traffic / (compulsory * n_rays)) if step_traffic is not None else None,
+                               'valu_instr_per_raywave': valu_rw, 'valu_busy_frac': km.get('valu_busy_frac'),
+                               'valu_per_evaluated_sample': (valu_rw / (S - (K - 1))) if valu_rw else None,
+                               # SURVEY 8(d)'s models over the WHOLE driver-timed step (both kernels are needed to produce a ray), beside the busy-ness figure:
+                               # `frac` says how busy the issue ports are while march_kernel runs, NOT how close the step is to a hard ceiling
+                               'frac_is': 'valu_issue_busy',
+                               'survey_flops_frac_step': FLOP_PER_REFERENCE_SAMPLE * S * n_rays / (dt / args.steps) / FP64_VECTOR_PEAK,
+                               'survey_bytes_over_hbm_peak_step': bytes_per_ray * n_rays / (dt / args.steps) / (HBM_PEAK_GBS * 1e9),
+                               'survey_bytes_note': 'SURVEY 8(d) gather bytes (64 S + 64 per ray) per second of step time over the HBM peak: above 1 because the gathers are '
+                                                    'cache-served (L1 / L2 / Infinity Cache) - a model rate, not a utilisation; the measured HBM fraction is hbm.step_measured_frac',
+                               'dependent_chain_note': 'figures of merit are VALU instructions and dependent-chain length PER EVALUATED SAMPLE (one sample in flight per lane, 4 waves per '
+                                                       'SIMD): round-5/6 A/Bs - 4.2 % fewer VALU bought 1.3 % (pk-diff), 6.3 % fewer (32-bit bookkeeping) bought 1-4 % box to box (LDS level records), 8.6 % fewer through LDS tiles LOST 7 % - the kernel '
+                                                       'is co-limited by the one-sample chain, so only fewer fp64-rate operations per sample or a shorter chain move it',
+                               'vgpr': ka_m['vgpr'], 'lds_bytes': ka_m['lds_static'] + ka_m['lds_dynamic'], 'scratch_bytes': ka_m['scratch'],
+                               'resources_source': 'hipFuncGetAttributes on the loaded code object + the launch\'s dynamic LDS size',
+                               'crossings': {'valu_instr_per_raywave': kc.get('valu_per_raywave'), 'valu_busy_frac': kc.get('valu_busy_frac'),
+                                             'vgpr': ka_c['vgpr'], 'lds_bytes': ka_c['lds_static'] + ka_c['lds_dynamic'], 'scratch_bytes': ka_c['scratch'],
+                                             'frac': (kc['valu_per_raywave'] * (n_rays / 64.0) / (pre_ms * 1e-3) / VALU_ISSUE_PEAK) if kc.get('valu_per_raywave') and pre_ms > 0 else None},
+                               'march_ms_per_step': march_ms, 'crossings_ms_per_step': pre_ms, 'march_launches_timed': n_march,
+                               'counters_source': prof_src if prof is not None else None, 'counters_note': None if prof is not None else prof_src,
+                               'source_hash': kernel_source_hash(), 'library_source_hash': R.load_library().rdr_source_hash().decode(),
+                               'hbm': {'peak_GBps': HBM_PEAK_GBS,
+                                       'algorithmic_bytes_per_ray': bytes_per_ray, 'compulsory_bytes_per_ray': compulsory,
+                                       'measured_GBps': (traffic / (march_ms * 1e-3) / 1e9) if traffic is not None else None,
+                                       'hbm_measured_frac': frac_hbm,
+                                       'step_traffic_bytes': step_traffic,
+                                       'step_measured_frac': (step_traffic / ((march_ms + pre_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS) if step_traffic is not None else None,
+                                       'gather_model_GBps': gather_GBps,
+                                       'gather_model_note': '(64*S+64) B/ray of SURVEY 8d x rays / march time: an ALGORITHMIC rate above the HBM peak because the '
+                                                            'gathers are L2/MALL hits - not a utilisation'}}
+            res['parity'] = ({'record': parity_src, 'rays_compared': parity.get('rays'), 'max_abs_wet_m': parity.get('max_abs_wet_m'),
+                              'max_abs_hydro_m': parity.get('max_abs_hydro_m'), 'nan_mask_mismatches': parity.get('nan_mask_mismatches'),
+                              'nparts_equal': parity.get('nparts_equal'), 'tolerance_m': parity.get('tolerance_m'), 'source_hash': parity.get('source_hash'),
+                              'what': 'every ray of this scene against the C oracle (tools/full_scene_parity.py), made with the kernels of this source hash'}
+                             if parity is not None else {'record': None, 'note': parity_src})
         res['config']['devices'] = devices
         res['config']['distinct_devices'] = len({(d_['uuid'], d_['pci']) for d_ in devices})
         if parity_sample is not None:
@@ -594,10 +631,10 @@ def main():
                 res['strong_scaling_efficiency'] = eff
         if e2e is not None:
             res['end_to_end'] = e2e
-        if world == 1 and args.cpu_sample > 0:
+        if world == 1 and args.full and args.cpu_sample > 0:
             pp = (hts_np, cube.ray_levels(rays.ht_min, zref)[2]) if args.per_pixel_ht else None
             res['cpu_baseline'] = cpu_baseline(args, rows, cols, xpts, ypts, inc_cols, hd, nparts, zref, out_w, out_h, pp)
-        if world == 1 and not args.no_secondary and not args.per_pixel_ht:
+        if world == 1 and args.full and not args.no_secondary and not args.per_pixel_ht:
             # the two gather workloads of BASELINE.json beside the headline (a few ms of GPU time each; their own lines: --workload c2 / c5)
             del los_t, out_w, out_h, rays, cube, wet, hyd
             torch.cuda.empty_cache()
@@ -751,6 +788,7 @@ def c2_measure(ctx, dev, n_side=1000, steps=20, warmup=3, oracle_sample=200000, 
     if sync is not None:
         sync()
     dt = time.perf_counter() - t0
+    last = list(out)                             # the arrays of the last timed step (the loops below compute them again)
     # the two halves by themselves, HIP events on the stream the kernels run on (the library's own pairs around every launch)
     ctx.set_profiling(True)
     for _ in range(steps):
@@ -766,7 +804,7 @@ def c2_measure(ctx, dev, n_side=1000, steps=20, warmup=3, oracle_sample=200000, 
     nodes = int(xg.size * yg.size * zl.size)
     r = dict(points_all=n_all, points_this_rank=cnt, p0=p0, nodes=nodes, grid=[int(zl.size), int(yg.size), int(xg.size)], step_s=dt / steps,
              build_ms=ms_b / steps, build_launches=n_b, gather_ms=ms_g / steps, gather_launches=n_g, inc=inc,
-             wet=out[0], hydro=out[1], has_nan=bool(keep[0].has_nan()),
+             wet=last[0], hydro=last[1], has_nan=bool(keep[0].has_nan()),
              mean_hydro=float(torch.nanmean(out[1]).item()), mean_wet=float(torch.nanmean(out[0]).item()), nan_fraction=float(torch.isnan(out[1]).double().mean().item()))
     if e2e:       # the same job through the host-buffer entry (rdr_point_delays: points up, delays down, everything between on the device)
         la, lo, hg = (np.ascontiguousarray(a[p0:p0 + cnt]) for a in (lats, lons, hgts))
@@ -871,6 +909,8 @@ def run_c2(args, ctx, dev, coll_dev, dist_on, rank, world, ndev, result_fd):
     osamp = (200000 if args.cpu_sample > 0 else 0) if world == 1 else 64 * max(args.parity_block, 0)
     m = c2_measure(ctx, dev, n_side=n_side, steps=args.steps, warmup=args.warmup, oracle_sample=osamp,
                    block=(p0, cnt), cube_tensors=cube_tensors, e2e=(world == 1 and not args.no_e2e), sync=(dist.barrier if dist_on else None))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'wet': m['wet'], 'hydro': m['hydro']})
     dt = m['step_s'] * args.steps
     rank_s = [dt]
     if dist_on:
@@ -1079,6 +1119,8 @@ def run_c5(args, ctx, dev, coll_dev, dist_on, rank, world, ndev, result_fd):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     wet_t, hyd_t = out
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'wet': wet_t, 'hydro': hyd_t})
     if args.dump:
         np.savez(f'{args.dump}.rank{rank}.npz', wet=wet_t.cpu().numpy(), hydro=hyd_t.cpu().numpy(), p0=p0, cnt=cnt)
     devices = device_identities(torch, dist, dist_on, args.backend, dev.index, rank, world)

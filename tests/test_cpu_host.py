@@ -382,3 +382,23 @@ def test_round6_host_logic_without_a_gpu():
     assert abs(eff - 40.0 / (8 * 5.5)) < 1e-15 and abs(one['value'] - 1.0e8 / 0.040) < 1e-3 and one['steps'] == 3
     one, eff = bench.scaling_reference('weak', 6.0, 1.6e7, 8, 6.3, 3, 'x')
     assert abs(eff - 6.0 / 6.3) < 1e-15 and abs(one['value'] - 1.6e7 / 0.006) < 1e-3
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: arrays within the budget are written whole; above it every array keeps the SAME seeded sample of its
+    elements (sorted flat indices), from run to run, and the files stay within the budget; non-float arrays are written as float64."""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location('bench_for_test', Path(__file__).resolve().parent.parent / 'bench.py')
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    w = torch.arange(300 * 200, dtype=torch.float64).reshape(300, 200); h = -w.float(); n = torch.arange(7, dtype=torch.int32)
+    bench.dump_outputs(str(tmp_path / 'whole'), {'wet': w, 'hydro': h, 'n': n})
+    assert np.array_equal(np.load(tmp_path / 'whole' / 'wet.npy'), w.reshape(-1).numpy()) and np.load(tmp_path / 'whole' / 'hydro.npy').dtype == np.float32
+    assert np.load(tmp_path / 'whole' / 'n.npy').dtype == np.float64
+    monkeypatch.setattr(bench, 'DUMP_BYTES_MAX', 200_000)
+    for run in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / run), {'wet': w, 'hydro': h})
+    a, b = np.load(tmp_path / 'a' / 'wet.npy'), np.load(tmp_path / 'b' / 'wet.npy')
+    assert np.array_equal(a, b) and 0 < a.size < w.numel() and np.all(np.diff(a) > 0)          # wet = its own flat index: sorted, distinct
+    assert np.array_equal(np.load(tmp_path / 'a' / 'hydro.npy'), -a.astype(np.float32))       # the same elements of every array
+    assert sum(f.stat().st_size for f in (tmp_path / 'a').iterdir()) <= 200_000

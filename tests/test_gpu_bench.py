@@ -5,6 +5,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -12,7 +13,7 @@ ROOT = Path(__file__).resolve().parent.parent
 
 
 def _bench(*args):
-    out = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--steps', '3', '--warmup', '1', '--rows', '640', '--cols', '704', '--cpu-sample', '96'] + list(args),
+    out = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--steps', '3', '--warmup', '1', '--rows', '640', '--cols', '704', '--cpu-sample', '96', '--full'] + list(args),
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
     lines = out.stdout.splitlines()          # the contract: stdout is ONE line, the JSON (library banners and logs go to stderr)
@@ -98,6 +99,30 @@ def test_bench_per_pixel_heights_line():
     assert d['config']['workload'].startswith('c3b') and 'end_to_end' not in d
     assert d['roofline']['kernel'].endswith('true>') and d['roofline']['frac'] is None     # (no counter digest is kept for the secondary workload)
     assert d['cpu_baseline']['gpu_vs_oracle_max_abs_m'] < 1e-6 and d['config']['nan_fraction'] == 0.0
+
+
+def test_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the line is the headline alone (no roofline, no CPU or end-to-end legs, no appendix); --steps sets the timed steps,
+    and --dump-outputs writes the delays of the last timed step - here the whole scene, equal to the --dump slab."""
+    def plain(*args):
+        out = subprocess.run([sys.executable, str(ROOT / 'bench.py')] + list(args), capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
+        lines = out.stdout.splitlines()
+        assert len(lines) == 1 and lines[0].startswith('{'), out.stdout[-2000:]
+        return json.loads(lines[0])
+    d = plain('--steps', '4', '--warmup', '1', '--rows', '640', '--cols', '704', '--dump-outputs', str(tmp_path / 'outs'), '--dump', str(tmp_path / 'slab'))
+    assert d['metric'].startswith('LOS rays/sec') and d['unit'] == 'rays/s' and d['higher_is_better'] is True and d['dtype'] == 'f64'
+    assert d['steps'] == 4 and d['warmup'] == 1 and abs(d['value'] * d['ms_per_step'] * 1e-3 - 640 * 704) < 1.0
+    for k in ('roofline', 'parity', 'cpu_baseline', 'end_to_end', 'secondary'):
+        assert k not in d, k
+    slab = np.load(tmp_path / 'slab.rank0.npz')
+    for k in ('wet', 'hydro'):
+        got = np.load(tmp_path / 'outs' / f'{k}.npy')
+        assert got.dtype == np.float64 and np.array_equal(got, slab[k].reshape(-1)) and np.isfinite(got).all()
+    # the time of ONE step does not depend on how many are timed: a loop that ran some other number of steps than --steps would put the
+    # two figures a factor of 10 apart (a 2000 x 2000 scene: a step of about 1.5 ms, well above the launch and synchronise overheads)
+    few, many = (plain('--steps', str(n), '--warmup', '2', '--rows', '2000', '--cols', '2000') for n in (2, 20))
+    assert few['steps'] == 2 and many['steps'] == 20 and 0.5 < few['ms_per_step'] / many['ms_per_step'] < 2.0, (few['ms_per_step'], many['ms_per_step'])
 
 
 def test_c2_line():

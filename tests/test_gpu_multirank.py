@@ -16,7 +16,7 @@ ROOT = Path(__file__).resolve().parent.parent
 
 def _bench(tmp_path, tag, *args):
     out = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--steps', '2', '--warmup', '1', '--cpu-sample', '0', '--cols', '1200',
-                          '--no-e2e', '--dump', str(tmp_path / tag)] + list(args), capture_output=True, text=True, timeout=900)
+                          '--no-e2e', '--full', '--dump', str(tmp_path / tag)] + list(args), capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
     lines = out.stdout.splitlines()          # the contract: stdout is ONE line, the JSON (library banners and logs go to stderr)
     assert len(lines) == 1 and lines[0].startswith('{'), out.stdout[-2000:]
@@ -95,9 +95,9 @@ def test_c5_station_workload_across_two_ranks(tmp_path):
     assert np.isfinite(a['hydro']).all() and a['hydro'].mean() > 50.0          # (refractivities, not delays: N units)
 
 
-# ---- world = 8 on ONE device (round 5): every branch an 8-GPU node will take, rehearsed --------------------------------------------------
+# ---- more than two ranks: every branch an 8-GPU node will take - three ranks sharing one device, and the eight ranks of such a node -----
 def _run(tmp_path, tag, *args, timeout=1200):
-    out = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--steps', '2', '--warmup', '1', '--cpu-sample', '0', '--no-e2e', '--dump', str(tmp_path / tag)] + list(args),
+    out = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--steps', '2', '--warmup', '1', '--cpu-sample', '0', '--no-e2e', '--full', '--dump', str(tmp_path / tag)] + list(args),
                          capture_output=True, text=True, timeout=timeout)
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
     lines = out.stdout.splitlines()
@@ -131,63 +131,104 @@ def _covers(shards, total):
     return pos == total
 
 
-def test_world8_strong_scaling_of_one_scene_matches_one_rank(tmp_path):
-    """`python bench.py --gpus 8` as the driver's scaling run launches it (self-launch through torch.distributed.run, eight ranks): BASELINE
-    configs[3] semantics on a reduced 2005 x 4000 scene - uneven row blocks (251 x 5 + 250 x 3), ONE packed cube broadcast, ONE MAX all-reduce
-    of K+4 doubles per step, max-over-ranks timing.  On a one-GPU box the ranks share the device (`--backend auto` -> gloo with device-resident
-    collective tensors: RCCL refuses duplicates); on an 8-GPU node the same command runs over RCCL.  The eight slabs equal the one-rank run of
-    the whole scene bit for bit; the line reports the world the backend saw, every rank's block and every rank's own time."""
+def _sizes(total, world):
+    """what shard_rows gives every rank: the first total % world blocks one longer"""
+    return [total // world + (1 if r < total % world else 0) for r in range(world)]
+
+
+def _needs_eight_devices():
+    """Eight ranks sharing one device would be nine or ten processes with that GPU open (ranks, launcher, the test process): more than a
+    node lets share one device.  With one device per rank the eight-rank runs go ahead; on fewer devices the three-rank runs stand in."""
+    import torch
+    n = torch.cuda.device_count()
+    if n < 8:
+        pytest.skip(f'needs 8 GPUs (one per rank), found {n}')
+
+
+def _strong_scene_matches_one_rank(tmp_path, world):
+    """`python bench.py --gpus N` as the driver's scaling run launches it (self-launch through torch.distributed.run): BASELINE configs[3]
+    semantics on a reduced 2005 x 4000 scene - uneven row blocks, ONE packed cube broadcast, ONE MAX all-reduce of K+4 doubles per step,
+    max-over-ranks timing.  Ranks that share a device go through `--backend auto` -> gloo with device-resident collective tensors (RCCL
+    refuses duplicates); with one device per rank the same command runs over RCCL.  The slabs equal the one-rank run of the whole scene bit
+    for bit; the line reports the world the backend saw, every rank's block and every rank's own time."""
     one = _run(tmp_path, 'one', '--gpus', '1', '--rows', '2005', '--cols', '4000', '--no-secondary')
-    eight = _run(tmp_path, 'eight', '--gpus', '8', '--total-rows', '2005', '--cols', '4000')
-    cfg = eight['config']
-    assert eight['n_gpus'] == 8 and eight['scaling'] == 'strong' and cfg['ranks'] == 8 and cfg['world_size_seen_by_backend'] == 8
-    assert cfg['backend'] in ('nccl', 'gloo') and cfg['ranks_per_device'] * cfg['devices_visible'] >= 8
+    many = _run(tmp_path, 'many', '--gpus', str(world), '--total-rows', '2005', '--cols', '4000')
+    cfg = many['config']
+    sizes = _sizes(2005, world)
+    assert len(set(sizes)) == 2                                                                            # the blocks are uneven
+    assert many['n_gpus'] == world and many['scaling'] == 'strong' and cfg['ranks'] == world and cfg['world_size_seen_by_backend'] == world
+    assert cfg['backend'] in ('nccl', 'gloo') and cfg['ranks_per_device'] * cfg['devices_visible'] >= world
     assert 'configs[3]' in cfg['workload'] and cfg['rays_per_step_all_gpus'] == 2005 * 4000
-    assert _covers(cfg['shards'], 2005) and [c for _, c in cfg['shards']] == [251] * 5 + [250] * 3
-    assert len(cfg['rank_ms_per_step']) == 8 and all(t > 0 for t in cfg['rank_ms_per_step'])
-    assert abs(max(cfg['rank_ms_per_step']) - eight['ms_per_step']) < 1e-6 * eight['ms_per_step']       # the line's time IS the slowest rank's
-    assert abs(eight['value'] * eight['ms_per_step'] * 1e-3 - 2005 * 4000) < 1.0
-    assert 'secondary' not in eight                                                                       # (an appendix of the one-GPU line only)
-    _self_contained(eight, 8, 2005 * 4000)
-    assert eight['one_gpu_same_scene']['same_bits_as_sharded_run'] is True
-    ps = eight['parity_sample']
-    assert ps['block'] == [250, 250] and ps['rays_compared_all_ranks'] == 8 * 250 * 250 and len(ps['per_rank_max_abs_m']) == 8
+    assert _covers(cfg['shards'], 2005) and [c for _, c in cfg['shards']] == sizes
+    assert len(cfg['rank_ms_per_step']) == world and all(t > 0 for t in cfg['rank_ms_per_step'])
+    assert abs(max(cfg['rank_ms_per_step']) - many['ms_per_step']) < 1e-6 * many['ms_per_step']         # the line's time IS the slowest rank's
+    assert abs(many['value'] * many['ms_per_step'] * 1e-3 - 2005 * 4000) < 1.0
+    assert 'secondary' not in many                                                                         # (an appendix of the one-GPU line only)
+    _self_contained(many, world, 2005 * 4000)
+    assert many['one_gpu_same_scene']['same_bits_as_sharded_run'] is True
+    ps = many['parity_sample']
+    nb = min(256, min(sizes))                                                                              # --parity-block, the same on every rank
+    assert ps['block'] == [nb, nb] and ps['rays_compared_all_ranks'] == world * nb * nb and len(ps['per_rank_max_abs_m']) == world
     assert ps['max_abs_wet_m'] < 1e-9 and ps['max_abs_hydro_m'] < 1e-9 and ps['nan_mask_mismatches'] == 0
     a = np.load(tmp_path / 'one.rank0.npz')
-    parts = [np.load(tmp_path / f'eight.rank{r}.npz') for r in range(8)]
+    parts = [np.load(tmp_path / f'many.rank{r}.npz') for r in range(world)]
     assert [int(p['row0']) for p in parts] == [r0 for r0, _ in cfg['shards']]
     assert all(np.array_equal(a['nparts'], p['nparts']) for p in parts)
     assert np.array_equal(a['hydro'], np.concatenate([p['hydro'] for p in parts])) and np.array_equal(a['wet'], np.concatenate([p['wet'] for p in parts]))
     assert np.isfinite(a['hydro']).all()
 
 
-def test_world8_station_and_point_workloads_match_one_rank(tmp_path):
-    """`--workload c5` (configs[4]) and `--workload c2` (configs[1]) on eight ranks: the cubes go out in packed broadcasts, every rank takes its
+def _point_workloads_match_one_rank(tmp_path, world):
+    """`--workload c5` (configs[4]) and `--workload c2` (configs[1]) on N ranks: the cubes go out in packed broadcasts, every rank takes its
     contiguous block of the point list, there is no data-path collective; blocks cover the list exactly and equal the one-rank result bit for bit."""
     one = _run(tmp_path, 'c5one', '--gpus', '1', '--workload', 'c5', '--stations', '400003')
-    eight = _run(tmp_path, 'c5eight', '--gpus', '8', '--workload', 'c5', '--stations', '400003')
-    cfg = eight['config']
-    assert eight['n_gpus'] == 8 and eight['scaling'] == 'strong' and cfg['world_size_seen_by_backend'] == 8 and _covers(cfg['shards'], 400003)
-    assert len(cfg['rank_ms_per_step']) == 8 and abs(eight['value'] * eight['ms_per_step'] * 1e-3 - 400003) < 1.0
-    _self_contained(eight, 8, 400003)
-    assert eight['one_gpu_same_scene']['same_bits_as_sharded_run'] is True and eight['parity_sample']['max_abs'] < 1e-9
-    assert eight['parity_sample']['points_compared_all_ranks'] == 8 * 2048
+    many = _run(tmp_path, 'c5many', '--gpus', str(world), '--workload', 'c5', '--stations', '400003')
+    cfg = many['config']
+    assert many['n_gpus'] == world and many['scaling'] == 'strong' and cfg['world_size_seen_by_backend'] == world and _covers(cfg['shards'], 400003)
+    assert [c for _, c in cfg['shards']] == _sizes(400003, world)
+    assert len(cfg['rank_ms_per_step']) == world and abs(many['value'] * many['ms_per_step'] * 1e-3 - 400003) < 1.0
+    _self_contained(many, world, 400003)
+    assert many['one_gpu_same_scene']['same_bits_as_sharded_run'] is True and many['parity_sample']['max_abs'] < 1e-9
+    assert many['parity_sample']['points_compared_all_ranks'] == world * 2048
     a = np.load(tmp_path / 'c5one.rank0.npz')
-    parts = [np.load(tmp_path / f'c5eight.rank{r}.npz') for r in range(8)]
+    parts = [np.load(tmp_path / f'c5many.rank{r}.npz') for r in range(world)]
     assert [int(p['p0']) for p in parts] == [r0 for r0, _ in cfg['shards']]
     assert np.array_equal(a['wet'], np.concatenate([p['wet'] for p in parts])) and np.array_equal(a['hydro'], np.concatenate([p['hydro'] for p in parts]))
     one = _run(tmp_path, 'c2one', '--gpus', '1', '--workload', 'c2', '--points', '301')
-    eight = _run(tmp_path, 'c2eight', '--gpus', '8', '--workload', 'c2', '--points', '301')
-    assert one['unit'] == 'points/s' and 'configs[1]' in eight['config']['workload'] and eight['config']['world_size_seen_by_backend'] == 8
-    assert eight['config']['points_all_gpus'] == 301 * 301 and abs(eight['value'] * eight['ms_per_step'] * 1e-3 - 301 * 301) < 1.0
-    assert eight['roofline']['bound'] == 'hbm' and eight['roofline']['frac'] > 0
-    _self_contained(eight, 8, 301 * 301)
-    assert eight['parity_sample']['max_abs_m'] < 1e-12 and eight['parity_sample']['nan_masks_equal'] is True
+    many = _run(tmp_path, 'c2many', '--gpus', str(world), '--workload', 'c2', '--points', '301')
+    assert one['unit'] == 'points/s' and 'configs[1]' in many['config']['workload'] and many['config']['world_size_seen_by_backend'] == world
+    assert many['config']['points_all_gpus'] == 301 * 301 and abs(many['value'] * many['ms_per_step'] * 1e-3 - 301 * 301) < 1.0
+    assert [c for _, c in many['config']['shards']] == _sizes(301 * 301, world)
+    assert many['roofline']['bound'] == 'hbm' and many['roofline']['frac'] > 0
+    _self_contained(many, world, 301 * 301)
+    assert many['parity_sample']['max_abs_m'] < 1e-12 and many['parity_sample']['nan_masks_equal'] is True
     a = np.load(tmp_path / 'c2one.rank0.npz')
-    parts = [np.load(tmp_path / f'c2eight.rank{r}.npz') for r in range(8)]
+    parts = [np.load(tmp_path / f'c2many.rank{r}.npz') for r in range(world)]
     assert sum(int(p['cnt']) for p in parts) == 301 * 301
     assert np.array_equal(a['wet'], np.concatenate([p['wet'] for p in parts])) and np.array_equal(a['hydro'], np.concatenate([p['hydro'] for p in parts]))
     assert np.isfinite(a['hydro']).all() and 1.5 < a['hydro'].mean() < 4.0                          # metres of slant delay at 39 deg incidence
+
+
+def test_world3_strong_scaling_of_one_scene_matches_one_rank(tmp_path):
+    """Three ranks sharing this device: uneven row blocks (669 + 668 x 2) of the 2005 x 4000 scene (see _strong_scene_matches_one_rank)."""
+    _strong_scene_matches_one_rank(tmp_path, 3)
+
+
+def test_world3_station_and_point_workloads_match_one_rank(tmp_path):
+    """Three ranks sharing this device: c5 and c2 sharded into uneven blocks (see _point_workloads_match_one_rank)."""
+    _point_workloads_match_one_rank(tmp_path, 3)
+
+
+def test_world8_strong_scaling_of_one_scene_matches_one_rank(tmp_path):
+    """Eight ranks, one per device, as on an 8-GPU node: row blocks 251 x 5 + 250 x 3 (see _strong_scene_matches_one_rank)."""
+    _needs_eight_devices()
+    _strong_scene_matches_one_rank(tmp_path, 8)
+
+
+def test_world8_station_and_point_workloads_match_one_rank(tmp_path):
+    """Eight ranks, one per device, as on an 8-GPU node (see _point_workloads_match_one_rank)."""
+    _needs_eight_devices()
+    _point_workloads_match_one_rank(tmp_path, 8)
 
 
 def test_nccl_preflight_is_one_clear_message(tmp_path):

@@ -14,6 +14,6 @@ PY
 rm -f gpurun_out/env0.rank0.npz gpurun_out/env1.rank0.npz
 for rep in 1 2 3; do
   for v in 0 1; do
-    env $V=$v python bench.py --steps 20 --warmup 5 --cpu-sample 0 --no-e2e --no-secondary "$@" 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$V=$v', round(d['value']/1e9,4), 'G rays/s  step', round(d['ms_per_step'],3), 'march', round(d['roofline']['march_ms_per_step'],3), 'crossings', round(d['roofline']['crossings_ms_per_step'],3))"
+    env $V=$v python bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --no-e2e --no-secondary "$@" 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$V=$v', round(d['value']/1e9,4), 'G rays/s  step', round(d['ms_per_step'],3), 'march', round(d['roofline']['march_ms_per_step'],3), 'crossings', round(d['roofline']['crossings_ms_per_step'],3))"
   done
 done

@@ -9,6 +9,6 @@ python $R/tools/e2e_zenith.py 1000 1000 40 2>/dev/null | tail -1 > $O/zenith_100
 python $R/tools/bench_slices.py 2>/dev/null | tail -2 > $O/bench_slices.txt
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -w $R/tools/probes/write_probe.hip -o /tmp/wp && /tmp/wp > $O/write_probe.txt
 python $R/tools/probes/pin_probe.py > $O/pin_probe.txt 2>/dev/null
-python $R/bench.py > $O/bench.json 2> $O/bench.err
-python $R/bench.py --per-pixel-ht > $O/bench_per_pixel.json 2>> $O/bench.err
+python $R/bench.py --full > $O/bench.json 2> $O/bench.err
+python $R/bench.py --full --per-pixel-ht > $O/bench_per_pixel.json 2>> $O/bench.err
 head -c 600 $O/*.json; cat $O/bench_slices.txt

@@ -8,8 +8,8 @@ cd /tmp && export TMPDIR=/tmp
 O=$R/gpurun_out/world8; rm -rf $O; mkdir -p $O
 run8() { tag=$1; shift; python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29517 $R/bench.py --gpus 8 "$@" > $O/$tag.json 2> $O/$tag.err; echo "$tag rc=$?"; tail -c 600 $O/$tag.json; }
 run1() { tag=$1; shift; python $R/bench.py --gpus 1 "$@" > $O/$tag.json 2> $O/$tag.err; echo "$tag rc=$?"; }
-run8 rays8 --steps 5 --warmup 2 --cpu-sample 0 --no-e2e
-run1 rays1 --steps 5 --warmup 2 --cpu-sample 0 --no-e2e --no-secondary --rows 10000 --cols 10000
+run8 rays8 --full --steps 5 --warmup 2 --cpu-sample 0 --no-e2e
+run1 rays1 --full --steps 5 --warmup 2 --cpu-sample 0 --no-e2e --no-secondary --rows 10000 --cols 10000
 run8 c5_8 --workload c5 --steps 5 --warmup 2 --cpu-sample 0
 run1 c5_1 --workload c5 --steps 5 --warmup 2 --cpu-sample 0
 run8 c2_8 --workload c2 --steps 5 --warmup 2 --cpu-sample 0 --no-e2e
