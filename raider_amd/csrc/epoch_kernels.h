@@ -1,0 +1,286 @@
+// Pass 2 of a time series (rdr_raytrace_slices_epochs): E weather epochs on ONE ray geometry, marched together.
+//
+//   march_epochs_kernel   the light slice loop of march_kernel (raider_kernels.h) with E cubes: per sample the shared part -
+//                         the ray polynomials, the x / y cell search, the z window, the corner offset - runs once; then E corner-pair
+//                         gathers (independent of each other: the ILP the one-epoch marcher lacks) and E (wet, hydro) accumulators.
+//
+// Per epoch the arithmetic is march_kernel's own: sample_finish_lerp on the same weights, the same trapezoid weights, the same
+// accumulation order - so epoch e's delays are bit for bit what rdr_raytrace_slices gives on cube e.  Generic rays (record field
+// WS_SCALE == 0) are left to march_kernel<T2, true>, launched once per epoch on the same records.  The f64 LDS staging of
+// march_kernel (STAGED) is not carried over: with E gathers per sample in flight the direct loads are what the stacked loop needs.
+//
+// Layout: pointer per epoch.  The E cubes share shape, axes and projection (checked on the host), so one element offset serves
+// every epoch and the corner-pair reads of an epoch are exactly the single-epoch kernel's (16 B / 32 B contiguous per corner pair).
+#pragma once
+#include "raider_kernels.h"
+
+namespace rdr {
+
+constexpr int EPOCHS_MAX = 4;          // epochs per stacked launch (DESIGN.md "Time series")
+
+template <typename T2, int E>
+struct EpochCubes { const T2* v[E]; };
+
+// E samples that share their cell and weights: one set of corners per epoch
+template <typename T2, int E>
+struct PendingSampleE {
+    T2 v[E][8];
+    double ty, tx, tz;
+};
+
+// gather_corners for E cubes of one shape: cell_xy once, the element offset once, E x 4 corner-pair loads
+template <typename T2, int E, bool IDX, bool NOCHECK>
+__device__ __forceinline__ void gather_corners_e(const CubeView<T2>& c, const EpochCubes<T2, E>& ev, const AxisTabs& m, double y, double x, int iz,
+                                                 PendingSampleE<T2, E>& s) {
+    int iy, ix;
+    cell_xy<IDX, NOCHECK>(m.ey, c.ny, y, c.y_lo, c.y_hi, c.inv_dy, c.exact_y, c.uni_y, iy, s.ty);
+    cell_xy<IDX, NOCHECK>(m.ex, c.nx, x, c.x_lo, c.x_hi, c.inv_dx, c.exact_x, c.uni_x, ix, s.tx);
+    if (c.small) {
+        unsigned col;
+        asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(col) : "v"((unsigned)iy), "s"((unsigned)c.nx), "v"((unsigned)ix));
+        const unsigned off = (__umul24(col, (unsigned)c.nz) + (unsigned)iz) * (unsigned)sizeof(T2);
+        const size_t rowx = (size_t)c.nz * sizeof(T2), rowy = (size_t)c.nx * rowx;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const char* b = reinterpret_cast<const char*>(ev.v[e]);
+            const T2* p00 = reinterpret_cast<const T2*>(b + off);
+            const T2* p01 = reinterpret_cast<const T2*>(b + rowx + off);
+            const T2* p10 = reinterpret_cast<const T2*>(b + rowy + off);
+            const T2* p11 = reinterpret_cast<const T2*>(b + rowy + rowx + off);
+            s.v[e][0] = p00[0]; s.v[e][1] = p00[1];
+            s.v[e][2] = p01[0]; s.v[e][3] = p01[1];
+            s.v[e][4] = p10[0]; s.v[e][5] = p10[1];
+            s.v[e][6] = p11[0]; s.v[e][7] = p11[1];
+        }
+    } else {
+        const int64_t o00 = ((int64_t)iy * c.nx + ix) * c.nz + iz, o01 = o00 + c.nz;
+        const int64_t o10 = o00 + (int64_t)c.nx * c.nz, o11 = o10 + c.nz;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const T2* p = ev.v[e];
+            s.v[e][0] = p[o00]; s.v[e][1] = p[o00 + 1];
+            s.v[e][2] = p[o01]; s.v[e][3] = p[o01 + 1];
+            s.v[e][4] = p[o10]; s.v[e][5] = p[o10 + 1];
+            s.v[e][6] = p[o11]; s.v[e][7] = p[o11 + 1];
+        }
+    }
+}
+
+// Occupancy per (dtype, E), the highest at which the compiler's resource report shows no scratch (DESIGN.md "Time series"): at four
+// waves per SIMD f32 / E = 2 spills 48-80 B per lane, at three f32 / E = 4 48-112 B and f64 / E = 2 16-32 B.
+template <typename T2, int E>
+struct EpochWaves { static constexpr int value = (sizeof(T2) == 8 && E <= 2) ? 3 : 2; };
+
+// GRID as in march_kernel: 1 REGULAR (exact axes, 32-bit offsets), 2 TABLES (nearly uniform axes, 32-bit offsets), 0 run-time flags.
+// Outputs: epoch e of slice-major ray index o at P.wet[e * estride + o] / P.hyd[e * estride + o].
+template <typename T2, int E, int GRID>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EpochWaves<T2, E>::value, EpochWaves<T2, E>::value)))
+void march_epochs_kernel(CubeView<T2> c_in, EpochCubes<T2, E> ev, RayParams P, int64_t estride) {
+    constexpr bool REGULAR = GRID == 1;
+    CubeView<T2> c = c_in;
+    if (REGULAR) { c.exact_y = 1; c.exact_x = 1; c.small = 1; }
+    if (GRID == 2) { c.exact_y = 0; c.exact_x = 0; c.uni_y = 1; c.uni_x = 1; c.small = 1; }
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const RaySmem m = carve_smem(smem_raw, c.ny, c.nx, c.nz, c.exact_y, c.exact_x);
+    fill_axes(c, m);
+    int K = 0, slice = -1;
+    double poison = 0.0;
+    bool clamp_lo = false, clamp_hi = false;
+    TileWalk walk(P.tile_count, P.tile_ctr, m.K + 2);
+    int64_t lt;
+    while (walk.next(P.tile_count, lt)) {
+        const int64_t tg = P.tile_begin + lt;
+        const int sl = (int)(tg / P.tiles_per_slice);
+        const int64_t t = tg - (int64_t)sl * P.tiles_per_slice;
+        if (sl != slice) {                                 // the slice's level table and partition: march_kernel's fill, verbatim
+            slice = sl;
+            K = fill_levels(c.nz, m, P.hts ? P.hts[sl] : P.ht, P.zref);
+            int tz = threadIdx.x;
+            asm volatile("" : "+v"(tz));
+            if (tz == 0) m.K[1] = 0;
+            __syncthreads();
+            for (int k = tz; k < K; k += BLOCK) {
+                int np;
+                if (P.nparts_override) np = P.nparts_override[(int64_t)sl * MAX_LEVELS + k];
+                else {
+                    const double parts = ceil(__longlong_as_double((long long)P.maxlen_bits[(int64_t)sl * MAX_LEVELS + k]) / P.max_seg) + 1.0;
+                    np = (parts >= 1.0 && parts <= (double)MAX_NPARTS) ? (int)parts : -1;
+                }
+                if (np < 2 || np > MAX_NPARTS) {
+                    np = 2;
+                    atomicOr(P.flags + sl, 16);
+                    m.K[1] = 1;
+                }
+                m.np[k] = np;
+                m.step[k] = 1.0 / ((double)np - 1.0);
+                m.hs[k] = 0.5e-6 * m.step[k];
+                const int kzk = m.kz[k], last = c.nz - 1;
+                const int zb = max(window2_base(c.nz, kzk), 0);
+                LevelRec r;
+                r.xv = m.xv[k]; r.hs = m.hs[k]; r.step = m.step[k];
+                r.zmid = m.ax.ez[min(zb + 1, last)].x; r.r0 = m.ax.ez[zb].y; r.r1 = m.ax.ez[min(zb + 1, last)].y;
+                r.gk = m.ax.ez[kzk].x; r.rk = m.ax.ez[kzk].y;
+                r.npkz = np | (kzk << 17); r.pad[0] = r.pad[1] = r.pad[2] = 0;
+                m.lev[k] = r;
+                if (k == K - 1) { r.hs = 0.0; r.npkz = 2 | (kzk << 17); m.lev[K] = r; }
+            }
+            __syncthreads();
+            const int flags_in = P.flags[sl];
+            poison = (m.K[1] || (flags_in & (1 | 32))) ? qnan() : 0.0;
+            clamp_lo = !(flags_in & 4);
+            clamp_hi = !(flags_in & 8);
+        }
+        int tl = threadIdx.x;
+        asm volatile("" : "+v"(tl));
+        int64_t i; bool active;
+        if (P.origin_mode == 0) {
+            const int64_t ty = t / P.tiles_x, tx = t - ty * P.tiles_x;
+            const int64_t row = ty * TILE + (tl >> 4), col = tx * TILE + (tl & 15);
+            active = row < P.ny && col < P.nx;
+            i = row * P.nx + col;
+        } else {
+            i = t * BLOCK + tl;
+            active = i < P.n;
+        }
+        const double* w = P.ws + (lt * BLOCK + tl);
+        const int64_t ns = P.nslots;
+        const double scale_rec = w[(int64_t)WS_SCALE * ns];
+        const bool mine = !active || scale_rec != 0.0;     // light rays (and tile padding); generic rays: march_kernel<T2, true>
+        double acc_w[E], acc_h[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) { acc_w[e] = 0.0; acc_h[e] = 0.0; }
+        RayPoly q;
+        double xc[PX];
+#pragma unroll
+        for (int n = 0; n < PN; ++n) {
+            q.h[n] = w[(int64_t)(WS_POLY_H + n) * ns];
+            q.lat[n] = w[(int64_t)(WS_POLY_LAT + n) * ns];
+            q.lon[n] = w[(int64_t)(WS_POLY_LON + n) * ns];
+        }
+#pragma unroll
+        for (int n = 0; n < PX; ++n) xc[n] = w[(int64_t)(WS_XPOLY + n) * ns];
+        const double scale = scale_rec;
+        const unsigned long long live = __builtin_amdgcn_ballot_w64(active && mine);
+        auto finish = [&](const PendingSampleE<T2, E>& s, double wv) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                PendingSample<T2> one;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) one.v[j] = s.v[e][j];
+                one.ty = s.ty; one.tx = s.tx; one.tz = s.tz;
+                double vw, vh;
+                sample_finish_lerp(one, vw, vh);
+                acc_w[e] = fma(wv, vw, acc_w[e]); acc_h[e] = fma(wv, vh, acc_h[e]);
+            }
+        };
+        auto run = [&](auto nochk) {
+            constexpr bool NC = decltype(nochk)::value;
+            typedef __attribute__((address_space(3))) const LevelRec LdsRec;
+            int la = (int)(size_t)m.lev;
+            asm volatile("" : "+v"(la));
+            const LdsRec* rec = (const LdsRec*)(size_t)(unsigned)la;
+            int npkz = __builtin_amdgcn_readfirstlane(rec->npkz);
+            int np = npkz & 0x1ffff, kz = npkz >> 17;
+            double hs = rec->hs;
+            double u_k = w[(int64_t)WS_U0 * ns];
+            double u_last = w[(int64_t)WS_U1 * ns];
+            double du = u_last - u_k;
+            if (K > 0) {                                   // the ray's very first sample (march_kernel: issue_top with MODE 1)
+                PendingSampleE<T2, E> s;
+                const double us = fma(0.0 * rec->step, du, u_k);
+                double ph = poly5(q.h, us);
+                const double plat = poly5(q.lat, us), plon = poly5(q.lon, us);
+                if (clamp_lo) { asm volatile("" ::: "memory"); ph = fmax(ph, c.z_lo); }
+                int iz;
+                window2_cell(m.ax.ez, c.nz, ph, window2_base(c.nz, kz - ((m.lo[0] <= m.ax.ez[kz].x) ? 1 : 0)), c.nz >= 4, iz, s.tz);
+                gather_corners_e<T2, E, true, NC>(c, ev, m.ax, plat, plon, iz, s);
+                finish(s, hs * fabs(du));
+            }
+#pragma unroll 1
+            for (int k = 0; k < K; ++k) {
+                const int zbase = window2_base(c.nz, kz);
+                const bool more = k + 1 < K;
+                const double w_mid = (2.0 * hs) * fabs(du);
+                if (np > 2) {
+                    const double step = rec->step, gk = rec->gk, rk = rec->rk;
+#pragma unroll 1
+                    for (int j = 1; j < np - 1; ++j) {
+                        PendingSampleE<T2, E> s;
+                        const double us = fma((double)j * step, du, u_k);
+                        const double ph = poly5(q.h, us), plat = poly5(q.lat, us), plon = poly5(q.lon, us);
+                        int iz = kz;
+                        s.tz = (ph - gk) * rk;
+                        if (!(s.tz >= 0.0) || !(s.tz <= 1.0)) cell_exact(m.ax.ez, c.nz, ph, iz, s.tz);   // rare
+                        gather_corners_e<T2, E, true, NC>(c, ev, m.ax, plat, plon, iz, s);
+                        finish(s, w_mid);
+                    }
+                }
+                PendingSampleE<T2, E> top;
+                {
+                    const double us = u_k + du;
+                    double ph = poly5(q.h, us);
+                    const double plat = poly5(q.lat, us), plon = poly5(q.lon, us);
+                    if (clamp_hi && !more) { asm volatile("" ::: "memory"); ph = fmin(ph, c.z_hi); }
+                    const double d = ph - rec->zmid;
+                    int iz; bool ok;
+                    if (__builtin_expect((__builtin_amdgcn_ballot_w64(!(d >= 0.0)) & live) == 0ULL, 1)) {
+                        iz = zbase + 1;
+                        top.tz = d * rec->r1;
+                        ok = top.tz <= 1.0;
+                    } else {
+                        double ds = d;
+                        asm volatile("" : "+v"(ds));
+                        const bool up = ds >= 0.0;
+                        iz = zbase + (int)up;
+                        top.tz = fma(ds, up ? rec->r1 : rec->r0, up ? 0.0 : 1.0);
+                        ok = (top.tz >= 0.0) & (top.tz <= 1.0);
+                    }
+                    if (!(ok & (c.nz >= 4))) cell_exact(m.ax.ez, c.nz, ph, iz, top.tz);                  // rare
+                    gather_corners_e<T2, E, true, NC>(c, ev, m.ax, plat, plon, iz, top);
+                }
+                const double t2 = poly7(xc, rec[1].xv);
+                const double du1 = t2 - u_last, hs1 = rec[1].hs;
+                u_last = t2;
+                const double w_top = fma(hs1, fabs(du1), hs * fabs(du));
+                npkz = __builtin_amdgcn_readfirstlane(rec[1].npkz);
+                finish(top, w_top);
+                u_k += du; du = du1; hs = hs1;
+                np = npkz & 0x1ffff; kz = npkz >> 17;
+                ++rec;
+            }
+        };
+        // the wave-wide no-check proof of march_kernel (bounds of the cell search from the polynomial coefficients)
+        bool lane_safe = false;
+        if (REGULAR) {
+            double u0r = w[(int64_t)WS_U0 * ns], u1r = w[(int64_t)WS_U1 * ns];
+            if (!active) {
+#pragma unroll
+                for (int n = 0; n < PN; ++n) { q.lat[n] = 0.0; q.lon[n] = 0.0; }
+                q.lat[0] = 0.5; q.lon[0] = 0.5;
+#pragma unroll
+                for (int n = 0; n < PX; ++n) xc[n] = 0.0;
+                u0r = 0.0; u1r = 0.0;
+            }
+            auto inside = [&](const double* cf, int n) {
+                const double r = 1.006 * (fabs(cf[1]) + fabs(cf[2]) + fabs(cf[3]) + fabs(cf[4]) + fabs(cf[5]));
+                return (cf[0] - r >= 0.0) & (cf[0] + r < (double)(n - 1));
+            };
+            double xs = 0.0;
+#pragma unroll
+            for (int n = 0; n < PX; ++n) xs += fabs(xc[n]);
+            lane_safe = mine && (fabs(u0r) <= 1.001) && (fabs(u1r) <= 1.001) && (xs <= 1.001) && inside(q.lat, c.ny) && inside(q.lon, c.nx);
+        }
+        if (REGULAR && __all(lane_safe)) run(std::integral_constant<bool, true>{});
+        else run(std::integral_constant<bool, false>{});
+        if (active && scale_rec != 0.0) {
+            const int64_t o = (int64_t)sl * P.n + i;
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                const double aw = acc_w[e] * scale, ah = acc_h[e] * scale;
+                P.wet[e * estride + o] = aw + poison; P.hyd[e * estride + o] = ah + poison;
+            }
+        }
+    }
+}
+
+}  // namespace rdr

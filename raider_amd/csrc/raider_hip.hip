@@ -324,6 +324,7 @@ static hipError_t launch_lds(void (*kern)(KArgs...), dim3 g, dim3 b, size_t sm, 
 #include "orbit_kernels.h"
 #include "native_kernels.h"
 #include "proj_kernels.h"
+#include "epoch_kernels.h"
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -1898,11 +1899,19 @@ static int launch_march(rdr_ctx* c, const rdr_cube* q, RayParams P, int64_t tb, 
 // object (hipFuncGetAttributes) - what bench.py prints, instead of a profiler's metadata column.
 int rdr_ray_kernel_attributes(rdr_ctx* c, const rdr_cube* q, int which, int32_t* vgprs, int32_t* static_lds, int32_t* dynamic_lds,
                               int32_t* scratch, int32_t* max_threads) {
-    if (!c || !q || which < 0 || which > 3) return fail(c, RDR_ERR_INVALID, "rdr_ray_kernel_attributes: bad argument");
+    if (!c || !q || which < 0 || which > 5) return fail(c, RDR_ERR_INVALID, "rdr_ray_kernel_attributes: bad argument");
     const void* fn = nullptr;
     const bool lcc = q->proj.kind == 1;
-    const bool pr = which >= 2;                    // 2 / 3: the per-ray-height instantiations of pass 1 / pass 2
-    if ((which & 1) == 0) {
+    const bool pr = which == 2 || which == 3;      // 2 / 3: the per-ray-height instantiations of pass 1 / pass 2
+    if (which >= 4) {                              // 4 / 5: the stacked time-series march (march_epochs_kernel), E = 2 / 4
+        const auto v32 = make_view<float2>(q);
+        const bool small = v32.small && (q->dtype == RDR_F32 || make_view<double2>(q).small);
+        const int grid = !small ? 0 : (q->exact[0] && q->exact[1]) ? 1 : (!q->exact[0] && !q->exact[1] && q->uni[0] && q->uni[1]) ? 2 : 0;
+#define RDR_EPOCH_FN(T2, E) (grid == 1 ? (const void*)march_epochs_kernel<T2, E, 1> : grid == 2 ? (const void*)march_epochs_kernel<T2, E, 2> : (const void*)march_epochs_kernel<T2, E, 0>)
+        if (q->dtype == RDR_F32) fn = which == 4 ? RDR_EPOCH_FN(float2, 2) : RDR_EPOCH_FN(float2, 4);
+        else fn = which == 4 ? RDR_EPOCH_FN(double2, 2) : RDR_EPOCH_FN(double2, 4);
+#undef RDR_EPOCH_FN
+    } else if ((which & 1) == 0) {
         if (q->dtype == RDR_F32) fn = pr ? (lcc ? (const void*)crossings_kernel<float2, false, true, 1, true> : (const void*)crossings_kernel<float2, false, false, 1, true>)
                                          : (lcc ? (const void*)crossings_kernel<float2, false, true, 1> : (const void*)crossings_kernel<float2, false, false, 1>);
         else fn = pr ? (lcc ? (const void*)crossings_kernel<double2, false, true, 1, true> : (const void*)crossings_kernel<double2, false, false, 1, true>)
@@ -2360,6 +2369,242 @@ int rdr_raytrace_slices_to_cube(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r
     rc = raytrace_slices_impl(c, q, r, hts, nslices, los_per_slice, zref, max_seg, nullptr, nullptr, K_out, nparts_out, ld, flags_out, planar);
     if (rc) return rc;
     return rdr_cube_create(c, hy.data(), r->ny, hx.data(), r->nx, hts, nslices, planar[0], planar[1], RDR_F64, r->nx, 1, r->ny * r->nx, RDR_DEVICE, out);
+}
+
+// ---- time series: E weather epochs through one ray geometry (rdr_raytrace_slices_epochs) ------------------------------------------
+// Every epoch must be the same grid: shape, dtype, bitwise-equal axes and the same projection - then one pass-1 record set (ray
+// polynomials, crossings, the slice partition) serves them all.  Returns RDR_OK or RDR_ERR_INVALID naming the first epoch that differs.
+static int epochs_check(rdr_ctx* c, const char* who, const rdr_cube* const* qs, int32_t ncubes) {
+    const std::string w(who);
+    if (!qs) return fail(c, RDR_ERR_INVALID, w + ": cubes is NULL");
+    if (ncubes <= 0) return fail(c, RDR_ERR_INVALID, w + ": ncubes must be >= 1");
+    for (int32_t e = 0; e < ncubes; ++e)
+        if (!qs[e]) return fail(c, RDR_ERR_INVALID, w + ": cubes[" + std::to_string(e) + "] is NULL");
+    const rdr_cube* a = qs[0];
+    for (int32_t e = 1; e < ncubes; ++e) {
+        const rdr_cube* b = qs[e];
+        const std::string tag = w + ": epoch " + std::to_string(e) + " ";
+        if (b->ny != a->ny || b->nx != a->nx || b->nz != a->nz)
+            return fail(c, RDR_ERR_INVALID, tag + "has shape (" + std::to_string(b->ny) + ", " + std::to_string(b->nx) + ", " + std::to_string(b->nz) +
+                                                 "), epoch 0 (" + std::to_string(a->ny) + ", " + std::to_string(a->nx) + ", " + std::to_string(a->nz) + ")");
+        if (b->dtype != a->dtype) return fail(c, RDR_ERR_INVALID, tag + "has another dtype than epoch 0 (float32 / float64 cubes do not mix)");
+        const char* names[3] = {"y", "x", "z"};
+        const std::vector<double>* ax[3] = {&a->ys, &a->xs, &a->zs};
+        const std::vector<double>* bx[3] = {&b->ys, &b->xs, &b->zs};
+        for (int k = 0; k < 3; ++k)
+            if (std::memcmp(ax[k]->data(), bx[k]->data(), ax[k]->size() * sizeof(double)) != 0)
+                return fail(c, RDR_ERR_INVALID, tag + "has another " + names[k] + " axis than epoch 0 (the axes must be bitwise equal)");
+        const LccParams &p = a->proj, &r = b->proj;
+        if (p.kind != r.kind || std::memcmp(&p.n, &r.n, sizeof(double)) || std::memcmp(&p.aF, &r.aF, sizeof(double)) || std::memcmp(&p.rho0, &r.rho0, sizeof(double)) ||
+            std::memcmp(&p.lam0, &r.lam0, sizeof(double)) || std::memcmp(&p.x0, &r.x0, sizeof(double)) || std::memcmp(&p.y0, &r.y0, sizeof(double)) ||
+            std::memcmp(&p.e, &r.e, sizeof(double)))
+            return fail(c, RDR_ERR_INVALID, tag + "has another projection (kind " + std::to_string(r.kind) + ") than epoch 0 (kind " + std::to_string(p.kind) + " or other parameters)");
+    }
+    return RDR_OK;
+}
+
+// epochs per stacked launch: 4, or RAIDER_HIP_EPOCHS_MAX = 1 / 2 / 4 (tools/bench_epochs.py compares them; 1 = the one-epoch march per epoch)
+static int epochs_max() {
+    const char* e = std::getenv("RAIDER_HIP_EPOCHS_MAX");
+    const int v = e ? std::atoi(e) : EPOCHS_MAX;
+    return v >= 4 ? 4 : v >= 2 ? 2 : 1;
+}
+
+template <typename T2, int E>
+static hipError_t launch_stacked(rdr_ctx* c, const rdr_cube* const* qs, int grid, const RayParams& P, int64_t estride, dim3 G, dim3 B, size_t sm) {
+    EpochCubes<T2, E> ev;
+    for (int j = 0; j < E; ++j) ev.v[j] = (const T2*)qs[j]->d_vals;
+    const CubeView<T2> V = make_view<T2>(qs[0]);
+    return grid == 1 ? launch_lds(march_epochs_kernel<T2, E, 1>, G, B, sm, c->stream, V, ev, P, estride)
+         : grid == 2 ? launch_lds(march_epochs_kernel<T2, E, 2>, G, B, sm, c->stream, V, ev, P, estride)
+                     : launch_lds(march_epochs_kernel<T2, E, 0>, G, B, sm, c->stream, V, ev, P, estride);
+}
+
+// pass 2 of D epochs over tiles [tb, tb+tc) on the records of ONE pass 1: groups of 4 / 2 epochs take the stacked marcher (plus the
+// generic kernel once per epoch, which returns at once when pass 1 found no generic ray); a last single epoch takes launch_march.
+// P.wet / P.hyd: epoch 0's [nslices][n] block, epoch e's is estride doubles further.
+static int launch_march_epochs(rdr_ctx* c, const rdr_cube* const* qs, int D, RayParams P, int64_t tb, int64_t tc, int64_t estride) {
+    const rdr_cube* q = qs[0];
+    const int emax = epochs_max();
+    const auto v32 = make_view<float2>(q);
+    const bool small = v32.small && (q->dtype == RDR_F32 || make_view<double2>(q).small);
+    const int grid = !small ? 0 : (q->exact[0] && q->exact[1]) ? 1 : (!q->exact[0] && !q->exact[1] && q->uni[0] && q->uni[1]) ? 2 : 0;
+    const int g = ray_grid(c, tc, 8);
+    const size_t sm = ray_smem(q);
+    const dim3 G(g), B(BLOCK);
+    for (int e = 0; e < D;) {
+        const int left = D - e;
+        const int ge = (left >= 4 && emax >= 4) ? 4 : (left >= 2 && emax >= 2) ? 2 : 1;
+        RayParams Pe = P;
+        Pe.wet = P.wet + (int64_t)e * estride; Pe.hyd = P.hyd + (int64_t)e * estride;
+        if (ge == 1) {
+            const int rc = launch_march(c, qs[e], Pe, tb, tc); if (rc) return rc;
+            ++e;
+            continue;
+        }
+        Pe.tile_begin = tb; Pe.tile_count = tc; Pe.nslots = tc * BLOCK;
+        HIPCHECK(c, hipMemsetAsync(c->d_tilectr + 16, 0, 8 * sizeof(int), c->stream));
+        Pe.tile_ctr = c->d_tilectr + 16;
+        hipError_t err = hipSuccess;
+        {
+            KTimer t(c, 1);
+            if (q->dtype == RDR_F32) err = ge == 4 ? launch_stacked<float2, 4>(c, qs + e, grid, Pe, estride, G, B, sm) : launch_stacked<float2, 2>(c, qs + e, grid, Pe, estride, G, B, sm);
+            else err = ge == 4 ? launch_stacked<double2, 4>(c, qs + e, grid, Pe, estride, G, B, sm) : launch_stacked<double2, 2>(c, qs + e, grid, Pe, estride, G, B, sm);
+        }
+        if (err != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("march_epochs_kernel launch: ") + hipGetErrorString(err));
+        for (int j = 0; j < ge; ++j) {                  // generic rays, epoch by epoch, on the same records and side buffer
+            RayParams Pj = Pe;
+            Pj.wet = Pe.wet + (int64_t)j * estride; Pj.hyd = Pe.hyd + (int64_t)j * estride;
+            HIPCHECK(c, hipMemsetAsync(c->d_tilectr + 24, 0, 8 * sizeof(int), c->stream));
+            Pj.tile_ctr = c->d_tilectr + 24;
+            const rdr_cube* qj = qs[e + j];
+            if (q->dtype == RDR_F32) err = launch_lds(march_kernel<float2, true>, G, B, sm, c->stream, make_view<float2>(qj), Pj, qj->proj);
+            else err = launch_lds(march_kernel<double2, true>, G, B, sm, c->stream, make_view<double2>(qj), Pj, qj->proj);
+            if (err != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("march_kernel launch: ") + hipGetErrorString(err));
+        }
+        e += ge;
+    }
+    return RDR_OK;
+}
+
+// keep == NULL: the public entry; keep != NULL: the delays stay in the context's scratch ([ncubes][nslices][n] planar, keep[0] = wet,
+// keep[1] = hydro) for rdr_raytrace_slices_epochs_to_cubes.
+static int raytrace_epochs_impl(rdr_ctx* c, const char* who, const rdr_cube* const* qs, int32_t D, const rdr_rays* r, const double* hts, int32_t nslices,
+                                int32_t los_per_slice, double zref, double max_seg, double* wet, double* hydro, int32_t* K_out, int32_t* nparts_out,
+                                int32_t ld, int32_t* flags_out, double** keep) {
+    const std::string w(who);
+    if (!c) return fail(nullptr, RDR_ERR_INVALID, w + ": NULL context");
+    int rc = epochs_check(c, who, qs, D); if (rc) return rc;
+    if (!r || !hts || (!keep && (!wet || !hydro))) return fail(c, RDR_ERR_INVALID, w + ": NULL argument");
+    const rdr_cube* q = qs[0];
+    for (int32_t e = 0; e < D; ++e) note_use(c, qs[e]);
+    if (nslices < 1 || nslices > MAX_SLICES) return fail(c, RDR_ERR_INVALID, w + ": 1..512 slices per call");
+    if (!(max_seg > 0)) return fail(c, RDR_ERR_INVALID, w + ": MAX_SEGMENT_LENGTH must be positive");
+    if (nparts_out && ld < (int32_t)q->nz - 1) return fail(c, RDR_ERR_INVALID, w + ": nparts_out needs a row length of at least nz-1");
+    rc = check_rays(c, r); if (rc) return rc;
+    if (r->n == 0) return fail(c, RDR_ERR_INVALID, w + ": empty ray batch");
+    if (r->origin_mode == RDR_ORIGIN_XYZ && nslices > 1) return fail(c, RDR_ERR_INVALID, w + ": XYZ origins belong to one height; use GRID or LLH origins");
+    if (r->hts) return fail(c, RDR_ERR_INVALID, w + ": per-ray heights (rays->hts) are not supported in a series");
+    std::vector<int> Ks(nslices);
+    int Kmax = 0;
+    for (int s = 0; s < nslices; ++s) {
+        std::vector<double> lo, hi; std::vector<int> kz;
+        Ks[s] = levels_host(q->zs, hts[s], zref, lo, hi, kz);
+        Kmax = std::max(Kmax, Ks[s]);
+        if (K_out) K_out[s] = Ks[s];
+    }
+    HIPCHECK(c, hipSetDevice(c->device));
+    RayParams P;
+    rc = stage_rays(c, r, P, los_per_slice ? nslices : 1); if (rc) return rc;
+    const int64_t per = P.ntiles;
+    const size_t nout = (size_t)r->n * nslices, total = nout * (size_t)D;
+    void *dw, *dh, *def;
+    const int out_loc = keep ? RDR_DEVICE : r->loc;
+    rc = stage_out(c, SLOT_OUT0, wet, total * 8, keep ? RDR_HOST : r->loc, &dw); if (rc) return rc;
+    rc = stage_out(c, SLOT_OUT1, hydro, total * 8, keep ? RDR_HOST : r->loc, &dh); if (rc) return rc;
+    rc = ensure(c, SLOT_OUT2, (size_t)D * nslices * sizeof(int), &def); if (rc) return rc;   // per-epoch RDR_FLAG_NAN_OUTPUT
+    if (keep) { keep[0] = (double*)dw; keep[1] = (double*)dh; }
+    const void* dht;
+    rc = stage_in(c, SLOT_AUX, hts, (size_t)nslices * 8, RDR_HOST, &dht); if (rc) return rc;
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    P.nslices = nslices; P.tiles_per_slice = per; P.hts = (const double*)dht; P.los_stride = los_per_slice ? r->n : 0;
+    P.ntiles = per * nslices;
+    P.ht = hts[0]; P.zref = zref; P.max_seg = max_seg;
+    P.wet = (double*)dw; P.hyd = (double*)dh;
+    HIPCHECK(c, hipMemsetAsync(c->d_maxlen, 0, (size_t)nslices * MAX_LEVELS * sizeof(unsigned long long), c->stream));
+    HIPCHECK(c, hipMemsetAsync(c->d_flags, 0, (size_t)nslices * sizeof(int), c->stream));
+    HIPCHECK(c, hipMemsetAsync(def, 0, (size_t)D * nslices * sizeof(int), c->stream));
+    c->wsig.valid = false;
+    const int64_t fit = ws_chunk_tiles(c, std::max(Kmax, 1));
+    if (per <= fit) {
+        // groups of whole slices whose records fit the workspace: ONE pass 1 per group, then every epoch's pass 2 on its records
+        const int64_t g = std::max<int64_t>(1, fit / per);
+        for (int64_t s0 = 0; s0 < nslices; s0 += g) {
+            const int64_t ns = std::min<int64_t>(g, nslices - s0);
+            RayParams Pg = P;
+            rc = ws_reserve(c, ns * per, std::max(Kmax, 1), Pg); if (rc) return rc;
+            rc = launch_crossings(c, q, Pg, s0 * per, ns * per); if (rc) return rc;
+            rc = launch_march_epochs(c, qs, D, Pg, s0 * per, ns * per, (int64_t)nout); if (rc) return rc;
+        }
+    } else {
+        // a single slice exceeds the workspace: per slice, pass 1 (reduction only), then chunked (store, every epoch's march) pairs
+        for (int s = 0; s < nslices; ++s) {
+            RayParams Ps = P;
+            Ps.ws = nullptr;
+            rc = launch_crossings(c, q, Ps, (int64_t)s * per, per); if (rc) return rc;
+            const int64_t chunk = std::min<int64_t>(per, fit);
+            RayParams Pw = P;
+            rc = ws_reserve(c, chunk, std::max(Kmax, 1), Pw); if (rc) return rc;
+            for (int64_t tb = 0; tb < per; tb += chunk) {
+                const int64_t tc = std::min<int64_t>(chunk, per - tb);
+                RayParams Pc = Pw;
+                Pc.maxlen_bits = nullptr;
+                rc = launch_crossings(c, q, Pc, (int64_t)s * per + tb, tc); if (rc) return rc;
+                Pc.maxlen_bits = P.maxlen_bits;
+                rc = launch_march_epochs(c, qs, D, Pc, (int64_t)s * per + tb, tc, (int64_t)nout); if (rc) return rc;
+            }
+        }
+    }
+    // a NaN anywhere in an epoch's slice -> RDR_FLAG_NAN_OUTPUT of that epoch and slice
+    hipLaunchKernelGGL(nan_scan_kernel, dim3(grid_for((int64_t)total, 256, c->num_cus * 8)), dim3(256), 0, c->stream, (const double*)dw,
+                       (const double*)dh, (int64_t)total, (int64_t)r->n, (int*)def);
+    HIPCHECK(c, hipGetLastError());
+    rc = finish_out(c, wet, dw, total * 8, out_loc); if (rc) return rc;
+    rc = finish_out(c, hydro, dh, total * 8, out_loc); if (rc) return rc;
+    const bool need_sync = r->loc == RDR_HOST || nparts_out || flags_out;
+    if (need_sync) {
+        std::vector<double> ml((size_t)nslices * MAX_LEVELS);
+        std::vector<int> f(nslices), ef((size_t)D * nslices);
+        int nslow = 0;
+        HIPCHECK(c, hipMemcpyAsync(ml.data(), c->d_maxlen, ml.size() * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(c, hipMemcpyAsync(f.data(), c->d_flags, (size_t)nslices * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(c, hipMemcpyAsync(ef.data(), def, ef.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(c, hipMemcpyAsync(&nslow, c->d_nslow, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(c, hipStreamSynchronize(c->stream));
+        c->last_nslow = nslow;
+        for (int s = 0; s < nslices; ++s) {
+            if (nparts_out) rdr_nparts(ml.data() + (size_t)s * MAX_LEVELS, Ks[s], max_seg, nparts_out + (size_t)s * ld);
+            if (flags_out)
+                for (int32_t e = 0; e < D; ++e) flags_out[(size_t)e * nslices + s] = f[s] | ef[(size_t)e * nslices + s];
+        }
+    }
+    return RDR_OK;
+}
+
+int rdr_raytrace_slices_epochs(rdr_ctx* c, const rdr_cube* const* cubes, int32_t ncubes, const rdr_rays* r, const double* hts, int32_t nslices,
+                               int32_t los_per_slice, double zref, double max_seg, double* wet, double* hydro, int32_t* K_out, int32_t* nparts_out,
+                               int32_t ld, int32_t* flags_out) {
+    return raytrace_epochs_impl(c, "rdr_raytrace_slices_epochs", cubes, ncubes, r, hts, nslices, los_per_slice, zref, max_seg, wet, hydro, K_out,
+                                nparts_out, ld, flags_out, nullptr);
+}
+
+int rdr_raytrace_slices_epochs_to_cubes(rdr_ctx* c, const rdr_cube* const* cubes, int32_t ncubes, const rdr_rays* r, const double* hts,
+                                        int32_t nslices, int32_t los_per_slice, double zref, double max_seg, int32_t* K_out, int32_t* nparts_out,
+                                        int32_t ld, int32_t* flags_out, rdr_cube** out) {
+    static const char* who = "rdr_raytrace_slices_epochs_to_cubes";
+    if (!c) return fail(nullptr, RDR_ERR_INVALID, std::string(who) + ": NULL context");
+    int rc = epochs_check(c, who, cubes, ncubes); if (rc) return rc;
+    if (!r || !hts || !out) return fail(c, RDR_ERR_INVALID, std::string(who) + ": NULL argument");
+    if (r->origin_mode != RDR_ORIGIN_GRID) return fail(c, RDR_ERR_INVALID, std::string(who) + ": the delay cubes are a GRID batch (xpts, ypts) x heights");
+    if (r->nx < 2 || r->ny < 2 || nslices < 2) return fail(c, RDR_ERR_INVALID, std::string(who) + ": the delay cubes need two nodes per axis");
+    HIPCHECK(c, hipSetDevice(c->device));
+    std::vector<double> hx, hy;
+    rc = axis_to_host(c, r->xpts, r->nx, r->loc, hx); if (rc) return rc;
+    rc = axis_to_host(c, r->ypts, r->ny, r->loc, hy); if (rc) return rc;
+    double* planar[2] = {nullptr, nullptr};
+    rc = raytrace_epochs_impl(c, who, cubes, ncubes, r, hts, nslices, los_per_slice, zref, max_seg, nullptr, nullptr, K_out, nparts_out, ld, flags_out, planar);
+    if (rc) return rc;
+    const size_t nout = (size_t)r->n * nslices;
+    for (int32_t e = 0; e < ncubes; ++e) out[e] = nullptr;
+    for (int32_t e = 0; e < ncubes; ++e) {
+        rc = rdr_cube_create(c, hy.data(), r->ny, hx.data(), r->nx, hts, nslices, planar[0] + e * nout, planar[1] + e * nout, RDR_F64, r->nx, 1,
+                             r->ny * r->nx, RDR_DEVICE, &out[e]);
+        if (rc) {
+            for (int32_t j = 0; j < e; ++j) { rdr_cube_destroy(out[j]); out[j] = nullptr; }
+            return rc;
+        }
+    }
+    return RDR_OK;
 }
 
 int rdr_top_of_atmosphere(rdr_ctx* c, const double* xyz, const double* los, int64_t n, double h, const double* factor, double* pos, int loc) {

@@ -320,13 +320,8 @@ def _cube_of(interpolators):
 # ------------------------------------------------------------------------------------------------
 # public API
 # ------------------------------------------------------------------------------------------------
-def tropo_delay(datetime, weather_model_file, aoi, los, height_levels=None, out_proj=4326, zref=None):
-    """delay.py:35-130: ZTD, projected STD, or ray-traced STD on an AOI.
-
-    weather_model_file: path to a processed weather-model NetCDF, an xarray.Dataset, or a mapping with
-    x, y, z, wet, hydro, wet_total, hydro_total (file order (z,y,x)) and optionally a 'proj' entry.
-    Returns (Dataset-like, None) for cube AOIs, else (wetDelay, hydroDelay) at the query points."""
-    crs = out_proj
+def _model_prelude(weather_model_file, aoi, height_levels, zref):
+    """delay.py:66-85: the model's fields, its CRS, the output heights and the integration top of one tropo_delay call."""
     var, get = _load_fields(weather_model_file)
     # CRS of the weather model (delay.py:66-73)
     wm_proj = None
@@ -350,6 +345,17 @@ def tropo_delay(datetime, weather_model_file, aoi, los, height_levels=None, out_
     if zref > toa:
         zref = toa
         logger.warning(f'Requested integration height (zref) is higher than top of weather model. Forcing to top ({toa}).')
+    return var, wm_proj, height_levels, zref
+
+
+def tropo_delay(datetime, weather_model_file, aoi, los, height_levels=None, out_proj=4326, zref=None):
+    """delay.py:35-130: ZTD, projected STD, or ray-traced STD on an AOI.
+
+    weather_model_file: path to a processed weather-model NetCDF, an xarray.Dataset, or a mapping with
+    x, y, z, wet, hydro, wet_total, hydro_total (file order (z,y,x)) and optionally a 'proj' entry.
+    Returns (Dataset-like, None) for cube AOIs, else (wetDelay, hydroDelay) at the query points."""
+    crs = out_proj
+    var, wm_proj, height_levels, zref = _model_prelude(weather_model_file, aoi, height_levels, zref)
 
     if _is_cube_aoi(aoi):
         ds = _get_delays_on_cube(datetime, weather_model_file, wm_proj, aoi, height_levels, los, crs, zref, _loaded=var)
@@ -388,6 +394,193 @@ def tropo_delay(datetime, weather_model_file, aoi, los, height_levels=None, out_
 
 
 getDelays = tropo_delay   # legacy name used by BASELINE.json's north_star
+
+
+# ------------------------------------------------------------------------------------------------
+# time series: one AOI and one LOS over a list of dates (cli/raider.py:159-400 loops calcDelays over date_start..date_end)
+# ------------------------------------------------------------------------------------------------
+class SeriesResult(list):
+    """[tropo_delay(t, f, ...) for t, f in zip(datetimes, files)], plus `routes`: per date 'stacked' (traced with the other
+    stacked dates in one library call) or 'per-date' (a plain tropo_delay call)."""
+    routes = ()
+
+
+def series_route(aoi, los, out_proj):
+    """The stacked route a series on this AOI / LOS could take: 'cube' (a ray-traced LOS on a lon/lat output grid - the batched
+    branch of _build_cube_ray), 'points' (a ray-traced LOS through _point_branch_on_device), or None (zenith / projected lines of
+    sight and everything else: one tropo_delay per date)."""
+    if los.is_Zenith() or los.is_Projected() or not hasattr(los, 'ray_batch_slices') or not _is_4326(out_proj):
+        return None
+    return 'cube' if _is_cube_aoi(aoi) else 'points'
+
+
+def epochs_compatible(a, b):
+    """None when two epoch cubes can share one ray geometry (rdr_raytrace_slices_epochs: same shape, dtype, bitwise-equal axes and
+    projection), else what differs.  a / b: anything with .shape, .dtype, .grid and .projection (engine.Cube)."""
+    if tuple(a.shape) != tuple(b.shape):
+        return 'shape'
+    if np.dtype(a.dtype) != np.dtype(b.dtype):
+        return 'dtype'
+    for name, ga, gb in zip('yxz', a.grid, b.grid):
+        if np.asarray(ga, dtype=np.float64).tobytes() != np.asarray(gb, dtype=np.float64).tobytes():
+            return f'{name} axis'
+    if a.projection != b.projection:
+        return 'projection'
+    return None
+
+
+def _series_plan(datetime, weather_model_file, aoi, los, height_levels, out_proj, zref, route):
+    """What tropo_delay(datetime, weather_model_file, ...) would trace on the stacked route, or None when that date takes the
+    per-date route.  Runs the call's prelude (file, CRS, heights, zref - and their log lines) in date order."""
+    var, wm_proj, height_levels, zref = _model_prelude(weather_model_file, aoi, height_levels, zref)
+    src = var if not isinstance(weather_model_file, (str, os.PathLike)) else weather_model_file
+    _ensure_output_grid(aoi, src, out_proj)
+    xpts, ypts = np.asarray(aoi.xpts, dtype=np.float64), np.asarray(aoi.ypts, dtype=np.float64)
+    ifWet, ifHydro = getInterpolators(src, kind='pointwise')
+    cube, fields = _cube_of([ifWet, ifHydro])
+    if list(fields) != [0, 1]:
+        return None
+    cube, projected = _with_model_crs(cube, wm_proj)
+    if not (projected or _is_4326(wm_proj)):
+        return None                                                    # (tropo_delay raises NotImplementedError itself)
+    if route == 'cube':
+        zpts = np.array(height_levels)
+        if zpts.size == 0:
+            return None
+    else:
+        zpts = np.array(height_levels, dtype=np.float64)
+        if zpts.ndim != 1 or min(xpts.size, ypts.size, zpts.size) < 2 or zpts.size > 512 or xpts.size + ypts.size + zpts.size > 100000:
+            return None
+        dz = np.diff(zpts)
+        if not (np.all(dz > 0) or np.all(dz < 0)):
+            return None
+    return dict(cube=cube, zpts=zpts, zref=zref, xpts=xpts, ypts=ypts, axes=(aoi.xpts, aoi.ypts), src=weather_model_file)
+
+
+def _stacked_cube(plans, datetimes, los, crs):
+    """The batched branch of _build_cube_ray + _get_delays_on_cube for every planned date, pass 1 shared: [(Dataset, None)]."""
+    from .engine import raytrace_slices_epochs
+    p0 = plans[0]
+    xpts, ypts, zpts, zref = p0['xpts'], p0['ypts'], p0['zpts'], p0['zref']
+    cubes = [p['cube'] for p in plans]
+    D = len(cubes)
+    outs = [[np.empty((zpts.size, ypts.size, xpts.size)) for _ in range(2)] for _ in range(D)]
+    any_nan = [False] * D
+    n_per = max(1, xpts.size * ypts.size)
+    # _build_cube_ray's slice budget with D x 16 B of delays per ray and slice (next to the 48 B of look vectors and targets)
+    budget = int(os.environ.get('RAIDER_HIP_SLICE_BUDGET_BYTES', 8 << 30))
+    chunk = int(min(512, max(1, budget // (n_per * (48 + 16 * D)))))
+    s0 = 0
+    while s0 < zpts.size:
+        zz = np.ascontiguousarray(zpts[s0:s0 + chunk], dtype=np.float64)
+        logger.info(f'Processing slices {s0 + 1}-{s0 + zz.size} / {len(zpts)} of {D} dates')
+        try:
+            rays = los.ray_batch_slices(xpts, ypts, zz)
+            dw, dh, K, _nparts, flags, nan_out = raytrace_slices_epochs(cubes, rays, zz, zref, 1000.0, want_nan=True)
+            if rays._torch_device is not None:
+                dw, dh = dw.cpu().numpy(), dh.cpu().numpy()
+        except (MemoryError, RuntimeError) as exc:
+            if chunk == 1 or not (isinstance(exc, MemoryError) or type(exc).__name__ == 'OutOfMemoryError'):
+                raise
+            chunk = max(1, chunk // 2)
+            logger.info(f'slice batch did not fit the device ({exc}); continuing with {chunk} slices per call')
+            continue
+        _raise_slice_failures(K, flags[0], zz, zpts[-1])
+        for e in range(D):
+            outs[e][0][s0:s0 + zz.size] = dw[e]
+            outs[e][1][s0:s0 + zz.size] = dh[e]
+            any_nan[e] = any_nan[e] or bool(nan_out[e].any())
+        s0 += zz.size
+    res = []
+    for e, p in enumerate(plans):
+        if any_nan[e]:
+            logger.critical('There are missing delay values. Check your inputs.')
+        ds = writeResultsToXarray(datetimes[e], *p['axes'], zpts, crs, outs[e][0], outs[e][1], p['src'], 'slant - raytracing')
+        res.append((ds, None))
+    return res
+
+
+def _stacked_points(plans, los, aoi, out_proj):
+    """_point_branch_on_device for every planned date: the intermediate cubes of all dates from one series call, then the gather
+    per date: [(wetDelay, hydroDelay)], or None when the batch does not fit (the dates then go one by one)."""
+    from .engine import raytrace_slices_epochs_to_cubes
+    p0 = plans[0]
+    xpts, ypts, zpts, zref = p0['xpts'], p0['ypts'], p0['zpts'], p0['zref']
+    D = len(plans)
+    if xpts.size * ypts.size * zpts.size * (64 + 16 * D) > int(os.environ.get('RAIDER_HIP_SLICE_BUDGET_BYTES', 8 << 30)):
+        return None
+    lats, lons = aoi.readLL()
+    hgts = aoi.readZ()
+    pts = (lats, lons, hgts) if _is_4326(out_proj) else (transformPoints(lats, lons, hgts, 4326, out_proj),)
+    from ._lib import DeviceOutOfMemory
+    cubes = [p['cube'] for p in plans]
+    try:
+        rays = los.ray_batch_slices(xpts, ypts, zpts)
+        dcubes, K, _nparts, flags = raytrace_slices_epochs_to_cubes(cubes, rays, zpts, zref, 1000.0)
+    except (MemoryError, RuntimeError) as exc:
+        if not (isinstance(exc, DeviceOutOfMemory) or type(exc).__name__ == 'OutOfMemoryError'):
+            raise
+        logger.info(f'the series did not fit the device in one piece ({exc}); continuing date by date')
+        return None
+    _raise_slice_failures(K, flags[0], zpts, zpts[-1])
+    res = []
+    for dc in dcubes:
+        wet, hyd = dc.interp_project(*pts)
+        if dc.has_nan():
+            logger.critical('There are missing delay values. Check your inputs.')
+        res.append((wet, hyd))
+    return res
+
+
+def tropo_delay_series(datetimes, weather_model_files, aoi, los, height_levels=None, out_proj=4326, zref=None):
+    """tropo_delay over a list of dates on ONE AOI and ONE line of sight - the date loop of cli/raider.py:159-400.  Returns a
+    SeriesResult equal, element for element, to [tropo_delay(t, f, aoi, los, height_levels, out_proj, zref) for t, f in zip(...)]
+    (values, Dataset attributes, NaN log lines; the first exception in date order is raised).
+
+    A ray-traced LOS on a lon/lat output grid (cube AOI) or through the station branch (points AOI) traces every date whose model
+    grid matches the first such date's (shape, dtype, axes, CRS) in one library call: pass 1 (ray polynomials, crossings, the slice
+    partition) once, pass 2 for up to four dates together (rdr_raytrace_slices_epochs).  Everything else - zenith and projected lines
+    of sight, the host fallbacks, dates on another grid, a single date - is one tropo_delay per date."""
+    datetimes = list(datetimes)
+    files = list(weather_model_files)
+    if len(datetimes) != len(files):
+        raise ValueError(f'{len(datetimes)} dates but {len(files)} weather model files')
+    route = series_route(aoi, los, out_proj) if len(files) > 1 else None
+    stacked = {}
+    if route is not None:
+        plans = {}
+        for i, (t, f) in enumerate(zip(datetimes, files)):
+            try:
+                p = _series_plan(t, f, aoi, los, height_levels, out_proj, zref, route)
+            except Exception:
+                break                                                  # this date raises in its own tropo_delay call, in date order
+            if p is None:
+                continue
+            first = next(iter(plans.values()), None)
+            if first is not None and (epochs_compatible(first['cube'], p['cube']) is not None or not np.array_equal(first['zpts'], p['zpts']) or
+                                      first['zref'] != p['zref']):
+                continue
+            plans[i] = p
+        if len(plans) > 1:
+            idx = sorted(plans)
+            try:
+                if route == 'cube':
+                    out = _stacked_cube([plans[i] for i in idx], [datetimes[i] for i in idx], los, out_proj)
+                else:
+                    out = _stacked_points([plans[i] for i in idx], los, aoi, out_proj)
+            except Exception:
+                out = None                                             # (the per-date calls below raise it again, in date order)
+            if out is not None:
+                stacked = dict(zip(idx, out))
+    res = SeriesResult()
+    routes = []
+    for i, (t, f) in enumerate(zip(datetimes, files)):
+        if i in stacked:
+            res.append(stacked[i]); routes.append('stacked')
+        else:
+            res.append(tropo_delay(t, f, aoi, los, height_levels, out_proj, zref)); routes.append('per-date')
+    res.routes = routes
+    return res
 
 
 class _Result(list):

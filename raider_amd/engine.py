@@ -501,6 +501,77 @@ class Cube:
             pass
 
 
+def epoch_groups(D, emax=4):
+    """How rdr_raytrace_slices_epochs splits D epochs into stacked launches (RAIDER_HIP_EPOCHS_MAX = emax: 1, 2 or 4): groups of
+    emax, then of 2, then a last single epoch that takes the one-epoch march."""
+    emax = 4 if emax >= 4 else (2 if emax >= 2 else 1)
+    out, left = [], int(D)
+    while left > 0:
+        g = 4 if (left >= 4 and emax >= 4) else (2 if (left >= 2 and emax >= 2) else 1)
+        out.append(g); left -= g
+    return out
+
+
+def _epoch_args(cubes, rays, hts):
+    """(cubes, ctx, C array of handles, hts, S) of a time-series call; the cubes' compatibility is checked by the library."""
+    cubes = list(cubes)
+    if not cubes:
+        raise ValueError('a series needs at least one epoch cube')
+    ctx = cubes[0].ctx
+    rays.adopt_stream(ctx)
+    if rays.ht_min is not None:
+        raise ValueError('per-ray heights (rays.hts) are not supported in a series')
+    hts = f64(np.atleast_1d(hts)).ravel()
+    S = hts.size
+    if rays.slices not in (0, S):
+        raise ValueError(f'the ray batch carries look vectors for {rays.slices} slices, {S} heights were given')
+    return cubes, ctx, (C.c_void_p * len(cubes))(*[c.handle for c in cubes]), hts, S
+
+
+def raytrace_slices_epochs(cubes, rays, hts, zref, max_seg=1000.0, out=None, want_partition=True, want_nan=False):
+    """Cube.raytrace_slices of ONE ray batch through D weather epochs `cubes` (same shape, dtype, axes and projection) in one
+    call: pass 1 once, pass 2 for up to four epochs together.  Epoch e's delays are bit for bit cubes[e].raytrace_slices(...)'s.
+    Returns (wet[D,S,...], hydro[D,S,...], K[S], nparts[S, nz-1], flags[D,S]) - K and nparts are shared by every epoch, the flags'
+    partition bits too; the last three are None when want_partition is False (fully asynchronous for device arrays).
+    want_nan=True: a sixth element, bool[D,S] = np.isnan(result[e, s]).any() as scanned on the device."""
+    cubes, ctx, handles, hts, S = _epoch_args(cubes, rays, hts)
+    D = len(cubes)
+    if out is not None:
+        wet, hyd = out
+    elif rays._torch_device is not None:
+        import torch
+        wet = torch.empty((D, S) + tuple(rays.shape), dtype=torch.float64, device=rays._torch_device)
+        hyd = torch.empty_like(wet)
+    else:
+        wet = _pinned.empty((D, S) + tuple(rays.shape)); hyd = _pinned.empty((D, S) + tuple(rays.shape))
+    rays.check_outputs(wet, hyd, slices=S * D)
+    ld = cubes[0].shape[2] - 1
+    if want_partition:
+        K = np.zeros(S, dtype=np.int32); nparts = np.zeros((S, ld), dtype=np.int32); flags = np.zeros((D, S), dtype=np.int32)
+        check(ctx.lib.rdr_raytrace_slices_epochs(ctx.handle, handles, D, C.byref(rays.struct), ptr(hts), S, int(rays.slices > 0), float(zref),
+                                                 float(max_seg), ptr(wet), ptr(hyd), ptr(K), ptr(nparts), ld, ptr(flags)), ctx.handle)
+        nan_out = (flags & L.FLAG_NAN_OUTPUT) != 0
+        flags &= ~np.int32(L.FLAG_NAN_OUTPUT)
+        return (wet, hyd, K, nparts, flags, nan_out) if want_nan else (wet, hyd, K, nparts, flags)
+    check(ctx.lib.rdr_raytrace_slices_epochs(ctx.handle, handles, D, C.byref(rays.struct), ptr(hts), S, int(rays.slices > 0), float(zref),
+                                             float(max_seg), ptr(wet), ptr(hyd), None, None, ld, None), ctx.handle)
+    return wet, hyd, None, None, None
+
+
+def raytrace_slices_epochs_to_cubes(cubes, rays, hts, zref, max_seg=1000.0):
+    """raytrace_slices_epochs() whose delays stay on the device: ([Cube with axes (ypts, xpts, hts)] * D, K[S], nparts[S, nz-1],
+    flags[D,S]) - what Cube.raytrace_slices_to_cube makes for each epoch.  GRID batches only."""
+    cubes, ctx, handles, hts, S = _epoch_args(cubes, rays, hts)
+    D = len(cubes)
+    ld = cubes[0].shape[2] - 1
+    K = np.zeros(S, dtype=np.int32); nparts = np.zeros((S, ld), dtype=np.int32); flags = np.zeros((D, S), dtype=np.int32)
+    hs = (C.c_void_p * D)()
+    check(ctx.lib.rdr_raytrace_slices_epochs_to_cubes(ctx.handle, handles, D, C.byref(rays.struct), ptr(hts), S, int(rays.slices > 0), float(zref),
+                                                      float(max_seg), ptr(K), ptr(nparts), ld, ptr(flags), hs), ctx.handle)
+    flags &= ~np.int32(L.FLAG_NAN_OUTPUT)
+    return [Cube._from_handle(ctx, C.c_void_p(h)) for h in hs], K, nparts, flags
+
+
 class Rays:
     """One ray batch = one (ny,nx) slice at one height (delay.py:256-273).  Keeps references to the
     arrays it points at."""
