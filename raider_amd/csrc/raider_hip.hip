@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -305,6 +306,12 @@ static inline int grid_for(int64_t n, int block, int max_blocks) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(g, max_blocks));
 }
 
+// Large host-buffer calls overlap their PCIe transfers with the kernels (interp_pipeline, raytrace_pipelined, the group-by-group
+// download of rdr_raytrace_slices) unless RAIDER_HIP_NO_PIPELINE is set.
+static bool pipelining() {
+    static const bool on = std::getenv("RAIDER_HIP_NO_PIPELINE") == nullptr;
+    return on;
+}
 
 // Launch with `sm` bytes of dynamic LDS; allocations beyond the 64 KB default need the kernel's limit raised first (long
 // non-uniform axes: their (node, 1/spacing) tables live in LDS, 16 B per node).
@@ -1373,8 +1380,7 @@ static int interp3_impl(rdr_ctx* c, const char* who, const rdr_cube* q, const do
     const size_t ystride = x ? 1 : 3;                                  // doubles per point behind `y`
     const bool quad = !B.vb && quad_wanted(c, q, n);
     if (quad) { rc = quad_build(c, q); if (rc) return rc; }
-    static const bool no_pipeline = std::getenv("RAIDER_HIP_NO_PIPELINE") != nullptr;
-    if (loc == RDR_HOST && n >= (1 << 18) && !no_pipeline) {
+    if (loc == RDR_HOST && n >= (1 << 18) && pipelining()) {
         static const int slots[6] = {SLOT_IN0, SLOT_IN1, SLOT_IN2, SLOT_IN3, SLOT_OUT0, SLOT_OUT1};
         return interp_pipeline(c, who, q, quad, y, x, z, n, Q, proj, wet, hydro, slots, B);
     }
@@ -1936,19 +1942,46 @@ int rdr_ray_kernel_attributes(rdr_ctx* c, const rdr_cube* q, int which, int32_t*
     return RDR_OK;
 }
 
-// pass 2 for the whole batch when no valid records are around: chunked (pass-1-store, pass-2) pairs
-static int march_chunked(rdr_ctx* c, const rdr_cube* q, const RayParams& P0, int K) {
-    const int64_t chunk = std::min<int64_t>(P0.ntiles, ws_chunk_tiles(c, K));
-    RayParams Pw = P0;
-    int rc = ws_reserve(c, chunk, K, Pw); if (rc) return rc;
-    for (int64_t tb = 0; tb < P0.ntiles; tb += chunk) {
-        const int64_t tc = std::min<int64_t>(chunk, P0.ntiles - tb);
-        RayParams P = Pw;
-        unsigned long long* keep = P.maxlen_bits;
-        P.maxlen_bits = nullptr;                      // store only, no reduction
-        rc = launch_crossings(c, q, P, tb, tc); if (rc) return rc;
-        P.maxlen_bits = keep;
-        rc = launch_march(c, q, P, tb, tc); if (rc) return rc;
+// The workspace schedule of pass 1 + pass 2 over `nslices` slices of `per` tiles each (tiles numbered slice-major), `fit` tiles of
+// ray records at a time (ws_chunk_tiles).  Whole slices fit: groups of up to `max_group` slices, each one pass 1 that stores the
+// records and one pass 2 on them, then after_group(first slice, slices).  Otherwise, per slice: pass 1 reduction only, then chunked
+// (pass-1 store, pass-2) pairs.  reduce == false: the partition is already on the device (rdr_ray_march[_device]) - pass 1 only
+// stores.  `march` is pass 2 (NULL: launch_march on q).
+static int ray_passes(rdr_ctx* c, const rdr_cube* q, const RayParams& P, int K, int64_t per, int64_t nslices, int64_t fit, int64_t max_group,
+                      bool reduce, const std::function<int(const RayParams&, int64_t, int64_t)>& march = nullptr,
+                      const std::function<int(int64_t, int64_t)>& after_group = nullptr) {
+    const auto pass2 = [&](const RayParams& Pm, int64_t tb, int64_t tc) { return march ? march(Pm, tb, tc) : launch_march(c, q, Pm, tb, tc); };
+    if (per <= fit) {
+        const int64_t g = std::min<int64_t>(max_group, std::max<int64_t>(1, fit / per));
+        for (int64_t s0 = 0; s0 < nslices; s0 += g) {
+            const int64_t ns = std::min<int64_t>(g, nslices - s0);
+            RayParams Pg = P;
+            if (!reduce) Pg.maxlen_bits = nullptr;
+            int rc = ws_reserve(c, ns * per, K, Pg); if (rc) return rc;
+            rc = launch_crossings(c, q, Pg, s0 * per, ns * per); if (rc) return rc;
+            Pg.maxlen_bits = P.maxlen_bits;
+            rc = pass2(Pg, s0 * per, ns * per); if (rc) return rc;
+            if (after_group) { rc = after_group(s0, ns); if (rc) return rc; }
+        }
+        return RDR_OK;
+    }
+    for (int64_t s = 0; s < nslices; ++s) {
+        int rc;
+        if (reduce) {
+            RayParams Ps = P;
+            Ps.ws = nullptr;
+            rc = launch_crossings(c, q, Ps, s * per, per); if (rc) return rc;
+        }
+        RayParams Pw = P;
+        rc = ws_reserve(c, fit, K, Pw); if (rc) return rc;
+        for (int64_t tb = 0; tb < per; tb += fit) {
+            const int64_t tc = std::min<int64_t>(fit, per - tb);
+            RayParams Pc = Pw;
+            Pc.maxlen_bits = nullptr;                      // store only, no reduction
+            rc = launch_crossings(c, q, Pc, s * per + tb, tc); if (rc) return rc;
+            Pc.maxlen_bits = P.maxlen_bits;
+            rc = pass2(Pc, s * per + tb, tc); if (rc) return rc;
+        }
     }
     return RDR_OK;
 }
@@ -2091,7 +2124,7 @@ int rdr_ray_march_device(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, doubl
     hipLaunchKernelGGL(unpack_partition_kernel, dim3(1), dim3(256), 0, c->stream, partition, K, c->d_maxlen, c->d_flags);
     HIPCHECK(c, hipGetLastError());
     if (reuse) { ws_attach(c, P); rc = launch_march(c, q, P, 0, P.ntiles); }
-    else rc = march_chunked(c, q, P, K);
+    else rc = ray_passes(c, q, P, K, P.ntiles, 1, ws_chunk_tiles(c, K), 1, false);
     c->wsig.valid = false;
     return rc;
 }
@@ -2121,7 +2154,7 @@ int rdr_ray_march(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, double ht, d
     rc = stage_out(c, SLOT_OUT1, hydro, (size_t)r->n * 8, r->loc, &dh); if (rc) return rc;
     P.wet = (double*)dw; P.hyd = (double*)dh;
     if (reuse) { ws_attach(c, P); rc = launch_march(c, q, P, 0, P.ntiles); }
-    else rc = march_chunked(c, q, P, K);
+    else rc = ray_passes(c, q, P, K, P.ntiles, 1, ws_chunk_tiles(c, K), 1, false);
     c->wsig.valid = false;
     if (rc) return rc;
     rc = finish_out(c, wet, dw, (size_t)r->n * 8, r->loc); if (rc) return rc;
@@ -2143,8 +2176,7 @@ int rdr_raytrace(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, double ht, do
     HIPCHECK(c, hipSetDevice(c->device));
     RayParams P;
     // large host-buffer batches with per-ray look vectors: overlap the PCIe transfers with the two passes (raytrace_pipelined)
-    static const bool no_pipeline = std::getenv("RAIDER_HIP_NO_PIPELINE") != nullptr;
-    bool pipelined = r->loc == RDR_HOST && r->n >= (1 << 21) && !no_pipeline;
+    bool pipelined = r->loc == RDR_HOST && r->n >= (1 << 21) && pipelining();
     const bool los_chunks = pipelined && r->los_mode == RDR_LOS_VEC;
     const bool hts_chunks = pipelined && r->hts != nullptr;
     rdr_rays rr = *r;
@@ -2176,16 +2208,9 @@ int rdr_raytrace(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, double ht, do
         if (los_chunks) { rc = ensure(c, SLOT_IN3, (size_t)r->n * 24, &dl); if (rc) return rc; }
         if (hts_chunks) { rc = ensure(c, SLOT_IN6, (size_t)r->n * 8, &dhts); if (rc) return rc; }
         rc = raytrace_pipelined(c, q, r, P, K, (double*)dl, (double*)dhts, (double*)dw, (double*)dh, wet, hydro); if (rc) return rc;
-    } else if (P.ntiles <= ws_chunk_tiles(c, K)) {
-        // whole batch fits: pass 1 reduces AND stores the ray records, pass 2 streams them back
-        rc = ws_reserve(c, P.ntiles, K, P); if (rc) return rc;
-        rc = launch_crossings(c, q, P, 0, P.ntiles); if (rc) return rc;
-        rc = launch_march(c, q, P, 0, P.ntiles); if (rc) return rc;
     } else {
-        // pass 1 (reduction only) over everything, then chunked (store, march) pairs
-        P.ws = nullptr;
-        rc = launch_crossings(c, q, P, 0, P.ntiles); if (rc) return rc;
-        rc = march_chunked(c, q, P, K); if (rc) return rc;
+        // one slice: pass 1 reduces AND stores the ray records when they all fit, pass 2 streams them back; else chunked
+        rc = ray_passes(c, q, P, K, P.ntiles, 1, ws_chunk_tiles(c, K), 1, true); if (rc) return rc;
     }
     if (!pipelined) {
         rc = finish_out(c, wet, dw, (size_t)r->n * 8, r->loc); if (rc) return rc;
@@ -2207,175 +2232,12 @@ int rdr_raytrace(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, double ht, do
     return RDR_OK;
 }
 
-// Several height slices of _build_cube_ray in ONE pass-1 / pass-2 launch pair (delay.py:256-323 loops over them): a production
-// job is ~20 heights x 1e4-1e5 rays (aria/prepFromGUNW.py:173,180), and one such slice fills a fraction of the chip.  Tiles are
-// numbered slice-major; per-level maxima / flags / nParts stay per slice (RayParams), so the result is what slice-by-slice
-// calls give, bit for bit.
-// keep == NULL: the public entry; keep != NULL: the delays stay in the context's scratch (planar [nslices][n], keep[0] = wet, keep[1] = hydro)
-// for rdr_raytrace_slices_to_cube - nothing is downloaded, the partition outputs are still read back.
-static int raytrace_slices_impl(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, const double* hts, int32_t nslices, int32_t los_per_slice,
-                                double zref, double max_seg, double* wet, double* hydro, int32_t* K_out, int32_t* nparts_out, int32_t ld,
-                                int32_t* flags_out, double** keep) {
-    if (!c || !q || !hts || (!keep && (!wet || !hydro))) return fail(c, RDR_ERR_INVALID, "rdr_raytrace_slices: NULL argument");
-    note_use(c, q);
-    if (nslices < 1 || nslices > MAX_SLICES) return fail(c, RDR_ERR_INVALID, "rdr_raytrace_slices: 1..512 slices per call");
-    if (!(max_seg > 0)) return fail(c, RDR_ERR_INVALID, "rdr_raytrace_slices: MAX_SEGMENT_LENGTH must be positive");
-    if (nparts_out && ld < (int32_t)q->nz - 1) return fail(c, RDR_ERR_INVALID, "rdr_raytrace_slices: nparts_out needs a row length of at least nz-1");
-    int rc = check_rays(c, r); if (rc) return rc;
-    if (r->origin_mode == RDR_ORIGIN_XYZ && nslices > 1) return fail(c, RDR_ERR_INVALID, "rdr_raytrace_slices: XYZ origins belong to one height; use GRID or LLH origins");
-    if (r->hts) return fail(c, RDR_ERR_INVALID, "rdr_raytrace_slices: per-ray heights (rays->hts) describe ONE batch; use rdr_raytrace");
-    std::vector<int> Ks(nslices);
-    int Kmax = 0;
-    for (int s = 0; s < nslices; ++s) {
-        std::vector<double> lo, hi; std::vector<int> kz;
-        Ks[s] = levels_host(q->zs, hts[s], zref, lo, hi, kz);
-        Kmax = std::max(Kmax, Ks[s]);
-        if (K_out) K_out[s] = Ks[s];
-    }
-    if (r->n == 0) return RDR_OK;
-    HIPCHECK(c, hipSetDevice(c->device));
-    RayParams P;
-    rc = stage_rays(c, r, P, los_per_slice ? nslices : 1); if (rc) return rc;
-    const int64_t per = P.ntiles;                                   // tiles of one slice
-    const size_t nout = (size_t)r->n * nslices;
-    void *dw, *dh;
-    const int out_loc = keep ? RDR_DEVICE : r->loc;                 // where the delays end up
-    rc = stage_out(c, SLOT_OUT0, wet, nout * 8, keep ? RDR_HOST : r->loc, &dw); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT1, hydro, nout * 8, keep ? RDR_HOST : r->loc, &dh); if (rc) return rc;
-    if (keep) { keep[0] = (double*)dw; keep[1] = (double*)dh; }
-    const void* dht;
-    rc = stage_in(c, SLOT_AUX, hts, (size_t)nslices * 8, RDR_HOST, &dht); if (rc) return rc;
-    HIPCHECK(c, hipStreamSynchronize(c->stream));                   // (hts is the caller's memory)
-    P.nslices = nslices; P.tiles_per_slice = per; P.hts = (const double*)dht; P.los_stride = los_per_slice ? r->n : 0;
-    P.ntiles = per * nslices;
-    P.ht = hts[0]; P.zref = zref; P.max_seg = max_seg;
-    P.wet = (double*)dw; P.hyd = (double*)dh;
-    HIPCHECK(c, hipMemsetAsync(c->d_maxlen, 0, (size_t)nslices * MAX_LEVELS * sizeof(unsigned long long), c->stream));
-    HIPCHECK(c, hipMemsetAsync(c->d_flags, 0, (size_t)nslices * sizeof(int), c->stream));
-    c->wsig.valid = false;
-    const int64_t fit = ws_chunk_tiles(c, std::max(Kmax, 1));
-    // Host outputs of a large batch come down slice group by slice group on the copy stream while the next groups are integrated
-    // (all kernels are enqueued first: a copy into pageable memory blocks the host thread, not the device).
-    static const bool no_pipeline = std::getenv("RAIDER_HIP_NO_PIPELINE") != nullptr;
-    const bool pipe = out_loc == RDR_HOST && nslices >= 2 && nout * 16 >= ((size_t)32 << 20) && per <= fit && !no_pipeline;
-    struct EventList {                                   // (destroyed on every exit path)
-        std::vector<hipEvent_t> v;
-        ~EventList() { for (auto& e : v) if (e) (void)hipEventDestroy(e); }
-    } gev_owner;
-    std::vector<hipEvent_t>& gev = gev_owner.v;
-    std::vector<std::pair<int64_t, int64_t>> groups;
-    bool downloaded = false;
-    if (per <= fit) {
-        // groups of whole slices whose records fit the workspace: one launch pair per group (usually one group; up to 8 when the
-        // outputs are downloaded group by group)
-        int64_t g = std::max<int64_t>(1, fit / per);
-        if (pipe) g = std::min<int64_t>(g, std::max<int64_t>(1, (nslices + 7) / 8));
-        for (int64_t s0 = 0; s0 < nslices; s0 += g) {
-            const int64_t ns = std::min<int64_t>(g, nslices - s0);
-            RayParams Pg = P;
-            rc = ws_reserve(c, ns * per, std::max(Kmax, 1), Pg); if (rc) return rc;
-            rc = launch_crossings(c, q, Pg, s0 * per, ns * per); if (rc) return rc;
-            rc = launch_march(c, q, Pg, s0 * per, ns * per); if (rc) return rc;
-            // a NaN anywhere in the slice's outputs -> RDR_FLAG_NAN_OUTPUT of that slice (the caller's np.isnan(...).any(), delay.py:187)
-            hipLaunchKernelGGL(nan_scan_kernel, dim3(grid_for(ns * r->n, 256, c->num_cus * 8)), dim3(256), 0, c->stream,
-                               (const double*)dw + (size_t)s0 * r->n, (const double*)dh + (size_t)s0 * r->n, (int64_t)ns * r->n, (int64_t)r->n,
-                               c->d_flags + s0);
-            HIPCHECK(c, hipGetLastError());
-            if (pipe) {
-                hipEvent_t e = nullptr;
-                if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess || hipEventRecord(e, c->stream) != hipSuccess) {
-                    if (e) (void)hipEventDestroy(e);
-                    return fail(c, RDR_ERR_HIP, "rdr_raytrace_slices: event");
-                }
-                gev.push_back(e); groups.emplace_back(s0, ns);
-            }
-        }
-        if (pipe) {
-            int status = RDR_OK;
-            for (size_t k = 0; k < groups.size() && status == RDR_OK; ++k) {
-                const size_t off = (size_t)groups[k].first * r->n, cnt = (size_t)groups[k].second * r->n;
-                if (hipStreamWaitEvent(c->copy_stream, gev[k], 0) != hipSuccess ||
-                    hipMemcpyAsync(wet + off, (const double*)dw + off, cnt * 8, hipMemcpyDeviceToHost, c->copy_stream) != hipSuccess ||
-                    hipMemcpyAsync(hydro + off, (const double*)dh + off, cnt * 8, hipMemcpyDeviceToHost, c->copy_stream) != hipSuccess)
-                    status = fail(c, RDR_ERR_HIP, "rdr_raytrace_slices: output download failed");
-            }
-            if (hipStreamSynchronize(c->copy_stream) != hipSuccess && status == RDR_OK) status = fail(c, RDR_ERR_HIP, "rdr_raytrace_slices: sync");
-            if (status != RDR_OK) return status;
-            downloaded = true;
-        }
-    } else {
-        // a single slice exceeds the workspace: per slice, pass 1 (reduction only) then chunked (store, march) pairs
-        for (int s = 0; s < nslices; ++s) {
-            RayParams Ps = P;
-            Ps.ws = nullptr;
-            rc = launch_crossings(c, q, Ps, (int64_t)s * per, per); if (rc) return rc;
-            const int64_t chunk = std::min<int64_t>(per, fit);
-            RayParams Pw = P;
-            rc = ws_reserve(c, chunk, std::max(Kmax, 1), Pw); if (rc) return rc;
-            for (int64_t tb = 0; tb < per; tb += chunk) {
-                const int64_t tc = std::min<int64_t>(chunk, per - tb);
-                RayParams Pc = Pw;
-                Pc.maxlen_bits = nullptr;
-                rc = launch_crossings(c, q, Pc, (int64_t)s * per + tb, tc); if (rc) return rc;
-                Pc.maxlen_bits = P.maxlen_bits;
-                rc = launch_march(c, q, Pc, (int64_t)s * per + tb, tc); if (rc) return rc;
-            }
-        }
-    }
-    if (!downloaded) {
-        if (per > fit) {        // (the chunked branch: scan the finished outputs before they leave)
-            hipLaunchKernelGGL(nan_scan_kernel, dim3(grid_for((int64_t)nout, 256, c->num_cus * 8)), dim3(256), 0, c->stream, (const double*)dw,
-                               (const double*)dh, (int64_t)nout, (int64_t)r->n, c->d_flags);
-            HIPCHECK(c, hipGetLastError());
-        }
-        rc = finish_out(c, wet, dw, nout * 8, out_loc); if (rc) return rc;
-        rc = finish_out(c, hydro, dh, nout * 8, out_loc); if (rc) return rc;
-    }
-    const bool need_sync = r->loc == RDR_HOST || nparts_out || flags_out;
-    if (need_sync) {
-        std::vector<double> ml((size_t)nslices * MAX_LEVELS);
-        std::vector<int> f(nslices);
-        int nslow = 0;
-        HIPCHECK(c, hipMemcpyAsync(ml.data(), c->d_maxlen, ml.size() * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHECK(c, hipMemcpyAsync(f.data(), c->d_flags, (size_t)nslices * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHECK(c, hipMemcpyAsync(&nslow, c->d_nslow, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHECK(c, hipStreamSynchronize(c->stream));
-        c->last_nslow = nslow;
-        for (int s = 0; s < nslices; ++s) {
-            if (nparts_out) rdr_nparts(ml.data() + (size_t)s * MAX_LEVELS, Ks[s], max_seg, nparts_out + (size_t)s * ld);
-            if (flags_out) flags_out[s] = f[s];
-        }
-    }
-    return RDR_OK;
-}
-
-int rdr_raytrace_slices(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, const double* hts, int32_t nslices, int32_t los_per_slice,
-                        double zref, double max_seg, double* wet, double* hydro, int32_t* K_out, int32_t* nparts_out, int32_t ld,
-                        int32_t* flags_out) {
-    return raytrace_slices_impl(c, q, r, hts, nslices, los_per_slice, zref, max_seg, wet, hydro, K_out, nparts_out, ld, flags_out, nullptr);
-}
-
-int rdr_raytrace_slices_to_cube(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, const double* hts, int32_t nslices, int32_t los_per_slice,
-                                double zref, double max_seg, int32_t* K_out, int32_t* nparts_out, int32_t ld, int32_t* flags_out,
-                                rdr_cube** out) {
-    if (!c || !q || !r || !hts || !out) return fail(c, RDR_ERR_INVALID, "rdr_raytrace_slices_to_cube: NULL argument");
-    if (r->origin_mode != RDR_ORIGIN_GRID) return fail(c, RDR_ERR_INVALID, "rdr_raytrace_slices_to_cube: the delay cube is a GRID batch (xpts, ypts) x heights");
-    if (r->nx < 2 || r->ny < 2 || nslices < 2) return fail(c, RDR_ERR_INVALID, "rdr_raytrace_slices_to_cube: the delay cube needs two nodes per axis");
-    HIPCHECK(c, hipSetDevice(c->device));
-    std::vector<double> hx, hy;
-    int rc = axis_to_host(c, r->xpts, r->nx, r->loc, hx); if (rc) return rc;
-    rc = axis_to_host(c, r->ypts, r->ny, r->loc, hy); if (rc) return rc;
-    double* planar[2] = {nullptr, nullptr};
-    rc = raytrace_slices_impl(c, q, r, hts, nslices, los_per_slice, zref, max_seg, nullptr, nullptr, K_out, nparts_out, ld, flags_out, planar);
-    if (rc) return rc;
-    return rdr_cube_create(c, hy.data(), r->ny, hx.data(), r->nx, hts, nslices, planar[0], planar[1], RDR_F64, r->nx, 1, r->ny * r->nx, RDR_DEVICE, out);
-}
-
-// ---- time series: E weather epochs through one ray geometry (rdr_raytrace_slices_epochs) ------------------------------------------
+// ---- height slices, and a time series of E weather epochs through one ray geometry (rdr_raytrace_slices[_epochs]) -----------------
 // Every epoch must be the same grid: shape, dtype, bitwise-equal axes and the same projection - then one pass-1 record set (ray
 // polynomials, crossings, the slice partition) serves them all.  Returns RDR_OK or RDR_ERR_INVALID naming the first epoch that differs.
 static int epochs_check(rdr_ctx* c, const char* who, const rdr_cube* const* qs, int32_t ncubes) {
     const std::string w(who);
+    if (!c) return fail(nullptr, RDR_ERR_INVALID, w + ": NULL context");
     if (!qs) return fail(c, RDR_ERR_INVALID, w + ": cubes is NULL");
     if (ncubes <= 0) return fail(c, RDR_ERR_INVALID, w + ": ncubes must be >= 1");
     for (int32_t e = 0; e < ncubes; ++e)
@@ -2467,24 +2329,25 @@ static int launch_march_epochs(rdr_ctx* c, const rdr_cube* const* qs, int D, Ray
     return RDR_OK;
 }
 
-// keep == NULL: the public entry; keep != NULL: the delays stay in the context's scratch ([ncubes][nslices][n] planar, keep[0] = wet,
-// keep[1] = hydro) for rdr_raytrace_slices_epochs_to_cubes.
-static int raytrace_epochs_impl(rdr_ctx* c, const char* who, const rdr_cube* const* qs, int32_t D, const rdr_rays* r, const double* hts, int32_t nslices,
-                                int32_t los_per_slice, double zref, double max_seg, double* wet, double* hydro, int32_t* K_out, int32_t* nparts_out,
-                                int32_t ld, int32_t* flags_out, double** keep) {
+// Several height slices of _build_cube_ray in ONE pass-1 / pass-2 launch pair (delay.py:256-323 loops over them): a production
+// job is ~20 heights x 1e4-1e5 rays (aria/prepFromGUNW.py:173,180), and one such slice fills a fraction of the chip.  Tiles are
+// numbered slice-major; per-level maxima / flags / nParts stay per slice (RayParams), so the result is what slice-by-slice
+// calls give, bit for bit.  The D epoch cubes qs[] (epochs_check) share that pass 1; pass 2 runs per epoch (launch_march_epochs),
+// epoch e's delays are block e of [D][nslices][n] and its flags row e of flags_out.  D = 1 is rdr_raytrace_slices.
+// The entries have checked their own arguments (NULL, the cubes, per-ray heights, a series' empty batch); `who` prefixes the rest.
+// keep == NULL: the public entries; keep != NULL: the delays stay in the context's scratch (planar, keep[0] = wet, keep[1] = hydro)
+// for the _to_cube(s) entries - nothing is downloaded, the partition outputs are still read back.
+static int raytrace_slices_impl(rdr_ctx* c, const char* who, const rdr_cube* const* qs, int32_t D, const rdr_rays* r, const double* hts,
+                                int32_t nslices, int32_t los_per_slice, double zref, double max_seg, double* wet, double* hydro,
+                                int32_t* K_out, int32_t* nparts_out, int32_t ld, int32_t* flags_out, double** keep) {
     const std::string w(who);
-    if (!c) return fail(nullptr, RDR_ERR_INVALID, w + ": NULL context");
-    int rc = epochs_check(c, who, qs, D); if (rc) return rc;
-    if (!r || !hts || (!keep && (!wet || !hydro))) return fail(c, RDR_ERR_INVALID, w + ": NULL argument");
     const rdr_cube* q = qs[0];
     for (int32_t e = 0; e < D; ++e) note_use(c, qs[e]);
     if (nslices < 1 || nslices > MAX_SLICES) return fail(c, RDR_ERR_INVALID, w + ": 1..512 slices per call");
     if (!(max_seg > 0)) return fail(c, RDR_ERR_INVALID, w + ": MAX_SEGMENT_LENGTH must be positive");
     if (nparts_out && ld < (int32_t)q->nz - 1) return fail(c, RDR_ERR_INVALID, w + ": nparts_out needs a row length of at least nz-1");
-    rc = check_rays(c, r); if (rc) return rc;
-    if (r->n == 0) return fail(c, RDR_ERR_INVALID, w + ": empty ray batch");
+    int rc = check_rays(c, r); if (rc) return rc;
     if (r->origin_mode == RDR_ORIGIN_XYZ && nslices > 1) return fail(c, RDR_ERR_INVALID, w + ": XYZ origins belong to one height; use GRID or LLH origins");
-    if (r->hts) return fail(c, RDR_ERR_INVALID, w + ": per-ray heights (rays->hts) are not supported in a series");
     std::vector<int> Ks(nslices);
     int Kmax = 0;
     for (int s = 0; s < nslices; ++s) {
@@ -2493,110 +2356,115 @@ static int raytrace_epochs_impl(rdr_ctx* c, const char* who, const rdr_cube* con
         Kmax = std::max(Kmax, Ks[s]);
         if (K_out) K_out[s] = Ks[s];
     }
+    if (r->n == 0) return RDR_OK;
     HIPCHECK(c, hipSetDevice(c->device));
     RayParams P;
     rc = stage_rays(c, r, P, los_per_slice ? nslices : 1); if (rc) return rc;
-    const int64_t per = P.ntiles;
+    const int64_t per = P.ntiles;                                   // tiles of one slice
     const size_t nout = (size_t)r->n * nslices, total = nout * (size_t)D;
-    void *dw, *dh, *def;
-    const int out_loc = keep ? RDR_DEVICE : r->loc;
+    void *dw, *dh;
+    const int out_loc = keep ? RDR_DEVICE : r->loc;                 // where the delays end up
     rc = stage_out(c, SLOT_OUT0, wet, total * 8, keep ? RDR_HOST : r->loc, &dw); if (rc) return rc;
     rc = stage_out(c, SLOT_OUT1, hydro, total * 8, keep ? RDR_HOST : r->loc, &dh); if (rc) return rc;
-    rc = ensure(c, SLOT_OUT2, (size_t)D * nslices * sizeof(int), &def); if (rc) return rc;   // per-epoch RDR_FLAG_NAN_OUTPUT
+    // RDR_FLAG_NAN_OUTPUT: one epoch's bits go straight into the slice flags; several epochs keep theirs apart ([D][nslices])
+    int* dnan = c->d_flags;
+    if (D > 1) { void* def; rc = ensure(c, SLOT_OUT2, (size_t)D * nslices * sizeof(int), &def); if (rc) return rc; dnan = (int*)def; }
     if (keep) { keep[0] = (double*)dw; keep[1] = (double*)dh; }
     const void* dht;
     rc = stage_in(c, SLOT_AUX, hts, (size_t)nslices * 8, RDR_HOST, &dht); if (rc) return rc;
-    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));                   // (hts is the caller's memory)
     P.nslices = nslices; P.tiles_per_slice = per; P.hts = (const double*)dht; P.los_stride = los_per_slice ? r->n : 0;
     P.ntiles = per * nslices;
     P.ht = hts[0]; P.zref = zref; P.max_seg = max_seg;
     P.wet = (double*)dw; P.hyd = (double*)dh;
     HIPCHECK(c, hipMemsetAsync(c->d_maxlen, 0, (size_t)nslices * MAX_LEVELS * sizeof(unsigned long long), c->stream));
     HIPCHECK(c, hipMemsetAsync(c->d_flags, 0, (size_t)nslices * sizeof(int), c->stream));
-    HIPCHECK(c, hipMemsetAsync(def, 0, (size_t)D * nslices * sizeof(int), c->stream));
+    if (D > 1) HIPCHECK(c, hipMemsetAsync(dnan, 0, (size_t)D * nslices * sizeof(int), c->stream));
     c->wsig.valid = false;
-    const int64_t fit = ws_chunk_tiles(c, std::max(Kmax, 1));
-    if (per <= fit) {
-        // groups of whole slices whose records fit the workspace: ONE pass 1 per group, then every epoch's pass 2 on its records
-        const int64_t g = std::max<int64_t>(1, fit / per);
-        for (int64_t s0 = 0; s0 < nslices; s0 += g) {
-            const int64_t ns = std::min<int64_t>(g, nslices - s0);
-            RayParams Pg = P;
-            rc = ws_reserve(c, ns * per, std::max(Kmax, 1), Pg); if (rc) return rc;
-            rc = launch_crossings(c, q, Pg, s0 * per, ns * per); if (rc) return rc;
-            rc = launch_march_epochs(c, qs, D, Pg, s0 * per, ns * per, (int64_t)nout); if (rc) return rc;
+    const int K = std::max(Kmax, 1);
+    const int64_t fit = ws_chunk_tiles(c, K);
+    // Host outputs of a large one-epoch batch come down slice group by slice group on the copy stream while the next groups are
+    // integrated (all kernels are enqueued first: a copy into pageable memory blocks the host thread, not the device).
+    const bool pipe = D == 1 && out_loc == RDR_HOST && nslices >= 2 && nout * 16 >= ((size_t)32 << 20) && per <= fit && pipelining();
+    // a NaN anywhere in the outputs of slices [s0, s0+ns) of [D][nslices] -> their RDR_FLAG_NAN_OUTPUT (the caller's np.isnan(...).any(), delay.py:187)
+    const auto nan_scan = [&](int64_t s0, int64_t ns) {
+        hipLaunchKernelGGL(nan_scan_kernel, dim3(grid_for(ns * r->n, 256, c->num_cus * 8)), dim3(256), 0, c->stream,
+                           (const double*)dw + (size_t)s0 * r->n, (const double*)dh + (size_t)s0 * r->n, (int64_t)ns * r->n, (int64_t)r->n, dnan + s0);
+        HIPCHECK(c, hipGetLastError());
+        return RDR_OK;
+    };
+    struct EventList {                                   // (destroyed on every exit path)
+        std::vector<hipEvent_t> v;
+        ~EventList() { for (auto& e : v) if (e) (void)hipEventDestroy(e); }
+    } gev_owner;
+    std::vector<hipEvent_t>& gev = gev_owner.v;
+    std::vector<std::pair<int64_t, int64_t>> groups;
+    // groups of whole slices: usually one; up to 8 when the outputs are downloaded group by group
+    rc = ray_passes(c, q, P, K, per, nslices, fit, pipe ? std::max<int64_t>(1, (nslices + 7) / 8) : nslices, true,
+                    [&](const RayParams& Pm, int64_t tb, int64_t tc) { return launch_march_epochs(c, qs, D, Pm, tb, tc, (int64_t)nout); },
+                    [&](int64_t s0, int64_t ns) {
+                        if (!pipe) return RDR_OK;
+                        const int rc_ = nan_scan(s0, ns); if (rc_) return rc_;
+                        hipEvent_t e = nullptr;
+                        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess || hipEventRecord(e, c->stream) != hipSuccess) {
+                            if (e) (void)hipEventDestroy(e);
+                            return fail(c, RDR_ERR_HIP, w + ": event");
+                        }
+                        gev.push_back(e); groups.emplace_back(s0, ns);
+                        return RDR_OK;
+                    });
+    if (rc) return rc;
+    if (pipe) {
+        int status = RDR_OK;
+        for (size_t k = 0; k < groups.size() && status == RDR_OK; ++k) {
+            const size_t off = (size_t)groups[k].first * r->n, cnt = (size_t)groups[k].second * r->n;
+            if (hipStreamWaitEvent(c->copy_stream, gev[k], 0) != hipSuccess ||
+                hipMemcpyAsync(wet + off, (const double*)dw + off, cnt * 8, hipMemcpyDeviceToHost, c->copy_stream) != hipSuccess ||
+                hipMemcpyAsync(hydro + off, (const double*)dh + off, cnt * 8, hipMemcpyDeviceToHost, c->copy_stream) != hipSuccess)
+                status = fail(c, RDR_ERR_HIP, w + ": output download failed");
         }
+        if (hipStreamSynchronize(c->copy_stream) != hipSuccess && status == RDR_OK) status = fail(c, RDR_ERR_HIP, w + ": sync");
+        if (status != RDR_OK) return status;
     } else {
-        // a single slice exceeds the workspace: per slice, pass 1 (reduction only), then chunked (store, every epoch's march) pairs
-        for (int s = 0; s < nslices; ++s) {
-            RayParams Ps = P;
-            Ps.ws = nullptr;
-            rc = launch_crossings(c, q, Ps, (int64_t)s * per, per); if (rc) return rc;
-            const int64_t chunk = std::min<int64_t>(per, fit);
-            RayParams Pw = P;
-            rc = ws_reserve(c, chunk, std::max(Kmax, 1), Pw); if (rc) return rc;
-            for (int64_t tb = 0; tb < per; tb += chunk) {
-                const int64_t tc = std::min<int64_t>(chunk, per - tb);
-                RayParams Pc = Pw;
-                Pc.maxlen_bits = nullptr;
-                rc = launch_crossings(c, q, Pc, (int64_t)s * per + tb, tc); if (rc) return rc;
-                Pc.maxlen_bits = P.maxlen_bits;
-                rc = launch_march_epochs(c, qs, D, Pc, (int64_t)s * per + tb, tc, (int64_t)nout); if (rc) return rc;
-            }
-        }
+        rc = nan_scan(0, (int64_t)D * nslices); if (rc) return rc;   // (scan the finished outputs before they leave)
+        rc = finish_out(c, wet, dw, total * 8, out_loc); if (rc) return rc;
+        rc = finish_out(c, hydro, dh, total * 8, out_loc); if (rc) return rc;
     }
-    // a NaN anywhere in an epoch's slice -> RDR_FLAG_NAN_OUTPUT of that epoch and slice
-    hipLaunchKernelGGL(nan_scan_kernel, dim3(grid_for((int64_t)total, 256, c->num_cus * 8)), dim3(256), 0, c->stream, (const double*)dw,
-                       (const double*)dh, (int64_t)total, (int64_t)r->n, (int*)def);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, wet, dw, total * 8, out_loc); if (rc) return rc;
-    rc = finish_out(c, hydro, dh, total * 8, out_loc); if (rc) return rc;
     const bool need_sync = r->loc == RDR_HOST || nparts_out || flags_out;
     if (need_sync) {
         std::vector<double> ml((size_t)nslices * MAX_LEVELS);
-        std::vector<int> f(nslices), ef((size_t)D * nslices);
+        std::vector<int> f(nslices), ef(D > 1 ? (size_t)D * nslices : 0);
         int nslow = 0;
         HIPCHECK(c, hipMemcpyAsync(ml.data(), c->d_maxlen, ml.size() * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHECK(c, hipMemcpyAsync(f.data(), c->d_flags, (size_t)nslices * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHECK(c, hipMemcpyAsync(ef.data(), def, ef.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        if (D > 1) HIPCHECK(c, hipMemcpyAsync(ef.data(), dnan, ef.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHECK(c, hipMemcpyAsync(&nslow, c->d_nslow, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHECK(c, hipStreamSynchronize(c->stream));
         c->last_nslow = nslow;
         for (int s = 0; s < nslices; ++s) {
             if (nparts_out) rdr_nparts(ml.data() + (size_t)s * MAX_LEVELS, Ks[s], max_seg, nparts_out + (size_t)s * ld);
             if (flags_out)
-                for (int32_t e = 0; e < D; ++e) flags_out[(size_t)e * nslices + s] = f[s] | ef[(size_t)e * nslices + s];
+                for (int32_t e = 0; e < D; ++e) flags_out[(size_t)e * nslices + s] = f[s] | (D > 1 ? ef[(size_t)e * nslices + s] : 0);
         }
     }
     return RDR_OK;
 }
 
-int rdr_raytrace_slices_epochs(rdr_ctx* c, const rdr_cube* const* cubes, int32_t ncubes, const rdr_rays* r, const double* hts, int32_t nslices,
-                               int32_t los_per_slice, double zref, double max_seg, double* wet, double* hydro, int32_t* K_out, int32_t* nparts_out,
-                               int32_t ld, int32_t* flags_out) {
-    return raytrace_epochs_impl(c, "rdr_raytrace_slices_epochs", cubes, ncubes, r, hts, nslices, los_per_slice, zref, max_seg, wet, hydro, K_out,
-                                nparts_out, ld, flags_out, nullptr);
-}
-
-int rdr_raytrace_slices_epochs_to_cubes(rdr_ctx* c, const rdr_cube* const* cubes, int32_t ncubes, const rdr_rays* r, const double* hts,
-                                        int32_t nslices, int32_t los_per_slice, double zref, double max_seg, int32_t* K_out, int32_t* nparts_out,
-                                        int32_t ld, int32_t* flags_out, rdr_cube** out) {
-    static const char* who = "rdr_raytrace_slices_epochs_to_cubes";
-    if (!c) return fail(nullptr, RDR_ERR_INVALID, std::string(who) + ": NULL context");
-    int rc = epochs_check(c, who, cubes, ncubes); if (rc) return rc;
-    if (!r || !hts || !out) return fail(c, RDR_ERR_INVALID, std::string(who) + ": NULL argument");
-    if (r->origin_mode != RDR_ORIGIN_GRID) return fail(c, RDR_ERR_INVALID, std::string(who) + ": the delay cubes are a GRID batch (xpts, ypts) x heights");
-    if (r->nx < 2 || r->ny < 2 || nslices < 2) return fail(c, RDR_ERR_INVALID, std::string(who) + ": the delay cubes need two nodes per axis");
+// The _to_cube(s) entries: raytrace_slices_impl with its delays left in scratch, made into D float64 cubes with axes (ypts, xpts, hts)
+// on the device.  The entries have checked that the batch is a GRID of at least two nodes per axis.
+static int raytrace_slices_to_cubes(rdr_ctx* c, const char* who, const rdr_cube* const* qs, int32_t D, const rdr_rays* r, const double* hts,
+                                    int32_t nslices, int32_t los_per_slice, double zref, double max_seg, int32_t* K_out, int32_t* nparts_out,
+                                    int32_t ld, int32_t* flags_out, rdr_cube** out) {
     HIPCHECK(c, hipSetDevice(c->device));
     std::vector<double> hx, hy;
-    rc = axis_to_host(c, r->xpts, r->nx, r->loc, hx); if (rc) return rc;
+    int rc = axis_to_host(c, r->xpts, r->nx, r->loc, hx); if (rc) return rc;
     rc = axis_to_host(c, r->ypts, r->ny, r->loc, hy); if (rc) return rc;
     double* planar[2] = {nullptr, nullptr};
-    rc = raytrace_epochs_impl(c, who, cubes, ncubes, r, hts, nslices, los_per_slice, zref, max_seg, nullptr, nullptr, K_out, nparts_out, ld, flags_out, planar);
+    rc = raytrace_slices_impl(c, who, qs, D, r, hts, nslices, los_per_slice, zref, max_seg, nullptr, nullptr, K_out, nparts_out, ld, flags_out, planar);
     if (rc) return rc;
     const size_t nout = (size_t)r->n * nslices;
-    for (int32_t e = 0; e < ncubes; ++e) out[e] = nullptr;
-    for (int32_t e = 0; e < ncubes; ++e) {
+    for (int32_t e = 0; e < D; ++e) out[e] = nullptr;
+    for (int32_t e = 0; e < D; ++e) {
         rc = rdr_cube_create(c, hy.data(), r->ny, hx.data(), r->nx, hts, nslices, planar[0] + e * nout, planar[1] + e * nout, RDR_F64, r->nx, 1,
                              r->ny * r->nx, RDR_DEVICE, &out[e]);
         if (rc) {
@@ -2605,6 +2473,58 @@ int rdr_raytrace_slices_epochs_to_cubes(rdr_ctx* c, const rdr_cube* const* cubes
         }
     }
     return RDR_OK;
+}
+
+static const char k_one_batch[] = "rdr_raytrace_slices: per-ray heights (rays->hts) describe ONE batch; use rdr_raytrace";
+
+// what a series refuses on top of the checks rdr_raytrace_slices makes (r is not NULL)
+static int series_rays_check(rdr_ctx* c, const std::string& w, const rdr_rays* r) {
+    if (r->n == 0) return fail(c, RDR_ERR_INVALID, w + ": empty ray batch");
+    if (r->hts) return fail(c, RDR_ERR_INVALID, w + ": per-ray heights (rays->hts) are not supported in a series");
+    return RDR_OK;
+}
+
+int rdr_raytrace_slices(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, const double* hts, int32_t nslices, int32_t los_per_slice,
+                        double zref, double max_seg, double* wet, double* hydro, int32_t* K_out, int32_t* nparts_out, int32_t ld,
+                        int32_t* flags_out) {
+    if (!c || !q || !hts || !wet || !hydro) return fail(c, RDR_ERR_INVALID, "rdr_raytrace_slices: NULL argument");
+    if (r && r->hts) return fail(c, RDR_ERR_INVALID, k_one_batch);
+    return raytrace_slices_impl(c, "rdr_raytrace_slices", &q, 1, r, hts, nslices, los_per_slice, zref, max_seg, wet, hydro, K_out, nparts_out,
+                                ld, flags_out, nullptr);
+}
+
+int rdr_raytrace_slices_to_cube(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, const double* hts, int32_t nslices, int32_t los_per_slice,
+                                double zref, double max_seg, int32_t* K_out, int32_t* nparts_out, int32_t ld, int32_t* flags_out,
+                                rdr_cube** out) {
+    if (!c || !q || !r || !hts || !out) return fail(c, RDR_ERR_INVALID, "rdr_raytrace_slices_to_cube: NULL argument");
+    if (r->origin_mode != RDR_ORIGIN_GRID) return fail(c, RDR_ERR_INVALID, "rdr_raytrace_slices_to_cube: the delay cube is a GRID batch (xpts, ypts) x heights");
+    if (r->nx < 2 || r->ny < 2 || nslices < 2) return fail(c, RDR_ERR_INVALID, "rdr_raytrace_slices_to_cube: the delay cube needs two nodes per axis");
+    if (r->hts) return fail(c, RDR_ERR_INVALID, k_one_batch);
+    return raytrace_slices_to_cubes(c, "rdr_raytrace_slices", &q, 1, r, hts, nslices, los_per_slice, zref, max_seg, K_out, nparts_out, ld,
+                                    flags_out, out);
+}
+
+int rdr_raytrace_slices_epochs(rdr_ctx* c, const rdr_cube* const* cubes, int32_t ncubes, const rdr_rays* r, const double* hts, int32_t nslices,
+                               int32_t los_per_slice, double zref, double max_seg, double* wet, double* hydro, int32_t* K_out, int32_t* nparts_out,
+                               int32_t ld, int32_t* flags_out) {
+    static const char* who = "rdr_raytrace_slices_epochs";
+    int rc = epochs_check(c, who, cubes, ncubes); if (rc) return rc;
+    if (!r || !hts || !wet || !hydro) return fail(c, RDR_ERR_INVALID, std::string(who) + ": NULL argument");
+    rc = series_rays_check(c, who, r); if (rc) return rc;
+    return raytrace_slices_impl(c, who, cubes, ncubes, r, hts, nslices, los_per_slice, zref, max_seg, wet, hydro, K_out, nparts_out, ld,
+                                flags_out, nullptr);
+}
+
+int rdr_raytrace_slices_epochs_to_cubes(rdr_ctx* c, const rdr_cube* const* cubes, int32_t ncubes, const rdr_rays* r, const double* hts,
+                                        int32_t nslices, int32_t los_per_slice, double zref, double max_seg, int32_t* K_out, int32_t* nparts_out,
+                                        int32_t ld, int32_t* flags_out, rdr_cube** out) {
+    static const char* who = "rdr_raytrace_slices_epochs_to_cubes";
+    int rc = epochs_check(c, who, cubes, ncubes); if (rc) return rc;
+    if (!r || !hts || !out) return fail(c, RDR_ERR_INVALID, std::string(who) + ": NULL argument");
+    if (r->origin_mode != RDR_ORIGIN_GRID) return fail(c, RDR_ERR_INVALID, std::string(who) + ": the delay cubes are a GRID batch (xpts, ypts) x heights");
+    if (r->nx < 2 || r->ny < 2 || nslices < 2) return fail(c, RDR_ERR_INVALID, std::string(who) + ": the delay cubes need two nodes per axis");
+    rc = series_rays_check(c, who, r); if (rc) return rc;
+    return raytrace_slices_to_cubes(c, who, cubes, ncubes, r, hts, nslices, los_per_slice, zref, max_seg, K_out, nparts_out, ld, flags_out, out);
 }
 
 int rdr_top_of_atmosphere(rdr_ctx* c, const double* xyz, const double* los, int64_t n, double h, const double* factor, double* pos, int loc) {

@@ -465,32 +465,17 @@ def _stacked_cube(plans, datetimes, los, crs):
     cubes = [p['cube'] for p in plans]
     D = len(cubes)
     outs = [[np.empty((zpts.size, ypts.size, xpts.size)) for _ in range(2)] for _ in range(D)]
-    any_nan = [False] * D
-    n_per = max(1, xpts.size * ypts.size)
-    # _build_cube_ray's slice budget with D x 16 B of delays per ray and slice (next to the 48 B of look vectors and targets)
-    budget = int(os.environ.get('RAIDER_HIP_SLICE_BUDGET_BYTES', 8 << 30))
-    chunk = int(min(512, max(1, budget // (n_per * (48 + 16 * D)))))
-    s0 = 0
-    while s0 < zpts.size:
-        zz = np.ascontiguousarray(zpts[s0:s0 + chunk], dtype=np.float64)
-        logger.info(f'Processing slices {s0 + 1}-{s0 + zz.size} / {len(zpts)} of {D} dates')
-        try:
-            rays = los.ray_batch_slices(xpts, ypts, zz)
-            dw, dh, K, _nparts, flags, nan_out = raytrace_slices_epochs(cubes, rays, zz, zref, 1000.0, want_nan=True)
-            if rays._torch_device is not None:
-                dw, dh = dw.cpu().numpy(), dh.cpu().numpy()
-        except (MemoryError, RuntimeError) as exc:
-            if chunk == 1 or not (isinstance(exc, MemoryError) or type(exc).__name__ == 'OutOfMemoryError'):
-                raise
-            chunk = max(1, chunk // 2)
-            logger.info(f'slice batch did not fit the device ({exc}); continuing with {chunk} slices per call')
-            continue
-        _raise_slice_failures(K, flags[0], zz, zpts[-1])
+
+    def trace(s0, zz):
+        rays = los.ray_batch_slices(xpts, ypts, zz)
+        dw, dh, K, _nparts, flags, nan_out = raytrace_slices_epochs(cubes, rays, zz, zref, 1000.0, want_nan=True)
+        if rays._torch_device is not None:
+            dw, dh = dw.cpu().numpy(), dh.cpu().numpy()
         for e in range(D):
             outs[e][0][s0:s0 + zz.size] = dw[e]
             outs[e][1][s0:s0 + zz.size] = dh[e]
-            any_nan[e] = any_nan[e] or bool(nan_out[e].any())
-        s0 += zz.size
+        return K, flags[0], nan_out
+    any_nan = _slice_batches(xpts, ypts, zpts, 48 + 16 * D, trace, f' of {D} dates')
     res = []
     for e, p in enumerate(plans):
         if any_nan[e]:
@@ -609,6 +594,37 @@ def _ensure_output_grid(aoi, weather_model_file, crs):
         y_spacing = np.diff(get('y')).mean()
         aoi.set_output_spacing(ll_res=np.min([x_spacing, y_spacing]))
         aoi.set_output_xygrid(crs)
+
+
+def _slice_batches(xpts, ypts, zpts, bytes_per_ray, trace, what=''):
+    """The slice loop of the batched ray-traced cube: trace(s0, zz) -> (K, flags, nan_out) integrates heights zz = zpts[s0:s0 + len(zz)]
+    and stores their delays.  Slices per call come from a byte budget, not a fixed count: a batch holds per ray and slice its look
+    vector (orbit-based ones depend on the height: 24 B, plus the 24 B target they were solved from) and 16 B of delays per date on
+    the device (`bytes_per_ray`), next to the 232 B ray records the library chunks by itself.  RAIDER_HIP_SLICE_BUDGET_BYTES (default
+    8 GiB), at most 512; a batch the device still cannot hold is halved until it fits.  Returns nan_out.any(axis=-1) over all batches:
+    what np.isnan(result).any() would find (delay.py:187), per date."""
+    n_per = max(1, xpts.size * ypts.size)
+    budget = int(os.environ.get('RAIDER_HIP_SLICE_BUDGET_BYTES', 8 << 30))
+    chunk = int(min(512, max(1, budget // (n_per * bytes_per_ray))))
+    any_nan = False
+    s0 = 0
+    while s0 < zpts.size:
+        zz = np.ascontiguousarray(zpts[s0:s0 + chunk], dtype=np.float64)
+        logger.info(f'Processing slices {s0 + 1}-{s0 + zz.size} / {len(zpts)}{what}')
+        try:
+            K, flags, nan_out = trace(s0, zz)
+        except (MemoryError, RuntimeError) as exc:
+            # out of DEVICE memory, told by status / class, not by the wording of a message: RDR_ERR_OOM arrives as
+            # _lib.DeviceOutOfMemory (a MemoryError), torch's allocator raises torch.OutOfMemoryError (a RuntimeError)
+            if chunk == 1 or not (isinstance(exc, MemoryError) or type(exc).__name__ == 'OutOfMemoryError'):
+                raise
+            chunk = max(1, chunk // 2)                                 # the device could not hold the batch: smaller ones
+            logger.info(f'slice batch did not fit the device ({exc}); continuing with {chunk} slices per call')
+            continue
+        _raise_slice_failures(K, flags, zz, zpts[-1])
+        any_nan = any_nan | nan_out.any(axis=-1)
+        s0 += zz.size
+    return any_nan
 
 
 def _raise_slice_failures(K, flags, zz, top):
@@ -774,43 +790,20 @@ def _build_cube_ray(xpts, ypts, zpts, los, model_crs, pts_crs, interpolators, ou
     if direct and grid_is_ll and hasattr(los, 'ray_batch_slices') and zpts.size > 0:
         # the whole height loop as one batched launch pair per <= 512 slices (Cube.raytrace_slices): bit-identical to the slice
         # loop below, but a production job (20 heights x 1e4-1e5 rays) fills the GPU instead of a tenth of it
-        any_nan = False
-        # slices per call from a byte budget, not a fixed count: a batch holds per ray and slice its look vector (orbit-based ones
-        # depend on the height: 24 B, plus the 24 B target they were solved from) and 16 B of delays on the device, next to the 232 B
-        # ray records the library chunks by itself.  RAIDER_HIP_SLICE_BUDGET_BYTES (default 8 GiB); a batch the device still cannot
-        # hold is halved until it fits.
-        n_per = max(1, xpts.size * ypts.size)
-        budget = int(os.environ.get('RAIDER_HIP_SLICE_BUDGET_BYTES', 8 << 30))
-        chunk = int(min(512, max(1, budget // (n_per * 64))))
-        s0 = 0
-        while s0 < zpts.size:
-            zz = np.ascontiguousarray(zpts[s0:s0 + chunk], dtype=np.float64)
-            logger.info(f'Processing slices {s0 + 1}-{s0 + zz.size} / {len(zpts)}')
-            try:
-                rays = los.ray_batch_slices(xpts, ypts, zz)
-                if rays._torch_device is None:
-                    _, _, K, _nparts, flags, nan_out = cube.raytrace_slices(rays, zz, MAX_TROPO_HEIGHT, MAX_SEGMENT_LENGTH, want_nan=True,
-                                                                            out=(outputArrs[0][s0:s0 + zz.size], outputArrs[1][s0:s0 + zz.size]))
-                    any_nan = any_nan or bool(nan_out.any())
-                else:           # a device-resident batch (orbit-based look vectors made on the GPU): device outputs, one download per field
-                    import torch
-                    dw, dh, K, _nparts, flags, nan_out = cube.raytrace_slices(rays, zz, MAX_TROPO_HEIGHT, MAX_SEGMENT_LENGTH, want_nan=True)
-                    any_nan = any_nan or bool(nan_out.any())
-                    torch.from_numpy(outputArrs[0][s0:s0 + zz.size]).copy_(dw); torch.from_numpy(outputArrs[1][s0:s0 + zz.size]).copy_(dh)
-                    del dw, dh
-            except (MemoryError, RuntimeError) as exc:
-                # out of DEVICE memory, told by status / class, not by the wording of a message: RDR_ERR_OOM arrives as
-                # _lib.DeviceOutOfMemory (a MemoryError), torch's allocator raises torch.OutOfMemoryError (a RuntimeError)
-                if chunk == 1 or not (isinstance(exc, MemoryError) or type(exc).__name__ == 'OutOfMemoryError'):
-                    raise
-                chunk = max(1, chunk // 2)                                 # the device could not hold the batch: smaller ones
-                logger.info(f'slice batch did not fit the device ({exc}); continuing with {chunk} slices per call')
-                continue
-            s0 += zz.size
-            _raise_slice_failures(K, flags, zz, zpts[-1])
+        def trace(s0, zz):
+            rays = los.ray_batch_slices(xpts, ypts, zz)
+            if rays._torch_device is None:
+                _, _, K, _nparts, flags, nan_out = cube.raytrace_slices(rays, zz, MAX_TROPO_HEIGHT, MAX_SEGMENT_LENGTH, want_nan=True,
+                                                                        out=(outputArrs[0][s0:s0 + zz.size], outputArrs[1][s0:s0 + zz.size]))
+            else:           # a device-resident batch (orbit-based look vectors made on the GPU): device outputs, one download per field
+                import torch
+                dw, dh, K, _nparts, flags, nan_out = cube.raytrace_slices(rays, zz, MAX_TROPO_HEIGHT, MAX_SEGMENT_LENGTH, want_nan=True)
+                torch.from_numpy(outputArrs[0][s0:s0 + zz.size]).copy_(dw); torch.from_numpy(outputArrs[1][s0:s0 + zz.size]).copy_(dh)
+            return K, flags, nan_out
+        any_nan = _slice_batches(xpts, ypts, zpts, 64, trace)
         # what np.isnan(result).any() would find (delay.py:187), already known from the device-side scan of every slice
         outputArrs = _Result(outputArrs)
-        outputArrs.has_nan = any_nan
+        outputArrs.has_nan = bool(any_nan)
         return outputArrs
     for hh, ht in enumerate(zpts):
         logger.info(f'Processing slice {hh + 1} / {len(zpts)}: {ht}')

@@ -444,53 +444,17 @@ class Cube:
         Returns (wet[S,...], hydro[S,...], K[S], nparts[S, nz-1], flags[S]); the last three are None when want_partition is
         False (fully asynchronous for device arrays).  K[s] == 0: build_ray -> None for that slice (its delays are 0).
         want_nan=True: a sixth element, bool[S] = np.isnan(result[s]).any() as scanned on the device before the download."""
-        rays.adopt_stream(self.ctx)
-        if rays.ht_min is not None:
-            raise ValueError('a batch with per-ray heights is ONE slice: use raytrace()')
-        hts = f64(np.atleast_1d(hts)).ravel()
-        S = hts.size
-        if rays.slices not in (0, S):
-            raise ValueError(f'the ray batch carries look vectors for {rays.slices} slices, {S} heights were given')
-        if out is not None:
-            wet, hyd = out
-        elif rays._torch_device is not None:
-            import torch
-            wet = torch.empty((S,) + tuple(rays.shape), dtype=torch.float64, device=rays._torch_device)
-            hyd = torch.empty_like(wet)
-        else:
-            wet = _pinned.empty((S,) + tuple(rays.shape)); hyd = _pinned.empty((S,) + tuple(rays.shape))
-        rays.check_outputs(wet, hyd, slices=S)
-        ld = self.shape[2] - 1
-        if want_partition:
-            K = np.zeros(S, dtype=np.int32); nparts = np.zeros((S, ld), dtype=np.int32); flags = np.zeros(S, dtype=np.int32)
-            check(self.ctx.lib.rdr_raytrace_slices(self.ctx.handle, self.handle, C.byref(rays.struct), ptr(hts), S, int(rays.slices > 0), float(zref),
-                                                   float(max_seg), ptr(wet), ptr(hyd), ptr(K), ptr(nparts), ld, ptr(flags)), self.ctx.handle)
-            # RDR_FLAG_NAN_OUTPUT (np.isnan(result).any() per slice, scanned on the device before the download) is reported apart
-            # from the partition flags, which stay what rdr_raytrace returns for the slice
-            nan_out = (flags & L.FLAG_NAN_OUTPUT) != 0
-            flags &= ~np.int32(L.FLAG_NAN_OUTPUT)
-            return (wet, hyd, K, nparts, flags, nan_out) if want_nan else (wet, hyd, K, nparts, flags)
-        check(self.ctx.lib.rdr_raytrace_slices(self.ctx.handle, self.handle, C.byref(rays.struct), ptr(hts), S, int(rays.slices > 0), float(zref),
-                                               float(max_seg), ptr(wet), ptr(hyd), None, None, ld, None), self.ctx.handle)
-        return wet, hyd, None, None, None
+        hts = _slice_heights(self.ctx, rays, hts, 'a batch with per-ray heights is ONE slice: use raytrace()')
+        return _trace_slices(self.ctx, self.ctx.lib.rdr_raytrace_slices, (self.handle,), (), self.shape[2] - 1, rays, hts, zref, max_seg, out,
+                             want_partition, want_nan)
 
     def raytrace_slices_to_cube(self, rays, hts, zref, max_seg=1000.0):
         """raytrace_slices() whose delays stay on the device: (Cube with axes (ypts, xpts, hts), K[S], nparts[S, nz-1], flags[S]) -
         the intermediate cube of tropo_delay's point branch for a ray-traced line of sight.  GRID batches only."""
-        rays.adopt_stream(self.ctx)
-        if rays.ht_min is not None:
-            raise ValueError('a batch with per-ray heights is ONE slice: use raytrace()')
-        hts = f64(np.atleast_1d(hts)).ravel()
-        S = hts.size
-        if rays.slices not in (0, S):
-            raise ValueError(f'the ray batch carries look vectors for {rays.slices} slices, {S} heights were given')
-        ld = self.shape[2] - 1
-        K = np.zeros(S, dtype=np.int32); nparts = np.zeros((S, ld), dtype=np.int32); flags = np.zeros(S, dtype=np.int32)
-        h = C.c_void_p()
-        check(self.ctx.lib.rdr_raytrace_slices_to_cube(self.ctx.handle, self.handle, C.byref(rays.struct), ptr(hts), S, int(rays.slices > 0), float(zref),
-                                                       float(max_seg), ptr(K), ptr(nparts), ld, ptr(flags), C.byref(h)), self.ctx.handle)
-        flags &= ~np.int32(L.FLAG_NAN_OUTPUT)
-        return Cube._from_handle(self.ctx, h), K, nparts, flags
+        hts = _slice_heights(self.ctx, rays, hts, 'a batch with per-ray heights is ONE slice: use raytrace()')
+        (cube,), K, nparts, flags = _trace_slices_to_cubes(self.ctx, self.ctx.lib.rdr_raytrace_slices_to_cube, (self.handle,), (), self.shape[2] - 1,
+                                                         rays, hts, zref, max_seg)
+        return cube, K, nparts, flags
 
     def __del__(self):
         try:
@@ -512,20 +476,67 @@ def epoch_groups(D, emax=4):
     return out
 
 
+def _slice_heights(ctx, rays, hts, per_ray_heights):
+    """hts as float64 after the checks every sliced call makes; `per_ray_heights`: the entry's refusal of a batch with per-ray heights."""
+    rays.adopt_stream(ctx)
+    if rays.ht_min is not None:
+        raise ValueError(per_ray_heights)
+    hts = f64(np.atleast_1d(hts)).ravel()
+    if rays.slices not in (0, hts.size):
+        raise ValueError(f'the ray batch carries look vectors for {rays.slices} slices, {hts.size} heights were given')
+    return hts
+
+
+def _partition_outputs(lead, S, ld):
+    """K[S], nparts[S, ld] and flags[lead + (S,)] of a sliced call (lead: () for one cube, (D,) for a series)."""
+    return np.zeros(S, dtype=np.int32), np.zeros((S, ld), dtype=np.int32), np.zeros(lead + (S,), dtype=np.int32)
+
+
+def _trace_slices(ctx, fn, cube_args, lead, ld, rays, hts, zref, max_seg, out, want_partition, want_nan):
+    """rdr_raytrace_slices[_epochs] (`fn`, cube arguments `cube_args`) into outputs of shape lead + (S,) + rays.shape: `out`, torch
+    tensors on the rays' device or page-locked host arrays.  RDR_FLAG_NAN_OUTPUT (np.isnan(result).any() per slice, scanned on the
+    device before the download) is reported apart from the partition flags, which stay what rdr_raytrace returns for the slice."""
+    S = hts.size
+    shape = lead + (S,) + tuple(rays.shape)
+    if out is not None:
+        wet, hyd = out
+    elif rays._torch_device is not None:
+        import torch
+        wet = torch.empty(shape, dtype=torch.float64, device=rays._torch_device)
+        hyd = torch.empty_like(wet)
+    else:
+        wet = _pinned.empty(shape); hyd = _pinned.empty(shape)
+    rays.check_outputs(wet, hyd, slices=S * int(np.prod(lead)))
+    args = (ctx.handle, *cube_args, C.byref(rays.struct), ptr(hts), S, int(rays.slices > 0), float(zref), float(max_seg), ptr(wet), ptr(hyd))
+    if not want_partition:
+        check(fn(*args, None, None, ld, None), ctx.handle)
+        return wet, hyd, None, None, None
+    K, nparts, flags = _partition_outputs(lead, S, ld)
+    check(fn(*args, ptr(K), ptr(nparts), ld, ptr(flags)), ctx.handle)
+    nan_out = (flags & L.FLAG_NAN_OUTPUT) != 0
+    flags &= ~np.int32(L.FLAG_NAN_OUTPUT)
+    return (wet, hyd, K, nparts, flags, nan_out) if want_nan else (wet, hyd, K, nparts, flags)
+
+
+def _trace_slices_to_cubes(ctx, fn, cube_args, lead, ld, rays, hts, zref, max_seg):
+    """rdr_raytrace_slices[_epochs]_to_cube[s]: ([Cube] * D, K, nparts, flags) as _trace_slices, D = 1 for lead == ()."""
+    S = hts.size
+    K, nparts, flags = _partition_outputs(lead, S, ld)
+    hs = (C.c_void_p * int(np.prod(lead)))()
+    check(fn(ctx.handle, *cube_args, C.byref(rays.struct), ptr(hts), S, int(rays.slices > 0), float(zref), float(max_seg), ptr(K), ptr(nparts),
+             ld, ptr(flags), hs), ctx.handle)
+    flags &= ~np.int32(L.FLAG_NAN_OUTPUT)
+    return [Cube._from_handle(ctx, C.c_void_p(h)) for h in hs], K, nparts, flags
+
+
 def _epoch_args(cubes, rays, hts):
-    """(cubes, ctx, C array of handles, hts, S) of a time-series call; the cubes' compatibility is checked by the library."""
+    """(cubes, ctx, (C array of handles, D), hts) of a time-series call; the cubes' compatibility is checked by the library."""
     cubes = list(cubes)
     if not cubes:
         raise ValueError('a series needs at least one epoch cube')
     ctx = cubes[0].ctx
-    rays.adopt_stream(ctx)
-    if rays.ht_min is not None:
-        raise ValueError('per-ray heights (rays.hts) are not supported in a series')
-    hts = f64(np.atleast_1d(hts)).ravel()
-    S = hts.size
-    if rays.slices not in (0, S):
-        raise ValueError(f'the ray batch carries look vectors for {rays.slices} slices, {S} heights were given')
-    return cubes, ctx, (C.c_void_p * len(cubes))(*[c.handle for c in cubes]), hts, S
+    hts = _slice_heights(ctx, rays, hts, 'per-ray heights (rays.hts) are not supported in a series')
+    return cubes, ctx, ((C.c_void_p * len(cubes))(*[c.handle for c in cubes]), len(cubes)), hts
 
 
 def raytrace_slices_epochs(cubes, rays, hts, zref, max_seg=1000.0, out=None, want_partition=True, want_nan=False):
@@ -534,42 +545,17 @@ def raytrace_slices_epochs(cubes, rays, hts, zref, max_seg=1000.0, out=None, wan
     Returns (wet[D,S,...], hydro[D,S,...], K[S], nparts[S, nz-1], flags[D,S]) - K and nparts are shared by every epoch, the flags'
     partition bits too; the last three are None when want_partition is False (fully asynchronous for device arrays).
     want_nan=True: a sixth element, bool[D,S] = np.isnan(result[e, s]).any() as scanned on the device."""
-    cubes, ctx, handles, hts, S = _epoch_args(cubes, rays, hts)
-    D = len(cubes)
-    if out is not None:
-        wet, hyd = out
-    elif rays._torch_device is not None:
-        import torch
-        wet = torch.empty((D, S) + tuple(rays.shape), dtype=torch.float64, device=rays._torch_device)
-        hyd = torch.empty_like(wet)
-    else:
-        wet = _pinned.empty((D, S) + tuple(rays.shape)); hyd = _pinned.empty((D, S) + tuple(rays.shape))
-    rays.check_outputs(wet, hyd, slices=S * D)
-    ld = cubes[0].shape[2] - 1
-    if want_partition:
-        K = np.zeros(S, dtype=np.int32); nparts = np.zeros((S, ld), dtype=np.int32); flags = np.zeros((D, S), dtype=np.int32)
-        check(ctx.lib.rdr_raytrace_slices_epochs(ctx.handle, handles, D, C.byref(rays.struct), ptr(hts), S, int(rays.slices > 0), float(zref),
-                                                 float(max_seg), ptr(wet), ptr(hyd), ptr(K), ptr(nparts), ld, ptr(flags)), ctx.handle)
-        nan_out = (flags & L.FLAG_NAN_OUTPUT) != 0
-        flags &= ~np.int32(L.FLAG_NAN_OUTPUT)
-        return (wet, hyd, K, nparts, flags, nan_out) if want_nan else (wet, hyd, K, nparts, flags)
-    check(ctx.lib.rdr_raytrace_slices_epochs(ctx.handle, handles, D, C.byref(rays.struct), ptr(hts), S, int(rays.slices > 0), float(zref),
-                                             float(max_seg), ptr(wet), ptr(hyd), None, None, ld, None), ctx.handle)
-    return wet, hyd, None, None, None
+    cubes, ctx, cube_args, hts = _epoch_args(cubes, rays, hts)
+    return _trace_slices(ctx, ctx.lib.rdr_raytrace_slices_epochs, cube_args, (len(cubes),), cubes[0].shape[2] - 1, rays, hts, zref, max_seg, out,
+                         want_partition, want_nan)
 
 
 def raytrace_slices_epochs_to_cubes(cubes, rays, hts, zref, max_seg=1000.0):
     """raytrace_slices_epochs() whose delays stay on the device: ([Cube with axes (ypts, xpts, hts)] * D, K[S], nparts[S, nz-1],
     flags[D,S]) - what Cube.raytrace_slices_to_cube makes for each epoch.  GRID batches only."""
-    cubes, ctx, handles, hts, S = _epoch_args(cubes, rays, hts)
-    D = len(cubes)
-    ld = cubes[0].shape[2] - 1
-    K = np.zeros(S, dtype=np.int32); nparts = np.zeros((S, ld), dtype=np.int32); flags = np.zeros((D, S), dtype=np.int32)
-    hs = (C.c_void_p * D)()
-    check(ctx.lib.rdr_raytrace_slices_epochs_to_cubes(ctx.handle, handles, D, C.byref(rays.struct), ptr(hts), S, int(rays.slices > 0), float(zref),
-                                                      float(max_seg), ptr(K), ptr(nparts), ld, ptr(flags), hs), ctx.handle)
-    flags &= ~np.int32(L.FLAG_NAN_OUTPUT)
-    return [Cube._from_handle(ctx, C.c_void_p(h)) for h in hs], K, nparts, flags
+    cubes, ctx, cube_args, hts = _epoch_args(cubes, rays, hts)
+    return _trace_slices_to_cubes(ctx, ctx.lib.rdr_raytrace_slices_epochs_to_cubes, cube_args, (len(cubes),), cubes[0].shape[2] - 1, rays, hts,
+                                  zref, max_seg)
 
 
 class Rays:
