@@ -224,6 +224,14 @@ int rdr_transform_tm(rdr_ctx* ctx, const double* params, int nparams, int direct
  * direction 0: in = (lat, lon) deg -> out = (y, x) m; 1: in = (y, x) m -> out = (lat, lon) deg. */
 int rdr_transform_cone(rdr_ctx* ctx, int kind, const double* params, int nparams, int direction, const double* in_a, const double* in_b,
                        int64_t n, double* out_a, double* out_b, int loc);
+/* Output grids in a PROJECTED CRS (out_proj = a UTM zone, an LCC or a polar-stereographic CRS; delay.py:207-209,259-263).
+ * grid_kind RDR_GRID_TM: params as rdr_transform_tm; RDR_PROJ_LCC / RDR_PROJ_STERE: params as rdr_cube_set_projection.
+ * rdr_grid_geodetic: lat[iy*nx+ix], lon[iy*nx+ix] (deg) of the node (ypts[iy], xpts[ix]) - `xx, yy = np.meshgrid(xpts, ypts)` then
+ * transformPoints(yy, xx, ., grid CRS, EPSG:4326) (delay.py:261-263), bit for bit what rdr_transform_tm / rdr_transform_cone direction 1
+ * return on the same nodes.  Axes and outputs at `loc`.  The origins of a ray-traced cube on such a grid (an LLH rdr_rays batch). */
+#define RDR_GRID_TM 3
+int rdr_grid_geodetic(rdr_ctx* ctx, int grid_kind, const double* params, int nparams, const double* xpts, int64_t nx, const double* ypts,
+                      int64_t ny, double* lat, double* lon, int loc);
 /* temporal blend, cli/raider.py:817-819: out = w1*a + w2*b (f32 cubes blend in f32, f64 in f64) */
 int rdr_cube_blend(rdr_ctx* ctx, const rdr_cube* a, double w1, const rdr_cube* b, double w2, rdr_cube** out);
 /* Azimuth-time-grid temporal interpolation.
@@ -273,6 +281,12 @@ int64_t rdr_cube_point_index_bytes(const rdr_cube* cube);
 /* _build_cube (delay.py:196-216) for model_crs == pts_crs: out[(iz*ny+iy)*nx+ix] = f(ypts[iy],xpts[ix],zpts[iz]) */
 int rdr_build_cube(rdr_ctx* ctx, const rdr_cube* cube, const double* xpts, int64_t nx, const double* ypts,
                    int64_t ny, const double* zpts, int64_t nz, double* wet, double* hydro, int loc);
+/* rdr_build_cube on an output grid in a projected CRS (grid_kind / params as rdr_grid_geodetic): replaces the per-height loop of
+ * delay.py:205-215 (transformPoints(yy, xx, ht, pts_crs, model_crs) + the interpolator calls).  The nodes are transformed once - the
+ * projection is 2-D - by the transform kernels, to lon/lat or, for a cube that carries a projection (rdr_cube_set_projection /
+ * rdr_cube_view: the model CRS), on to the model's cone; the gather is rdr_build_cube's.  Same bits as that loop. */
+int rdr_build_cube_grid(rdr_ctx* ctx, const rdr_cube* cube, int grid_kind, const double* params, int nparams, const double* xpts, int64_t nx,
+                        const double* ypts, int64_t ny, const double* zpts, int64_t nz, double* wet, double* hydro, int loc);
 /* 1 / 0: the result of the last rdr_build_cube call with HOST arrays on this ctx holds / does not hold a NaN - the scan the caller
  * runs over the result (delay.py:187) done on the device before the download; -1: unknown (no such call yet, or device arrays). */
 int rdr_last_nan_output(rdr_ctx* ctx);
@@ -282,6 +296,10 @@ int rdr_last_nan_output(rdr_ctx* ctx);
  * ("There are missing delay values").  Needs two nodes per axis (scipy's grid rule), nz <= 512. */
 int rdr_build_cube_to_cube(rdr_ctx* ctx, const rdr_cube* cube, const double* xpts, int64_t nx, const double* ypts, int64_t ny,
                            const double* zpts, int64_t nz, int loc, rdr_cube** out);
+/* rdr_build_cube_to_cube on an output grid in a projected CRS (as rdr_build_cube_grid); the new cube's axes are (ypts, xpts, zpts) in
+ * that CRS. */
+int rdr_build_cube_grid_to_cube(rdr_ctx* ctx, const rdr_cube* cube, int grid_kind, const double* params, int nparams, const double* xpts,
+                                int64_t nx, const double* ypts, int64_t ny, const double* zpts, int64_t nz, int loc, rdr_cube** out);
 /* rdr_interp3 on the two-epoch temporal blend w1 * a + w2 * b (cli/raider.py:817-819) WITHOUT making the blended cube: the blend is
  * applied at the eight corners of every point, in the cubes' own dtype with blend_kernel's arithmetic - the same bits as rdr_cube_blend
  * followed by rdr_interp3.  It reads eight lines per point instead of four and none of the blend's 24 B per cell: the better deal for a
@@ -304,6 +322,12 @@ int rdr_interp3_blend_cube(rdr_ctx* ctx, const rdr_cube* a, double w1, const rdr
 int rdr_point_delays(rdr_ctx* ctx, const rdr_cube* cube, const double* xpts, int64_t nx, const double* ypts, int64_t ny, const double* zpts,
                      int64_t nz, const double* y, const double* x, const double* z, int64_t n, int proj_mode, const double* proj, double inc0,
                      double* wet, double* hydro, int32_t* cube_has_nan);
+/* rdr_point_delays with the intermediate grid in a projected CRS (grid_kind / params as rdr_grid_geodetic; the query points y, x, z
+ * in that CRS): the point branch of delay.py:96-128 for out_proj = UTM / LCC / polar stereographic in one call (the reference's
+ * per-height loop delay.py:205-215 for the cube, then the gather). */
+int rdr_point_delays_grid(rdr_ctx* ctx, const rdr_cube* cube, int grid_kind, const double* params, int nparams, const double* xpts, int64_t nx,
+                          const double* ypts, int64_t ny, const double* zpts, int64_t nz, const double* y, const double* x, const double* z, int64_t n,
+                          int proj_mode, const double* proj, double inc0, double* wet, double* hydro, int32_t* cube_has_nan);
 /* Conventional.__call__ tail (losreader.py:130-133): delay / cosd(inc) in place, inc[n] in degrees (what inc_hd_to_enu(...)[..., -1]
  * holds for an incidence raster).  The reference projects wet and hydro in two calls: either pointer may be NULL. */
 int rdr_project_cosinc(rdr_ctx* ctx, double* wet, double* hydro, const double* inc, int64_t n, int loc);
@@ -356,8 +380,9 @@ int rdr_raytrace_slices(rdr_ctx* ctx, const rdr_cube* cube, const rdr_rays* rays
                         int32_t* nparts_out, int32_t ld, int32_t* flags_out);
 
 /* rdr_raytrace_slices whose delays STAY on the device as a new float64 cube with axes (rays->ypts, rays->xpts, hts): the intermediate
- * cube of tropo_delay's point branch for a ray-traced line of sight (delay.py:96-121).  GRID batches, >= 2 nodes per axis, strictly
- * monotonic hts; the partition outputs are as for rdr_raytrace_slices. */
+ * cube of tropo_delay's point branch for a ray-traced line of sight (delay.py:96-121).  GRID batches, or LLH batches of a projected
+ * output grid (origins from rdr_grid_geodetic) that carry the grid's axes in xpts[nx] / ypts[ny] with n == nx * ny; >= 2 nodes per
+ * axis, strictly monotonic hts; the partition outputs are as for rdr_raytrace_slices. */
 int rdr_raytrace_slices_to_cube(rdr_ctx* ctx, const rdr_cube* cube, const rdr_rays* rays, const double* hts, int32_t nslices,
                                 int32_t los_per_slice, double zref, double max_seg, int32_t* K_out, int32_t* nparts_out, int32_t ld,
                                 int32_t* flags_out, rdr_cube** out);
@@ -375,7 +400,8 @@ int rdr_raytrace_slices_epochs(rdr_ctx* ctx, const rdr_cube* const* cubes, int32
                                int32_t* K_out, int32_t* nparts_out, int32_t ld, int32_t* flags_out);
 
 /* rdr_raytrace_slices_epochs whose delays stay on the device: out[ncubes] new float64 cubes with axes (rays->ypts, rays->xpts, hts),
- * as rdr_raytrace_slices_to_cube makes one - the intermediate cubes of a series of station queries.  GRID batches only. */
+ * as rdr_raytrace_slices_to_cube makes one - the intermediate cubes of a series of station queries.  The batches rdr_raytrace_slices_to_cube
+ * takes. */
 int rdr_raytrace_slices_epochs_to_cubes(rdr_ctx* ctx, const rdr_cube* const* cubes, int32_t ncubes, const rdr_rays* rays,
                                         const double* hts, int32_t nslices, int32_t los_per_slice, double zref, double max_seg,
                                         int32_t* K_out, int32_t* nparts_out, int32_t ld, int32_t* flags_out, rdr_cube** out);

@@ -19,6 +19,7 @@ RDR_F32, RDR_F64 = 0, 1
 RDR_BYTESWAPPED = 0x100
 RDR_HOST, RDR_DEVICE = 0, 1
 ORIGIN_GRID, ORIGIN_LLH, ORIGIN_XYZ = 0, 1, 2
+RDR_PROJ_LCC, RDR_PROJ_STERE, RDR_GRID_TM = 1, 2, 3
 LOS_VEC, LOS_INC_HD, LOS_INC_HD_SCALAR, LOS_ZENITH = 0, 1, 2, 3
 FLAG_ANY_NAN, FLAG_ANY_FINITE, FLAG_FIRST_NOT_BELOW, FLAG_LAST_NOT_ABOVE, FLAG_DIVERGED, FLAG_BAD_HEIGHT, FLAG_NAN_OUTPUT = 1, 2, 4, 8, 16, 32, 64
 
@@ -83,6 +84,7 @@ SYMBOLS = [
     ('rdr_project_points', C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, _VP, _VP, C.c_int]),
     ('rdr_transform_tm', C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, C.c_int64, _VP, _VP, C.c_int]),
     ('rdr_transform_cone', C.c_int, [_VP, C.c_int, _VP, C.c_int, C.c_int, _VP, _VP, C.c_int64, _VP, _VP, C.c_int]),
+    ('rdr_grid_geodetic', C.c_int, [_VP, C.c_int, _VP, C.c_int, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_int]),
     ('rdr_cube_blend', C.c_int, [_VP, _VP, C.c_double, _VP, C.c_double, C.POINTER(_VP)]),
     ('rdr_cube_read', C.c_int, [_VP, _VP, _VP, _VP]),
     ('rdr_cube_point_index', C.c_int, [_VP, _VP, C.c_int]),
@@ -93,9 +95,13 @@ SYMBOLS = [
     ('rdr_interp3_blend_cube', C.c_int, [_VP, _VP, C.c_double, _VP, C.c_double, _VP, _VP, _VP, C.c_int64, _VP, _VP, C.c_int]),
     ('rdr_build_cube', C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_int]),
     ('rdr_build_cube_to_cube', C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, C.c_int, C.POINTER(_VP)]),
+    ('rdr_build_cube_grid', C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, C.c_int]),
+    ('rdr_build_cube_grid_to_cube', C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, C.c_int, C.POINTER(_VP)]),
     ('rdr_last_nan_output', C.c_int, [_VP]),
     ('rdr_point_delays', C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, C.c_int, _VP, C.c_double, _VP, _VP,
                                    c_ip]),
+    ('rdr_point_delays_grid', C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, C.c_int,
+                                        _VP, C.c_double, _VP, _VP, c_ip]),
     ('rdr_project_cosinc', C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int]),
     ('rdr_project_divide', C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int]),
     ('rdr_ray_levels', C.c_int, [_VP, C.c_double, C.c_double, c_ip, _VP, _VP, _VP]),

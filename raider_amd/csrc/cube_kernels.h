@@ -622,6 +622,46 @@ __global__ __launch_bounds__(256) void build_cube_setup_kernel(CubeView<T2> c, L
     }
 }
 
+// build_cube_setup_kernel for an output grid in a projected CRS (rdr_build_cube_grid): node i's cube coordinates (qy[i], qx[i]) were
+// made beforehand by the transform kernels (transformPoints(yy, xx, ht, pts_crs, model_crs), delay.py:207-209 - once per node, the
+// projection is 2-D); the cells and weights are those of the kernel above.
+template <typename T2>
+__global__ __launch_bounds__(256) void build_cube_setup_table_kernel(CubeView<T2> c, const double* __restrict__ qys, const double* __restrict__ qxs,
+                                                                     int64_t nodes, const double* __restrict__ zpts, int64_t nz,
+                                                                     BuildNode* __restrict__ nodes_out, BuildLevel* __restrict__ levels_out, int axes_in_lds) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const double* s_y = c.axes;
+    if (axes_in_lds) {
+        double* t = reinterpret_cast<double*>(smem_raw);
+        for (int i = threadIdx.x; i < c.ny + c.nx + c.nz; i += blockDim.x) t[i] = c.axes[i];
+        __syncthreads();
+        s_y = t;
+    }
+    const double* s_x = s_y + c.ny;
+    const double* s_z = s_x + c.nx;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nodes + nz; i += (int64_t)gridDim.x * blockDim.x) {
+        if (i >= nodes) {
+            const double z = zpts[i - nodes];
+            BuildLevel L; L.cz = -1; L.tz = 0.0; L.pad = 0;
+            if ((z >= c.z_lo) && (z <= c.z_hi)) {
+                L.cz = find_cell(s_z, c.nz, z, c.z_lo, c.inv_dz, c.uni_z);
+                L.tz = (z - s_z[L.cz]) / (s_z[L.cz + 1] - s_z[L.cz]);
+            }
+            levels_out[i - nodes] = L;
+            continue;
+        }
+        const double qy = qys[i], qx = qxs[i];
+        BuildNode N; N.cy = -1; N.cx = 0; N.ty = 0.0; N.tx = 0.0;
+        if ((qy >= c.y_lo) && (qy <= c.y_hi) && (qx >= c.x_lo) && (qx <= c.x_hi)) {
+            N.cy = find_cell(s_y, c.ny, qy, c.y_lo, c.inv_dy, c.uni_y);
+            N.cx = find_cell(s_x, c.nx, qx, c.x_lo, c.inv_dx, c.uni_x);
+            N.ty = (qy - s_y[N.cy]) / (s_y[N.cy + 1] - s_y[N.cy]);
+            N.tx = (qx - s_x[N.cx]) / (s_x[N.cx + 1] - s_x[N.cx]);
+        }
+        nodes_out[i] = N;
+    }
+}
+
 template <typename T2>
 __global__ __launch_bounds__(256) void build_cube_kernel(const T2* __restrict__ cv, int cny, int cnx, int cnz, const BuildNode* __restrict__ nrec,
                                                          const BuildLevel* __restrict__ lrec, int64_t nx, int64_t ny, int64_t nz, int64_t zchunk,

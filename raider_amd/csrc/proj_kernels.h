@@ -123,4 +123,17 @@ __global__ __launch_bounds__(256) void cone_kernel(LccParams L, int dir, const d
     }
 }
 
+// `xx, yy = np.meshgrid(xpts, ypts)` of an output grid (delay.py:205,261), row-major (ny, nx): the input of tm_kernel / cone_kernel
+// direction 1 for a projected grid (rdr_grid_geodetic, rdr_build_cube_grid) - the transforms themselves stay those kernels, so the
+// nodes come out bit for bit as transformPoints gives them.
+__global__ __launch_bounds__(256) void grid_mesh_kernel(const double* __restrict__ xpts, int64_t nx, const double* __restrict__ ypts, int64_t ny,
+                                                        double* __restrict__ yy, double* __restrict__ xx) {
+    const int64_t n = nx * ny;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t iy = i / nx;
+        yy[i] = ypts[iy];
+        xx[i] = xpts[i - iy * nx];
+    }
+}
+
 }  // namespace rdr

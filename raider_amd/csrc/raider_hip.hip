@@ -993,6 +993,75 @@ int rdr_transform_tm(rdr_ctx* c, const double* p, int np, int direction, const d
     return RDR_OK;
 }
 
+// ---- output grids in a projected CRS (transformPoints of delay.py:207-209,262-263 on the (ny, nx) meshgrid) -------------------------
+// grid_kind RDR_GRID_TM: params as rdr_transform_tm; RDR_PROJ_LCC / RDR_PROJ_STERE: params as rdr_cube_set_projection.
+struct GridCrs { int kind; TmParams T; LccParams L; };
+
+static int grid_crs(rdr_ctx* c, const char* who, int kind, const double* p, int np, GridCrs& g) {
+    const std::string w(who);
+    g.kind = kind;
+    if (kind == RDR_GRID_TM) {
+        if (!p || np < 7) return fail(c, RDR_ERR_INVALID, w + ": RDR_GRID_TM needs 7 parameters (a, es, lat_0, lon_0, k_0, x_0, y_0)");
+        if (!(p[0] > 0) || p[1] < 0 || p[1] >= 1 || std::fabs(p[2]) > 90 || !(p[4] > 0)) return fail(c, RDR_ERR_INVALID, w + ": invalid transverse-Mercator parameters");
+        g.T = tm_setup(p[0], p[1], p[2], p[3], p[4], p[5], p[6]);
+        return RDR_OK;
+    }
+    if (kind == RDR_PROJ_LCC || kind == RDR_PROJ_STERE) return cone_params(c, who, kind, p, np, g.L);
+    return fail(c, RDR_ERR_INVALID, w + ": grid_kind is RDR_GRID_TM, RDR_PROJ_LCC or RDR_PROJ_STERE");
+}
+
+static int grid_counts(rdr_ctx* c, const char* who, int64_t nx, int64_t ny) {
+    if (nx < 0 || ny < 0) return fail(c, RDR_ERR_INVALID, std::string(who) + ": negative count");
+    if (nx > ((int64_t)1 << 31) || ny > ((int64_t)1 << 31) || (nx > 0 && ny > ((int64_t)1 << 34) / nx))
+        return fail(c, RDR_ERR_INVALID, std::string(who) + ": grid too large");
+    return RDR_OK;
+}
+
+// The nodes of the grid (device axes dx[nx], dy[ny]) as (lat, lon) deg, or - model->kind == 1 - as (y, x) in the conic model CRS: the
+// meshgrid, then tm_kernel / cone_kernel direction 1 (then cone_kernel direction 0 with the model's cone), each launched as
+// rdr_transform_tm / rdr_transform_cone launch it - the same bits as transformPoints.  t0, t1, u0, u1: nx*ny doubles of scratch each;
+// (*oy, *ox) point into them.
+static int grid_nodes(rdr_ctx* c, const GridCrs& g, const double* dx, int64_t nx, const double* dy, int64_t ny, const LccParams* model,
+                      double* t0, double* t1, double* u0, double* u1, const double** oy, const double** ox) {
+    const int64_t n = nx * ny;
+    const dim3 gs(grid_for(n, 256, c->num_cus * 8));
+    hipLaunchKernelGGL(grid_mesh_kernel, gs, dim3(256), 0, c->stream, dx, nx, dy, ny, t0, t1);
+    if (g.kind == RDR_GRID_TM) hipLaunchKernelGGL(tm_kernel, gs, dim3(256), 0, c->stream, g.T, 1, (const double*)t0, (const double*)t1, n, u0, u1);
+    else hipLaunchKernelGGL(cone_kernel, gs, dim3(256), 0, c->stream, g.L, 1, (const double*)t0, (const double*)t1, n, u0, u1);
+    *oy = u0; *ox = u1;
+    if (model && model->kind == 1) {
+        hipLaunchKernelGGL(cone_kernel, gs, dim3(256), 0, c->stream, *model, 0, (const double*)u0, (const double*)u1, n, t0, t1);
+        *oy = t0; *ox = t1;
+    }
+    HIPCHECK(c, hipGetLastError());
+    return RDR_OK;
+}
+
+int rdr_grid_geodetic(rdr_ctx* c, int grid_kind, const double* params, int nparams, const double* xpts, int64_t nx, const double* ypts, int64_t ny,
+                      double* lat, double* lon, int loc) {
+    static const char* who = "rdr_grid_geodetic";
+    if (!c || !xpts || !ypts || !lat || !lon) return fail(c, RDR_ERR_INVALID, "rdr_grid_geodetic: NULL argument");
+    GridCrs g;
+    int rc = grid_crs(c, who, grid_kind, params, nparams, g); if (rc) return rc;
+    rc = grid_counts(c, who, nx, ny); if (rc) return rc;
+    const int64_t n = nx * ny;
+    if (n == 0) return RDR_OK;
+    HIPCHECK(c, hipSetDevice(c->device));
+    const void *dx, *dy; void *t, *ola, *olo;
+    rc = stage_in(c, SLOT_IN0, xpts, (size_t)nx * 8, loc, &dx); if (rc) return rc;
+    rc = stage_in(c, SLOT_IN1, ypts, (size_t)ny * 8, loc, &dy); if (rc) return rc;
+    rc = ensure(c, SLOT_IN2, (size_t)n * 16, &t); if (rc) return rc;
+    rc = stage_out(c, SLOT_OUT0, lat, (size_t)n * 8, loc, &ola); if (rc) return rc;
+    rc = stage_out(c, SLOT_OUT1, lon, (size_t)n * 8, loc, &olo); if (rc) return rc;
+    const double *oy, *ox;
+    rc = grid_nodes(c, g, (const double*)dx, nx, (const double*)dy, ny, nullptr, (double*)t, (double*)t + n, (double*)ola, (double*)olo, &oy, &ox);
+    if (rc) return rc;
+    rc = finish_out(c, lat, ola, (size_t)n * 8, loc); if (rc) return rc;
+    rc = finish_out(c, lon, olo, (size_t)n * 8, loc); if (rc) return rc;
+    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return RDR_OK;
+}
+
 int rdr_cube_blend(rdr_ctx* c, const rdr_cube* a, double w1, const rdr_cube* b, double w2, rdr_cube** out) {
     if (!c || !a || !b || !out) return fail(c, RDR_ERR_INVALID, "rdr_cube_blend: NULL argument");
     note_use(c, a); note_use(c, b);
@@ -1434,7 +1503,8 @@ int rdr_interp3_project(rdr_ctx* c, const rdr_cube* q, const double* y, const do
 // _build_cube (delay.py:196-216).  keep == NULL: the public entry (results to the caller's wet / hydro at `loc`); keep != NULL: the results
 // stay in the context's scratch (planar (z,y,x), keep[0] = wet, keep[1] = hydro) for rdr_build_cube_to_cube, nothing is downloaded.
 static int build_cube_impl(rdr_ctx* c, const rdr_cube* q, const double* xpts, int64_t nx, const double* ypts, int64_t ny,
-                           const double* zpts, int64_t nz, double* wet, double* hydro, int loc, double** keep, const double** dev_yxz = nullptr) {
+                           const double* zpts, int64_t nz, double* wet, double* hydro, int loc, double** keep, const double** dev_yxz = nullptr,
+                           const GridCrs* grid = nullptr) {
     if (!c || !q || !xpts || !ypts || !zpts || (!keep && (!wet || !hydro))) return fail(c, RDR_ERR_INVALID, "rdr_build_cube: NULL argument");
     note_use(c, q);
     if (nx < 0 || ny < 0 || nz < 0) return fail(c, RDR_ERR_INVALID, "rdr_build_cube: negative count");
@@ -1460,6 +1530,8 @@ static int build_cube_impl(rdr_ctx* c, const rdr_cube* q, const double* xpts, in
     void *dn, *dl;
     rc = ensure(c, SLOT_IN3, (size_t)nodes * sizeof(BuildNode), &dn); if (rc) return rc;
     rc = ensure(c, SLOT_IN4, (size_t)nz * sizeof(BuildLevel), &dl); if (rc) return rc;
+    double* tbl = nullptr;                        // a projected grid (rdr_build_cube_grid): its nodes in the cube's CRS, 4 x 8 B per node of scratch
+    if (grid) { void* t; rc = ensure(c, SLOT_IN1, (size_t)nodes * 32, &t); if (rc) return rc; tbl = (double*)t; }
     const int64_t ntile = ((nx + 63) / 64) * ((ny + 3) / 4);
     const int64_t want_tiles = (int64_t)c->num_cus * 8;
     int64_t nchunks = std::min<int64_t>(nz, std::max<int64_t>(1, (want_tiles + ntile - 1) / ntile));
@@ -1473,16 +1545,26 @@ static int build_cube_impl(rdr_ctx* c, const rdr_cube* q, const double* xpts, in
     {
         KTimer t(c, 2);
         const int gs = grid_for(nodes + nz, 256, c->num_cus * 8);
+        const double *qy = nullptr, *qx = nullptr;
+        if (grid) { rc = grid_nodes(c, *grid, (const double*)dx, nx, (const double*)dy, ny, &q->proj, tbl, tbl + nodes, tbl + 2 * nodes, tbl + 3 * nodes, &qy, &qx); if (rc) return rc; }
         hipError_t e;
         if (q->dtype == RDR_F32) {
-            e = launch_lds(build_cube_setup_kernel<float2>, dim3(gs), dim3(256), axes_smem(q), c->stream, make_view<float2>(q), q->proj, (const double*)dx, nx,
-                           (const double*)dy, ny, (const double*)dz, nz, (BuildNode*)dn, (BuildLevel*)dl, (int)axes_fit_lds(q));
+            if (grid)
+                e = launch_lds(build_cube_setup_table_kernel<float2>, dim3(gs), dim3(256), axes_smem(q), c->stream, make_view<float2>(q), qy, qx, nodes,
+                               (const double*)dz, nz, (BuildNode*)dn, (BuildLevel*)dl, (int)axes_fit_lds(q));
+            else
+                e = launch_lds(build_cube_setup_kernel<float2>, dim3(gs), dim3(256), axes_smem(q), c->stream, make_view<float2>(q), q->proj, (const double*)dx, nx,
+                               (const double*)dy, ny, (const double*)dz, nz, (BuildNode*)dn, (BuildLevel*)dl, (int)axes_fit_lds(q));
             if (e == hipSuccess)
                 e = launch_lds(build_cube_kernel<float2>, g, dim3(256), sm, c->stream, (const float2*)q->d_vals, (int)q->ny, (int)q->nx, (int)q->nz,
                                (const BuildNode*)dn, (const BuildLevel*)dl, nx, ny, nz, zchunk, (double*)dw, (double*)dh);
         } else {
-            e = launch_lds(build_cube_setup_kernel<double2>, dim3(gs), dim3(256), axes_smem(q), c->stream, make_view<double2>(q), q->proj, (const double*)dx, nx,
-                           (const double*)dy, ny, (const double*)dz, nz, (BuildNode*)dn, (BuildLevel*)dl, (int)axes_fit_lds(q));
+            if (grid)
+                e = launch_lds(build_cube_setup_table_kernel<double2>, dim3(gs), dim3(256), axes_smem(q), c->stream, make_view<double2>(q), qy, qx, nodes,
+                               (const double*)dz, nz, (BuildNode*)dn, (BuildLevel*)dl, (int)axes_fit_lds(q));
+            else
+                e = launch_lds(build_cube_setup_kernel<double2>, dim3(gs), dim3(256), axes_smem(q), c->stream, make_view<double2>(q), q->proj, (const double*)dx, nx,
+                               (const double*)dy, ny, (const double*)dz, nz, (BuildNode*)dn, (BuildLevel*)dl, (int)axes_fit_lds(q));
             if (e == hipSuccess)
                 e = launch_lds(build_cube_kernel<double2>, g, dim3(256), sm, c->stream, (const double2*)q->d_vals, (int)q->ny, (int)q->nx, (int)q->nz,
                                (const BuildNode*)dn, (const BuildLevel*)dl, nx, ny, nz, zchunk, (double*)dw, (double*)dh);
@@ -1513,6 +1595,15 @@ int rdr_build_cube(rdr_ctx* c, const rdr_cube* q, const double* xpts, int64_t nx
     return build_cube_impl(c, q, xpts, nx, ypts, ny, zpts, nz, wet, hydro, loc, nullptr);
 }
 
+int rdr_build_cube_grid(rdr_ctx* c, const rdr_cube* q, int grid_kind, const double* params, int nparams, const double* xpts, int64_t nx,
+                        const double* ypts, int64_t ny, const double* zpts, int64_t nz, double* wet, double* hydro, int loc) {
+    if (!c || !q || !xpts || !ypts || !zpts || !wet || !hydro) return fail(c, RDR_ERR_INVALID, "rdr_build_cube_grid: NULL argument");
+    GridCrs g;
+    int rc = grid_crs(c, "rdr_build_cube_grid", grid_kind, params, nparams, g); if (rc) return rc;
+    rc = grid_counts(c, "rdr_build_cube_grid", nx, ny); if (rc) return rc;
+    return build_cube_impl(c, q, xpts, nx, ypts, ny, zpts, nz, wet, hydro, loc, nullptr, nullptr, &g);
+}
+
 int rdr_last_nan_output(rdr_ctx* c) { return c ? c->last_nan_output : -1; }
 
 // host copy of an axis given at `loc` (the cube keeps its axes on the host as well)
@@ -1526,10 +1617,9 @@ static int axis_to_host(rdr_ctx* c, const double* a, int64_t n, int loc, std::ve
     return RDR_OK;
 }
 
-int rdr_build_cube_to_cube(rdr_ctx* c, const rdr_cube* q, const double* xpts, int64_t nx, const double* ypts, int64_t ny,
-                           const double* zpts, int64_t nz, int loc, rdr_cube** out) {
-    if (!c || !q || !xpts || !ypts || !zpts || !out) return fail(c, RDR_ERR_INVALID, "rdr_build_cube_to_cube: NULL argument");
-    if (nx < 2 || ny < 2 || nz < 2) return fail(c, RDR_ERR_INVALID, "rdr_build_cube_to_cube: the delay cube needs two nodes per axis");
+static int build_to_cube(rdr_ctx* c, const char* who, const rdr_cube* q, const GridCrs* grid, const double* xpts, int64_t nx, const double* ypts,
+                         int64_t ny, const double* zpts, int64_t nz, int loc, rdr_cube** out) {
+    if (nx < 2 || ny < 2 || nz < 2) return fail(c, RDR_ERR_INVALID, std::string(who) + ": the delay cube needs two nodes per axis");
     HIPCHECK(c, hipSetDevice(c->device));
     std::vector<double> hx, hy, hz;
     int rc = axis_to_host(c, xpts, nx, loc, hx); if (rc) return rc;
@@ -1537,11 +1627,27 @@ int rdr_build_cube_to_cube(rdr_ctx* c, const rdr_cube* q, const double* xpts, in
     rc = axis_to_host(c, zpts, nz, loc, hz); if (rc) return rc;
     double* planar[2] = {nullptr, nullptr};
     const double* dev_yxz[3] = {nullptr, nullptr, nullptr};       // the axes as the build has them on the device (scratch slot / the caller's arrays)
-    rc = build_cube_impl(c, q, xpts, nx, ypts, ny, zpts, nz, nullptr, nullptr, loc, planar, dev_yxz); if (rc) return rc;
+    rc = build_cube_impl(c, q, xpts, nx, ypts, ny, zpts, nz, nullptr, nullptr, loc, planar, dev_yxz, grid); if (rc) return rc;
     // planar (z,y,x) results -> interleaved (y,x,z) cube with axes (ypts, xpts, zpts): what getInterpolators(ds, 'ztd') builds from the
     // Dataset of writeResultsToXarray (delay.py:113, delayFcns.py:40-41), descending axes flipped as scipy does; its NaN scan
     // (delayFcns.py:50-52 on this cube == np.isnan(result).any(), delay.py:187) comes with the packing
     return cube_create_impl(c, hy.data(), ny, hx.data(), nx, hz.data(), nz, planar[0], planar[1], RDR_F64, nx, 1, ny * nx, RDR_DEVICE, out, dev_yxz);
+}
+
+int rdr_build_cube_to_cube(rdr_ctx* c, const rdr_cube* q, const double* xpts, int64_t nx, const double* ypts, int64_t ny,
+                           const double* zpts, int64_t nz, int loc, rdr_cube** out) {
+    if (!c || !q || !xpts || !ypts || !zpts || !out) return fail(c, RDR_ERR_INVALID, "rdr_build_cube_to_cube: NULL argument");
+    return build_to_cube(c, "rdr_build_cube_to_cube", q, nullptr, xpts, nx, ypts, ny, zpts, nz, loc, out);
+}
+
+int rdr_build_cube_grid_to_cube(rdr_ctx* c, const rdr_cube* q, int grid_kind, const double* params, int nparams, const double* xpts, int64_t nx,
+                                const double* ypts, int64_t ny, const double* zpts, int64_t nz, int loc, rdr_cube** out) {
+    static const char* who = "rdr_build_cube_grid_to_cube";
+    if (!c || !q || !xpts || !ypts || !zpts || !out) return fail(c, RDR_ERR_INVALID, "rdr_build_cube_grid_to_cube: NULL argument");
+    GridCrs g;
+    int rc = grid_crs(c, who, grid_kind, params, nparams, g); if (rc) return rc;
+    rc = grid_counts(c, who, nx, ny); if (rc) return rc;
+    return build_to_cube(c, who, q, &g, xpts, nx, ypts, ny, zpts, nz, loc, out);
 }
 
 
@@ -1550,14 +1656,14 @@ int rdr_build_cube_to_cube(rdr_ctx* c, const rdr_cube* q, const double* xpts, in
 // points -> delay / cos(inc).  Everything is enqueued before anything is waited for: the points travel up (copy stream) while the
 // intermediate cube is built (ctx stream), the cube lives in the context's scratch (no allocation per call), its NaN verdict
 // (delay.py:187) comes back with the final synchronisation.  Same kernels, same arithmetic as the separate entries: same bits.
-int rdr_point_delays(rdr_ctx* c, const rdr_cube* q, const double* xpts, int64_t nx, const double* ypts, int64_t ny, const double* zpts, int64_t nz,
-                     const double* y, const double* x, const double* z, int64_t n, int proj_mode, const double* proj, double inc0,
-                     double* wet, double* hydro, int32_t* cube_has_nan) {
-    if (!c || !q || !xpts || !ypts || !zpts) return fail(c, RDR_ERR_INVALID, "rdr_point_delays: NULL argument");
-    if (nx < 2 || ny < 2 || nz < 2) return fail(c, RDR_ERR_INVALID, "rdr_point_delays: the delay cube needs two nodes per axis");
-    if (nz > MAX_LEVELS) return fail(c, RDR_ERR_INVALID, "rdr_point_delays: more than 512 height levels");
-    if (ny + nx + nz > 100000) return fail(c, RDR_ERR_INVALID, "rdr_point_delays: axes too long");
-    int rc = point_query_args(c, "rdr_point_delays", y, x, z, n, proj_mode, proj, wet, hydro); if (rc) return rc;
+static int point_delays_impl(rdr_ctx* c, const char* who, const rdr_cube* q, const GridCrs* grid, const double* xpts, int64_t nx, const double* ypts,
+                             int64_t ny, const double* zpts, int64_t nz, const double* y, const double* x, const double* z, int64_t n, int proj_mode,
+                             const double* proj, double inc0, double* wet, double* hydro, int32_t* cube_has_nan) {
+    const std::string w(who);
+    if (nx < 2 || ny < 2 || nz < 2) return fail(c, RDR_ERR_INVALID, w + ": the delay cube needs two nodes per axis");
+    if (nz > MAX_LEVELS) return fail(c, RDR_ERR_INVALID, w + ": more than 512 height levels");
+    if (ny + nx + nz > 100000) return fail(c, RDR_ERR_INVALID, w + ": axes too long");
+    int rc = point_query_args(c, who, y, x, z, n, proj_mode, proj, wet, hydro); if (rc) return rc;
     int fy, fx, fz;
     if (axis_check(ypts, ny, &fy) || axis_check(xpts, nx, &fx) || axis_check(zpts, nz, &fz))
         return fail(c, RDR_ERR_INVALID, "The points in each dimension must be strictly ascending or descending (and >= 2)");
@@ -1582,7 +1688,7 @@ int rdr_point_delays(rdr_ctx* c, const rdr_cube* q, const double* xpts, int64_t 
     StreamsQuiesce quiesce(c);                  // (`ax`, the caller's points and outputs: nothing may still be copying when an error returns)
     HIPCHECK(c, hipMemcpyAsync(daxes, ax.data(), ax.size() * 8, hipMemcpyHostToDevice, c->stream));
     double* planar[2] = {nullptr, nullptr};
-    rc = build_cube_impl(c, q, xpts, nx, ypts, ny, zpts, nz, nullptr, nullptr, RDR_HOST, planar); if (rc) return rc;
+    rc = build_cube_impl(c, q, xpts, nx, ypts, ny, zpts, nz, nullptr, nullptr, RDR_HOST, planar, nullptr, grid); if (rc) return rc;
     int* const nf = c->d_flags + MAX_SLICES + 2;
     HIPCHECK(c, hipMemsetAsync(nf, 0, sizeof(int), c->stream));
     if (nx >= 8 && nz >= 8)        // planar (z, y, x) results: x is contiguous - the LDS-transposing packer (cube_kernels.h)
@@ -1600,7 +1706,7 @@ int rdr_point_delays(rdr_ctx* c, const rdr_cube* q, const double* xpts, int64_t 
         PointQuery Q; std::memset(&Q, 0, sizeof(Q));
         Q.pmode = proj_mode; Q.inc0 = inc0;
         static const int slots[6] = {SLOT_PT0, SLOT_PT1, SLOT_PT2, SLOT_PT3, SLOT_PT4, SLOT_PT5};
-        rc = interp_pipeline(c, "rdr_point_delays", &tmp, false, y, x, z, n, Q, proj, wet, hydro, slots); if (rc) return rc;
+        rc = interp_pipeline(c, who, &tmp, false, y, x, z, n, Q, proj, wet, hydro, slots); if (rc) return rc;
     } else HIPCHECK(c, hipStreamSynchronize(c->stream));
     quiesce.armed = false;                      // (both branches have synchronised)
     if (cube_has_nan) *cube_has_nan = c->h_word[0] != 0;
@@ -1611,6 +1717,23 @@ int rdr_point_delays(rdr_ctx* c, const rdr_cube* q, const double* xpts, int64_t 
         if (b.p && b.cap > keep) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
     }
     return RDR_OK;
+}
+
+int rdr_point_delays(rdr_ctx* c, const rdr_cube* q, const double* xpts, int64_t nx, const double* ypts, int64_t ny, const double* zpts, int64_t nz,
+                     const double* y, const double* x, const double* z, int64_t n, int proj_mode, const double* proj, double inc0,
+                     double* wet, double* hydro, int32_t* cube_has_nan) {
+    if (!c || !q || !xpts || !ypts || !zpts) return fail(c, RDR_ERR_INVALID, "rdr_point_delays: NULL argument");
+    return point_delays_impl(c, "rdr_point_delays", q, nullptr, xpts, nx, ypts, ny, zpts, nz, y, x, z, n, proj_mode, proj, inc0, wet, hydro, cube_has_nan);
+}
+
+int rdr_point_delays_grid(rdr_ctx* c, const rdr_cube* q, int grid_kind, const double* params, int nparams, const double* xpts, int64_t nx,
+                          const double* ypts, int64_t ny, const double* zpts, int64_t nz, const double* y, const double* x, const double* z, int64_t n,
+                          int proj_mode, const double* proj, double inc0, double* wet, double* hydro, int32_t* cube_has_nan) {
+    static const char* who = "rdr_point_delays_grid";
+    if (!c || !q || !xpts || !ypts || !zpts) return fail(c, RDR_ERR_INVALID, "rdr_point_delays_grid: NULL argument");
+    GridCrs g;
+    const int rc = grid_crs(c, who, grid_kind, params, nparams, g); if (rc) return rc;
+    return point_delays_impl(c, who, q, &g, xpts, nx, ypts, ny, zpts, nz, y, x, z, n, proj_mode, proj, inc0, wet, hydro, cube_has_nan);
 }
 
 static int project_impl(rdr_ctx* c, const char* who, double* wet, double* hydro, int pmode, const double* proj, int64_t n, int loc) {
@@ -2451,7 +2574,8 @@ static int raytrace_slices_impl(rdr_ctx* c, const char* who, const rdr_cube* con
 }
 
 // The _to_cube(s) entries: raytrace_slices_impl with its delays left in scratch, made into D float64 cubes with axes (ypts, xpts, hts)
-// on the device.  The entries have checked that the batch is a GRID of at least two nodes per axis.
+// on the device.  The entries have checked that the batch is a GRID (or an LLH batch with its grid's axes, cube_batch) of at least two
+// nodes per axis.
 static int raytrace_slices_to_cubes(rdr_ctx* c, const char* who, const rdr_cube* const* qs, int32_t D, const rdr_rays* r, const double* hts,
                                     int32_t nslices, int32_t los_per_slice, double zref, double max_seg, int32_t* K_out, int32_t* nparts_out,
                                     int32_t ld, int32_t* flags_out, rdr_cube** out) {
@@ -2473,6 +2597,13 @@ static int raytrace_slices_to_cubes(rdr_ctx* c, const char* who, const rdr_cube*
         }
     }
     return RDR_OK;
+}
+
+// the batches a delay cube can be made of: GRID, or LLH origins of a projected output grid (rdr_grid_geodetic) that carry the grid's
+// axes in xpts / ypts with n == nx * ny
+static bool cube_batch(const rdr_rays* r) {
+    if (r->origin_mode == RDR_ORIGIN_GRID) return true;
+    return r->origin_mode == RDR_ORIGIN_LLH && r->xpts && r->ypts && r->nx > 0 && r->ny > 0 && r->nx <= r->n / r->ny && r->nx * r->ny == r->n;
 }
 
 static const char k_one_batch[] = "rdr_raytrace_slices: per-ray heights (rays->hts) describe ONE batch; use rdr_raytrace";
@@ -2497,7 +2628,7 @@ int rdr_raytrace_slices_to_cube(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r
                                 double zref, double max_seg, int32_t* K_out, int32_t* nparts_out, int32_t ld, int32_t* flags_out,
                                 rdr_cube** out) {
     if (!c || !q || !r || !hts || !out) return fail(c, RDR_ERR_INVALID, "rdr_raytrace_slices_to_cube: NULL argument");
-    if (r->origin_mode != RDR_ORIGIN_GRID) return fail(c, RDR_ERR_INVALID, "rdr_raytrace_slices_to_cube: the delay cube is a GRID batch (xpts, ypts) x heights");
+    if (!cube_batch(r)) return fail(c, RDR_ERR_INVALID, "rdr_raytrace_slices_to_cube: the delay cube is a GRID batch (xpts, ypts) x heights, or an LLH batch of nx * ny rays with its grid's axes");
     if (r->nx < 2 || r->ny < 2 || nslices < 2) return fail(c, RDR_ERR_INVALID, "rdr_raytrace_slices_to_cube: the delay cube needs two nodes per axis");
     if (r->hts) return fail(c, RDR_ERR_INVALID, k_one_batch);
     return raytrace_slices_to_cubes(c, "rdr_raytrace_slices", &q, 1, r, hts, nslices, los_per_slice, zref, max_seg, K_out, nparts_out, ld,
@@ -2521,7 +2652,7 @@ int rdr_raytrace_slices_epochs_to_cubes(rdr_ctx* c, const rdr_cube* const* cubes
     static const char* who = "rdr_raytrace_slices_epochs_to_cubes";
     int rc = epochs_check(c, who, cubes, ncubes); if (rc) return rc;
     if (!r || !hts || !out) return fail(c, RDR_ERR_INVALID, std::string(who) + ": NULL argument");
-    if (r->origin_mode != RDR_ORIGIN_GRID) return fail(c, RDR_ERR_INVALID, std::string(who) + ": the delay cubes are a GRID batch (xpts, ypts) x heights");
+    if (!cube_batch(r)) return fail(c, RDR_ERR_INVALID, std::string(who) + ": the delay cubes are a GRID batch (xpts, ypts) x heights, or an LLH batch of nx * ny rays with its grid's axes");
     if (r->nx < 2 || r->ny < 2 || nslices < 2) return fail(c, RDR_ERR_INVALID, std::string(who) + ": the delay cubes need two nodes per axis");
     rc = series_rays_check(c, who, r); if (rc) return rc;
     return raytrace_slices_to_cubes(c, who, cubes, ncubes, r, hts, nslices, los_per_slice, zref, max_seg, K_out, nparts_out, ld, flags_out, out);

@@ -378,8 +378,8 @@ def tropo_delay(datetime, weather_model_file, aoi, los, height_levels=None, out_
     pts = (lats, lons, hgts) if _is_4326(out_proj) else (transformPoints(lats, lons, hgts, 4326, out_proj),)
     res = _point_branch_on_device(weather_model_file, wm_proj, aoi, height_levels, los, crs, zref, var, pts, kw)
     if res is None:
-        # jobs the device route does not take (an output CRS that is neither the model's nor lon/lat, a one-node grid axis, > 512
-        # heights): the reference's own sequence
+        # jobs the device route does not take (an output CRS that is neither the model's, nor lon/lat, nor a UTM / conic CRS, a one-node
+        # grid axis, > 512 heights): the reference's own sequence
         ds = _get_delays_on_cube(datetime, weather_model_file, wm_proj, aoi, height_levels, los, crs, zref, _loaded=var)
         try:
             ifWet, ifHydro = getInterpolators(ds, 'ztd')
@@ -406,12 +406,20 @@ class SeriesResult(list):
 
 
 def series_route(aoi, los, out_proj):
-    """The stacked route a series on this AOI / LOS could take: 'cube' (a ray-traced LOS on a lon/lat output grid - the batched
-    branch of _build_cube_ray), 'points' (a ray-traced LOS through _point_branch_on_device), or None (zenith / projected lines of
-    sight and everything else: one tropo_delay per date)."""
+    """The stacked route a series on this AOI / LOS could take with a LON/LAT output grid: 'cube' (a ray-traced LOS on a lon/lat output
+    grid - the batched branch of _build_cube_ray), 'points' (a ray-traced LOS through _point_branch_on_device), or None (zenith /
+    projected lines of sight and everything else: one tropo_delay per date).  stacked_route answers for every output CRS."""
     if los.is_Zenith() or los.is_Projected() or not hasattr(los, 'ray_batch_slices') or not _is_4326(out_proj):
         return None
     return 'cube' if _is_cube_aoi(aoi) else 'points'
+
+
+def stacked_route(aoi, los, out_proj):
+    """series_route for any output CRS: a UTM / conic output grid (grid_projection) stacks as a lon/lat one does - its ray origins are
+    made on the device (Rays.grid(..., crs=...)).  What tropo_delay_series follows."""
+    if _is_4326(out_proj) or grid_projection(out_proj) is None:
+        return series_route(aoi, los, out_proj)
+    return series_route(aoi, los, 4326)
 
 
 def epochs_compatible(a, b):
@@ -466,8 +474,10 @@ def _stacked_cube(plans, datetimes, los, crs):
     D = len(cubes)
     outs = [[np.empty((zpts.size, ypts.size, xpts.size)) for _ in range(2)] for _ in range(D)]
 
+    kw = _ray_crs_kw(crs)
+
     def trace(s0, zz):
-        rays = los.ray_batch_slices(xpts, ypts, zz)
+        rays = los.ray_batch_slices(xpts, ypts, zz, **kw)
         dw, dh, K, _nparts, flags, nan_out = raytrace_slices_epochs(cubes, rays, zz, zref, 1000.0, want_nan=True)
         if rays._torch_device is not None:
             dw, dh = dw.cpu().numpy(), dh.cpu().numpy()
@@ -500,7 +510,7 @@ def _stacked_points(plans, los, aoi, out_proj):
     from ._lib import DeviceOutOfMemory
     cubes = [p['cube'] for p in plans]
     try:
-        rays = los.ray_batch_slices(xpts, ypts, zpts)
+        rays = los.ray_batch_slices(xpts, ypts, zpts, **_ray_crs_kw(out_proj))
         dcubes, K, _nparts, flags = raytrace_slices_epochs_to_cubes(cubes, rays, zpts, zref, 1000.0)
     except (MemoryError, RuntimeError) as exc:
         if not (isinstance(exc, DeviceOutOfMemory) or type(exc).__name__ == 'OutOfMemoryError'):
@@ -522,7 +532,7 @@ def tropo_delay_series(datetimes, weather_model_files, aoi, los, height_levels=N
     SeriesResult equal, element for element, to [tropo_delay(t, f, aoi, los, height_levels, out_proj, zref) for t, f in zip(...)]
     (values, Dataset attributes, NaN log lines; the first exception in date order is raised).
 
-    A ray-traced LOS on a lon/lat output grid (cube AOI) or through the station branch (points AOI) traces every date whose model
+    A ray-traced LOS on a lon/lat, UTM or conic output grid (cube AOI) or through the station branch (points AOI) traces every date whose model
     grid matches the first such date's (shape, dtype, axes, CRS) in one library call: pass 1 (ray polynomials, crossings, the slice
     partition) once, pass 2 for up to four dates together (rdr_raytrace_slices_epochs).  Everything else - zenith and projected lines
     of sight, the host fallbacks, dates on another grid, a single date - is one tropo_delay per date."""
@@ -530,7 +540,7 @@ def tropo_delay_series(datetimes, weather_model_files, aoi, los, height_levels=N
     files = list(weather_model_files)
     if len(datetimes) != len(files):
         raise ValueError(f'{len(datetimes)} dates but {len(files)} weather model files')
-    route = series_route(aoi, los, out_proj) if len(files) > 1 else None
+    route = stacked_route(aoi, los, out_proj) if len(files) > 1 else None
     stacked = {}
     if route is not None:
         plans = {}
@@ -648,8 +658,8 @@ def _point_branch_on_device(weather_model_file, wm_proj, aoi, heights, los, crs,
     """_get_delays_on_cube (delay.py:133-193) + the second-stage interpolation (delay.py:110-128) with the intermediate cube - what
     getInterpolators(ds, 'ztd') would wrap, axes (aoi.ypts, aoi.xpts, heights) - left ON THE DEVICE.  `pts`: (y, x, z) arrays or one
     packed array, in the output CRS; `kw`: inc= / divisor= of a projected line of sight.  Returns (wetDelay, hydroDelay), or None for
-    the jobs that need the host sequence (an output grid that is neither the model's CRS nor lon/lat, a one-node axis, > 512
-    heights).  Same kernels, same arithmetic as _build_cube / _build_cube_ray + the interpolators: the values are theirs bit for bit."""
+    the jobs that need the host sequence (an output grid that is neither the model's CRS, nor lon/lat, nor a UTM / conic CRS
+    (grid_projection), a one-node axis, > 512 heights).  Same kernels, same arithmetic as _build_cube / _build_cube_ray + the interpolators: the values are theirs bit for bit."""
     zpts = np.array(heights, dtype=np.float64)
     if _loaded is not None and not isinstance(weather_model_file, (str, os.PathLike)):
         weather_model_file = _loaded
@@ -661,6 +671,8 @@ def _point_branch_on_device(weather_model_file, wm_proj, aoi, heights, los, crs,
     if not (np.all(dz > 0) or np.all(dz < 0)):
         return None                                                    # (scipy's grid rule: the host sequence raises what it raises)
     from ._lib import DeviceOutOfMemory
+    grid = None if (_is_4326(crs) or _same_crs(wm_proj, crs)) else grid_projection(crs)
+    ray_kw = _ray_crs_kw(crs)
     try:
         if los.is_Zenith() or los.is_Projected():
             ifWet, ifHydro = getInterpolators(weather_model_file, 'total')
@@ -671,11 +683,15 @@ def _point_branch_on_device(weather_model_file, wm_proj, aoi, heights, los, crs,
                 cube, projected = _with_model_crs(cube, wm_proj)
                 if not projected:
                     return None
+            elif grid is not None:                                        # a UTM / conic grid: rdr_point_delays_grid
+                cube, projected = _with_model_crs(cube, 4326 if _is_4326(wm_proj) else wm_proj)
+                if not (projected or _is_4326(wm_proj)):
+                    return None
             else:
                 return None
-            wet, hyd, has_nan = cube.point_delays(xpts, ypts, zpts, *pts, **kw)
+            wet, hyd, has_nan = cube.point_delays(xpts, ypts, zpts, *pts, grid=grid, **kw)
         else:
-            if not (_is_4326(crs) and hasattr(los, 'ray_batch_slices')):
+            if ray_kw is None or not hasattr(los, 'ray_batch_slices'):
                 return None
             ifWet, ifHydro = getInterpolators(weather_model_file, kind='pointwise')
             cube, projected = _with_model_crs(ifWet.cube, wm_proj)
@@ -685,7 +701,7 @@ def _point_branch_on_device(weather_model_file, wm_proj, aoi, heights, los, crs,
             # the device next to the 16 B per cell of the cube itself); larger jobs take the chunked host sequence
             if xpts.size * ypts.size * zpts.size * 80 > int(os.environ.get('RAIDER_HIP_SLICE_BUDGET_BYTES', 8 << 30)):
                 return None
-            rays = los.ray_batch_slices(xpts, ypts, zpts)
+            rays = los.ray_batch_slices(xpts, ypts, zpts, **ray_kw)
             dcube, K, _nparts, flags = cube.raytrace_slices_to_cube(rays, zpts, zref, 1000.0)
             _raise_slice_failures(K, flags, zpts, zpts[-1])
             wet, hyd = dcube.interp_project(*pts, **kw)
@@ -743,8 +759,8 @@ def _build_cube(xpts, ypts, zpts, model_crs, pts_crs, interpolators):
     zpts = np.asarray(zpts)
     if _is_4326(model_crs):
         cube, _ = _with_model_crs(cube, 4326)              # (a cube that carries a projection: this call gets an unprojected view of it)
-    def hinted(c):
-        res = c.build_cube(xpts, ypts, zpts, want_nan=True)
+    def hinted(c, grid=None):
+        res = c.build_cube(xpts, ypts, zpts, want_nan=True, grid=grid)
         out = _Result(res[f] for f in fields)
         if len(out) == 2:                                 # what np.isnan(result).any() would find (delay.py:187): known from the device scan
             out.has_nan = res[2]                          # (part of the call's own result: the cube may be serving other threads)
@@ -755,6 +771,13 @@ def _build_cube(xpts, ypts, zpts, model_crs, pts_crs, interpolators):
         pcube, projected = _with_model_crs(cube, model_crs)
         if projected:
             return hinted(pcube)                           # lon/lat nodes projected to the model's LCC grid on the device
+    grid = None if _same_crs(model_crs, pts_crs) else grid_projection(pts_crs)
+    if grid is not None:
+        # a UTM / conic output grid: its nodes transformed once on the device (the projection is 2-D), then the gather of every height
+        # (rdr_build_cube_grid) - the loop below in one call, same bits
+        pcube, projected = (cube, True) if _is_4326(model_crs) else _with_model_crs(cube, model_crs)
+        if projected:
+            return hinted(pcube, grid)
     xx, yy = np.meshgrid(xpts, ypts)
     outputArrs = [np.zeros((zpts.size, len(ypts), len(xpts))) for _ in interpolators]
     for ii, ht in enumerate(zpts):
@@ -763,6 +786,14 @@ def _build_cube(xpts, ypts, zpts, model_crs, pts_crs, interpolators):
         for mm, f in enumerate(fields):
             outputArrs[mm][ii, ...] = res[f]
     return outputArrs
+
+
+def _ray_crs_kw(crs):
+    """The keyword a ray-batch constructor (Raytracing.ray_batch_slices, Rays.grid) takes for an output grid in `crs`: {} for lon/lat,
+    {'crs': crs} for a projected CRS the device transforms (grid_projection), None for anything else."""
+    if _is_4326(crs):
+        return {}
+    return {'crs': crs} if grid_projection(crs) is not None else None
 
 
 def _build_cube_ray(xpts, ypts, zpts, los, model_crs, pts_crs, interpolators, outputArrs=None,
@@ -787,11 +818,13 @@ def _build_cube_ray(xpts, ypts, zpts, los, model_crs, pts_crs, interpolators, ou
     direct = output_created_here and list(fields) == [0, 1]
 
     grid_is_ll = _is_4326(pts_crs)
-    if direct and grid_is_ll and hasattr(los, 'ray_batch_slices') and zpts.size > 0:
+    kw = {} if grid_is_ll else _ray_crs_kw(pts_crs)
+    if direct and (grid_is_ll or kw) and hasattr(los, 'ray_batch_slices') and zpts.size > 0:
         # the whole height loop as one batched launch pair per <= 512 slices (Cube.raytrace_slices): bit-identical to the slice
-        # loop below, but a production job (20 heights x 1e4-1e5 rays) fills the GPU instead of a tenth of it
+        # loop below, but a production job (20 heights x 1e4-1e5 rays) fills the GPU instead of a tenth of it.  A UTM / conic output
+        # grid: the origins are its nodes' lat / lon, made on the device once (rdr_grid_geodetic) - an LLH batch
         def trace(s0, zz):
-            rays = los.ray_batch_slices(xpts, ypts, zz)
+            rays = los.ray_batch_slices(xpts, ypts, zz, **kw)
             if rays._torch_device is None:
                 _, _, K, _nparts, flags, nan_out = cube.raytrace_slices(rays, zz, MAX_TROPO_HEIGHT, MAX_SEGMENT_LENGTH, want_nan=True,
                                                                         out=(outputArrs[0][s0:s0 + zz.size], outputArrs[1][s0:s0 + zz.size]))
@@ -916,6 +949,24 @@ def _builtin_crs(crs):
     if st is not None:
         return 'cone', dict(st, proj='stere')
     return None
+
+
+def grid_projection(crs):
+    """(grid_kind, params) of an output grid in a projected CRS the device transforms - the `grid` argument of Cube.build_cube /
+    Cube.point_delays / grid_geodetic (rdr_build_cube_grid, rdr_point_delays_grid, rdr_grid_geodetic): transverse Mercator (every UTM
+    zone) -> (RDR_GRID_TM, [a, es, lat_0, lon_0, k_0, x_0, y_0]); Lambert conformal conic / polar stereographic -> (RDR_PROJ_LCC /
+    RDR_PROJ_STERE, the parameters of rdr_cube_set_projection).  None for lon/lat, ECEF and every other CRS."""
+    from ._lib import RDR_GRID_TM
+    from .utilFcns import cone_abi, tm_abi
+    try:
+        kind = _builtin_crs(crs)
+    except NotImplementedError:                                       # (an oblique stereographic CRS)
+        return None
+    if kind is None or kind[0] not in ('tm', 'cone'):
+        return None
+    if kind[0] == 'tm':
+        return RDR_GRID_TM, tm_abi(kind[1])
+    return cone_abi(kind[1])
 
 
 def transformPoints(lats, lons, hgts, old_proj, new_proj):

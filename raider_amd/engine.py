@@ -303,33 +303,48 @@ class Cube:
             mode, parr = 3, f64(np.broadcast_to(np.asarray(divisor, dtype=np.float64), shape)).reshape(-1)
         return ya, xa, za, n, shape, mode, parr, inc0
 
-    def point_delays(self, xpts, ypts, zpts, y, x=None, z=None, inc=None, divisor=None):
+    def point_delays(self, xpts, ypts, zpts, y, x=None, z=None, inc=None, divisor=None, grid=None):
         """tropo_delay's point branch for a zenith / projected line of sight in ONE library call (rdr_point_delays): _build_cube of THIS
         (total-delay) cube on the output grid (xpts, ypts, zpts), the intermediate cube kept in device scratch, both fields gathered
         at the points (y, x, z: three arrays, or y = packed [..., 3]) and divided by cosd(inc) / `divisor` - delay.py:96-128,
-        losreader.py:130-133.  Returns (wet, hydro, has_nan): has_nan = the intermediate cube holds a NaN (delay.py:187)."""
+        losreader.py:130-133.  Returns (wet, hydro, has_nan): has_nan = the intermediate cube holds a NaN (delay.py:187).
+        grid=(grid_kind, params) (delay.grid_projection): the output grid and the points are in that projected CRS (rdr_point_delays_grid)."""
         gx, gy, gz = f64(xpts).ravel(), f64(ypts).ravel(), f64(np.atleast_1d(zpts)).ravel()
         ya, xa, za, n, shape, mode, parr, inc0 = self._point_args(y, x, z, inc, divisor)
         wet = _pinned.empty((n,)); hyd = _pinned.empty((n,))
         flag = C.c_int32(0)
-        check(self.ctx.lib.rdr_point_delays(self.ctx.handle, self.handle, ptr(gx), gx.size, ptr(gy), gy.size, ptr(gz), gz.size, ptr(ya), ptr(xa), ptr(za), n,
-                                            mode, ptr(parr), inc0, ptr(wet), ptr(hyd), C.byref(flag)), self.ctx.handle)
+        tail = (ptr(gx), gx.size, ptr(gy), gy.size, ptr(gz), gz.size, ptr(ya), ptr(xa), ptr(za), n, mode, ptr(parr), inc0, ptr(wet), ptr(hyd), C.byref(flag))
+        if grid is None:
+            check(self.ctx.lib.rdr_point_delays(self.ctx.handle, self.handle, *tail), self.ctx.handle)
+        else:
+            kind, gp = grid[0], f64(grid[1])
+            check(self.ctx.lib.rdr_point_delays_grid(self.ctx.handle, self.handle, int(kind), ptr(gp), gp.size, *tail), self.ctx.handle)
         return wet.reshape(shape), hyd.reshape(shape), bool(flag.value)
 
-    def build_delay_cube(self, xpts, ypts, zpts):
+    def build_delay_cube(self, xpts, ypts, zpts, grid=None):
         """_build_cube (delay.py:196-216) whose result stays on the device: a float64 `Cube` with axes (ypts, xpts, zpts) - the
         intermediate delay cube of tropo_delay's point branch (delay.py:96-121), ready for interp_project().  Its has_nan() is the
-        np.isnan(...).any() of delay.py:187."""
+        np.isnan(...).any() of delay.py:187.  grid: as build_cube (rdr_build_cube_grid_to_cube)."""
         x, y, z = f64(xpts).ravel(), f64(ypts).ravel(), f64(np.atleast_1d(zpts)).ravel()
         h = C.c_void_p()
-        check(self.ctx.lib.rdr_build_cube_to_cube(self.ctx.handle, self.handle, ptr(x), x.size, ptr(y), y.size, ptr(z), z.size, L.RDR_HOST, C.byref(h)),
-              self.ctx.handle)
+        tail = (ptr(x), x.size, ptr(y), y.size, ptr(z), z.size, L.RDR_HOST, C.byref(h))
+        if grid is None:
+            check(self.ctx.lib.rdr_build_cube_to_cube(self.ctx.handle, self.handle, *tail), self.ctx.handle)
+        else:
+            gp = f64(grid[1])
+            check(self.ctx.lib.rdr_build_cube_grid_to_cube(self.ctx.handle, self.handle, int(grid[0]), ptr(gp), gp.size, *tail), self.ctx.handle)
         return Cube._from_handle(self.ctx, h)
 
-    def build_cube(self, xpts, ypts, zpts, out=None, want_nan=False):
+    def build_cube(self, xpts, ypts, zpts, out=None, want_nan=False, grid=None):
         """_build_cube (delay.py:196-216): (wet, hydro) of shape (nz, ny, nx).  want_nan=True (host arrays): (wet, hydro, has_nan) with
         has_nan = np.isnan(result).any() as scanned on the device (None: not scanned) - part of the RESULT, not state of this object:
-        a cached cube serves several threads."""
+        a cached cube serves several threads.  grid=(grid_kind, params) (delay.grid_projection): xpts / ypts are the axes of a grid in that
+        projected CRS, transformed on the device to lon/lat or to this cube's projection (rdr_build_cube_grid)."""
+        if grid is None:
+            build = lambda *a: self.ctx.lib.rdr_build_cube(self.ctx.handle, self.handle, *a)
+        else:
+            gp = f64(grid[1])
+            build = lambda *a: self.ctx.lib.rdr_build_cube_grid(self.ctx.handle, self.handle, int(grid[0]), ptr(gp), gp.size, *a)
         if _is_dev(xpts):
             import torch
             self.ctx.adopt_torch_stream(xpts)
@@ -339,16 +354,14 @@ class Cube:
             wet, hyd = out if out is not None else (torch.empty((nz, ny, nx), dtype=torch.float64, device=xpts.device),
                                                     torch.empty((nz, ny, nx), dtype=torch.float64, device=xpts.device))
             _dev_f64(wet, 'out[0]', nx * ny * nz); _dev_f64(hyd, 'out[1]', nx * ny * nz)
-            check(self.ctx.lib.rdr_build_cube(self.ctx.handle, self.handle, ptr(xpts), nx, ptr(ypts), ny, ptr(zpts), nz,
-                                              ptr(wet), ptr(hyd), L.RDR_DEVICE), self.ctx.handle)
+            check(build(ptr(xpts), nx, ptr(ypts), ny, ptr(zpts), nz, ptr(wet), ptr(hyd), L.RDR_DEVICE), self.ctx.handle)
             return (wet, hyd, None) if want_nan else (wet, hyd)       # (device results are not scanned: the call stays asynchronous)
         x, y, z = f64(xpts).ravel(), f64(ypts).ravel(), f64(np.atleast_1d(zpts)).ravel()
         # (large cubes in recycled page-locked memory: the 640 MB of a 1000 x 1000 x 40 zenith cube come down in 12 ms instead of 40-120 ms
         # into freshly mapped pageable pages - _pinned.py)
         wet = _pinned.empty((z.size, y.size, x.size)); hyd = _pinned.empty((z.size, y.size, x.size))
         with self.ctx.lock:          # (the verdict is context state: read it before another thread's build on this context replaces it)
-            check(self.ctx.lib.rdr_build_cube(self.ctx.handle, self.handle, ptr(x), x.size, ptr(y), y.size, ptr(z), z.size,
-                                              ptr(wet), ptr(hyd), L.RDR_HOST), self.ctx.handle)
+            check(build(ptr(x), x.size, ptr(y), y.size, ptr(z), z.size, ptr(wet), ptr(hyd), L.RDR_HOST), self.ctx.handle)
             f = self.ctx.lib.rdr_last_nan_output(self.ctx.handle)
         if want_nan:
             return wet, hyd, (None if f < 0 else bool(f))             # np.isnan(result).any(), scanned on the device
@@ -450,7 +463,8 @@ class Cube:
 
     def raytrace_slices_to_cube(self, rays, hts, zref, max_seg=1000.0):
         """raytrace_slices() whose delays stay on the device: (Cube with axes (ypts, xpts, hts), K[S], nparts[S, nz-1], flags[S]) -
-        the intermediate cube of tropo_delay's point branch for a ray-traced line of sight.  GRID batches only."""
+        the intermediate cube of tropo_delay's point branch for a ray-traced line of sight.  GRID batches, or batches of a projected grid
+        (Rays.grid(..., crs=...))."""
         hts = _slice_heights(self.ctx, rays, hts, 'a batch with per-ray heights is ONE slice: use raytrace()')
         (cube,), K, nparts, flags = _trace_slices_to_cubes(self.ctx, self.ctx.lib.rdr_raytrace_slices_to_cube, (self.handle,), (), self.shape[2] - 1,
                                                          rays, hts, zref, max_seg)
@@ -640,18 +654,27 @@ class Rays:
                 raise ValueError('output arrays must be C-contiguous float64 NumPy arrays')
 
     @classmethod
-    def grid(cls, xpts, ypts, los=None, inc=None, hd=None, zenith=False, slices=0, hts=None):
+    def grid(cls, xpts, ypts, los=None, inc=None, hd=None, zenith=False, slices=0, hts=None, crs=None, geodetic=None):
         """Origins on meshgrid(xpts, ypts) (delay.py:242).  LOS: `los` (ny,nx,3) ECEF unit vectors, or
         inc/hd (scalars or (ny,nx) arrays, degrees), or zenith.  slices=S: los / inc / hd carry a leading slice axis of
         length S (look vectors that depend on the slice height; Cube.raytrace_slices).
         hts=(ny,nx): PER-PIXEL origin heights (a scene on a DEM) instead of one slice height - no reference semantics, the rule
-        is in include/raider_hip.h (rdr_rays.hts); then pass ht=None to the ray-tracing calls."""
+        is in include/raider_hip.h (rdr_rays.hts); then pass ht=None to the ray-tracing calls.
+        crs=: xpts / ypts are the axes of a grid in a PROJECTED CRS (UTM, LCC, polar stereographic: delay.grid_projection) - the
+        origins are its nodes' (lat, lon), made on the device (grid_geodetic; `geodetic` = those two (ny,nx) arrays when the caller
+        has them already): an LLH batch that carries the grid's axes, what Rays.points(lat, lon, ...) on transformPoints' nodes is
+        (delay.py:259-263), bit for bit."""
         r = cls()
         r.slices = int(slices)
         nx = xpts.numel() if _is_dev(xpts) else np.size(xpts)
         ny = ypts.numel() if _is_dev(ypts) else np.size(ypts)
-        r.struct.origin_mode = L.ORIGIN_GRID
         r.struct.nx, r.struct.ny, r.struct.n = nx, ny, nx * ny
+        if crs is None:
+            r.struct.origin_mode = L.ORIGIN_GRID
+        else:
+            lat, lon = geodetic if geodetic is not None else grid_geodetic(crs, xpts, ypts)
+            r.struct.origin_mode = L.ORIGIN_LLH
+            r._set('lat', lat); r._set('lon', lon)
         r._set('xpts', xpts); r._set('ypts', ypts)
         r.shape = (ny, nx)
         r._set_heights(hts)
@@ -790,6 +813,45 @@ def torch_device_or_none():
     import os
     idx = int(os.environ.get('RAIDER_HIP_DEVICE', os.environ.get('LOCAL_RANK', '-1')))
     return torch.device('cuda', idx if idx >= 0 else torch.cuda.current_device())
+
+
+def grid_geodetic(crs, xpts, ypts, device='auto', ctx=None):
+    """(lat, lon) deg, each (ny, nx), of the nodes of meshgrid(xpts, ypts) in a projected CRS - transformPoints(yy, xx, ., crs, 4326)
+    (delay.py:261-263) in one call (rdr_grid_geodetic), bit for bit.  `crs`: a CRS, or (grid_kind, params) as delay.grid_projection
+    gives.  device='auto': torch tensors on the GPU when the axes are device tensors, or torch is loaded / the grid is large (the origins
+    of a ray batch then stay there); None: NumPy arrays; a torch device: tensors there."""
+    import sys
+    from .delay import grid_projection
+    g = crs if isinstance(crs, tuple) else grid_projection(crs)
+    if g is None:
+        raise ValueError(f'{crs!r} is not a projected CRS the device transforms (transverse Mercator / UTM, Lambert conformal conic, polar stereographic)')
+    ctx = ctx or Context.default()
+    gp = f64(g[1])
+    nx = xpts.numel() if _is_dev(xpts) else np.size(xpts)
+    ny = ypts.numel() if _is_dev(ypts) else np.size(ypts)
+    if device == 'auto':
+        if _is_dev(xpts) and xpts.is_cuda:
+            device = xpts.device
+        else:
+            device = torch_device_or_none() if (nx * ny >= 1_000_000 or 'torch' in sys.modules) else None
+    if device is None:
+        x, y = f64(_as_numpy(xpts)).ravel(), f64(_as_numpy(ypts)).ravel()
+        lat, lon = np.empty((ny, nx)), np.empty((ny, nx))
+        ctx.set_stream(-1)
+        check(ctx.lib.rdr_grid_geodetic(ctx.handle, int(g[0]), ptr(gp), gp.size, ptr(x), nx, ptr(y), ny, ptr(lat), ptr(lon), L.RDR_HOST), ctx.handle)
+        return lat, lon
+    import torch
+    x = torch.as_tensor(xpts, dtype=torch.float64, device=device).contiguous().reshape(-1)
+    y = torch.as_tensor(ypts, dtype=torch.float64, device=device).contiguous().reshape(-1)
+    lat = torch.empty((ny, nx), dtype=torch.float64, device=device)
+    lon = torch.empty_like(lat)
+    ctx.adopt_torch_stream(lat)
+    check(ctx.lib.rdr_grid_geodetic(ctx.handle, int(g[0]), ptr(gp), gp.size, ptr(x), nx, ptr(y), ny, ptr(lat), ptr(lon), L.RDR_DEVICE), ctx.handle)
+    return lat, lon
+
+
+def _as_numpy(a):
+    return a.cpu().numpy() if _is_dev(a) else np.asarray(a)
 
 
 def lla2ecef_device(lat, lon, h, ctx=None):

@@ -229,12 +229,13 @@ class Raytracing(LOS):
             return Rays.grid(xpts, ypts, los=self._lv)
         return Rays.grid(xpts, ypts, inc=self._inc, hd=self._hd)
 
-    def _orbit_rays(self, xpts, ypts, hts, slices):
+    def _orbit_rays(self, xpts, ypts, hts, slices, crs=None):
         """Orbit-based look vectors for every (height, y, x) target in ONE zero-Doppler launch.  With torch on the GPU the targets,
         the look vectors and the ray batch stay on the device (grid -> ECEF -> look vectors -> Rays, no host round trip: for a
-        1000 x 1000 x 8 job the host route spends 20x the kernels' time moving 48 B per target back and forth); otherwise NumPy."""
+        1000 x 1000 x 8 job the host route spends 20x the kernels' time moving 48 B per target back and forth); otherwise NumPy.
+        crs=: a projected output grid (Rays.grid(..., crs=...)): the targets are its nodes' (lat, lon) at each height."""
         import sys
-        from .engine import Rays, lla2ecef_device, torch_device_or_none
+        from .engine import Rays, grid_geodetic, lla2ecef_device, torch_device_or_none
         # (importing torch costs a second or two once per process: worth it for anything but a small one-off job)
         big = np.size(xpts) * np.size(ypts) * np.size(hts) >= 1_000_000
         dev = torch_device_or_none() if (big or 'torch' in sys.modules) else None
@@ -243,29 +244,40 @@ class Raytracing(LOS):
             xt = torch.as_tensor(np.ascontiguousarray(xpts, dtype=np.float64), device=dev)
             yt = torch.as_tensor(np.ascontiguousarray(ypts, dtype=np.float64), device=dev)
             ht = torch.as_tensor(np.ascontiguousarray(hts, dtype=np.float64), device=dev)
-            xyz = lla2ecef_device(yt[None, :, None], xt[None, None, :], ht[:, None, None])         # (S, ny, nx, 3)
+            if crs is None:
+                geo = None
+                xyz = lla2ecef_device(yt[None, :, None], xt[None, None, :], ht[:, None, None])         # (S, ny, nx, 3)
+            else:
+                geo = grid_geodetic(crs, xt, yt)
+                xyz = lla2ecef_device(geo[0][None], geo[1][None], ht[:, None, None])
             los = self._orbit.look_vectors(xyz)
             del xyz
-            return Rays.grid(xt, yt, los=los if slices else los[0], slices=slices)
+            return Rays.grid(xt, yt, los=los if slices else los[0], slices=slices, crs=crs, geodetic=geo)
         from .utilFcns import lla2ecef
-        xx, yy = np.meshgrid(xpts, ypts)
+        if crs is None:
+            geo = None
+            xx, yy = np.meshgrid(xpts, ypts)
+        else:
+            geo = grid_geodetic(crs, xpts, ypts, device=None)
+            yy, xx = geo
         xyz = np.stack([np.stack(lla2ecef(yy, xx, np.full(yy.shape, float(h))), axis=-1) for h in hts], axis=0)
         los = self._orbit.look_vectors(xyz)
-        return Rays.grid(xpts, ypts, los=los if slices else los[0], slices=slices)
+        return Rays.grid(xpts, ypts, los=los if slices else los[0], slices=slices, crs=crs, geodetic=geo)
 
-    def ray_batch_slices(self, xpts, ypts, hts):
+    def ray_batch_slices(self, xpts, ypts, hts, crs=None):
         """Engine fast path for the whole height loop of _build_cube_ray: ONE `Rays` batch covering every slice.  Look vectors
         given as arrays / incidence + heading are the same for every height (as in getLookVectors); orbit-based ones depend on
-        the target height (losreader.py:219-255) and are solved for all slices in one zero-Doppler launch."""
+        the target height (losreader.py:219-255) and are solved for all slices in one zero-Doppler launch.  crs=: the axes are those
+        of a grid in a projected CRS (UTM, LCC, polar stereographic; delay.py:259-263) - an LLH batch on its nodes (Rays.grid)."""
         from .engine import Rays
         hts = np.atleast_1d(np.asarray(hts, dtype=np.float64))
         if self._lv is None and self._inc is None:
             if self._orbit is None:
                 raise ValueError('The orbit has not been set (call setTime)')
-            return self._orbit_rays(xpts, ypts, hts, slices=hts.size)
+            return self._orbit_rays(xpts, ypts, hts, slices=hts.size, crs=crs)
         if self._lv is not None:
-            return Rays.grid(xpts, ypts, los=self._lv)
-        return Rays.grid(xpts, ypts, inc=self._inc, hd=self._hd)
+            return Rays.grid(xpts, ypts, los=self._lv, crs=crs)
+        return Rays.grid(xpts, ypts, inc=self._inc, hd=self._hd, crs=crs)
 
     def getIntersectionWithHeight(self, height):
         """losreader.py:257-263: where the rays from `self._xyz` along `self._look_vecs` reach `height` (getTopOfAtmosphere)."""

@@ -82,6 +82,21 @@ def utm_params(epsg):
     return None
 
 
+def cone_abi(params):
+    """(kind, parameter array) of a conic CRS as the C ABI takes it (RDR_PROJ_LCC / RDR_PROJ_STERE; rdr_transform_cone)."""
+    if params.get('proj', 'lcc') == 'stere':
+        lat_ts = params.get('lat_ts')
+        return 2, np.array([params['a'], params['es'], params['lat_0'], np.nan if lat_ts is None else lat_ts, params.get('k_0', 1.0), params['lon_0'],
+                            params.get('x_0', 0.0), params.get('y_0', 0.0)], dtype=np.float64)
+    return 1, np.array([params['a'], params['es'], params['lat_1'], params['lat_2'], params['lat_0'], params['lon_0'], params.get('x_0', 0.0),
+                        params.get('y_0', 0.0)], dtype=np.float64)
+
+
+def tm_abi(params):
+    """The parameter array of a transverse-Mercator CRS as the C ABI takes it (rdr_transform_tm, RDR_GRID_TM)."""
+    return np.array([params[k] for k in ('a', 'es', 'lat_0', 'lon_0', 'k_0', 'x_0', 'y_0')], dtype=np.float64)
+
+
 def conic(a_in, b_in, params, inverse=False):
     """Forward: (lat, lon) deg -> (y, x) m; inverse: (y, x) m -> (lat, lon) deg for a conic model CRS, on the GPU (rdr_transform_cone).
     params: dict(proj='lcc', a, es, lat_1, lat_2, lat_0, lon_0, x_0, y_0) (HRRR, models/hrrr.py:248-259) or
@@ -92,15 +107,7 @@ def conic(a_in, b_in, params, inverse=False):
     shp = a_in.shape
     ua, ub = f64(a_in).ravel(), f64(b_in).ravel()
     oa, ob = np.empty(ua.size), np.empty(ua.size)
-    if params.get('proj', 'lcc') == 'stere':
-        kind = 2
-        lat_ts = params.get('lat_ts')
-        p = np.array([params['a'], params['es'], params['lat_0'], np.nan if lat_ts is None else lat_ts, params.get('k_0', 1.0), params['lon_0'],
-                      params.get('x_0', 0.0), params.get('y_0', 0.0)], dtype=np.float64)
-    else:
-        kind = 1
-        p = np.array([params['a'], params['es'], params['lat_1'], params['lat_2'], params['lat_0'], params['lon_0'], params.get('x_0', 0.0),
-                      params.get('y_0', 0.0)], dtype=np.float64)
+    kind, p = cone_abi(params)
     ctx = Context.default()
     check(ctx.lib.rdr_transform_cone(ctx.handle, kind, ptr(p), p.size, int(bool(inverse)), ptr(ua), ptr(ub), ua.size, ptr(oa), ptr(ob), L.RDR_HOST),
           ctx.handle)
@@ -117,7 +124,7 @@ def transverse_mercator(a_in, b_in, params, inverse=False):
     shp = a_in.shape
     ua, ub = f64(a_in).ravel(), f64(b_in).ravel()
     oa, ob = np.empty(ua.size), np.empty(ua.size)
-    p = np.array([params[k] for k in ('a', 'es', 'lat_0', 'lon_0', 'k_0', 'x_0', 'y_0')], dtype=np.float64)
+    p = tm_abi(params)
     ctx = Context.default()
     check(ctx.lib.rdr_transform_tm(ctx.handle, ptr(p), p.size, int(bool(inverse)), ptr(ua), ptr(ub), ua.size, ptr(oa), ptr(ob), L.RDR_HOST), ctx.handle)
     return oa.reshape(shp), ob.reshape(shp)
