@@ -158,7 +158,7 @@ int rdr_clock_sample_begin(rdr_ctx* ctx, double ms);
 int rdr_clock_sample_end(rdr_ctx* ctx, double* ghz);
 /* diagnostics: resources of the light ray kernel a GRID + look-vector batch on `cube` launches (which 0: pass 1 crossings_kernel,
  * 1: pass 2 march_kernel; 2 / 3: their per-ray-height instantiations, rdr_rays.hts; 4 / 5: the stacked march of
- * rdr_raytrace_slices_epochs for 2 / 4 epochs), read from the loaded code object (hipFuncGetAttributes): vector registers per lane, static LDS bytes,
+ * rdr_raytrace_slices_epochs for 2 / 4 epochs; 6 / 7: the per-ray-height stacked march of rdr_raytrace_epochs for 2 / 4 epochs), read from the loaded code object (hipFuncGetAttributes): vector registers per lane, static LDS bytes,
  * dynamic LDS bytes of the launch (axis / level tables), scratch bytes per lane, max threads per block.  Any output may be NULL. */
 int rdr_ray_kernel_attributes(rdr_ctx* ctx, const rdr_cube* cube, int which, int32_t* vgprs, int32_t* static_lds, int32_t* dynamic_lds,
                               int32_t* scratch, int32_t* max_threads);
@@ -392,7 +392,7 @@ int rdr_raytrace_slices_to_cube(rdr_ctx* ctx, const rdr_cube* cube, const rdr_ra
  * partition - runs once per chunk whatever ncubes is; pass 2 marches up to four epochs together (one cell search and address per
  * sample, one corner gather per epoch).  Epoch e's delays are bit for bit those of rdr_raytrace_slices on cubes[e].
  * The cubes must share shape, dtype, bitwise-equal axes and the projection (else RDR_ERR_INVALID naming the first epoch that
- * differs); rays with per-ray heights (rays->hts) are refused.  wet / hydro: [ncubes][nslices][n].  K_out[nslices] and
+ * differs); rays with per-ray heights (rays->hts) are refused (rdr_raytrace_epochs takes them).  wet / hydro: [ncubes][nslices][n].  K_out[nslices] and
  * nparts_out[nslices][ld] are shared by every epoch (the partition depends on geometry and levels only); flags_out[ncubes][nslices]:
  * the partition bits are equal across epochs, RDR_FLAG_NAN_OUTPUT is the epoch's own.  ncubes == 1 is rdr_raytrace_slices. */
 int rdr_raytrace_slices_epochs(rdr_ctx* ctx, const rdr_cube* const* cubes, int32_t ncubes, const rdr_rays* rays, const double* hts,
@@ -405,6 +405,19 @@ int rdr_raytrace_slices_epochs(rdr_ctx* ctx, const rdr_cube* const* cubes, int32
 int rdr_raytrace_slices_epochs_to_cubes(rdr_ctx* ctx, const rdr_cube* const* cubes, int32_t ncubes, const rdr_rays* rays,
                                         const double* hts, int32_t nslices, int32_t los_per_slice, double zref, double max_seg,
                                         int32_t* K_out, int32_t* nparts_out, int32_t ld, int32_t* flags_out, rdr_cube** out);
+
+/* A time series on ONE ray batch with ONE height per ray: rdr_raytrace of the same batch through ncubes weather epochs - a SAR scene
+ * on a DEM (rays->hts, `ht` <= min(hts) as for rdr_raytrace) traced for every acquisition date, or a plain batch at height `ht`.
+ * GRID, LLH and XYZ origins, every LOS mode.  Pass 1 - ray polynomials, level crossings, the per-level maxima, every ray's first
+ * level - runs once (per chunk when the ray records exceed the workspace limit); pass 2 marches up to four epochs together: per
+ * sample one set of polynomial evaluations, one cell search and one element offset, then one corner gather per epoch.  Epoch e's
+ * delays are bit for bit those of rdr_raytrace on cubes[e].  The cubes must share shape, dtype, bitwise-equal axes and the
+ * projection (else RDR_ERR_INVALID naming the first epoch that differs).  wet / hydro: [ncubes][n], epoch-major.  nparts_out[K] and
+ * *flags_out (either may be NULL; a device batch then stays asynchronous) belong to pass 1 and are shared by every epoch, as
+ * rdr_raytrace returns them; statuses are rdr_raytrace's.  ncubes == 1 is rdr_raytrace; only then is a large host batch uploaded
+ * through the pipelined path. */
+int rdr_raytrace_epochs(rdr_ctx* ctx, const rdr_cube* const* cubes, int32_t ncubes, const rdr_rays* rays, double ht, double zref,
+                        double max_seg, double* wet, double* hydro, int32_t* nparts_out, int32_t* flags_out);
 
 /* Materialising variants for API parity on small inputs:
  * getTopOfAtmosphere (losreader.py:706-733): factor==NULL -> 10 iterations with factor 1, else 3 */

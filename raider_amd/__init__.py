@@ -7,4 +7,4 @@ hand-written HIP kernels behind the C ABI of include/raider_hip.h.  No CPU fallb
 __version__ = '0.1.0'
 
 from ._lib import Context, NoLevels, load as load_library  # noqa: F401
-from .engine import Cube, Rays, grid_geodetic, nparts_from_maxlen, raytrace_slices_epochs, raytrace_slices_epochs_to_cubes  # noqa: F401
+from .engine import Cube, Rays, grid_geodetic, nparts_from_maxlen, raytrace_epochs, raytrace_slices_epochs, raytrace_slices_epochs_to_cubes  # noqa: F401

@@ -116,6 +116,7 @@ SYMBOLS = [
                                              _VP, _VP, _VP, _VP, C.c_int32, _VP]),
     ('rdr_raytrace_slices_epochs_to_cubes', C.c_int, [_VP, C.POINTER(_VP), C.c_int32, C.POINTER(RdrRays), _VP, C.c_int32, C.c_int32, C.c_double,
                                                       C.c_double, _VP, _VP, C.c_int32, _VP, C.POINTER(_VP)]),
+    ('rdr_raytrace_epochs', C.c_int, [_VP, C.POINTER(_VP), C.c_int32, C.POINTER(RdrRays), C.c_double, C.c_double, C.c_double, _VP, _VP, _VP, c_ip]),
     ('rdr_top_of_atmosphere', C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_double, _VP, _VP, C.c_int]),
     ('rdr_build_ray', C.c_int, [_VP, _VP, C.c_int64, C.c_double, _VP, _VP, C.c_int64, C.c_double, c_ip, _VP, _VP, _VP, C.c_int]),
     ('rdr_lla2ecef', C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, _VP, C.c_int]),

@@ -338,7 +338,7 @@ static hipError_t launch_lds(void (*kern)(KArgs...), dim3 g, dim3 b, size_t sm, 
 // ------------------------------------------------------------------------------------------------
 // (definitions below get C linkage from their extern "C" declarations in include/raider_hip.h)
 
-int rdr_version(void) { return 101; }
+int rdr_version(void) { return 102; }
 
 // sha256[:16] over the sources of this translation unit, handed in by the build recipe (-DRDR_SOURCE_HASH=...; __graft_entry__.build):
 // lets the loader prove that the binary it opened was compiled from the tree it sits in (mtimes do not survive a copy).
@@ -2028,11 +2028,19 @@ static int launch_march(rdr_ctx* c, const rdr_cube* q, RayParams P, int64_t tb, 
 // object (hipFuncGetAttributes) - what bench.py prints, instead of a profiler's metadata column.
 int rdr_ray_kernel_attributes(rdr_ctx* c, const rdr_cube* q, int which, int32_t* vgprs, int32_t* static_lds, int32_t* dynamic_lds,
                               int32_t* scratch, int32_t* max_threads) {
-    if (!c || !q || which < 0 || which > 5) return fail(c, RDR_ERR_INVALID, "rdr_ray_kernel_attributes: bad argument");
+    if (!c || !q || which < 0 || which > 7) return fail(c, RDR_ERR_INVALID, "rdr_ray_kernel_attributes: bad argument");
     const void* fn = nullptr;
     const bool lcc = q->proj.kind == 1;
     const bool pr = which == 2 || which == 3;      // 2 / 3: the per-ray-height instantiations of pass 1 / pass 2
-    if (which >= 4) {                              // 4 / 5: the stacked time-series march (march_epochs_kernel), E = 2 / 4
+    if (which >= 6) {                              // 6 / 7: the stacked per-ray-height march (march_epochs_pr_kernel), E = 2 / 4
+        const auto v32 = make_view<float2>(q);
+        const bool small = v32.small && (q->dtype == RDR_F32 || make_view<double2>(q).small);
+        const bool regular = small && q->exact[0] && q->exact[1];
+#define RDR_EPOCH_PR_FN(T2, E) (regular ? (const void*)march_epochs_pr_kernel<T2, E, 1> : (const void*)march_epochs_pr_kernel<T2, E, 0>)
+        if (q->dtype == RDR_F32) fn = which == 6 ? RDR_EPOCH_PR_FN(float2, 2) : RDR_EPOCH_PR_FN(float2, 4);
+        else fn = which == 6 ? RDR_EPOCH_PR_FN(double2, 2) : RDR_EPOCH_PR_FN(double2, 4);
+#undef RDR_EPOCH_PR_FN
+    } else if (which >= 4) {                       // 4 / 5: the stacked time-series march (march_epochs_kernel), E = 2 / 4
         const auto v32 = make_view<float2>(q);
         const bool small = v32.small && (q->dtype == RDR_F32 || make_view<double2>(q).small);
         const int grid = !small ? 0 : (q->exact[0] && q->exact[1]) ? 1 : (!q->exact[0] && !q->exact[1] && q->uni[0] && q->uni[1]) ? 2 : 0;
@@ -2452,6 +2460,72 @@ static int launch_march_epochs(rdr_ctx* c, const rdr_cube* const* qs, int D, Ray
     return RDR_OK;
 }
 
+// Epochs of the next stacked launch of a per-ray-height series (1: the one-epoch march on the shared pass 1).  f32 cubes: 4, 2, 1 as
+// the sliced series.  f64 cubes: pairs - the E = 4 instantiation is spill-free at one wave per SIMD only (EpochWavesPR; DESIGN.md 5d has
+// the measurements) - unless RAIDER_HIP_EPOCHS_PR_F64_MAX = 1 / 2 / 4 says otherwise (tools/bench_epochs.py compares them).
+// RAIDER_HIP_EPOCHS_MAX caps both.
+static int epochs_pr_group(int dtype, int left, int emax) {
+    const char* env = std::getenv("RAIDER_HIP_EPOCHS_PR_F64_MAX");
+    const int f64_max = env ? std::atoi(env) : 2;
+    if (dtype == RDR_F64) emax = std::min(emax, f64_max);
+    return (left >= 4 && emax >= 4) ? 4 : (left >= 2 && emax >= 2) ? 2 : 1;
+}
+
+template <typename T2, int E>
+static hipError_t launch_stacked_pr(rdr_ctx* c, const rdr_cube* const* qs, int grid, const RayParams& P, int64_t estride, dim3 G, dim3 B, size_t sm) {
+    EpochCubes<T2, E> ev;
+    for (int j = 0; j < E; ++j) ev.v[j] = (const T2*)qs[j]->d_vals;
+    const CubeView<T2> V = make_view<T2>(qs[0]);
+    return grid == 1 ? launch_lds(march_epochs_pr_kernel<T2, E, 1>, G, B, sm, c->stream, V, ev, P, estride)
+                     : launch_lds(march_epochs_pr_kernel<T2, E, 0>, G, B, sm, c->stream, V, ev, P, estride);
+}
+
+// launch_march_epochs for a batch with per-ray heights (P.ht_ray; one slice): the stacked groups take march_epochs_pr_kernel, a single
+// epoch launch_march (whose per-ray-height instantiation it is bit for bit).  A batch without them is launch_march_epochs' own.
+static int launch_march_epochs_pr(rdr_ctx* c, const rdr_cube* const* qs, int D, RayParams P, int64_t tb, int64_t tc, int64_t estride) {
+    if (!P.ht_ray) return launch_march_epochs(c, qs, D, P, tb, tc, estride);
+    const rdr_cube* q = qs[0];
+    const int emax = epochs_max();
+    const auto v32 = make_view<float2>(q);
+    const bool small = v32.small && (q->dtype == RDR_F32 || make_view<double2>(q).small);
+    const int grid = (small && q->exact[0] && q->exact[1]) ? 1 : 0;     // (launch_march's choice for per-ray heights)
+    const int g = ray_grid(c, tc, 8);
+    const size_t sm = ray_smem(q);
+    const dim3 G(g), B(BLOCK);
+    for (int e = 0; e < D;) {
+        const int ge = epochs_pr_group(q->dtype, D - e, emax);
+        RayParams Pe = P;
+        Pe.wet = P.wet + (int64_t)e * estride; Pe.hyd = P.hyd + (int64_t)e * estride;
+        if (ge == 1) {
+            const int rc = launch_march(c, qs[e], Pe, tb, tc); if (rc) return rc;
+            ++e;
+            continue;
+        }
+        Pe.tile_begin = tb; Pe.tile_count = tc; Pe.nslots = tc * BLOCK;
+        HIPCHECK(c, hipMemsetAsync(c->d_tilectr + 16, 0, 8 * sizeof(int), c->stream));
+        Pe.tile_ctr = c->d_tilectr + 16;
+        hipError_t err = hipSuccess;
+        {
+            KTimer t(c, 1);
+            if (q->dtype == RDR_F32) err = ge == 4 ? launch_stacked_pr<float2, 4>(c, qs + e, grid, Pe, estride, G, B, sm) : launch_stacked_pr<float2, 2>(c, qs + e, grid, Pe, estride, G, B, sm);
+            else err = ge == 4 ? launch_stacked_pr<double2, 4>(c, qs + e, grid, Pe, estride, G, B, sm) : launch_stacked_pr<double2, 2>(c, qs + e, grid, Pe, estride, G, B, sm);
+        }
+        if (err != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("march_epochs_pr_kernel launch: ") + hipGetErrorString(err));
+        for (int j = 0; j < ge; ++j) {                  // generic rays, epoch by epoch, on the same records and side buffer
+            RayParams Pj = Pe;
+            Pj.wet = Pe.wet + (int64_t)j * estride; Pj.hyd = Pe.hyd + (int64_t)j * estride;
+            HIPCHECK(c, hipMemsetAsync(c->d_tilectr + 24, 0, 8 * sizeof(int), c->stream));
+            Pj.tile_ctr = c->d_tilectr + 24;
+            const rdr_cube* qj = qs[e + j];
+            if (q->dtype == RDR_F32) err = launch_lds(march_kernel<float2, true>, G, B, sm, c->stream, make_view<float2>(qj), Pj, qj->proj);
+            else err = launch_lds(march_kernel<double2, true>, G, B, sm, c->stream, make_view<double2>(qj), Pj, qj->proj);
+            if (err != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("march_kernel launch: ") + hipGetErrorString(err));
+        }
+        e += ge;
+    }
+    return RDR_OK;
+}
+
 // Several height slices of _build_cube_ray in ONE pass-1 / pass-2 launch pair (delay.py:256-323 loops over them): a production
 // job is ~20 heights x 1e4-1e5 rays (aria/prepFromGUNW.py:173,180), and one such slice fills a fraction of the chip.  Tiles are
 // numbered slice-major; per-level maxima / flags / nParts stay per slice (RayParams), so the result is what slice-by-slice
@@ -2656,6 +2730,56 @@ int rdr_raytrace_slices_epochs_to_cubes(rdr_ctx* c, const rdr_cube* const* cubes
     if (r->nx < 2 || r->ny < 2 || nslices < 2) return fail(c, RDR_ERR_INVALID, std::string(who) + ": the delay cubes need two nodes per axis");
     rc = series_rays_check(c, who, r); if (rc) return rc;
     return raytrace_slices_to_cubes(c, who, cubes, ncubes, r, hts, nslices, los_per_slice, zref, max_seg, K_out, nparts_out, ld, flags_out, out);
+}
+
+// rdr_raytrace for D epoch cubes on ONE ray batch, per-ray heights (rays->hts) included: one pass 1 through ray_passes' workspace
+// schedule, every chunk's pass 2 through launch_march_epochs_pr.  Epoch e's delays are block e of [D][n]; nparts_out / flags_out are
+// pass 1's, shared by every epoch.  D = 1 is rdr_raytrace itself (with its pipelined host upload).
+int rdr_raytrace_epochs(rdr_ctx* c, const rdr_cube* const* cubes, int32_t ncubes, const rdr_rays* r, double ht, double zref, double max_seg,
+                        double* wet, double* hydro, int32_t* nparts_out, int32_t* flags_out) {
+    static const char* who = "rdr_raytrace_epochs";
+    int rc = epochs_check(c, who, cubes, ncubes); if (rc) return rc;
+    if (!wet || !hydro) return fail(c, RDR_ERR_INVALID, std::string(who) + ": NULL argument");
+    if (ncubes == 1) return rdr_raytrace(c, cubes[0], r, ht, zref, max_seg, wet, hydro, nparts_out, flags_out);
+    const rdr_cube* q = cubes[0];
+    for (int32_t e = 0; e < ncubes; ++e) note_use(c, cubes[e]);
+    if (!(max_seg > 0)) return fail(c, RDR_ERR_INVALID, std::string(who) + ": MAX_SEGMENT_LENGTH must be positive");
+    rc = check_rays(c, r); if (rc) return rc;
+    std::vector<double> lo, hi; std::vector<int> kz;
+    const int K = levels_host(q->zs, ht, zref, lo, hi, kz);
+    if (K == 0) return fail(c, RDR_ERR_NO_LEVELS, "no weather-model interval contributes to the ray integral (build_ray -> None)");
+    if (r->n == 0) return RDR_OK;
+    HIPCHECK(c, hipSetDevice(c->device));
+    RayParams P;
+    rc = stage_rays(c, r, P); if (rc) return rc;
+    P.ht = ht; P.zref = zref; P.max_seg = max_seg;
+    const size_t total = (size_t)r->n * (size_t)ncubes;
+    void *dw, *dh;
+    rc = stage_out(c, SLOT_OUT0, wet, total * 8, r->loc, &dw); if (rc) return rc;
+    rc = stage_out(c, SLOT_OUT1, hydro, total * 8, r->loc, &dh); if (rc) return rc;
+    P.wet = (double*)dw; P.hyd = (double*)dh;
+    HIPCHECK(c, hipMemsetAsync(c->d_maxlen, 0, MAX_LEVELS * sizeof(unsigned long long), c->stream));
+    HIPCHECK(c, hipMemsetAsync(c->d_flags, 0, sizeof(int), c->stream));
+    c->wsig.valid = false;
+    rc = ray_passes(c, q, P, K, P.ntiles, 1, ws_chunk_tiles(c, K), 1, true,
+                    [&](const RayParams& Pm, int64_t tb, int64_t tc) { return launch_march_epochs_pr(c, cubes, ncubes, Pm, tb, tc, (int64_t)r->n); });
+    if (rc) return rc;
+    rc = finish_out(c, wet, dw, total * 8, r->loc); if (rc) return rc;
+    rc = finish_out(c, hydro, dh, total * 8, r->loc); if (rc) return rc;
+    const bool need_sync = r->loc == RDR_HOST || nparts_out || flags_out;
+    if (need_sync) {
+        std::vector<double> ml(K);
+        int f = 0, nslow = 0;
+        HIPCHECK(c, hipMemcpyAsync(ml.data(), c->d_maxlen, (size_t)K * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(c, hipMemcpyAsync(&f, c->d_flags, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(c, hipMemcpyAsync(&nslow, c->d_nslow, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(c, hipStreamSynchronize(c->stream));
+        c->last_nslow = nslow;
+        if (nparts_out) rdr_nparts(ml.data(), K, max_seg, nparts_out);
+        if (flags_out) *flags_out = f;
+        return flags_to_status(c, f);
+    }
+    return RDR_OK;
 }
 
 int rdr_top_of_atmosphere(rdr_ctx* c, const double* xyz, const double* los, int64_t n, double h, const double* factor, double* pos, int loc) {

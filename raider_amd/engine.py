@@ -572,6 +572,42 @@ def raytrace_slices_epochs_to_cubes(cubes, rays, hts, zref, max_seg=1000.0):
                                   zref, max_seg)
 
 
+def raytrace_epochs(cubes, rays, ht, zref, max_seg=1000.0, out=None, want_nparts=True):
+    """Cube.raytrace of ONE ray batch through D weather epochs `cubes` (same shape, dtype, axes and projection) in one call: a
+    scene on a DEM (Rays.grid(..., hts=dem) / Rays.points(..., hts=...), ht=None) or a plain batch at height ht, traced for every
+    date.  Pass 1 runs once, pass 2 marches up to four epochs together; epoch e's delays are bit for bit
+    cubes[e].raytrace(rays, ht, zref)'s.  Returns (wet[D, ...], hydro[D, ...], nparts[K], flags) - nparts and flags belong to pass
+    1 and are shared by every epoch; they are None when want_nparts is False (fully asynchronous for device arrays)."""
+    cubes = list(cubes)
+    if not cubes:
+        raise ValueError('raytrace_epochs needs at least one epoch cube')
+    if rays.slices > 0:
+        raise ValueError('raytrace_epochs takes ONE batch: these rays carry look vectors for height slices (use raytrace_slices_epochs)')
+    ctx = cubes[0].ctx
+    rays.adopt_stream(ctx)
+    ht = rays.table_height(ht)
+    D = len(cubes)
+    shape = (D,) + tuple(rays.shape)
+    if out is not None:
+        wet, hyd = out
+    elif rays._torch_device is not None:
+        import torch
+        wet = torch.empty(shape, dtype=torch.float64, device=rays._torch_device)
+        hyd = torch.empty_like(wet)
+    else:
+        wet = _pinned.empty(shape); hyd = _pinned.empty(shape)
+    rays.check_outputs(wet, hyd, slices=D)
+    handles = (C.c_void_p * D)(*[c.handle for c in cubes])
+    args = (ctx.handle, handles, D, C.byref(rays.struct), float(ht), float(zref), float(max_seg), ptr(wet), ptr(hyd))
+    if not want_nparts:
+        check(ctx.lib.rdr_raytrace_epochs(*args, None, None), ctx.handle)
+        return wet, hyd, None, None
+    nparts = np.zeros(len(cubes[0].ray_levels(ht, zref)[0]), dtype=np.int32)
+    flags = C.c_int32()
+    check(ctx.lib.rdr_raytrace_epochs(*args, ptr(nparts), C.byref(flags)), ctx.handle)
+    return wet, hyd, nparts, flags.value
+
+
 class Rays:
     """One ray batch = one (ny,nx) slice at one height (delay.py:256-273).  Keeps references to the
     arrays it points at."""
