@@ -165,6 +165,9 @@ int rdr_ray_kernel_attributes(rdr_ctx* ctx, const rdr_cube* cube, int which, int
 /* diagnostics: rays the static classification sent to the generic-geodesy kernels in the last ray pass 1 whose result this ctx read
  * back (rdr_ray_prepass, and rdr_raytrace / rdr_raytrace_slices when they synchronise); -1 for a NULL ctx */
 int64_t rdr_generic_ray_count(rdr_ctx* ctx);
+/* diagnostics: 64-ray waves of the last rdr_ray_prepass that left the per-level length loop of pass 1 out because their length bounds
+ * could not raise any level maximum of the slice (0 with RAIDER_HIP_PASS1_SKIP=0; results never depend on it); -1 for a NULL ctx */
+int64_t rdr_skipped_wave_count(rdr_ctx* ctx);
 
 /* ---- weather cube ----------------------------------------------------------------------------
  * Replaces getInterpolators (tools/RAiDER/delayFcns.py:23-58): the two fields of one processed weather

@@ -69,6 +69,7 @@ SYMBOLS = [
     ('rdr_set_side_capacity', C.c_int, [_VP, C.c_int64]),
     ('rdr_trim', C.c_int, [_VP, C.c_int64, c_lp]),
     ('rdr_generic_ray_count', C.c_int64, [_VP]),
+    ('rdr_skipped_wave_count', C.c_int64, [_VP]),
     ('rdr_profile_get', C.c_int, [_VP, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     ('rdr_clock_sample_begin', C.c_int, [_VP, C.c_double]),
     ('rdr_clock_sample_end', C.c_int, [_VP, c_dp]),
@@ -334,6 +335,10 @@ class Context:
     def generic_ray_count(self):
         """Rays the last synchronising ray pass 1 left to the generic-geodesy kernels (diagnostics)."""
         return int(self.lib.rdr_generic_ray_count(self.handle))
+
+    def skipped_wave_count(self):
+        """64-ray waves of the last ray_prepass that skipped pass 1's per-level length loop (diagnostics; RAIDER_HIP_PASS1_SKIP)."""
+        return int(self.lib.rdr_skipped_wave_count(self.handle))
 
     def clock_sample(self, ms):
         """Start sampling the shader clock for `ms` milliseconds of wall time (one sleeping wave on the copy stream); returns a

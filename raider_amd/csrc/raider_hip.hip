@@ -52,7 +52,7 @@ struct rdr_ctx {
     unsigned long long* d_maxlen = nullptr;   // [MAX_SLICES][MAX_LEVELS]
     int* d_flags = nullptr;                   // [MAX_SLICES]
     int* d_nparts = nullptr;                  // [MAX_LEVELS] (rdr_ray_march's host-given partition)
-    int* d_nslow = nullptr;                   // [1] rays sent to the generic kernels by the last pass 1
+    int* d_nslow = nullptr;                   // [2] rays sent to the generic kernels by the last pass 1; waves of it that skipped the level loop
     int* d_tilectr = nullptr;                 // [4][8] per-XCD tile counters of the four ray-kernel launches of a step
     // value buffers of destroyed cubes, kept for the next cube of the same size: a job that blends / builds a cube per date or per call
     // (cli/raider.py:817-819, the intermediate cubes of the point branch) then allocates nothing - hipMalloc + hipFree of a 400 MB cube
@@ -83,6 +83,7 @@ struct rdr_ctx {
     const struct rdr_cube* nan_owner[NAN_SLOTS] = {};
     int nan_next = 0;
     int64_t side_forced = -1;                 // rdr_set_side_capacity
+    int64_t last_nskip = 0;                   // waves of the last rdr_ray_prepass that skipped the per-level length loop
     int64_t last_nslow = 0;                   // generic rays seen by the last pass 1 whose count the host happened to read back
     int wall_khz = 0;                         // rate of the wall counter (rdr_clock_sample_begin)
     int last_nan_output = -1;                 // rdr_build_cube (host arrays): 1 / 0 = its last result holds / does not hold a NaN; -1 unknown
@@ -378,13 +379,13 @@ int rdr_create(int device, rdr_ctx** out) {
         HIPCHECK(nullptr, hipMalloc((void**)&c->d_maxlen, (size_t)MAX_SLICES * MAX_LEVELS * sizeof(unsigned long long)));
         HIPCHECK(nullptr, hipMalloc((void**)&c->d_flags, (MAX_SLICES + 4) * sizeof(int)));      // (+ the cube packer's NaN word)
         HIPCHECK(nullptr, hipMalloc((void**)&c->d_nparts, MAX_LEVELS * sizeof(int)));
-        HIPCHECK(nullptr, hipMalloc((void**)&c->d_nslow, sizeof(int)));
+        HIPCHECK(nullptr, hipMalloc((void**)&c->d_nslow, 2 * sizeof(int)));
         HIPCHECK(nullptr, hipMalloc((void**)&c->d_tilectr, 32 * sizeof(int)));
         HIPCHECK(nullptr, hipMalloc((void**)&c->d_sidectr, sizeof(int)));
         HIPCHECK(nullptr, hipMemset(c->d_sidectr, 0, sizeof(int)));
         HIPCHECK(nullptr, hipHostMalloc((void**)&c->h_word, 16 * sizeof(int), hipHostMallocDefault));
         HIPCHECK(nullptr, hipHostMalloc((void**)&c->nan_words, rdr_ctx::NAN_SLOTS * sizeof(int), hipHostMallocDefault));
-        HIPCHECK(nullptr, hipMemset(c->d_nslow, 0, sizeof(int)));
+        HIPCHECK(nullptr, hipMemset(c->d_nslow, 0, 2 * sizeof(int)));
         return RDR_OK;
     }();
     if (rc) { rdr_destroy(c); return rc; }
@@ -547,6 +548,7 @@ int rdr_set_side_capacity(rdr_ctx* c, int64_t columns) {
 }
 
 int64_t rdr_generic_ray_count(rdr_ctx* c) { return c ? c->last_nslow : -1; }
+int64_t rdr_skipped_wave_count(rdr_ctx* c) { return c ? c->last_nskip : -1; }
 
 int rdr_set_profiling(rdr_ctx* c, int on) {
     if (!c) return fail(nullptr, RDR_ERR_INVALID, "ctx is NULL");
@@ -1955,14 +1957,25 @@ static bool wsig_match(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, double 
 // pass 1 over tiles [tb, tb+tc): optional reduction (P.maxlen_bits != null) and/or record store (P.ws != null)
 // nslots_total > 0: the launch is one chunk of a larger record buffer (field stride nslots_total, P.ws already offset to the
 // chunk's first slot) and the slow-ray count accumulates over the chunks (reset_nslow only for the first one).
+// RAIDER_HIP_PASS1_SKIP=0: every wave runs the per-level length loop of pass 1 (the A/B switch of the wave bound; read once per process)
+static bool pass1_skip_on() {
+    static const int on = []() { const char* e = std::getenv("RAIDER_HIP_PASS1_SKIP"); return e ? std::atoi(e) : 1; }();
+    return on != 0;
+}
+
 static int launch_crossings(rdr_ctx* c, const rdr_cube* q, RayParams P, int64_t tb, int64_t tc, int64_t nslots_total = 0, bool reset_nslow = true) {
     P.tile_begin = tb; P.tile_count = tc; P.nslots = nslots_total > 0 ? nslots_total : tc * BLOCK;
+    // the lon/lat slice instantiations may skip the level loop per wave; their two tables lie behind the common LDS layout and are
+    // allocated for that launch alone (a cube whose tables leave no room for them is traced without the skip, as before)
+    const bool skippable = pass1_skip_on() && q->proj.kind != 1 && !P.ht_ray && P.maxlen_bits != nullptr &&
+                           ray_lds_total(q) + skip_smem_bytes(q->nz) <= c->lds_max;
+    P.skip_levels = skippable ? 1 : 0;
     const int g = ray_grid(c, tc, 8);
     if (ray_lds_total(q) > c->lds_max)
         return fail(c, RDR_ERR_INVALID, "ray tracing: the cube's non-uniform horizontal axes and level tables need " + std::to_string(ray_lds_total(q)) +
                     " B of LDS per workgroup, the device offers " + std::to_string(c->lds_max) + " (resample the cube to uniform axes or crop it)");
     if (reset_nslow) {
-        HIPCHECK(c, hipMemsetAsync(c->d_nslow, 0, sizeof(int), c->stream));
+        HIPCHECK(c, hipMemsetAsync(c->d_nslow, 0, 2 * sizeof(int), c->stream));
         HIPCHECK(c, hipMemsetAsync(c->d_sidectr, 0, sizeof(int), c->stream));
     }
     HIPCHECK(c, hipMemsetAsync(c->d_tilectr, 0, 16 * sizeof(int), c->stream));
@@ -1971,12 +1984,13 @@ static int launch_crossings(rdr_ctx* c, const rdr_cube* q, RayParams P, int64_t 
     hipError_t e = hipSuccess;
     {
         KTimer t(c, 0);
+        const size_t sm_light = sm + (skippable ? skip_smem_bytes(q->nz) : 0);
         const bool lcc = q->proj.kind == 1;
         // input form of the batch, fixed at compile time for the two hot ones (crossings_kernel's OM parameter)
         const int om = P.origin_mode != RDR_ORIGIN_GRID ? 0 : (P.los_mode == RDR_LOS_VEC ? 1 : 2);
         const dim3 G(g), B(BLOCK);
-#define RDR_LAUNCH_X(T2, LCC_, OM_) e = (P.ht_ray ? launch_lds(crossings_kernel<T2, false, LCC_, OM_, true>, G, B, sm, c->stream, make_view<T2>(q), P, q->proj) \
-                                                  : launch_lds(crossings_kernel<T2, false, LCC_, OM_, false>, G, B, sm, c->stream, make_view<T2>(q), P, q->proj))
+#define RDR_LAUNCH_X(T2, LCC_, OM_) e = (P.ht_ray ? launch_lds(crossings_kernel<T2, false, LCC_, OM_, true>, G, B, sm_light, c->stream, make_view<T2>(q), P, q->proj) \
+                                                  : launch_lds(crossings_kernel<T2, false, LCC_, OM_, false>, G, B, sm_light, c->stream, make_view<T2>(q), P, q->proj))
 #define RDR_LAUNCH_X_OM(T2, LCC_) do { if (om == 1) RDR_LAUNCH_X(T2, LCC_, 1); else if (om == 2) RDR_LAUNCH_X(T2, LCC_, 2); else RDR_LAUNCH_X(T2, LCC_, 0); } while (0)
         if (q->dtype == RDR_F32) { if (lcc) RDR_LAUNCH_X_OM(float2, true); else RDR_LAUNCH_X_OM(float2, false); }
         else { if (lcc) RDR_LAUNCH_X_OM(double2, true); else RDR_LAUNCH_X_OM(double2, false); }
@@ -2199,12 +2213,12 @@ int rdr_ray_prepass(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, double ht,
         rc = launch_crossings(c, q, P, 0, P.ntiles); if (rc) return rc;
         if (keep) wsig_set(c, q, r, ht, zref, K, true);
     }
-    int f = 0, nslow = 0;
+    int f = 0, nslow[2] = {0, 0};
     HIPCHECK(c, hipMemcpyAsync(maxlen, c->d_maxlen, (size_t)K * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipMemcpyAsync(&f, c->d_flags, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(&nslow, c->d_nslow, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(nslow, c->d_nslow, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
-    c->last_nslow = nslow;
+    c->last_nslow = nslow[0]; c->last_nskip = nslow[1];
     if (flags) *flags = f;
     return RDR_OK;
 }

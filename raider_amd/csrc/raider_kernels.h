@@ -443,7 +443,7 @@ struct RayParams {
     unsigned long long* maxlen_bits;   // [nslices][MAX_LEVELS] per-level max ray length (bit pattern of a non-negative double); nullptr: no reduction
     int* flags;                        // [nslices] RDR_FLAG_* bits (OR-reduced)
     const int* nparts_override;        // [nslices][MAX_LEVELS] or nullptr -> ceil(maxlen/max_seg)+1
-    int* nslow;                        // number of rays the static classification sent to the generic (slow) kernels
+    int* nslow;                        // [2] number of rays the static classification sent to the generic (slow) kernels; waves of pass 1 that skipped
     int* tile_ctr;                     // [8] per-XCD next-tile counters of this launch (zeroed by the host)
     // pass 1 -> pass 2 workspace (this launch covers tiles [tile_begin, tile_begin + tile_count))
     double* ws; int64_t nslots;
@@ -455,6 +455,8 @@ struct RayParams {
     // tiling of the whole batch
     int64_t ntiles; int tiles_x;
     int stage_f64;                     // light march on f64 cubes: stage every level's footprint of a wave in LDS (0: the direct gathers)
+    int skip_levels;                   // pass 1, lon/lat slice kernels: a wave whose length bounds cannot raise any level maximum leaves the per-level loop
+                                       // out (0: never; != 0 only on a launch that allocated skip_smem_bytes); such waves are counted in nslow[1]
 };
 
 // The slice-uniform level table of build_ray (losreader.py:785-808), computed by one thread into LDS from the LDS z table.
@@ -565,6 +567,16 @@ inline size_t ray_smem_bytes(int64_t ny, int64_t nx, int64_t nz, int exact_y, in
            + (size_t)nz * 4 * 2 + 16;             // kz, np, K
 }
 
+// Pass 1's two tables BEHIND the common layout - only the launch of a crossings_kernel instantiation that skips (RayParams::skip_levels)
+// allocates them, every other ray kernel launches with ray_smem_bytes as it is.  Addressed from m.K afresh wherever they are used (a base kept in a register across the
+// polynomial fit is one more value for the allocator to spill):
+//   dabs [7][nz]: |xv[k]^n - xv[k-1]^n|, n = 1..7, of the slice's levels k >= 2 (0 below) - the wave bound of a level length;
+//   floor [nz]  : the per-level maximum the workgroup had folded into mxcol when it took its current tile (a u64 bit pattern, like mxcol).
+__device__ __forceinline__ double* skip_dabs(const RaySmem& m) { return reinterpret_cast<double*>(m.K + 4); }
+__device__ __forceinline__ unsigned long long* skip_floor(const RaySmem& m, int nz) { return reinterpret_cast<unsigned long long*>(m.K + 4) + 7 * nz; }
+inline size_t skip_smem_bytes(int64_t nz) { return (size_t)nz * 8 * 8; }
+
+
 // Axis tables: once per workgroup.
 template <typename T2>
 __device__ __forceinline__ void fill_axes(const CubeView<T2>& c, const RaySmem& m) {
@@ -634,6 +646,27 @@ __device__ __forceinline__ void tile_trig(double v, int lane, const LccParams& p
     }
 }
 
+// Maximum of a non-negative float over the 64 lanes of a wave, as a wave-uniform value: six DPP steps (within quads, within rows of 16,
+// then row 0 -> 1, 2 -> 3 and rows 0-1 -> 2-3) leave it in lane 63.  Non-negative floats order like their bit patterns, so the steps are
+// unsigned maxima (v_max_u32 with a DPP operand: one instruction each).  Every lane of the wave must be active.
+__device__ __forceinline__ float wave_max_nonneg(float x) {
+    unsigned v = (unsigned)__float_as_int(x);
+    // (a lane a step leaves out - the rows outside a broadcast's row mask - reads 0, the identity of the unsigned maximum)
+#define RDR_DPP_MAX(ctrl, rows) v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rows, 0xF, false))
+    RDR_DPP_MAX(0xB1, 0xF);     // quad_perm [1, 0, 3, 2]
+    RDR_DPP_MAX(0x4E, 0xF);     // quad_perm [2, 3, 0, 1]
+    RDR_DPP_MAX(0x141, 0xF);    // row_half_mirror
+    RDR_DPP_MAX(0x140, 0xF);    // row_mirror
+    RDR_DPP_MAX(0x142, 0xA);    // row_bcast:15 into rows 1 and 3
+    RDR_DPP_MAX(0x143, 0xC);    // row_bcast:31 into rows 2 and 3
+#undef RDR_DPP_MAX
+    return __int_as_float(__builtin_amdgcn_readlane((int)v, 63));
+}
+
+// A float that is not below |x| (x finite): the product exceeds |x| by 2^-22 |x|, its rounding to float takes back at most 2^-24 |x| -
+// or, where the float is subnormal or flushed, at most 2^-126 absolutely, which the caller's absolute margin covers.
+__device__ __forceinline__ float float_above_abs(double x) { return (float)(fabs(x) * (1.0 + 0x1p-22)); }
+
 // ---- pass 1: per-ray set-up + level crossings (build_ray, losreader.py:772-835) ------------------------------------
 // Optional outputs (both may be on): the per-level batch maximum of the ray length + flags (what delay.py:283,306-311
 // reduce over the slice) and the workspace record for pass 2.
@@ -656,9 +689,15 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
     const int los_mode = OM == 1 ? 0 : P.los_mode;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const RaySmem m = carve_smem(smem_raw, c.ny, c.nx, c.nz, c.exact_y, c.exact_x);
+    // The instantiations whose waves may skip the per-level length loop (below): not the per-ray-height ones (their loop starts per lane), and
+    // not on conic cubes (those spill around the fit already, and the decision added 8 to 16 B of scratch to them).
+    constexpr bool SKIPPABLE = !SLOW && !PR && !LCC;
+    if (SKIPPABLE && threadIdx.x == 0) m.K[3] = 0;        // the workgroup's count of waves that skipped (before the barrier of fill_axes)
     fill_axes(c, m);
     const int tid = threadIdx.x;
     const bool reduce = P.maxlen_bits != nullptr;
+    // (kernel-uniform; read through an opaque copy at every use, so that no flag of it is carried across the tile body)
+    auto skip_on = [&]() { if (!SKIPPABLE || !reduce) return false; int on = P.skip_levels; asm volatile("" : "+s"(on)); return on != 0; };
     // per-level maximum of the ray length over a slice (delay.py:283): every lane folds its length into column lane%16 of
     // the workgroup's LDS table with one ds_max_u64 (non-negative doubles order like their bit patterns); the columns are
     // combined when the workgroup leaves the slice (flush).  NaN lengths are left out here and reported through the flags,
@@ -696,7 +735,36 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
             int tz = threadIdx.x;
             asm volatile("" : "+v"(tz));
             if (reduce) for (int k = tz; k < K * MXCOLS; k += BLOCK) m.mxcol[k] = 0ULL;
+            if (skip_on()) {
+                double* const dabs = skip_dabs(m);
+                unsigned long long* const flr = skip_floor(m, c.nz);
+                // the slice's table of the wave bound (below): |v_k^n - v_(k-1)^n| for the levels the bound is used for, and a floor of 0
+                for (int k = tz; k < K; k += BLOCK) {
+                    const double v1 = m.xv[k], v0 = k >= 2 ? m.xv[k - 1] : v1;
+                    double p1 = v1, p0 = v0;
+#pragma unroll
+                    for (int n = 0; n < 7; ++n) { dabs[n * c.nz + k] = fabs(p1 - p0); p1 *= v1; p0 *= v0; }
+                    flr[k] = 0ULL;
+                }
+            }
             __syncthreads();
+        }
+        if (skip_on()) {
+            unsigned long long* const flr = skip_floor(m, c.nz);
+            // the floor of this tile's skip decisions: what the workgroup's earlier tiles have folded into the columns (the barriers of
+            // walk.next() are behind us).  It only ever trails the columns, and a stale floor merely skips less.  GRID origins have the
+            // barrier of the tile's sines / cosines between this store and the decisions that read it; list origins have none: a wave
+            // that is ahead may read an entry before or after its refresh.  That is sound because either value is a maximum the columns
+            // have held in THIS slice (the slice change zeroes the floor before its own barrier) and an aligned 64-bit LDS store is one
+            // ds_write_b64, which does not tear.
+            int tf = threadIdx.x;
+            asm volatile("" : "+v"(tf));
+            for (int k = tf; k < K; k += BLOCK) {
+                unsigned long long v = 0ULL;
+#pragma unroll
+                for (int cc = 0; cc < MXCOLS; ++cc) v = max(v, m.mxcol[k * MXCOLS + cc]);
+                flr[k] = v;
+            }
         }
         // The thread index as the tile body sees it: an opaque per-tile copy, so that nothing derived from it (LDS addresses, record
         // pointers, row / column offsets) is hoisted out of the tile loop and kept live - or spilled - across the polynomial fit.
@@ -962,6 +1030,57 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
                         atomicMax(&mxc[k * MXCOLS], (unsigned long long)__double_as_longlong(k > k0 ? fmax(fabs(L), 0.0) : 0.0));
                     }
                 }
+                // Can this wave raise any level maximum at all?  Most cannot: the lengths go with the secant of the incidence angle, and
+                // after a few tiles the workgroup's columns hold the lengths of rays near the far edge of the swath.  A level k >= 2 has
+                //   L_k = |X(v_k) - X(v_(k-1))|,  X(v) = sum xm[n] v^n   =>   L_k <= sum_{n>=1} |xm[n]| |v_k^n - v_(k-1)^n|
+                // for every ray, hence  L_k <= sum_{n>=1} A[n] Dabs[n][k]  with A[n] the wave's maximum of |xm[n]| over the lanes that count (the
+                // others enter as 0 - their xm is 0, or NaN under tile padding, and the loop folds 0 for them either way) and Dabs the slice's table.  The COMPUTED length may exceed the exact one by the rounding of the two Horner
+                // chains, each within 8 ulp of sum_{n>=0} |xm[n]| |v|^n <= S = sum |xm[n]| (|v| <= 1 from level 1 on): 2^-49 S with the
+                // subtraction's own rounding; the table entries carry 2^-49 absolutely (six products each side, one subtraction), which
+                // the A[n] multiply to at most 7 x 2^-49 max(S); the float maxima are rounded up
+                // (float_above_abs) short of 2^-122 in all, and the seven-term sum of the bound rounds by
+                // a few ulp relatively.  B_k = (1 + 2^-30) sum A[n] Dabs[n][k] + 2^-44 max(S) + 2^-120 covers all of it with room to spare,
+                // and both margins are far below the difference between two neighbouring columns of a scene.  If B_k <= floor[k] for every
+                // level - an equal value does not change a maximum - nothing this wave computes in the loop below can change a column.
+                // Level 1 starts from the ten-iteration crossing of level 0, which is not a value of X: it is always computed.  A NaN
+                // or infinite coefficient of a lane that counts (S not finite) takes the loop.  One decision per wave and tile; lane j bounds levels j and j + 64.
+                bool skip = false;
+                if constexpr (SKIPPABLE) {
+                    if (K > 2 && K <= 128 && skip_on()) {
+                        const double* const dabs = skip_dabs(m);
+                        const unsigned long long* const flr = skip_floor(m, c.nz);
+                        double S = fabs(xm[0]);
+#pragma unroll
+                        for (int n = 1; n < PX; ++n) S += fabs(xm[n]);
+                        if (!cnt) S = 0.0;
+                        const bool finite = !__any(!(S < __builtin_inf()));
+                        const float a0 = wave_max_nonneg(finite ? float_above_abs(S) : 0.0f);
+                        if (finite && a0 == 0.0f) skip = true;                                 // nothing but lanes that do not count
+                        else if (finite) {
+                            const int lane = tl & 63;
+                            const int ka = min(lane, K - 1), kb = min(lane + 64, K - 1);
+                            double Ba = 0.0, Bb = 0.0;
+#pragma unroll
+                            for (int n = 1; n < PX; ++n) {
+                                const double an = (double)wave_max_nonneg(cnt ? float_above_abs(xm[n]) : 0.0f);
+                                Ba = fma(an, dabs[(n - 1) * c.nz + ka], Ba);
+                                if (K > 64) Bb = fma(an, dabs[(n - 1) * c.nz + kb], Bb);
+                            }
+                            const double margin = fma((double)a0, 0x1p-44, 0x1p-120);
+                            Ba = fma(Ba, 1.0 + 0x1p-30, margin);
+                            Bb = fma(Bb, 1.0 + 0x1p-30, margin);
+                            bool ok = lane < 2 || lane >= K || (unsigned long long)__double_as_longlong(Ba) <= flr[ka];
+                            if (K > 64) ok = ok && (lane + 64 >= K || (unsigned long long)__double_as_longlong(Bb) <= flr[kb]);
+                            skip = !__any(!ok);
+                            if (skip && lane == 0) atomicAdd(m.K + 3, 1);                      // (diagnostics: rdr_skipped_wave_count)
+                        }
+                    }
+                }
+                if (skip) {
+                    const double L = poly7(xm, m.xv[1]) - s_hi;
+                    atomicMax(&mxc[MXCOLS], (unsigned long long)__double_as_longlong(fmax(fabs(L), 0.0)));
+                    k = K;
+                }
                 for (; k + 2 <= K; k += 2) {
                     const double v0 = m.xv[k], v1 = m.xv[k + 1];
                     const double sa = poly7(xm, v0), sb = poly7(xm, v1);
@@ -983,6 +1102,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
         }
     }
     flush();
+    if (skip_on()) {
+        __syncthreads();
+        if (threadIdx.x == 0 && m.K[3] > 0) atomicAdd(P.nslow + 1, m.K[3]);
+    }
 }
 
 // ---- pass 2: trapezoid integration of both fields along every ray (delay.py:285-323) -------------------------------
