@@ -447,6 +447,22 @@ int rdr_ecmwf_model_levels(rdr_ctx* ctx, const float* z_surf, const float* lnsp,
                            const double* a, const double* b, int32_t nlev, int64_t ny, int64_t nx, double R_d,
                            double* p_out, double* zs_out, int loc);
 
+/* Front end of the cube producer for states on pressure levels, or on levels that carry their own height field: ERA-5 / HRES
+ * pressure-level files (models/ecmwf.py:252-303), and the same steps where other providers take them (geopotential height with 2-D
+ * latitudes on a projected grid; geometric heights with a 3-D pressure field).  Inputs in FILE layout [nlev, ny, nx], x contiguous,
+ * all f64: height with height_kind 0 = geopotential m2 s-2, divided by g0 (ecmwf.py:284), 1 = geopotential height m - both then
+ * through WeatherModel._get_heights (weatherModel.py:326-330) = utilFcns.geo_to_ht (:378-410) - 2 = geometric height m, moved only;
+ * p: p_ndim 1 = the level list [nlev] in Pa, broadcast (ecmwf.py:292), 3 = a field; t; hum (q or rh, moved only); lats: lat_ndim
+ * 1 = [ny], 2 = [ny, nx], in the file's row / column order.  top_first: level 0 of the file is the top (else the surface);
+ * rows_descending / cols_descending: latitudes / longitudes run downwards in the file (ecmwf.py:264-275).
+ * zs_out, p_out, t_out, hum_out: [ny, nx, nlev] f64, levels surface -> top, rows and columns ascending (ecmwf.py:295-303) - the
+ * layout rdr_cubes_from_model_levels takes.  Inputs live at `loc`, outputs at `out_loc` (host in -> device out feeds the producer
+ * without a round trip). */
+int rdr_pressure_level_state(rdr_ctx* ctx, const double* height, int height_kind, const double* p, int p_ndim, const double* t,
+                             const double* hum, const double* lats, int lat_ndim, int64_t nlev, int64_t ny, int64_t nx,
+                             int top_first, int rows_descending, int cols_descending, double* zs_out, double* p_out,
+                             double* t_out, double* hum_out, int loc, int out_loc);
+
 /* Cube producer (models/weatherModel.py:235-262: _find_e -> _uniform_in_z -> _checkForNans -> wet/hydro refractivity ->
  * _adjust_grid -> _getZTD): model-level columns zs3/p/t/hum [ny, nx, nlev] (heights ascending along the last axis,
  * humidity_type 0 = specific humidity q, 1 = relative humidity %) are resampled to the uniform levels new_z[nz] and

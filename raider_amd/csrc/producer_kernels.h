@@ -178,6 +178,22 @@ __global__ __launch_bounds__(256) void producer_kernel(ProducerParams P) {
 // values and move by METRES with a last-bit change of logf - no other platform can reproduce that realisation of the round-off
 // (the test suite's float32 NumPy restatement does, on x86: tests/test_ref_files.py), and a float32 evaluation here would only
 // add a second, different one.  DESIGN.md 6.5.
+// utilFcns.geo_to_ht (:378-410) for one latitude: _get_g_ll (:351-353) and get_Re (:356-375) once per column, then
+// h = (gh Re) / (g_ll / g0 Re - gh) per level.  Shared by both front ends below: same geopotential height and latitude, same bits.
+struct GeoToHt { double re, gre; };
+__device__ __forceinline__ GeoToHt geo_to_ht_at(double lat_deg) {
+    const double g0 = 9.80665;
+    const double lat = lat_deg * DEG_TO_RAD;
+    const double c2 = cos(2.0 * lat);
+    const double g_ll = 9.80616 * (1.0 - 0.002637 * c2 + 0.0000059 * (c2 * c2));         // _get_g_ll
+    const double cl = cos(lat), sl = sin(lat);
+    GeoToHt c;
+    c.re = sqrt(1.0 / ((cl * cl) / (6378137.0 * 6378137.0) + (sl * sl) / (6356752.0 * 6356752.0)));   // get_Re
+    c.gre = g_ll / g0 * c.re;
+    return c;
+}
+__device__ __forceinline__ double geo_to_ht(const GeoToHt& c, double gh) { return (gh * c.re) / (c.gre - gh); }
+
 __global__ __launch_bounds__(256) void ecmwf_levels_kernel(const float* __restrict__ z_surf, const float* __restrict__ lnsp,
                                                            const float* __restrict__ t, const float* __restrict__ q,
                                                            const float* __restrict__ lats, const double* __restrict__ a,
@@ -187,12 +203,7 @@ __global__ __launch_bounds__(256) void ecmwf_levels_kernel(const float* __restri
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const double g0 = 9.80665;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < ncol; i += stride) {
-        const double lat = (double)lats[i / nx] * DEG_TO_RAD;
-        const double c2 = cos(2.0 * lat);
-        const double g_ll = 9.80616 * (1.0 - 0.002637 * c2 + 0.0000059 * (c2 * c2));         // _get_g_ll
-        const double cl = cos(lat), sl = sin(lat);
-        const double re = sqrt(1.0 / ((cl * cl) / (6378137.0 * 6378137.0) + (sl * sl) / (6356752.0 * 6356752.0)));   // get_Re
-        const double gre = g_ll / g0 * re;
+        const GeoToHt gc = geo_to_ht_at((double)lats[i / nx]);
         const double sp = exp((double)lnsp[i]), zs0 = (double)z_surf[i];
         double z_h = 0.0;
         for (int lev = nlev; lev >= 1; --lev) {
@@ -207,7 +218,72 @@ __global__ __launch_bounds__(256) void ecmwf_levels_kernel(const float* __restri
             z_h += trd * dlogp;
             const int64_t o = i * nlev + (nlev - lev);
             p_out[o] = ph;
-            zs_out[o] = (gh * re) / (gre - gh);                                              // geo_to_ht
+            zs_out[o] = geo_to_ht(gc, gh);
         }
+    }
+}
+
+// ---- pressure-level (or own-height-field) model state -> the producer's columns ------------------------------------------------
+// models/ecmwf.py:252-303 (_load_pressure_level) and its kin in the other providers: a height field, pressure, temperature and
+// humidity in FILE layout (nlev, ny, nx), x contiguous -> zs, p, t, hum in the producer's layout (ny, nx, nlev), levels surface ->
+// top, rows and columns ascending.  height_kind 0: geopotential (m2 s-2) / g0 (:284) -> geo_to_ht (WeatherModel._get_heights,
+// weatherModel.py:326-330); 1: geopotential height (m) -> geo_to_ht; 2: geometric height, moved only.  Pressure is the level list
+// broadcast (:292) or a 3-D field; latitudes (file row / column order) one per row or one per node.
+// A workgroup moves a 32 (x) x 32 (level) tile of one row through LDS, as pack_cube_xfast_kernel does: reads coalesced along x
+// (256 B per half-wave and field), writes coalesced along the levels.  Tiles are [level][x] doubles with rows of 33: the transposed
+// ds_read_b64 of a half-wave then walks dwords 66 apart - 32 distinct even banks of 64 - and the row-wise writes are contiguous.
+struct PressureLevelParams {
+    const double* height; const double* p; const double* t; const double* hum; const double* lats;     // file layout
+    int64_t nlev, ny, nx;
+    int height_kind, p_3d, lat_2d, top_first, flip_rows, flip_cols;
+    double* zs_out; double* p_out; double* t_out; double* hum_out;                                     // [ny, nx, nlev]
+};
+
+__global__ __launch_bounds__(256) void pressure_levels_kernel(PressureLevelParams P) {
+    __shared__ double tile[4][32][33];
+    const int64_t nlev = P.nlev, ny = P.ny, nx = P.nx;
+    const int64_t tx_n = (nx + 31) / 32, tz_n = (nlev + 31) / 32, ntiles = ny * tx_n * tz_n;
+    const int lx = threadIdx.x & 31, lr = threadIdx.x >> 5;          // 32 lanes along the fast axis, 8 rows per pass
+    const double g0 = 9.80665;
+    for (int64_t tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {    // tiles of the OUTPUT: (iy, ix, iz) ascending, surface first
+        const int64_t tz = tl % tz_n, r = tl / tz_n, tx = r % tx_n, iy = r / tx_n;
+        const int64_t jy = P.flip_rows ? ny - 1 - iy : iy;
+        const int64_t x0 = tx * 32, z0 = tz * 32;
+        {                                                            // read: lanes along x, rows = levels
+            const int64_t ix = x0 + lx;
+            if (ix < nx) {
+                const int64_t jx = P.flip_cols ? nx - 1 - ix : ix;
+                GeoToHt gc;
+                if (P.height_kind != 2) gc = geo_to_ht_at(P.lats[P.lat_2d ? jy * nx + jx : jy]);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int64_t iz = z0 + lr + 8 * k;
+                    if (iz < nlev) {
+                        const int64_t jz = P.top_first ? nlev - 1 - iz : iz;
+                        const int64_t src = (jz * ny + jy) * nx + jx;
+                        double h = P.height[src];
+                        if (P.height_kind == 0) h = h / g0;
+                        if (P.height_kind != 2) h = geo_to_ht(gc, h);
+                        tile[0][lr + 8 * k][lx] = h;
+                        tile[1][lr + 8 * k][lx] = P.p_3d ? P.p[src] : P.p[jz];
+                        tile[2][lr + 8 * k][lx] = P.t[src];
+                        tile[3][lr + 8 * k][lx] = P.hum[src];
+                    }
+                }
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {                                // write: lanes along the levels, rows = x
+            const int64_t iz = z0 + lx, ix = x0 + lr + 8 * k;
+            if (ix < nx && iz < nlev) {
+                const int64_t dst = (iy * nx + ix) * nlev + iz;
+                P.zs_out[dst] = tile[0][lx][lr + 8 * k];
+                P.p_out[dst] = tile[1][lx][lr + 8 * k];
+                P.t_out[dst] = tile[2][lx][lr + 8 * k];
+                P.hum_out[dst] = tile[3][lx][lr + 8 * k];
+            }
+        }
+        __syncthreads();
     }
 }

@@ -3001,6 +3001,50 @@ int rdr_ecmwf_model_levels(rdr_ctx* c, const float* z_surf, const float* lnsp, c
     return RDR_OK;
 }
 
+int rdr_pressure_level_state(rdr_ctx* c, const double* height, int height_kind, const double* p, int p_ndim, const double* t, const double* hum,
+                             const double* lats, int lat_ndim, int64_t nlev, int64_t ny, int64_t nx, int top_first, int rows_descending,
+                             int cols_descending, double* zs_out, double* p_out, double* t_out, double* hum_out, int loc, int out_loc) {
+    if (!c || !height || !p || !t || !hum || !lats || !zs_out || !p_out || !t_out || !hum_out)
+        return fail(c, RDR_ERR_INVALID, "rdr_pressure_level_state: NULL argument");
+    if (nlev < 1 || ny < 1 || nx < 1) return fail(c, RDR_ERR_INVALID, "rdr_pressure_level_state: empty grid");
+    if (nlev > ((int64_t)1 << 40) / ny / nx) return fail(c, RDR_ERR_INVALID, "rdr_pressure_level_state: grid too large");
+    if (height_kind < 0 || height_kind > 2)
+        return fail(c, RDR_ERR_INVALID, "rdr_pressure_level_state: height_kind must be 0 (geopotential), 1 (geopotential height) or 2 (geometric height)");
+    if ((p_ndim != 1 && p_ndim != 3) || (lat_ndim != 1 && lat_ndim != 2))
+        return fail(c, RDR_ERR_INVALID, "rdr_pressure_level_state: pressure is a level list (1) or a field (3), latitude per row (1) or per node (2)");
+    if ((top_first | rows_descending | cols_descending) & ~1) return fail(c, RDR_ERR_INVALID, "rdr_pressure_level_state: order flags must be 0 or 1");
+    if ((loc != RDR_HOST && loc != RDR_DEVICE) || (out_loc != RDR_HOST && out_loc != RDR_DEVICE))
+        return fail(c, RDR_ERR_INVALID, "rdr_pressure_level_state: loc and out_loc must be RDR_HOST or RDR_DEVICE");
+    HIPCHECK(c, hipSetDevice(c->device));
+    const size_t nb = (size_t)nlev * ny * nx * 8;
+    PressureLevelParams P;
+    const void* d;
+    int rc;
+    rc = stage_in(c, SLOT_IN0, height, nb, loc, &d); if (rc) return rc; P.height = (const double*)d;
+    rc = stage_in(c, SLOT_IN1, p, p_ndim == 3 ? nb : (size_t)nlev * 8, loc, &d); if (rc) return rc; P.p = (const double*)d;
+    rc = stage_in(c, SLOT_IN2, t, nb, loc, &d); if (rc) return rc; P.t = (const double*)d;
+    rc = stage_in(c, SLOT_IN3, hum, nb, loc, &d); if (rc) return rc; P.hum = (const double*)d;
+    rc = stage_in(c, SLOT_IN4, lats, (size_t)ny * (lat_ndim == 2 ? nx : 1) * 8, loc, &d); if (rc) return rc; P.lats = (const double*)d;
+    void *dz, *dp, *dt_, *dh;
+    rc = stage_out(c, SLOT_OUT0, zs_out, nb, out_loc, &dz); if (rc) return rc;
+    rc = stage_out(c, SLOT_OUT1, p_out, nb, out_loc, &dp); if (rc) return rc;
+    rc = stage_out(c, SLOT_OUT2, t_out, nb, out_loc, &dt_); if (rc) return rc;
+    rc = stage_out(c, SLOT_AUX, hum_out, nb, out_loc, &dh); if (rc) return rc;
+    P.nlev = nlev; P.ny = ny; P.nx = nx;
+    P.height_kind = height_kind; P.p_3d = p_ndim == 3; P.lat_2d = lat_ndim == 2;
+    P.top_first = top_first; P.flip_rows = rows_descending; P.flip_cols = cols_descending;
+    P.zs_out = (double*)dz; P.p_out = (double*)dp; P.t_out = (double*)dt_; P.hum_out = (double*)dh;
+    const int64_t ntiles = ny * ((nx + 31) / 32) * ((nlev + 31) / 32);
+    hipLaunchKernelGGL(pressure_levels_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)c->num_cus * 16))), dim3(256), 0, c->stream, P);
+    HIPCHECK(c, hipGetLastError());
+    rc = finish_out(c, zs_out, dz, nb, out_loc); if (rc) return rc;
+    rc = finish_out(c, p_out, dp, nb, out_loc); if (rc) return rc;
+    rc = finish_out(c, t_out, dt_, nb, out_loc); if (rc) return rc;
+    rc = finish_out(c, hum_out, dh, nb, out_loc); if (rc) return rc;
+    if (out_loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return RDR_OK;
+}
+
 int rdr_orbit_look_vectors(rdr_ctx* c, const double* sv_t, const double* sv_pos, const double* sv_vel, int64_t nsv, const double* xyz,
                            int64_t n, double threshold, int maxiter, double* los, double* aztime, double* srange, int loc) {
     if (!c || !sv_t || !sv_pos || !sv_vel || !xyz || !los) return fail(c, RDR_ERR_INVALID, "rdr_orbit_look_vectors: NULL argument");

@@ -3,8 +3,10 @@
 Mirrors the processing chain of the reference's WeatherModel.load (tools/RAiDER/models/weatherModel.py:235-262):
 ``_find_e`` -> ``_uniform_in_z`` -> ``_checkForNans`` -> wet / hydrostatic refractivity -> ``_adjust_grid`` -> ``_getZTD``,
 but lands the result directly in the two device cubes the delay kernels read (no NetCDF round trip through
-``write()`` / ``getInterpolators``).  Reading GRIB/NetCDF model files and the geopotential -> height conversion stay with
-the caller (they are I/O, not part of this path).
+``write()`` / ``getInterpolators``).  Two front ends make the producer's (zs, p, t, hum) columns from a raw state, on the device:
+``ecmwf_model_levels`` (ECMWF hybrid model levels) and ``pressure_level_state`` (pressure levels, or levels that carry their own
+height field: geopotential -> geometric height, the pressure broadcast, the re-ordering and the flips).  Raw ERA-5 / HRES NetCDF
+files of both kinds are read here; the other providers' download formats stay with the caller (they are I/O, not part of this path).
 """
 import ctypes as C
 
@@ -270,3 +272,159 @@ def load_ecmwf_model_levels(path, ll_bounds=None, new_z=None, return_state=False
         new_z = np.flipud(tab['level_heights'])                                                            # ecmwf.py:44
     return cubes_from_model_levels(raw['lons'].astype(np.float64), raw['lats'].astype(np.float64), zs, p, up(raw['t']), up(raw['q']), 'q',
                                    new_z=new_z, return_state=return_state, ctx=ctx)
+
+
+# ------------------------------------------------------------------------------------------------
+# Pressure levels, or levels with their own height field -> the producer's inputs
+# ------------------------------------------------------------------------------------------------
+def ecmwf_pressure_level_heights():
+    """The heights ECMWF pressure-level states are resampled to (models/ecmwf.py:38-40: LEVELS_25_HEIGHTS of
+    models/model_levels.py, shipped as data: one number per line), descending as the reference's table is."""
+    from pathlib import Path
+    return np.loadtxt(Path(__file__).resolve().parent / 'data' / 'ecmwf_pl_heights.txt', dtype=np.float64)
+
+
+def _check_level_state(height, p, t, hum, lats, height_kind):
+    """Shapes of a (nlev, ny, nx) state, before anything touches the device: (nlev, ny, nx), p_ndim, lat_ndim."""
+    if height_kind not in (0, 1, 2):
+        raise ValueError(f'height_kind must be 0 (geopotential), 1 (geopotential height) or 2 (geometric height); got {height_kind!r}')
+    shape = tuple(int(v) for v in height.shape)
+    if len(shape) != 3 or 0 in shape:
+        raise ValueError(f'the height field must be (nlev, ny, nx); got {shape}')
+    nlev, ny, nx = shape
+    if tuple(t.shape) != shape or tuple(hum.shape) != shape:
+        raise ValueError(f'temperature and humidity must have the shape of the height field {shape}; got {tuple(t.shape)} and {tuple(hum.shape)}')
+    if tuple(p.shape) not in ((nlev,), shape):
+        raise ValueError(f'pressure must be the level list ({nlev},) or a field {shape}; got {tuple(p.shape)}')
+    if tuple(lats.shape) not in ((ny,), (ny, nx)):
+        raise ValueError(f'latitudes must be ({ny},) or ({ny}, {nx}); got {tuple(lats.shape)}')
+    return shape, len(p.shape), len(lats.shape)
+
+
+def pressure_level_state(height, p, t, hum, lats, height_kind=0, top_first=True, rows_descending=False, cols_descending=False,
+                         device_out=False, ctx=None):
+    """What the reference holds after ECMWF._load_pressure_level (models/ecmwf.py:252-303), on the GPU (rdr_pressure_level_state):
+    height, t, hum (nlev, ny, nx) in file layout; height_kind 0 = geopotential (m2 s-2, / g0 as :284), 1 = geopotential height (m) -
+    both through WeatherModel._get_heights / utilFcns.geo_to_ht - 2 = geometric height (m); p the level list (nlev,) in Pa (:292)
+    or a field; lats (ny,) or (ny, nx) in the file's order; top_first: the first level is the top; rows_descending /
+    cols_descending: latitudes / longitudes run downwards in the file -> (zs, p, t, hum), each (ny, nx, nlev) float64, levels
+    surface -> top, rows and columns ascending: the producer's layout.  NumPy in -> NumPy out (tensors on the GPU with
+    device_out=True); torch tensors on the GPU in -> tensors out."""
+    dev = _is_dev(height)
+    as_np = lambda v: v.cpu().numpy() if _is_dev(v) else np.asarray(v)
+    if not dev:
+        height, p, t, hum, lats = (as_np(v) for v in (height, p, t, hum, lats))
+    (nlev, ny, nx), p_ndim, lat_ndim = _check_level_state(height, p, t, hum, lats, height_kind)
+    ctx = ctx or Context.default()
+    if dev or device_out:
+        import torch
+    if dev:
+        if not height.is_cuda:
+            raise TypeError(f'pressure_level_state takes NumPy arrays or tensors on the GPU (got a tensor on {height.device})')
+        arrs = [(v if _is_dev(v) else torch.as_tensor(np.asarray(v))).to(device=height.device, dtype=torch.float64).contiguous()
+                for v in (height, p, t, hum, lats)]
+        device = height.device
+    else:
+        arrs = [f64(v) for v in (height, p, t, hum, lats)]
+        if device_out:
+            from .engine import torch_device_or_none
+            device = torch_device_or_none()
+            if device is None:
+                raise RuntimeError('device_out=True needs torch with a GPU for the output tensors')
+    if dev or device_out:
+        outs = [torch.empty((ny, nx, nlev), dtype=torch.float64, device=device) for _ in range(4)]
+        ctx.adopt_torch_stream(outs[0])
+    else:
+        outs = [np.empty((ny, nx, nlev)) for _ in range(4)]
+    check(ctx.lib.rdr_pressure_level_state(
+        ctx.handle, ptr(arrs[0]), int(height_kind), ptr(arrs[1]), p_ndim, ptr(arrs[2]), ptr(arrs[3]), ptr(arrs[4]), lat_ndim, nlev, ny, nx,
+        int(bool(top_first)), int(bool(rows_descending)), int(bool(cols_descending)), *(ptr(o) for o in outs),
+        L.RDR_DEVICE if dev else L.RDR_HOST, L.RDR_DEVICE if (dev or device_out) else L.RDR_HOST), ctx.handle)
+    return tuple(outs)
+
+
+def cubes_from_pressure_levels(xs, ys, height, p, t, hum, lats, height_kind=0, humidity_type='q', new_z=None, proj=4326, top_first=True,
+                               rows_descending=False, cols_descending=False, k1=0.776, k2=0.233, k3=3.75e3, zmin=_ZMIN, return_state=False,
+                               ctx=None):
+    """WeatherModel.load (weatherModel.py:235-262) for a state on pressure levels or with its own height field: pressure_level_state
+    -> cubes_from_model_levels, the columns staying on the device in between.  xs, ys: the cube's ascending axes (degrees, or metres
+    of the projected CRS `proj`, which the ProcessedModel carries to tropo_delay); the other arguments as in pressure_level_state
+    and cubes_from_model_levels.  With return_state=True the model also holds the loaded columns, `levels` = (zs, p, t, hum)."""
+    if humidity_type not in ('q', 'rh'):
+        raise RuntimeError('Not a valid humidity type')        # weatherModel.py:340-341
+    xs, ys = f64(xs), f64(ys)
+    dev = _is_dev(height)
+    if not dev:
+        height, p, t, hum, lats = (v.cpu().numpy() if _is_dev(v) else np.asarray(v) for v in (height, p, t, hum, lats))
+    shape, _, _ = _check_level_state(height, p, t, hum, lats, height_kind)
+    if shape[1:] != (ys.size, xs.size):
+        raise ValueError(f'the state must be (nlev, ny, nx) = (nlev, {ys.size}, {xs.size}); got {shape}')
+    ctx = ctx or Context.default()
+    levels = pressure_level_state(height, p, t, hum, lats, height_kind, top_first, rows_descending, cols_descending, device_out=True, ctx=ctx)
+    m = cubes_from_model_levels(xs, ys, *levels, humidity_type, new_z=new_z, k1=k1, k2=k2, k3=k3, zmin=zmin, return_state=return_state, ctx=ctx)
+    m.proj = proj
+    if return_state:
+        host = (lambda v: v) if dev else (lambda v: v.cpu().numpy())         # NumPy in -> NumPy out
+        m.t, m.p, m.e = host(m.t), host(m.p), host(m.e)
+        m.levels = tuple(host(v) for v in levels)
+    return m
+
+
+def read_ecmwf_pressure_level_file(path, ll_bounds=None):
+    """Raw ERA-5 / HRES pressure-level file as the CDS / MARS write it (NetCDF-3, packed int16 `z, t, q` on (time, level, latitude,
+    longitude)) -> dict(z, t, q (nlev, ny, nx), level (nlev,) in Pa, lats (ny,), lons (nx,)) in the FILE's order, float64, with
+    longitudes above 180 wrapped and everything cut to ll_bounds = (S, N, W, E); top_first, rows_descending, cols_descending: the
+    order flags pressure_level_state takes; ys, xs: the ascending axes of the cube.  Mirrors what ECMWF._load_pressure_level reads
+    (models/ecmwf.py:252-279: the values, level * 100, the longitude wrap); its flips are the flags.  The packed values are decoded
+    as the CF convention has it for int16 data whose scale and offset are float64: in float64.  Host-side I/O (scipy)."""
+    from scipy.io import netcdf_file
+    with netcdf_file(str(path), 'r', mmap=False) as f:
+        def decode(name):
+            v = f.variables[name]
+            raw = np.array(v.data)
+            out = raw.astype(np.float64)
+            out *= np.float64(getattr(v, 'scale_factor', 1.0))
+            out += np.float64(getattr(v, 'add_offset', 0.0))
+            fill = getattr(v, '_FillValue', None)
+            if fill is not None:
+                out[raw == fill] = np.nan
+            return np.squeeze(out)
+        z, t, q = decode('z'), decode('t'), decode('q')
+        lats = np.array(f.variables['latitude'].data, dtype=np.float64)
+        lons = np.array(f.variables['longitude'].data, dtype=np.float64)
+        level = np.array(f.variables['level'].data, dtype=np.float64) * 100          # ecmwf.py:260
+    lons[lons > 180] -= 360                                                          # ecmwf.py:279
+    if z.ndim != 3 or z.shape != (level.size, lats.size, lons.size):
+        raise ValueError(f'{path}: z is {z.shape}, expected one time step on (level, latitude, longitude) = ({level.size}, {lats.size}, {lons.size})')
+    if ll_bounds is not None:
+        S, N, W, E = ll_bounds
+        my, mx = (S <= lats) & (N >= lats), (W <= lons) & (E >= lons)
+        lats, lons = lats[my], lons[mx]
+        z, t, q = (v[:, my][:, :, mx] for v in (z, t, q))
+    if z.size == 0:
+        raise RuntimeError('There is no data in z, you may have a problem with your mask')           # ecmwf.py:332-333
+    order = {}
+    for name, axis in (('level', level), ('lats', lats), ('lons', lons)):
+        d = np.diff(axis)
+        if not (np.all(d > 0) or np.all(d < 0)):
+            raise ValueError(f'{path}: {name} is not strictly monotonic')
+        order[name] = bool(axis.size > 1 and d[0] < 0)
+    c = np.ascontiguousarray
+    return dict(z=c(z), t=c(t), q=c(q), level=level, lats=c(lats), lons=c(lons), ys=np.sort(lats), xs=np.sort(lons),
+                top_first=not order['level'], rows_descending=order['lats'], cols_descending=order['lons'])
+
+
+def load_ecmwf_pressure_levels(path, ll_bounds=None, new_z=None, return_state=False, ctx=None):
+    """WeatherModel.load for a raw ERA-5 / HRES pressure-level file (weatherModel.py:235-262 with ECMWF._load_pressure_level,
+    models/ecmwf.py:252-303): file -> geometric heights, broadcast pressures, surface-first ascending columns -> e -> uniform z
+    levels -> NaN fill -> refractivities -> padded bottom level -> ZTDs, everything after the file read on the GPU.  Returns the
+    ProcessedModel that tropo_delay / getInterpolators take.
+    For a file as the CDS writes it (latitudes descending, levels top first) the columns are the reference's.  The reference
+    re-orders `z` by other statements than `t` and `q` (:262-275); for a file with ascending latitudes those leave its heights
+    mirrored in latitude and top first under surface-first temperatures.  Here every field follows the order flags of the file."""
+    raw = read_ecmwf_pressure_level_file(path, ll_bounds)
+    if new_z is None:
+        new_z = np.flipud(ecmwf_pressure_level_heights())                                                  # ecmwf.py:39
+    return cubes_from_pressure_levels(raw['xs'], raw['ys'], raw['z'], raw['level'], raw['t'], raw['q'], raw['lats'], height_kind=0,
+                                      humidity_type='q', new_z=new_z, top_first=raw['top_first'], rows_descending=raw['rows_descending'],
+                                      cols_descending=raw['cols_descending'], return_state=return_state, ctx=ctx)
