@@ -331,6 +331,30 @@ int rdr_point_delays(rdr_ctx* ctx, const rdr_cube* cube, const double* xpts, int
 int rdr_point_delays_grid(rdr_ctx* ctx, const rdr_cube* cube, int grid_kind, const double* params, int nparams, const double* xpts, int64_t nx,
                           const double* ypts, int64_t ny, const double* zpts, int64_t nz, const double* y, const double* x, const double* z, int64_t n,
                           int proj_mode, const double* proj, double inc0, double* wet, double* hydro, int32_t* cube_has_nan);
+/* A DATE SERIES at query points: rdr_interp3_project on `ncubes` cubes of one grid (same shape, dtype, bitwise-equal axes and
+ * projection, as rdr_raytrace_slices_epochs: RDR_ERR_INVALID names the first epoch that differs) in one pass - the second stage of
+ * the point branch (delay.py:110-128) for every date of the loop of cli/raider.py:159-400.  The points - and a shared proj - go up
+ * once; per point the cell search, the weights and the address are made once, then eight corner loads and scipy's sum
+ * (_rgi.py:490-498) per epoch, up to four epochs per launch: epoch e's values are bit for bit rdr_interp3_project's on cubes[e].
+ * wet / hydro: [ncubes][n].  proj_stride 0: one proj[n] for every epoch; n: proj[ncubes][n] (Conventional with an orbit file calls
+ * setTime per date, losreader.py:122-128: its divisor may differ by date).  Host arrays of >= 2^18 points are chunked through the
+ * three-stream pipeline of rdr_interp3_project.  ncubes == 1 is rdr_interp3_project itself.  loc == RDR_DEVICE: nothing is uploaded,
+ * and the one-cube gather per date measured faster than the stacked one (profiles/r13_point_series_before_routing.json), so the entry
+ * runs rdr_interp3_project's kernels date by date. */
+int rdr_interp3_project_epochs(rdr_ctx* ctx, const rdr_cube* const* cubes, int32_t ncubes, const double* y, const double* x, const double* z,
+                               int64_t n, int proj_mode, const double* proj, int64_t proj_stride, double inc0, double* wet, double* hydro, int loc);
+/* rdr_point_delays / rdr_point_delays_grid for a date series (delay.py:96-128 per date): the ncubes intermediate cubes are built one
+ * after the other into one scratch allocation (RDR_ERR_OOM when it does not fit: go date by date), the points travel up once under the
+ * first build, one gather pass serves every date.  nparams 0: the output grid is in lon/lat or the model CRS (rdr_point_delays:
+ * grid_kind / params unused); else grid_kind / params as rdr_point_delays_grid.  wet / hydro: [ncubes][n]; proj / proj_stride as
+ * rdr_interp3_project_epochs; cube_has_nan[ncubes] (may be NULL): the scan of delay.py:187 per date.  Host arrays in, host arrays out. */
+int rdr_point_delays_epochs(rdr_ctx* ctx, const rdr_cube* const* cubes, int32_t ncubes, int grid_kind, const double* params, int nparams,
+                            const double* xpts, int64_t nx, const double* ypts, int64_t ny, const double* zpts, int64_t nz, const double* y,
+                            const double* x, const double* z, int64_t n, int proj_mode, const double* proj, int64_t proj_stride, double inc0,
+                            double* wet, double* hydro, int32_t* cube_has_nan);
+/* Host bytes of query points and divisors copied to the device since the last of the two calls above began, counted where the copies
+ * are issued (diagnostics: a series uploads its points once, not once per date); -1: NULL context. */
+int64_t rdr_point_upload_bytes(const rdr_ctx* ctx);
 /* Conventional.__call__ tail (losreader.py:130-133): delay / cosd(inc) in place, inc[n] in degrees (what inc_hd_to_enu(...)[..., -1]
  * holds for an incidence raster).  The reference projects wet and hydro in two calls: either pointer may be NULL. */
 int rdr_project_cosinc(rdr_ctx* ctx, double* wet, double* hydro, const double* inc, int64_t n, int loc);

@@ -7,4 +7,5 @@ hand-written HIP kernels behind the C ABI of include/raider_hip.h.  No CPU fallb
 __version__ = '0.1.0'
 
 from ._lib import Context, NoLevels, load as load_library  # noqa: F401
-from .engine import Cube, Rays, grid_geodetic, nparts_from_maxlen, raytrace_epochs, raytrace_slices_epochs, raytrace_slices_epochs_to_cubes  # noqa: F401
+from .engine import (Cube, Rays, grid_geodetic, interp_project_epochs, nparts_from_maxlen, point_delays_epochs, raytrace_epochs,  # noqa: F401
+                     raytrace_slices_epochs, raytrace_slices_epochs_to_cubes)

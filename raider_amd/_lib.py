@@ -103,6 +103,10 @@ SYMBOLS = [
                                    c_ip]),
     ('rdr_point_delays_grid', C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, C.c_int,
                                         _VP, C.c_double, _VP, _VP, c_ip]),
+    ('rdr_interp3_project_epochs', C.c_int, [_VP, C.POINTER(_VP), C.c_int32, _VP, _VP, _VP, C.c_int64, C.c_int, _VP, C.c_int64, C.c_double, _VP, _VP, C.c_int]),
+    ('rdr_point_delays_epochs', C.c_int, [_VP, C.POINTER(_VP), C.c_int32, C.c_int, _VP, C.c_int, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP,
+                                          C.c_int64, C.c_int, _VP, C.c_int64, C.c_double, _VP, _VP, c_ip]),
+    ('rdr_point_upload_bytes', C.c_int64, [_VP]),
     ('rdr_project_cosinc', C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int]),
     ('rdr_project_divide', C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int]),
     ('rdr_ray_levels', C.c_int, [_VP, C.c_double, C.c_double, c_ip, _VP, _VP, _VP]),
@@ -352,6 +356,10 @@ class Context:
             check(self.lib.rdr_clock_sample_end(self.handle, C.byref(g)), self.handle)
             return float(g.value)
         return end
+
+    def point_upload_bytes(self):
+        """Host bytes of query points and divisors the last interp_project_epochs / point_delays_epochs call copied to the device."""
+        return int(self.lib.rdr_point_upload_bytes(self.handle))
 
     def profile_get(self, which):
         """(launch count, total ms) of kernel kind `which` since set_profiling(True)."""

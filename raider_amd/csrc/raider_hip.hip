@@ -86,6 +86,7 @@ struct rdr_ctx {
     int64_t last_nskip = 0;                   // waves of the last rdr_ray_prepass that skipped the per-level length loop
     int64_t last_nslow = 0;                   // generic rays seen by the last pass 1 whose count the host happened to read back
     int wall_khz = 0;                         // rate of the wall counter (rdr_clock_sample_begin)
+    int64_t point_upload_bytes = 0;           // host bytes of query points / divisors the last rdr_*_epochs point call copied up (rdr_point_upload_bytes)
     int last_nan_output = -1;                 // rdr_build_cube (host arrays): 1 / 0 = its last result holds / does not hold a NaN; -1 unknown
     size_t ws_limit = (size_t)48 << 30;       // cap on that workspace; bigger batches are marched in chunks
     // which ray batch the stored records belong to (a later rdr_ray_march reuses them only for the identical batch)
@@ -1357,16 +1358,24 @@ struct StreamsQuiesce {
 // the ctx stream is still doing (rdr_point_delays: the build of the intermediate cube).  `slots`: device scratch for y, x, z, proj,
 // wet, hydro.  Synchronises all three streams before it returns.  (A download into pageable memory blocks the host thread instead of
 // overlapping: still correct.)
-static int interp_pipeline(rdr_ctx* c, const char* who, const rdr_cube* q, bool quad, const double* y, const double* x, const double* z, int64_t n,
-                           PointQuery Q, const double* proj, double* wet, double* hydro, const int* slots, const BlendSpec& B = BlendSpec()) {
+// One cube (vals == NULL, D = 1: launch_interp with its quad / blend variants) or a date series (vals[D]: the value buffers of D cubes on
+// q's grid, launch_interp_epochs): chunk k of the points - and of a shared divisor - goes up ONCE, the epoch groups gather from it, the D
+// result chunks (wet / hydro are [D][n]) come down.  pstride == n: per-date divisors proj[D][n] go up with their chunk, D pieces.
+// Every host-to-device copy of points and divisors is counted in c->point_upload_bytes.
+static void launch_interp_epochs(rdr_ctx* c, const rdr_cube* q, const void* const* vals, int D, const PointQuery& Q, int64_t pstride, int64_t cnt, int64_t estride,
+                                 double* dw, double* dh);
+static int interp_pipeline_impl(rdr_ctx* c, const char* who, const rdr_cube* q, bool quad, const BlendSpec& B, const void* const* vals, int D, const double* y,
+                                const double* x, const double* z, int64_t n, PointQuery Q, const double* proj, int64_t pstride, double* wet, double* hydro,
+                                const int* slots) {
     const bool has_proj = Q.pmode == 1 || Q.pmode == 3;
     const size_t ystride = x ? 1 : 3;
+    const int64_t np = pstride ? D : 1;
     void *dy, *dx = nullptr, *dz = nullptr, *dp = nullptr, *dw = nullptr, *dh = nullptr;
     int rc = ensure(c, slots[0], (size_t)n * ystride * 8, &dy); if (rc) return rc;
     if (x) { rc = ensure(c, slots[1], (size_t)n * 8, &dx); if (rc) return rc; rc = ensure(c, slots[2], (size_t)n * 8, &dz); if (rc) return rc; }
-    if (has_proj) { rc = ensure(c, slots[3], (size_t)n * 8, &dp); if (rc) return rc; }
-    if (wet) { rc = ensure(c, slots[4], (size_t)n * 8, &dw); if (rc) return rc; }
-    if (hydro) { rc = ensure(c, slots[5], (size_t)n * 8, &dh); if (rc) return rc; }
+    if (has_proj) { rc = ensure(c, slots[3], (size_t)n * np * 8, &dp); if (rc) return rc; }
+    if (wet) { rc = ensure(c, slots[4], (size_t)n * D * 8, &dw); if (rc) return rc; }
+    if (hydro) { rc = ensure(c, slots[5], (size_t)n * D * 8, &dh); if (rc) return rc; }
     // chunks of >= 512 k points (a copy call costs 10-20 us: 1 MB copies would spend as long on calls as on bytes), at most 8
     const int nchunk = (int)std::max<int64_t>(1, std::min<int64_t>(8, n >> 19));
     struct EventList { std::vector<hipEvent_t> v; ~EventList() { for (auto& e : v) if (e) (void)hipEventDestroy(e); } } evs;
@@ -1374,32 +1383,47 @@ static int interp_pipeline(rdr_ctx* c, const char* who, const rdr_cube* q, bool 
     for (auto& e : evs.v)
         if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(c, RDR_ERR_HIP, std::string(who) + ": event creation failed");
     StreamsQuiesce quiesce(c);                  // (declared after the events: they are destroyed only once the streams are idle)
+    auto up = [&](void* dst, const void* src, size_t bytes) {
+        c->point_upload_bytes += (int64_t)bytes;
+        return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->copy_stream);
+    };
     for (int k = 0; k < nchunk; ++k) {
         const int64_t o = n * k / nchunk, cnt = n * (k + 1) / nchunk - o;
-        HIPCHECK(c, hipMemcpyAsync((double*)dy + o * ystride, y + o * ystride, (size_t)cnt * ystride * 8, hipMemcpyHostToDevice, c->copy_stream));
+        HIPCHECK(c, up((double*)dy + o * ystride, y + o * ystride, (size_t)cnt * ystride * 8));
         if (x) {
-            HIPCHECK(c, hipMemcpyAsync((double*)dx + o, x + o, (size_t)cnt * 8, hipMemcpyHostToDevice, c->copy_stream));
-            HIPCHECK(c, hipMemcpyAsync((double*)dz + o, z + o, (size_t)cnt * 8, hipMemcpyHostToDevice, c->copy_stream));
+            HIPCHECK(c, up((double*)dx + o, x + o, (size_t)cnt * 8));
+            HIPCHECK(c, up((double*)dz + o, z + o, (size_t)cnt * 8));
         }
-        if (has_proj) HIPCHECK(c, hipMemcpyAsync((double*)dp + o, proj + o, (size_t)cnt * 8, hipMemcpyHostToDevice, c->copy_stream));
+        if (has_proj)
+            for (int64_t e = 0; e < np; ++e) HIPCHECK(c, up((double*)dp + e * n + o, proj + e * n + o, (size_t)cnt * 8));
         HIPCHECK(c, hipEventRecord(evs.v[2 * k], c->copy_stream));
         HIPCHECK(c, hipStreamWaitEvent(c->stream, evs.v[2 * k], 0));
         PointQuery Qk = Q;
         Qk.y = (const double*)dy + o * ystride;
         Qk.x = x ? (const double*)dx + o : nullptr; Qk.z = x ? (const double*)dz + o : nullptr;
         Qk.proj = has_proj ? (const double*)dp + o : nullptr;
-        launch_interp(c, q, Qk, cnt, dw ? (double*)dw + o : nullptr, dh ? (double*)dh + o : nullptr, quad, B);
+        double* const dwk = dw ? (double*)dw + o : nullptr;
+        double* const dhk = dh ? (double*)dh + o : nullptr;
+        if (vals) launch_interp_epochs(c, q, vals, D, Qk, pstride, cnt, n, dwk, dhk);
+        else launch_interp(c, q, Qk, cnt, dwk, dhk, quad, B);
         HIPCHECK(c, hipGetLastError());
         HIPCHECK(c, hipEventRecord(evs.v[2 * k + 1], c->stream));
         HIPCHECK(c, hipStreamWaitEvent(c->down_stream, evs.v[2 * k + 1], 0));
-        if (wet) HIPCHECK(c, hipMemcpyAsync(wet + o, (double*)dw + o, (size_t)cnt * 8, hipMemcpyDeviceToHost, c->down_stream));
-        if (hydro) HIPCHECK(c, hipMemcpyAsync(hydro + o, (double*)dh + o, (size_t)cnt * 8, hipMemcpyDeviceToHost, c->down_stream));
+        for (int64_t e = 0; e < D; ++e) {
+            if (wet) HIPCHECK(c, hipMemcpyAsync(wet + e * n + o, (double*)dw + e * n + o, (size_t)cnt * 8, hipMemcpyDeviceToHost, c->down_stream));
+            if (hydro) HIPCHECK(c, hipMemcpyAsync(hydro + e * n + o, (double*)dh + e * n + o, (size_t)cnt * 8, hipMemcpyDeviceToHost, c->down_stream));
+        }
     }
     HIPCHECK(c, hipStreamSynchronize(c->down_stream));
     HIPCHECK(c, hipStreamSynchronize(c->copy_stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     quiesce.armed = false;
     return RDR_OK;
+}
+
+static int interp_pipeline(rdr_ctx* c, const char* who, const rdr_cube* q, bool quad, const double* y, const double* x, const double* z, int64_t n,
+                           PointQuery Q, const double* proj, double* wet, double* hydro, const int* slots, const BlendSpec& B = BlendSpec()) {
+    return interp_pipeline_impl(c, who, q, quad, B, nullptr, 1, y, x, z, n, Q, proj, 0, wet, hydro, slots);
 }
 
 static int point_query_args(rdr_ctx* c, const char* who, const double* y, const double* x, const double* z, int64_t n, int pmode, const double* proj,
@@ -1409,6 +1433,12 @@ static int point_query_args(rdr_ctx* c, const char* who, const double* y, const 
     if (pmode < 0 || pmode > 3) return fail(c, RDR_ERR_INVALID, std::string(who) + ": proj_mode is 0 (none), 1 (incidence array), 2 (one incidence) or 3 (divisor array)");
     if (n > 0 && (pmode == 1 || pmode == 3) && !proj) return fail(c, RDR_ERR_INVALID, std::string(who) + ": proj_mode 1 / 3 need the proj array");
     return RDR_OK;
+}
+
+// stage_in for query points and divisors: what is really copied from the host is counted (rdr_point_upload_bytes)
+static int stage_points_in(rdr_ctx* ctx, int s, const void* src, size_t bytes, int loc, const void** dev) {
+    if (src && loc != RDR_DEVICE) ctx->point_upload_bytes += (int64_t)bytes;
+    return stage_in(ctx, s, src, bytes, loc, dev);
 }
 
 // the point query behind rdr_interp3 / rdr_interp3_project: y/x/z three arrays (x != NULL) or y = packed (n,3); pmode / proj / inc0 as
@@ -1456,12 +1486,12 @@ static int interp3_impl(rdr_ctx* c, const char* who, const rdr_cube* q, const do
         return interp_pipeline(c, who, q, quad, y, x, z, n, Q, proj, wet, hydro, slots, B);
     }
     const void* d; void *dw = nullptr, *dh = nullptr;
-    rc = stage_in(c, SLOT_IN0, y, (size_t)n * ystride * 8, loc, &d); if (rc) return rc; Q.y = (const double*)d;
+    rc = stage_points_in(c, SLOT_IN0, y, (size_t)n * ystride * 8, loc, &d); if (rc) return rc; Q.y = (const double*)d;
     if (x) {
-        rc = stage_in(c, SLOT_IN1, x, (size_t)n * 8, loc, &d); if (rc) return rc; Q.x = (const double*)d;
-        rc = stage_in(c, SLOT_IN2, z, (size_t)n * 8, loc, &d); if (rc) return rc; Q.z = (const double*)d;
+        rc = stage_points_in(c, SLOT_IN1, x, (size_t)n * 8, loc, &d); if (rc) return rc; Q.x = (const double*)d;
+        rc = stage_points_in(c, SLOT_IN2, z, (size_t)n * 8, loc, &d); if (rc) return rc; Q.z = (const double*)d;
     }
-    if (has_proj) { rc = stage_in(c, SLOT_IN3, proj, (size_t)n * 8, loc, &d); if (rc) return rc; Q.proj = (const double*)d; }
+    if (has_proj) { rc = stage_points_in(c, SLOT_IN3, proj, (size_t)n * 8, loc, &d); if (rc) return rc; Q.proj = (const double*)d; }
     if (wet) { rc = stage_out(c, SLOT_OUT0, wet, (size_t)n * 8, loc, &dw); if (rc) return rc; }
     if (hydro) { rc = stage_out(c, SLOT_OUT1, hydro, (size_t)n * 8, loc, &dh); if (rc) return rc; }
     launch_interp(c, q, Q, n, (double*)dw, (double*)dh, quad, B);
@@ -1653,6 +1683,41 @@ int rdr_build_cube_grid_to_cube(rdr_ctx* c, const rdr_cube* q, int grid_kind, co
 }
 
 
+// The intermediate cube of the point branch as a scratch object: shape and axes of the output grid (descending axes flipped as scipy
+// does, fy / fx / fz say which), no buffers yet.  Returns non-zero when an axis is not strictly monotonic.
+static int scratch_cube_init(rdr_cube& tmp, rdr_ctx* c, const double* xpts, int64_t nx, const double* ypts, int64_t ny, const double* zpts, int64_t nz,
+                             int* fy, int* fx, int* fz) {
+    if (axis_check(ypts, ny, fy) || axis_check(xpts, nx, fx) || axis_check(zpts, nz, fz)) return -1;
+    tmp.ctx = c; tmp.ny = ny; tmp.nx = nx; tmp.nz = nz; tmp.dtype = RDR_F64;
+    tmp.ys.assign(ypts, ypts + ny); tmp.xs.assign(xpts, xpts + nx); tmp.zs.assign(zpts, zpts + nz);
+    if (*fy) std::reverse(tmp.ys.begin(), tmp.ys.end());
+    if (*fx) std::reverse(tmp.xs.begin(), tmp.xs.end());
+    if (*fz) std::reverse(tmp.zs.begin(), tmp.zs.end());
+    axis_uniformity(tmp.ys, &tmp.uni[0], &tmp.inv_d[0], &tmp.exact[0]);
+    axis_uniformity(tmp.xs, &tmp.uni[1], &tmp.inv_d[1], &tmp.exact[1]);
+    axis_uniformity(tmp.zs, &tmp.uni[2], &tmp.inv_d[2]);
+    return 0;
+}
+
+// planar (z, y, x) build results -> the interleaved (y, x, z) values of the intermediate cube, NaN verdict into *nf
+static void pack_planar(rdr_ctx* c, double* const* planar, double2* dvals, int64_t ny, int64_t nx, int64_t nz, int fy, int fx, int fz, int* nf) {
+    if (nx >= 8 && nz >= 8)        // x is contiguous - the LDS-transposing packer (cube_kernels.h)
+        hipLaunchKernelGGL((pack_cube_xfast_kernel<double, double2, false>), dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(ny * ((nx + 31) / 32) * ((nz + 31) / 32), (int64_t)c->num_cus * 16))),
+                           dim3(256), 0, c->stream, (const double*)planar[0], (const double*)planar[1], dvals, ny, nx, nz, nx, ny * nx, fy, fx, fz, nf);
+    else
+        hipLaunchKernelGGL((pack_cube_kernel<double, double2, false>), dim3(grid_for(ny * nx * nz, 256, c->num_cus * 8)), dim3(256), 0, c->stream,
+                           (const double*)planar[0], (const double*)planar[1], dvals, ny, nx, nz, nx, (int64_t)1, ny * nx, fy, fx, fz, nf);
+}
+
+// a large job's intermediates (16 B per cell of the cube + 16 B per cell of planar results) are not kept for the life of the context
+static void scratch_trim_point_delays(rdr_ctx* c) {
+    static const size_t keep = []() { const char* e = std::getenv("RAIDER_HIP_SCRATCH_KEEP_BYTES"); return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)4 << 30; }();
+    for (int s_ : {SLOT_TMPCUBE, SLOT_OUT0, SLOT_OUT1}) {
+        DevBuf& b = c->slot[s_];
+        if (b.p && b.cap > keep) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
+    }
+}
+
 // tropo_delay's point branch for a zenith / projected line of sight (delay.py:96-128) in ONE call: _build_cube on the output grid
 // (xpts, ypts, zpts) -> the intermediate cube packed as getInterpolators(ds, 'ztd') would wrap it -> trilinear gather at the query
 // points -> delay / cos(inc).  Everything is enqueued before anything is waited for: the points travel up (copy stream) while the
@@ -1666,20 +1731,12 @@ static int point_delays_impl(rdr_ctx* c, const char* who, const rdr_cube* q, con
     if (nz > MAX_LEVELS) return fail(c, RDR_ERR_INVALID, w + ": more than 512 height levels");
     if (ny + nx + nz > 100000) return fail(c, RDR_ERR_INVALID, w + ": axes too long");
     int rc = point_query_args(c, who, y, x, z, n, proj_mode, proj, wet, hydro); if (rc) return rc;
+    // the intermediate cube: a scratch object (values and axes in context slots), never destroyed
     int fy, fx, fz;
-    if (axis_check(ypts, ny, &fy) || axis_check(xpts, nx, &fx) || axis_check(zpts, nz, &fz))
+    rdr_cube tmp;
+    if (scratch_cube_init(tmp, c, xpts, nx, ypts, ny, zpts, nz, &fy, &fx, &fz))
         return fail(c, RDR_ERR_INVALID, "The points in each dimension must be strictly ascending or descending (and >= 2)");
     HIPCHECK(c, hipSetDevice(c->device));
-    // the intermediate cube: a scratch object (values and axes in context slots), never destroyed
-    rdr_cube tmp;
-    tmp.ctx = c; tmp.ny = ny; tmp.nx = nx; tmp.nz = nz; tmp.dtype = RDR_F64;
-    tmp.ys.assign(ypts, ypts + ny); tmp.xs.assign(xpts, xpts + nx); tmp.zs.assign(zpts, zpts + nz);
-    if (fy) std::reverse(tmp.ys.begin(), tmp.ys.end());
-    if (fx) std::reverse(tmp.xs.begin(), tmp.xs.end());
-    if (fz) std::reverse(tmp.zs.begin(), tmp.zs.end());
-    axis_uniformity(tmp.ys, &tmp.uni[0], &tmp.inv_d[0], &tmp.exact[0]);
-    axis_uniformity(tmp.xs, &tmp.uni[1], &tmp.inv_d[1], &tmp.exact[1]);
-    axis_uniformity(tmp.zs, &tmp.uni[2], &tmp.inv_d[2]);
     const size_t total = (size_t)ny * nx * nz;
     void *dvals, *daxes;
     rc = ensure(c, SLOT_TMPCUBE, total * sizeof(double2), &dvals); if (rc) return rc;
@@ -1693,12 +1750,7 @@ static int point_delays_impl(rdr_ctx* c, const char* who, const rdr_cube* q, con
     rc = build_cube_impl(c, q, xpts, nx, ypts, ny, zpts, nz, nullptr, nullptr, RDR_HOST, planar, nullptr, grid); if (rc) return rc;
     int* const nf = c->d_flags + MAX_SLICES + 2;
     HIPCHECK(c, hipMemsetAsync(nf, 0, sizeof(int), c->stream));
-    if (nx >= 8 && nz >= 8)        // planar (z, y, x) results: x is contiguous - the LDS-transposing packer (cube_kernels.h)
-        hipLaunchKernelGGL((pack_cube_xfast_kernel<double, double2, false>), dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(ny * ((nx + 31) / 32) * ((nz + 31) / 32), (int64_t)c->num_cus * 16))),
-                           dim3(256), 0, c->stream, (const double*)planar[0], (const double*)planar[1], (double2*)dvals, ny, nx, nz, nx, ny * nx, fy, fx, fz, nf);
-    else
-        hipLaunchKernelGGL((pack_cube_kernel<double, double2, false>), dim3(grid_for((int64_t)total, 256, c->num_cus * 8)), dim3(256), 0, c->stream,
-                           (const double*)planar[0], (const double*)planar[1], (double2*)dvals, ny, nx, nz, nx, (int64_t)1, ny * nx, fy, fx, fz, nf);
+    pack_planar(c, planar, (double2*)dvals, ny, nx, nz, fy, fx, fz, nf);
     HIPCHECK(c, hipGetLastError());
     // (into a page-locked word: a pageable destination would stall the host here until the cube is built - and the upload of the
     // points, which is to run UNDER that build, with it)
@@ -1712,12 +1764,7 @@ static int point_delays_impl(rdr_ctx* c, const char* who, const rdr_cube* q, con
     } else HIPCHECK(c, hipStreamSynchronize(c->stream));
     quiesce.armed = false;                      // (both branches have synchronised)
     if (cube_has_nan) *cube_has_nan = c->h_word[0] != 0;
-    // a large job's intermediates (16 B per cell of the cube + 16 B per cell of planar results) are not kept for the life of the context
-    static const size_t keep = []() { const char* e = std::getenv("RAIDER_HIP_SCRATCH_KEEP_BYTES"); return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)4 << 30; }();
-    for (int s_ : {SLOT_TMPCUBE, SLOT_OUT0, SLOT_OUT1}) {
-        DevBuf& b = c->slot[s_];
-        if (b.p && b.cap > keep) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
-    }
+    scratch_trim_point_delays(c);
     return RDR_OK;
 }
 
@@ -2415,6 +2462,175 @@ static int epochs_max() {
     const char* e = std::getenv("RAIDER_HIP_EPOCHS_MAX");
     const int v = e ? std::atoi(e) : EPOCHS_MAX;
     return v >= 4 ? 4 : v >= 2 ? 2 : 1;
+}
+
+// ---- a date series at query points (rdr_interp3_project_epochs, rdr_point_delays_epochs) --------------------------------------------
+// The gather of D epochs that share one grid: `q` describes that grid (shape, axes, dtype), vals[e] is epoch e's value buffer.
+template <typename T2, int E>
+static void launch_points_stacked(rdr_ctx* c, const rdr_cube* q, const void* const* vals, const PointQuery& Q, int64_t pstride, int64_t cnt, int64_t estride,
+                                  double* dw, double* dh) {
+    EpochCubes<T2, E> ev;
+    for (int j = 0; j < E; ++j) ev.v[j] = (const T2*)vals[j];
+    const int g = grid_for(cnt, 256, c->num_cus * 8);
+    hipLaunchKernelGGL((interp_points_epochs_kernel<T2, E>), dim3(g), dim3(256), axes_smem(q), c->stream, make_view<T2>(q), ev, Q, pstride, cnt, estride, dw, dh,
+                       (int)axes_fit_lds(q));
+}
+
+// groups of 4, then 2, then 1 epochs (engine.epoch_groups; RAIDER_HIP_EPOCHS_MAX caps the group).  dw / dh: epoch 0's block, epoch e's is
+// estride doubles further; Q.proj: epoch 0's divisors, epoch e's pstride doubles further (pstride 0: shared).
+static void launch_interp_epochs(rdr_ctx* c, const rdr_cube* q, const void* const* vals, int D, const PointQuery& Q, int64_t pstride, int64_t cnt, int64_t estride,
+                                 double* dw, double* dh) {
+    const int emax = epochs_max();
+    for (int e = 0; e < D;) {
+        const int left = D - e;
+        const int ge = (left >= 4 && emax >= 4) ? 4 : (left >= 2 && emax >= 2) ? 2 : 1;
+        PointQuery Qe = Q;
+        if (Qe.proj) Qe.proj += (int64_t)e * pstride;
+        double* we = dw ? dw + (int64_t)e * estride : nullptr;
+        double* he = dh ? dh + (int64_t)e * estride : nullptr;
+        KTimer t(c, 2);
+        if (q->dtype == RDR_F32) {
+            if (ge == 4) launch_points_stacked<float2, 4>(c, q, vals + e, Qe, pstride, cnt, estride, we, he);
+            else if (ge == 2) launch_points_stacked<float2, 2>(c, q, vals + e, Qe, pstride, cnt, estride, we, he);
+            else launch_points_stacked<float2, 1>(c, q, vals + e, Qe, pstride, cnt, estride, we, he);
+        } else {
+            if (ge == 4) launch_points_stacked<double2, 4>(c, q, vals + e, Qe, pstride, cnt, estride, we, he);
+            else if (ge == 2) launch_points_stacked<double2, 2>(c, q, vals + e, Qe, pstride, cnt, estride, we, he);
+            else launch_points_stacked<double2, 1>(c, q, vals + e, Qe, pstride, cnt, estride, we, he);
+        }
+        e += ge;
+    }
+}
+
+// the checks the two entries share, after epochs_check: the point query's own, and the divisor stride
+static int epochs_point_args(rdr_ctx* c, const char* who, const double* y, const double* x, const double* z, int64_t n, int pmode, const double* proj,
+                             int64_t proj_stride, const double* wet, const double* hydro) {
+    int rc = point_query_args(c, who, y, x, z, n, pmode, proj, wet, hydro); if (rc) return rc;
+    if (proj_stride != 0 && proj_stride != n)
+        return fail(c, RDR_ERR_INVALID, std::string(who) + ": proj_stride is 0 (one proj[n] for every epoch) or n (proj[ncubes][n]), got " + std::to_string(proj_stride));
+    return RDR_OK;
+}
+
+int rdr_interp3_project_epochs(rdr_ctx* c, const rdr_cube* const* cubes, int32_t ncubes, const double* y, const double* x, const double* z, int64_t n,
+                               int proj_mode, const double* proj, int64_t proj_stride, double inc0, double* wet, double* hydro, int loc) {
+    static const char* who = "rdr_interp3_project_epochs";
+    int rc = epochs_check(c, who, cubes, ncubes); if (rc) return rc;
+    rc = epochs_point_args(c, who, y, x, z, n, proj_mode, proj, proj_stride, wet, hydro); if (rc) return rc;
+    if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, std::string(who) + ": loc is RDR_HOST or RDR_DEVICE");
+    c->point_upload_bytes = 0;
+    if (ncubes == 1) return interp3_impl(c, who, cubes[0], y, x, z, n, proj_mode, proj, inc0, wet, hydro, loc);
+    if (loc == RDR_DEVICE) {
+        // Device-resident points: there is no upload to share, and the one-cube gather per date is the faster one (measured, DESIGN.md 5d:
+        // it keeps one cube's lines in L2 at a time and takes the corner-quad copy on large cubes) - the per-date loop behind this entry.
+        const int64_t ps = (proj_mode == 1 || proj_mode == 3) ? proj_stride : 0;
+        for (int32_t e = 0; e < ncubes; ++e) {
+            rc = interp3_impl(c, who, cubes[e], y, x, z, n, proj_mode, proj ? proj + (int64_t)e * ps : nullptr, inc0, wet ? wet + (int64_t)e * n : nullptr,
+                              hydro ? hydro + (int64_t)e * n : nullptr, loc);
+            if (rc) return rc;
+        }
+        return RDR_OK;
+    }
+    const rdr_cube* q = cubes[0];
+    for (int32_t e = 0; e < ncubes; ++e) note_use(c, cubes[e]);
+    if (n == 0) return RDR_OK;
+    HIPCHECK(c, hipSetDevice(c->device));
+    const int D = ncubes;
+    std::vector<const void*> vals((size_t)D);
+    for (int e = 0; e < D; ++e) vals[(size_t)e] = cubes[e]->d_vals;
+    PointQuery Q; std::memset(&Q, 0, sizeof(Q));
+    Q.pmode = proj_mode; Q.inc0 = inc0;
+    const bool has_proj = proj_mode == 1 || proj_mode == 3;
+    const int64_t pstride = has_proj ? proj_stride : 0;
+    const int64_t np = pstride ? D : 1;
+    const size_t ystride = x ? 1 : 3;
+    if (loc == RDR_HOST && n >= (1 << 18) && pipelining()) {
+        static const int slots[6] = {SLOT_IN0, SLOT_IN1, SLOT_IN2, SLOT_IN3, SLOT_OUT0, SLOT_OUT1};
+        return interp_pipeline_impl(c, who, q, false, BlendSpec(), vals.data(), D, y, x, z, n, Q, proj, pstride, wet, hydro, slots);
+    }
+    const void* d; void *dw = nullptr, *dh = nullptr;
+    rc = stage_points_in(c, SLOT_IN0, y, (size_t)n * ystride * 8, loc, &d); if (rc) return rc; Q.y = (const double*)d;
+    if (x) {
+        rc = stage_points_in(c, SLOT_IN1, x, (size_t)n * 8, loc, &d); if (rc) return rc; Q.x = (const double*)d;
+        rc = stage_points_in(c, SLOT_IN2, z, (size_t)n * 8, loc, &d); if (rc) return rc; Q.z = (const double*)d;
+    }
+    if (has_proj) { rc = stage_points_in(c, SLOT_IN3, proj, (size_t)n * np * 8, loc, &d); if (rc) return rc; Q.proj = (const double*)d; }
+    if (wet) { rc = stage_out(c, SLOT_OUT0, wet, (size_t)n * D * 8, loc, &dw); if (rc) return rc; }
+    if (hydro) { rc = stage_out(c, SLOT_OUT1, hydro, (size_t)n * D * 8, loc, &dh); if (rc) return rc; }
+    launch_interp_epochs(c, q, vals.data(), D, Q, pstride, n, n, (double*)dw, (double*)dh);
+    HIPCHECK(c, hipGetLastError());
+    rc = finish_out(c, wet, dw, (size_t)n * D * 8, loc); if (rc) return rc;
+    rc = finish_out(c, hydro, dh, (size_t)n * D * 8, loc); if (rc) return rc;
+    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return RDR_OK;
+}
+
+int64_t rdr_point_upload_bytes(const rdr_ctx* c) { return c ? c->point_upload_bytes : -1; }
+
+// point_delays_impl for D dates: the D intermediate cubes built one after the other (build_cube_impl + the packer, as there) into D
+// regions of one scratch allocation, each with its own NaN word; the points travel up ONCE on the copy stream under the first build;
+// one gather pass (interp_pipeline_impl) then serves every date.  Same kernels and arithmetic per date as rdr_point_delays[_grid]:
+// the same bits.
+int rdr_point_delays_epochs(rdr_ctx* c, const rdr_cube* const* cubes, int32_t ncubes, int grid_kind, const double* params, int nparams,
+                            const double* xpts, int64_t nx, const double* ypts, int64_t ny, const double* zpts, int64_t nz,
+                            const double* y, const double* x, const double* z, int64_t n, int proj_mode, const double* proj, int64_t proj_stride, double inc0,
+                            double* wet, double* hydro, int32_t* cube_has_nan) {
+    static const char* who = "rdr_point_delays_epochs";
+    const std::string w(who);
+    int rc = epochs_check(c, who, cubes, ncubes); if (rc) return rc;
+    if (!xpts || !ypts || !zpts) return fail(c, RDR_ERR_INVALID, w + ": NULL argument");
+    if (nparams < 0) return fail(c, RDR_ERR_INVALID, w + ": negative nparams");
+    GridCrs g;
+    const GridCrs* grid = nullptr;
+    if (nparams > 0) { rc = grid_crs(c, who, grid_kind, params, nparams, g); if (rc) return rc; grid = &g; }
+    rc = epochs_point_args(c, who, y, x, z, n, proj_mode, proj, proj_stride, wet, hydro); if (rc) return rc;
+    c->point_upload_bytes = 0;
+    if (ncubes == 1) return point_delays_impl(c, who, cubes[0], grid, xpts, nx, ypts, ny, zpts, nz, y, x, z, n, proj_mode, proj, inc0, wet, hydro, cube_has_nan);
+    if (nx < 2 || ny < 2 || nz < 2) return fail(c, RDR_ERR_INVALID, w + ": the delay cube needs two nodes per axis");
+    if (nz > MAX_LEVELS) return fail(c, RDR_ERR_INVALID, w + ": more than 512 height levels");
+    if (ny + nx + nz > 100000) return fail(c, RDR_ERR_INVALID, w + ": axes too long");
+    // the intermediate cubes: ONE scratch description (shape, axes), D value regions
+    int fy, fx, fz;
+    rdr_cube tmp;
+    if (scratch_cube_init(tmp, c, xpts, nx, ypts, ny, zpts, nz, &fy, &fx, &fz))
+        return fail(c, RDR_ERR_INVALID, "The points in each dimension must be strictly ascending or descending (and >= 2)");
+    HIPCHECK(c, hipSetDevice(c->device));
+    const int D = ncubes;
+    const size_t total = (size_t)ny * nx * nz;
+    void *dvals, *daxes, *dnan;
+    rc = ensure(c, SLOT_TMPCUBE, total * sizeof(double2) * (size_t)D, &dvals); if (rc) return rc;      // (does not fit: RDR_ERR_OOM, the caller goes date by date)
+    rc = ensure(c, SLOT_TMPAXES, (size_t)(ny + nx + nz) * 8, &daxes); if (rc) return rc;
+    rc = ensure(c, SLOT_OUT2, (size_t)D * sizeof(int), &dnan); if (rc) return rc;
+    tmp.d_vals = dvals; tmp.d_axes = (double*)daxes;
+    std::vector<double> ax;
+    ax.insert(ax.end(), tmp.ys.begin(), tmp.ys.end()); ax.insert(ax.end(), tmp.xs.begin(), tmp.xs.end()); ax.insert(ax.end(), tmp.zs.begin(), tmp.zs.end());
+    std::vector<const void*> vals((size_t)D);
+    std::vector<int> nanw((size_t)D, 0);
+    StreamsQuiesce quiesce(c);                  // (`ax`, `nanw`, the caller's points and outputs: nothing may still be copying when an error returns)
+    HIPCHECK(c, hipMemcpyAsync(daxes, ax.data(), ax.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemsetAsync(dnan, 0, (size_t)D * sizeof(int), c->stream));
+    for (int e = 0; e < D; ++e) {
+        double2* dv = (double2*)dvals + (size_t)e * total;
+        vals[(size_t)e] = dv;
+        int* const nf = (int*)dnan + e;
+        double* planar[2] = {nullptr, nullptr};
+        rc = build_cube_impl(c, cubes[e], xpts, nx, ypts, ny, zpts, nz, nullptr, nullptr, RDR_HOST, planar, nullptr, grid); if (rc) return rc;
+        pack_planar(c, planar, dv, ny, nx, nz, fy, fx, fz, nf);
+        HIPCHECK(c, hipGetLastError());
+    }
+    if (n > 0) {
+        PointQuery Q; std::memset(&Q, 0, sizeof(Q));
+        Q.pmode = proj_mode; Q.inc0 = inc0;
+        const int64_t pstride = (proj_mode == 1 || proj_mode == 3) ? proj_stride : 0;
+        static const int slots[6] = {SLOT_PT0, SLOT_PT1, SLOT_PT2, SLOT_PT3, SLOT_PT4, SLOT_PT5};
+        rc = interp_pipeline_impl(c, who, &tmp, false, BlendSpec(), vals.data(), D, y, x, z, n, Q, proj, pstride, wet, hydro, slots); if (rc) return rc;
+    }
+    // the D NaN words, after everything else has been enqueued (a pageable destination: the host waits here, with nothing left to overlap)
+    HIPCHECK(c, hipMemcpyAsync(nanw.data(), dnan, (size_t)D * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    quiesce.armed = false;
+    if (cube_has_nan) for (int e = 0; e < D; ++e) cube_has_nan[e] = nanw[(size_t)e] != 0;
+    scratch_trim_point_delays(c);
+    return RDR_OK;
 }
 
 template <typename T2, int E>

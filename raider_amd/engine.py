@@ -608,6 +608,100 @@ def raytrace_epochs(cubes, rays, ht, zref, max_seg=1000.0, out=None, want_nparts
     return wet, hyd, nparts, flags.value
 
 
+def _series_proj_args(D, n, shape, inc, divisor):
+    """(proj_mode, proj array, proj_stride, inc0) of a series point query on host arrays: `inc` / `divisor` of the points' shape are
+    shared by every date (stride 0); with a leading axis of length D they are per date (stride n)."""
+    if inc is not None and divisor is not None:
+        raise ValueError('give inc= or divisor=, not both')
+    arr = inc if inc is not None else divisor
+    if arr is None:
+        return 0, None, 0, 0.0
+    if np.ndim(arr) == 0 and inc is not None:
+        return 2, None, 0, float(arr)
+    mode = 1 if inc is not None else 3
+    a = np.asarray(arr, dtype=np.float64)
+    if a.ndim == len(shape) + 1:
+        if a.shape[0] != D:
+            raise ValueError(f'the per-date {"inc" if inc is not None else "divisor"} has a leading axis of {a.shape[0]}, the series has {D} dates')
+        return mode, f64(np.broadcast_to(a, (D,) + tuple(shape))).reshape(-1), n, 0.0
+    return mode, f64(np.broadcast_to(a, shape)).reshape(-1), 0, 0.0
+
+
+def _series_cubes(cubes):
+    cubes = list(cubes)
+    if not cubes:
+        raise ValueError('a series needs at least one epoch cube')
+    return cubes, cubes[0].ctx, (C.c_void_p * len(cubes))(*[c.handle for c in cubes])
+
+
+def interp_project_epochs(cubes, y, x=None, z=None, inc=None, divisor=None):
+    """Cube.interp_project at ONE point set on D cubes of one grid (same shape, dtype, axes and projection) - a date series at
+    stations or pixels - in one call (rdr_interp3_project_epochs): the points go up once, the cell search and the weights are made
+    once per point, up to four dates are gathered per launch.  Epoch e's values are bit for bit cubes[e].interp_project(...)'s.
+    Points as Cube.interp_project (host arrays or float64 device tensors; three arrays or y = packed [..., 3]); `inc` / `divisor` of
+    the points' shape serve every date, with a leading axis of length D they are per date.  Returns (wet[D, ...], hydro[D, ...]).
+    Host arrays take the stacked gather; device tensors have no upload to share and measured slower stacked than date by date on large cubes, so the
+    library runs the one-cube gather per date for them behind this call."""
+    cubes, ctx, handles = _series_cubes(cubes)
+    D = len(cubes)
+    if _is_dev(y):
+        import torch
+        if inc is not None and divisor is not None:
+            raise ValueError('give inc= or divisor=, not both')
+        ctx.adopt_torch_stream(y)
+        if x is None:
+            if y.shape[-1] != 3:
+                raise ValueError(f'The requested sample points xi have dimension {y.shape[-1]} but this RegularGridInterpolator has dimension 3')
+            shape, n = tuple(y.shape[:-1]), y.numel() // 3
+            _dev_f64(y, 'pts')
+        else:
+            shape, n = tuple(y.shape), y.numel()
+            for t, what in ((y, 'y'), (x, 'x'), (z, 'z')):
+                _dev_f64(t, what, n)
+        arr = inc if inc is not None else divisor
+        if arr is not None and _is_dev(arr):
+            mode, inc0 = (1 if inc is not None else 3), 0.0
+            if arr.dim() == len(shape) + 1:
+                if arr.shape[0] != D:
+                    raise ValueError(f'the per-date {"inc" if inc is not None else "divisor"} has a leading axis of {arr.shape[0]}, the series has {D} dates')
+                parr, pstride = _dev_f64(arr, 'inc / divisor', D * n), n
+            else:
+                parr, pstride = _dev_f64(arr, 'inc / divisor', n), 0
+        else:
+            mode, parr, pstride, inc0 = _series_proj_args(D, n, shape, inc, divisor)
+            if parr is not None:
+                parr = torch.from_numpy(parr if parr.flags.writeable else parr.copy()).to(y.device)
+        wet = torch.empty((D,) + shape, dtype=torch.float64, device=y.device); hyd = torch.empty_like(wet)
+        check(ctx.lib.rdr_interp3_project_epochs(ctx.handle, handles, D, ptr(y), ptr(x), ptr(z), n, mode, ptr(parr), pstride, inc0, ptr(wet), ptr(hyd),
+                                                 L.RDR_DEVICE), ctx.handle)
+        return wet, hyd
+    ya, xa, za, n, shape, _, _, _ = Cube._point_args(y, x, z, None, None)
+    mode, parr, pstride, inc0 = _series_proj_args(D, n, shape, inc, divisor)
+    wet = _pinned.empty((D, n)); hyd = _pinned.empty((D, n))
+    check(ctx.lib.rdr_interp3_project_epochs(ctx.handle, handles, D, ptr(ya), ptr(xa), ptr(za), n, mode, ptr(parr), pstride, inc0, ptr(wet), ptr(hyd),
+                                             L.RDR_HOST), ctx.handle)
+    return wet.reshape((D,) + tuple(shape)), hyd.reshape((D,) + tuple(shape))
+
+
+def point_delays_epochs(cubes, xpts, ypts, zpts, y, x=None, z=None, inc=None, divisor=None, grid=None):
+    """Cube.point_delays for D (total-delay) cubes of one grid in ONE library call (rdr_point_delays_epochs): the D intermediate cubes
+    are built one after the other into device scratch, the points travel up once under the first build, one gather pass serves every
+    date.  Date e's values are bit for bit cubes[e].point_delays(...)'s.  `inc` / `divisor` as interp_project_epochs; grid as
+    Cube.point_delays.  Returns (wet[D, ...], hydro[D, ...], has_nan[D])."""
+    cubes, ctx, handles = _series_cubes(cubes)
+    D = len(cubes)
+    gx, gy, gz = f64(xpts).ravel(), f64(ypts).ravel(), f64(np.atleast_1d(zpts)).ravel()
+    ya, xa, za, n, shape, _, _, _ = Cube._point_args(y, x, z, None, None)
+    mode, parr, pstride, inc0 = _series_proj_args(D, n, shape, inc, divisor)
+    wet = _pinned.empty((D, n)); hyd = _pinned.empty((D, n))
+    flags = np.zeros(D, dtype=np.int32)
+    kind, gp = (0, None) if grid is None else (int(grid[0]), f64(grid[1]))
+    check(ctx.lib.rdr_point_delays_epochs(ctx.handle, handles, D, kind, ptr(gp), 0 if gp is None else gp.size, ptr(gx), gx.size, ptr(gy), gy.size,
+                                          ptr(gz), gz.size, ptr(ya), ptr(xa), ptr(za), n, mode, ptr(parr), pstride, inc0, ptr(wet), ptr(hyd),
+                                          flags.ctypes.data_as(L.c_ip)), ctx.handle)
+    return wet.reshape((D,) + tuple(shape)), hyd.reshape((D,) + tuple(shape)), flags != 0
+
+
 class Rays:
     """One ray batch = one (ny,nx) slice at one height (delay.py:256-273).  Keeps references to the
     arrays it points at."""
