@@ -248,6 +248,24 @@ int rdr_cube_blend(rdr_ctx* ctx, const rdr_cube* a, double w1, const rdr_cube* b
 int rdr_inverse_time_weights(rdr_ctx* ctx, const double* az, int64_t n, const double* dates, int32_t nd, double window_s,
                              double regularizer, double* weights, int loc);
 int rdr_cube_blend_weighted(rdr_ctx* ctx, const rdr_cube* const* cubes, int32_t nd, const double* weights, int loc, rdr_cube** out);
+/* The whole 'azimuth_time_grid' branch of combine_weather_files (cli/raider.py:791-832, 891-916) in ONE pass, nothing in between
+ * materialised: per voxel of the model grid lla2ecef of (lat2d, lon2d, z) -> zero-Doppler azimuth time + one-way range delay on the
+ * orbit, truncated to milliseconds (get_azimuth_time_grid, s1_azimuth_timing.py:90-147; threshold 1e-7, <= 100 iterations) ->
+ * the weights of rdr_inverse_time_weights -> the sums of rdr_cube_blend_weighted, bit for bit what those entries give on the same
+ * time grid.  pointwise[nd] and / or total[nd] (either array may be NULL): the nd (1..8) model epochs, each array on one grid (shape,
+ * dtype, bitwise-equal axes, projection; RDR_ERR_INVALID names the first epoch that differs) and both arrays on the same grid (their
+ * dtypes may differ).  lat2d, lon2d: [ny*nx] degrees in the cubes' ascending axis order, at `loc`.  sv_t / sv_pos / sv_vel: the state
+ * vectors as rdr_orbit_look_vectors takes them (HOST; strictly increasing; 4 <= nsv <= 320, the table the kernel keeps in LDS).
+ * dates_s[nd]: model times in seconds relative to dates[0]; window_s / reg as rdr_inverse_time_weights; offset_us = (the epoch sv_t
+ * counts from, truncated to milliseconds) - dates[0], in microseconds.  *out_pointwise / *out_total: new f64 cubes with epoch 0's
+ * axes and projection (NULL where the source array is NULL).  time_grid (may be NULL): [nz][ny][nx] acquisition times in seconds
+ * relative to dates[0], at `loc`.  *flags (HOST; the call synchronises): bit 0 = a voxel's solve failed or left the orbit span (its
+ * outputs are NaN: "The Time Grid return nans", cli/raider.py:913-914), bit 1 = no date lay inside the window anywhere ("No dates
+ * provided are within temporal window"). */
+int rdr_cube_blend_azimuth_time(rdr_ctx* ctx, const rdr_cube* const* pointwise, const rdr_cube* const* total, int32_t nd, const double* lat2d,
+                                const double* lon2d, int loc, const double* sv_t, const double* sv_pos, const double* sv_vel, int64_t nsv,
+                                const double* dates_s, double window_s, double reg, int64_t offset_us, rdr_cube** out_pointwise,
+                                rdr_cube** out_total, double* time_grid, int32_t* flags);
 
 /* GUNW radian conversion (aria/calcGUNW.py:54-59): out = delay * (-4 pi / wavelength) for both fields;
  * dtype RDR_F32 multiplies in f32 by the f32-rounded factor (NumPy weak-scalar rule), RDR_F64 in f64.  In place allowed. */

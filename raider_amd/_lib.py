@@ -21,6 +21,7 @@ RDR_HOST, RDR_DEVICE = 0, 1
 ORIGIN_GRID, ORIGIN_LLH, ORIGIN_XYZ = 0, 1, 2
 RDR_PROJ_LCC, RDR_PROJ_STERE, RDR_GRID_TM = 1, 2, 3
 LOS_VEC, LOS_INC_HD, LOS_INC_HD_SCALAR, LOS_ZENITH = 0, 1, 2, 3
+ORBIT_LDS_MAX_SV = 320          # csrc/orbit_kernels.h: state vectors the LDS tables of the fast orbit kernels hold
 FLAG_ANY_NAN, FLAG_ANY_FINITE, FLAG_FIRST_NOT_BELOW, FLAG_LAST_NOT_ABOVE, FLAG_DIVERGED, FLAG_BAD_HEIGHT, FLAG_NAN_OUTPUT = 1, 2, 4, 8, 16, 32, 64
 
 c_dp = C.POINTER(C.c_double)
@@ -131,6 +132,8 @@ SYMBOLS = [
     ('rdr_ray_march_device', C.c_int, [_VP, _VP, _VP, C.c_double, C.c_double, C.c_double, _VP, _VP, _VP]),
     ('rdr_inverse_time_weights', C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int32, C.c_double, C.c_double, _VP, C.c_int]),
     ('rdr_cube_blend_weighted', C.c_int, [_VP, C.POINTER(_VP), C.c_int32, _VP, C.c_int, C.POINTER(_VP)]),
+    ('rdr_cube_blend_azimuth_time', C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_VP), C.c_int32, _VP, _VP, C.c_int, _VP, _VP, _VP, C.c_int64, _VP, C.c_double,
+                                              C.c_double, C.c_int64, C.POINTER(_VP), C.POINTER(_VP), _VP, c_ip]),
     ('rdr_delays_to_phase', C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, C.c_double, _VP, _VP, C.c_int]),
     ('rdr_ecmwf_model_levels', C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int32, C.c_int64, C.c_int64, C.c_double, _VP, _VP, C.c_int]),
     ('rdr_pressure_level_state', C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, _VP, _VP, _VP, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int,

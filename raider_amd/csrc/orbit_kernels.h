@@ -129,11 +129,16 @@ __device__ __forceinline__ void orbit_eval_seg(const OrbitSegRegs& r, double t, 
     }
 }
 
-__global__ __launch_bounds__(256) void orbit_los_fast_kernel(const double* __restrict__ st, const double* __restrict__ sp, const double* __restrict__ sv, int nsv,
-                                                             const double* __restrict__ xyz, int64_t n, double threshold, int maxiter,
-                                                             double* __restrict__ los, double* __restrict__ aztime, double* __restrict__ srange) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char orbit_smem[];
-    double* s_t = reinterpret_cast<double*>(orbit_smem);
+// The LDS tables of one workgroup and the solve on them, shared by every kernel that needs a zero-Doppler time per lane
+// (orbit_los_fast_kernel below, aztime_blend_kernel in aztime_kernels.h).
+struct OrbitTables { const double *s_t, *s_p, *s_v, *s_seg; int nsv; double t_first, t_last, inv_dt; };
+
+constexpr size_t orbit_tables_bytes(int64_t nsv) { return ((size_t)nsv * 7 + (size_t)(nsv - 3) * 16) * sizeof(double); }
+
+// built by the whole workgroup (two barriers): smem holds orbit_tables_bytes(nsv)
+__device__ __forceinline__ OrbitTables orbit_tables_build(unsigned char* smem, const double* __restrict__ st, const double* __restrict__ sp,
+                                                          const double* __restrict__ sv, int nsv) {
+    double* s_t = reinterpret_cast<double*>(smem);
     double* s_p = s_t + nsv;
     double* s_v = s_p + 3 * nsv;
     double* s_seg = s_v + 3 * nsv;                    // [nsv - 3][16]: inv[4][3] then sum[4]
@@ -153,45 +158,68 @@ __global__ __launch_bounds__(256) void orbit_los_fast_kernel(const double* __res
         }
     }
     __syncthreads();
-    const double t_first = s_t[0], t_last = s_t[nsv - 1];
-    const double inv_dt = (double)(nsv - 1) / (t_last - t_first);
-    auto segment = [&](double t) {                    // i0 of orbit_hermite: first index with t < st[idx], minus 2, clamped
-        int lo = (int)fmin(fmax((t - t_first) * inv_dt, 0.0), (double)(nsv - 1)) + 1;   // exact for uniform times, a guess otherwise
-        while (lo > 0 && t < s_t[lo - 1]) --lo;
-        while (lo < nsv && !(t < s_t[lo])) ++lo;
-        return min(max(lo - 2, 0), nsv - 4);
-    };
+    OrbitTables T;
+    T.s_t = s_t; T.s_p = s_p; T.s_v = s_v; T.s_seg = s_seg; T.nsv = nsv;
+    T.t_first = s_t[0]; T.t_last = s_t[nsv - 1];
+    T.inv_dt = (double)(nsv - 1) / (T.t_last - T.t_first);
+    return T;
+}
+
+// i0 of orbit_hermite: first index with t < st[idx], minus 2, clamped
+__device__ __forceinline__ int orbit_segment(const OrbitTables& T, double t) {
+    int lo = (int)fmin(fmax((t - T.t_first) * T.inv_dt, 0.0), (double)(T.nsv - 1)) + 1;   // exact for uniform times, a guess otherwise
+    while (lo > 0 && t < T.s_t[lo - 1]) --lo;
+    while (lo < T.nsv && !(t < T.s_t[lo])) ++lo;
+    return min(max(lo - 2, 0), T.nsv - 4);
+}
+
+// Newton from the orbit mid time for the target (tx, ty, tz).  true: t = azimuth time, pos = the sensor there; false (no convergence,
+// outside the orbit span, a NaN target): t = NaN.
+__device__ __forceinline__ bool orbit_zero_doppler(const OrbitTables& T, double tx, double ty, double tz, double threshold, int maxiter,
+                                                   double& t, double* pos) {
+    t = 0.5 * (T.t_first + T.t_last);                 // start at the orbit mid time
+    double vel[3];
+    OrbitSegRegs r;
+    int cur = -1;
+    bool ok = false;
+    for (int it = 0; it < maxiter; ++it) {
+        const int i0 = orbit_segment(T, t);
+        if (i0 != cur) { orbit_load_seg(T.s_t, T.s_p, T.s_v, T.s_seg, i0, r); cur = i0; }
+        orbit_eval_seg(r, t, pos, vel);
+        const double dx = tx - pos[0], dy = ty - pos[1], dz = tz - pos[2];
+        const double fn = dx * vel[0] + dy * vel[1] + dz * vel[2];            // zero-Doppler condition
+        const double fnp = -(vel[0] * vel[0] + vel[1] * vel[1] + vel[2] * vel[2]);
+        const double step = fn / fnp;
+        t -= step;
+        if (fabs(step) < threshold) { ok = true; break; }
+        if (!(t == t)) break;                         // NaN target: no point in iterating on
+    }
+    if (ok && t >= T.t_first && t <= T.t_last && tx == tx && ty == ty && tz == tz) {
+        const int i0 = orbit_segment(T, t);
+        if (i0 != cur) { orbit_load_seg(T.s_t, T.s_p, T.s_v, T.s_seg, i0, r); cur = i0; }
+        orbit_eval_seg(r, t, pos, vel);
+        return true;
+    }
+    t = qnan();
+    return false;
+}
+
+__global__ __launch_bounds__(256) void orbit_los_fast_kernel(const double* __restrict__ st, const double* __restrict__ sp, const double* __restrict__ sv, int nsv,
+                                                             const double* __restrict__ xyz, int64_t n, double threshold, int maxiter,
+                                                             double* __restrict__ los, double* __restrict__ aztime, double* __restrict__ srange) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char orbit_smem[];
+    const OrbitTables T = orbit_tables_build(orbit_smem, st, sp, sv, nsv);
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const double tx = xyz[3 * i], ty = xyz[3 * i + 1], tz = xyz[3 * i + 2];
-        double t = 0.5 * (t_first + t_last);              // start at the orbit mid time
-        double pos[3], vel[3];
-        OrbitSegRegs r;
-        int cur = -1;
-        bool ok = false;
-        for (int it = 0; it < maxiter; ++it) {
-            const int i0 = segment(t);
-            if (i0 != cur) { orbit_load_seg(s_t, s_p, s_v, s_seg, i0, r); cur = i0; }
-            orbit_eval_seg(r, t, pos, vel);
-            const double dx = tx - pos[0], dy = ty - pos[1], dz = tz - pos[2];
-            const double fn = dx * vel[0] + dy * vel[1] + dz * vel[2];            // zero-Doppler condition
-            const double fnp = -(vel[0] * vel[0] + vel[1] * vel[1] + vel[2] * vel[2]);
-            const double step = fn / fnp;
-            t -= step;
-            if (fabs(step) < threshold) { ok = true; break; }
-            if (!(t == t)) break;                         // NaN target: no point in iterating on
-        }
+        double t, pos[3];
         double l0 = qnan(), l1 = qnan(), l2 = qnan(), rg = qnan();
-        if (ok && t >= t_first && t <= t_last && tx == tx && ty == ty && tz == tz) {
-            const int i0 = segment(t);
-            if (i0 != cur) { orbit_load_seg(s_t, s_p, s_v, s_seg, i0, r); cur = i0; }
-            orbit_eval_seg(r, t, pos, vel);
+        if (orbit_zero_doppler(T, tx, ty, tz, threshold, maxiter, t, pos)) {
             const double dx = pos[0] - tx, dy = pos[1] - ty, dz = pos[2] - tz;
             rg = sqrt(dx * dx + dy * dy + dz * dz);
             l0 = dx / rg; l1 = dy / rg; l2 = dz / rg;                               // losreader.py:251-252
-        } else t = qnan();
+        }
         los[3 * i] = l0; los[3 * i + 1] = l1; los[3 * i + 2] = l2;
         if (aztime) aztime[i] = t;
         if (srange) srange[i] = rg;
     }
 }
-

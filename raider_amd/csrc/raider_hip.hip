@@ -331,6 +331,7 @@ static hipError_t launch_lds(void (*kern)(KArgs...), dim3 g, dim3 b, size_t sm, 
 #include "cube_kernels.h"
 #include "producer_kernels.h"
 #include "orbit_kernels.h"
+#include "aztime_kernels.h"
 #include "native_kernels.h"
 #include "proj_kernels.h"
 #include "epoch_kernels.h"
@@ -3296,6 +3297,114 @@ int rdr_orbit_look_vectors(rdr_ctx* c, const double* sv_t, const double* sv_pos,
     if (aztime) { rc = finish_out(c, aztime, da, (size_t)n * 8, loc); if (rc) return rc; }
     if (srange) { rc = finish_out(c, srange, dr, (size_t)n * 8, loc); if (rc) return rc; }
     if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return RDR_OK;
+}
+
+// ---- azimuth-time-grid combination in one pass (aztime_kernels.h) ------------------------------------------------------------------
+// two epoch arrays of one call must lie on one grid (the dtype may differ: pointwise cubes are f32, total cubes f64)
+static int same_grid_check(rdr_ctx* c, const char* who, const rdr_cube* a, const rdr_cube* b) {
+    const LccParams &p = a->proj, &r = b->proj;
+    if (a->ny != b->ny || a->nx != b->nx || a->nz != b->nz || a->ys != b->ys || a->xs != b->xs || a->zs != b->zs || p.kind != r.kind ||
+        std::memcmp(&p.n, &r.n, sizeof(double)) || std::memcmp(&p.aF, &r.aF, sizeof(double)) || std::memcmp(&p.rho0, &r.rho0, sizeof(double)) ||
+        std::memcmp(&p.lam0, &r.lam0, sizeof(double)) || std::memcmp(&p.x0, &r.x0, sizeof(double)) || std::memcmp(&p.y0, &r.y0, sizeof(double)) ||
+        std::memcmp(&p.e, &r.e, sizeof(double)))
+        return fail(c, RDR_ERR_INVALID, std::string(who) + ": the pointwise and the total cubes are not on the same grid / projection");
+    return RDR_OK;
+}
+
+int rdr_cube_blend_azimuth_time(rdr_ctx* c, const rdr_cube* const* pointwise, const rdr_cube* const* total, int32_t nd, const double* lat2d,
+                                const double* lon2d, int loc, const double* sv_t, const double* sv_pos, const double* sv_vel, int64_t nsv,
+                                const double* dates_s, double window_s, double reg, int64_t offset_us, rdr_cube** out_pointwise,
+                                rdr_cube** out_total, double* time_grid, int32_t* flags) {
+    static const char* who = "rdr_cube_blend_azimuth_time";
+    const std::string w(who);
+    if (!c) return fail(nullptr, RDR_ERR_INVALID, w + ": NULL context");
+    if (!pointwise && !total) return fail(c, RDR_ERR_INVALID, w + ": pointwise and total are both NULL");
+    if (nd < 1 || nd > 8) return fail(c, RDR_ERR_INVALID, w + ": nd must be 1..8");
+    if (pointwise && !out_pointwise) return fail(c, RDR_ERR_INVALID, w + ": out_pointwise is NULL");
+    if (total && !out_total) return fail(c, RDR_ERR_INVALID, w + ": out_total is NULL");
+    if (!lat2d || !lon2d) return fail(c, RDR_ERR_INVALID, w + ": lat2d / lon2d is NULL");
+    if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, w + ": loc must be RDR_HOST or RDR_DEVICE");
+    if (!sv_t || !sv_pos || !sv_vel) return fail(c, RDR_ERR_INVALID, w + ": sv_t / sv_pos / sv_vel is NULL");
+    if (nsv < 4) return fail(c, RDR_ERR_INVALID, "state_to_los: At least 4 state vectors are required for orbit interpolation");
+    if (nsv > ORBIT_LDS_MAX_SV) return fail(c, RDR_ERR_INVALID, w + ": nsv exceeds the " + std::to_string(ORBIT_LDS_MAX_SV) + " state vectors the LDS tables hold");
+    for (int64_t i = 1; i < nsv; ++i) if (!(sv_t[i] > sv_t[i - 1])) return fail(c, RDR_ERR_INVALID, w + ": state-vector times must be strictly increasing");
+    if (!dates_s) return fail(c, RDR_ERR_INVALID, w + ": dates_s is NULL");
+    if (!flags) return fail(c, RDR_ERR_INVALID, w + ": flags is NULL");
+    if (!(reg >= 0.0)) return fail(c, RDR_ERR_INVALID, w + ": reg must be >= 0");
+    AzTimeArgs A; std::memset(&A, 0, sizeof(A));
+    A.D.nd = nd; A.D.reg = reg;
+    for (int i = 0; i < nd; ++i) {
+        if (!(dates_s[i] == dates_s[i])) return fail(c, RDR_ERR_INVALID, w + ": dates_s holds a NaN");
+        A.D.date[i] = dates_s[i];
+        for (int j = 0; j < i; ++j) if (dates_s[j] == dates_s[i]) return fail(c, RDR_ERR_INVALID, "Dates provided must be unique");
+    }
+    if (window_s < 0) {                                  // s1_azimuth_timing.py:375-376: infer the model time step
+        if (nd < 2) return fail(c, RDR_ERR_INVALID, w + ": the temporal window cannot be inferred from one date");
+        window_s = std::fabs(dates_s[1] - dates_s[0]);
+        for (int i = 2; i < nd; ++i) window_s = std::min(window_s, std::fabs(dates_s[i] - dates_s[0]));
+    }
+    if (!(window_s == window_s)) return fail(c, RDR_ERR_INVALID, w + ": window_s is NaN");
+    A.D.window = window_s;
+    int rc;
+    if (pointwise) { rc = epochs_check(c, who, pointwise, nd); if (rc) return rc; }
+    if (total) { rc = epochs_check(c, who, total, nd); if (rc) return rc; }
+    if (pointwise && total) { rc = same_grid_check(c, who, pointwise[0], total[0]); if (rc) return rc; }
+    const rdr_cube* a = pointwise ? pointwise[0] : total[0];
+    for (int i = 0; i < nd; ++i) {
+        if (pointwise) { note_use(c, pointwise[i]); A.P.v[i] = pointwise[i]->d_vals; }
+        if (total) { note_use(c, total[i]); A.T.v[i] = total[i]->d_vals; }
+    }
+    A.P.nd = A.T.nd = nd;
+    HIPCHECK(c, hipSetDevice(c->device));
+    const int64_t nvox = a->ny * a->nx * a->nz;
+    const size_t n2 = (size_t)a->ny * a->nx;
+    // the (small) state-vector table always comes from the host, as in rdr_orbit_look_vectors; lat2d / lon2d / the time grid follow `loc`
+    void* dtab;
+    rc = ensure(c, SLOT_AUX, (size_t)nsv * 7 * 8, &dtab); if (rc) return rc;
+    double* dt_ = (double*)dtab; double* dp_ = dt_ + nsv; double* dv_ = dp_ + 3 * nsv;
+    const HostPart parts[3] = {{sv_t, (size_t)nsv * 8}, {sv_pos, (size_t)nsv * 24}, {sv_vel, (size_t)nsv * 24}};
+    rc = upload_parts(c, dtab, parts, 3); if (rc) return rc;
+    const void *dla, *dlo; void* dg = nullptr;
+    rc = stage_in(c, SLOT_IN0, lat2d, n2 * 8, loc, &dla); if (rc) return rc;
+    rc = stage_in(c, SLOT_IN1, lon2d, n2 * 8, loc, &dlo); if (rc) return rc;
+    if (time_grid) { rc = stage_out(c, SLOT_OUT0, time_grid, (size_t)nvox * 8, loc, &dg); if (rc) return rc; }
+    rdr_cube* q[2] = {nullptr, nullptr};
+    for (int k = 0; k < 2; ++k) {
+        if (!(k == 0 ? pointwise : total)) continue;
+        q[k] = new rdr_cube();
+        q[k]->ctx = c; q[k]->ny = a->ny; q[k]->nx = a->nx; q[k]->nz = a->nz; q[k]->dtype = RDR_F64;
+        q[k]->ys = a->ys; q[k]->xs = a->xs; q[k]->zs = a->zs; q[k]->proj = a->proj;
+        rc = cube_alloc(c, q[k]);
+        if (rc) { for (rdr_cube* x : q) if (x) rdr_cube_destroy(x); return rc; }
+    }
+    auto drop = [&]() { if (q[0]) rdr_cube_destroy(q[0]); if (q[1]) rdr_cube_destroy(q[1]); };
+    A.st = dt_; A.sp = dp_; A.sv = dv_; A.nsv = (int)nsv;
+    A.lat2d = (const double*)dla; A.lon2d = (const double*)dlo; A.zs = root(a)->d_axes + a->ny + a->nx;
+    A.ny = a->ny; A.nx = a->nx; A.nz = a->nz;
+    A.offset_us = (long long)offset_us;
+    A.out_p = q[0] ? (double2*)q[0]->d_vals : nullptr; A.out_t = q[1] ? (double2*)q[1]->d_vals : nullptr;
+    A.tgrid = (double*)dg; A.flags = c->d_flags;
+    hipError_t e = hipMemsetAsync(c->d_flags, 0, sizeof(int), c->stream);
+    if (e == hipSuccess) {
+        KTimer t(c, 3);
+        const int g = grid_for(nvox, 256, c->num_cus * 8);
+        const size_t smem = orbit_tables_bytes(nsv);
+        const bool pf = !pointwise || pointwise[0]->dtype == RDR_F32, tf = !total || total[0]->dtype == RDR_F32;
+        if (pf && tf) hipLaunchKernelGGL((aztime_blend_kernel<float2, float2>), dim3(g), dim3(256), smem, c->stream, A);
+        else if (pf) hipLaunchKernelGGL((aztime_blend_kernel<float2, double2>), dim3(g), dim3(256), smem, c->stream, A);
+        else if (tf) hipLaunchKernelGGL((aztime_blend_kernel<double2, float2>), dim3(g), dim3(256), smem, c->stream, A);
+        else hipLaunchKernelGGL((aztime_blend_kernel<double2, double2>), dim3(g), dim3(256), smem, c->stream, A);
+        e = hipGetLastError();
+    }
+    int f = 0;
+    if (e == hipSuccess && time_grid && loc == RDR_HOST) e = hipMemcpyAsync(time_grid, dg, (size_t)nvox * 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&f, c->d_flags, sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { (void)hipGetLastError(); drop(); return fail(c, e == hipErrorOutOfMemory ? RDR_ERR_OOM : RDR_ERR_HIP, w + ": " + hipGetErrorString(e)); }
+    *flags = (f & 1) | ((f & 4) ? 0 : 2);
+    if (out_pointwise) *out_pointwise = q[0];
+    if (out_total) *out_total = q[1];
     return RDR_OK;
 }
 

@@ -5,7 +5,8 @@ The reference interpolates 2-3 hourly weather cubes to the per-voxel Sentinel-1 
   get_inverse_weights_for_dates (:326-399) normalised inverse-|dt| weights of the model times, masked to one model step
   combine_weather_files (cli/raider.py:791-832)   ds_out[var] = sum(w_i * ds_i[var])
 Here the geometry solve, the weights and the weighted combination all run on the device; the date bookkeeping
-(get_n_closest_datetimes, get_times_for_azimuth_interpolation) is host logic.  The SLC / orbit-file lookup of
+(get_n_closest_datetimes, get_times_for_azimuth_interpolation) is host logic.  combine_cubes_azimuth_time runs the three steps as ONE
+kernel (rdr_cube_blend_azimuth_time): no mesh, no time grid, no weight arrays in between.  The SLC / orbit-file lookup of
 get_s1_azimuth_time_grid (:150-216) needs the network (asf_search, s1_orbits) and is out of scope: pass an Orbit.
 """
 import ctypes as C
@@ -155,3 +156,66 @@ def combine_weather_cubes_azimuth_time(pointwise_cubes, total_cubes, times, time
         raise ValueError('The Time Grid return nans meaning no orbit was downloaded.')      # cli/raider.py:913-914
     wgts = get_inverse_weights_for_dates(time_grid, list(times), temporal_window_hours=temporal_window_hours, ctx=ctx)
     return combine_cubes(pointwise_cubes, wgts, ctx=ctx), combine_cubes(total_cubes, wgts, ctx=ctx)
+
+
+def combine_cubes_azimuth_time(pointwise_cubes, total_cubes, times, lat2d, lon2d, orb, temporal_window_hours=None, inverse_regularizer=1e-9,
+                               return_time_grid=False, ctx=None):
+    """get_azimuth_time_grid -> get_inverse_weights_for_dates -> combine_cubes for both cube sets in ONE device pass
+    (rdr_cube_blend_azimuth_time): the same bits as the staged chain gives on the same time grid, without the (nz, ny, nx) mesh, the
+    time grid or the weight arrays ever existing.  pointwise_cubes / total_cubes: the model epochs on one grid (either may be None);
+    times: their model datetimes; lat2d, lon2d: (ny, nx) degrees on the cubes' ascending axes (NumPy, or torch tensors on the GPU);
+    orb: an orbits.Orbit with at most _lib.ORBIT_LDS_MAX_SV state vectors.  Returns (pointwise, total, time grid): two new f64 Cubes
+    (None where the set is None) and, with return_time_grid=True, the (nz, ny, nx) acquisition times in seconds relative to times[0]
+    (else None).  Raises what combine_weather_cubes_azimuth_time raises: the reference's ValueError for a voxel whose solve failed,
+    'No dates provided are within temporal window' when that holds at every voxel."""
+    times = list(times)
+    if len(set(times)) != len(times):
+        raise ValueError('Dates provided must be unique')
+    if len(times) == 0:
+        raise ValueError('No dates provided')
+    if not all(isinstance(d, dt.datetime) for d in times):
+        raise TypeError('dates must be all datetimes')
+    if len(times) == 1 and temporal_window_hours is None:
+        raise ValueError('min() arg is an empty sequence')        # what the reference's window inference raises
+    first = (pointwise_cubes or total_cubes)
+    if not first:
+        raise ValueError('combine_cubes_azimuth_time: no cubes')
+    nd = len(times)
+    for cubes in (pointwise_cubes, total_cubes):
+        if cubes and len(cubes) != nd:
+            raise ValueError(f'{len(cubes)} cubes but {nd} model times')
+    ctx = ctx or first[0].ctx
+    ny, nx, nz = first[0].shape
+    dev = hasattr(lat2d, 'data_ptr')
+    if dev:
+        import torch
+        la, lo = lat2d.to(torch.float64).contiguous(), lon2d.to(torch.float64).contiguous()
+        ctx.adopt_torch_stream(la)
+        grid = torch.empty((nz, ny, nx), dtype=torch.float64, device=la.device) if return_time_grid else None
+    else:
+        la, lo = f64(lat2d), f64(lon2d)
+        grid = np.empty((nz, ny, nx)) if return_time_grid else None
+    if tuple(la.shape) != (ny, nx) or tuple(lo.shape) != (ny, nx):
+        raise ValueError(f'lat2d / lon2d must be (ny, nx) = ({ny}, {nx}); got {tuple(la.shape)} and {tuple(lo.shape)}')
+    d_s = f64(_seconds(times, times[0]))
+    window = -1.0 if temporal_window_hours is None else float(temporal_window_hours) * 3600.0
+    offset_us = int((np.datetime64(orb.epoch, 'ms').astype('datetime64[us]') - np.datetime64(times[0], 'us')).astype(np.int64))
+    handles = lambda cubes: (C.c_void_p * nd)(*[c.handle for c in cubes]) if cubes else None
+    hp, ht, flags = C.c_void_p(), C.c_void_p(), C.c_int32(0)
+    check(ctx.lib.rdr_cube_blend_azimuth_time(ctx.handle, handles(pointwise_cubes), handles(total_cubes), nd, ptr(la), ptr(lo),
+                                              L.RDR_DEVICE if dev else L.RDR_HOST, ptr(orb.time), ptr(orb.position), ptr(orb.velocity),
+                                              orb.time.size, ptr(d_s), window, float(inverse_regularizer), offset_us,
+                                              C.byref(hp) if pointwise_cubes else None, C.byref(ht) if total_cubes else None, ptr(grid),
+                                              C.byref(flags)), ctx.handle)
+    outs = []
+    for h, cubes in ((hp, pointwise_cubes), (ht, total_cubes)):
+        if not cubes:
+            outs.append(None); continue
+        out = Cube._from_handle(ctx, h)
+        out.projection = cubes[0].projection
+        outs.append(out)
+    if flags.value & 1:
+        raise ValueError('The Time Grid return nans meaning no orbit was downloaded.')      # cli/raider.py:913-914
+    if flags.value & 2:
+        raise ValueError('No dates provided are within temporal window')
+    return outs[0], outs[1], grid

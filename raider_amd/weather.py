@@ -55,11 +55,12 @@ class ProcessedModel:
         if k in ('wet_total', 'hydro_total'): return np.ascontiguousarray(self.total.read()[k == 'hydro_total'].transpose(2, 0, 1))
         raise KeyError(k)
 
-    def to_netcdf(self, path, time=None, model_name='ERA-5', format='NETCDF4'):
+    def to_netcdf(self, path, time=None, model_name='ERA-5', format='NETCDF4', attrs=None):
         """The processed weather-model file of WeatherModel.write (weatherModel.py:659-724): dims z, y, x; variables wet, hydro
         (f32), wet_total, hydro_total (f64) - and t, p, e (f32) when the model was produced with return_state=True - with the
         reference's units / standard_name / grid_mapping attributes, 2-D latitude / longitude, the `proj` grid-mapping variable
-        carrying `crs_wkt`, and the global attributes.  format='NETCDF4' (what the reference writes through xarray): HDF5 via
+        carrying `crs_wkt`, and the global attributes (plus `attrs`, e.g. Date1 / Date2 of a combined model, cli/raider.py:820-821; the
+        pointwise fields of a model combined with per-voxel weights are float64 and are written as such).  format='NETCDF4' (what the reference writes through xarray): HDF5 via
         raider_amd.h5write, coordinate variables typed as in the reference's files (x, y f32; z f64); 'NETCDF3_64BIT': classic
         format through scipy.  Either is read back by tropo_delay / getInterpolators, xarray and netCDF4."""
         import datetime as dt
@@ -71,7 +72,8 @@ class ProcessedModel:
         ys, xs, zs = self.pointwise.grid
         wet, hyd = self.pointwise.read(); wt, ht = self.total.read()                     # (y, x, z)
         zyx = lambda v: np.ascontiguousarray(np.asarray(v).transpose(2, 0, 1))
-        fields = [('wet', wet, 'f4', 'dimentionless', 'wet_refractivity'), ('hydro', hyd, 'f4', 'dimentionless', 'hydrostatic_refractivity'),
+        ptyp = 'f8' if np.dtype(self.pointwise.dtype) == np.float64 else 'f4'
+        fields = [('wet', wet, ptyp, 'dimentionless', 'wet_refractivity'), ('hydro', hyd, ptyp, 'dimentionless', 'hydrostatic_refractivity'),
                   ('wet_total', wt, 'f8', 'm', 'total_wet_refractivity'), ('hydro_total', ht, 'f8', 'm', 'total_hydrostatic_refractivity')]
         if self.t is not None:
             fields = [('t', self.t, 'f4', 'K', 'temperature'), ('p', self.p, 'f4', 'Pa', 'pressure'), ('e', self.e, 'f4', 'Pa', 'humidity')] + fields
@@ -79,6 +81,7 @@ class ProcessedModel:
         if time is not None:
             gattrs['datetime'] = time.strftime('%Y_%m_%dT%H_%M_%S')
         gattrs['date_created'] = dt.datetime.now().strftime('%Y_%m_%dT%H_%M_%S')
+        gattrs.update(attrs or {})
         # EPSG:4326 as current PROJ releases spell it in WKT2:2019 (what pyproj's CRS.to_cf() puts into the reference's files)
         crs_wkt = ('GEOGCRS["WGS 84",ENSEMBLE["World Geodetic System 1984 ensemble",MEMBER["World Geodetic System 1984 (Transit)"],'
                    'MEMBER["World Geodetic System 1984 (G730)"],MEMBER["World Geodetic System 1984 (G873)"],MEMBER["World Geodetic System 1984 (G1150)"],'
