@@ -1,13 +1,14 @@
 // Pass 2 of a time series (rdr_raytrace_slices_epochs, rdr_raytrace_epochs): E weather epochs on ONE ray geometry, marched together.
 //
-//   march_epochs_pr_kernel  the same for a batch with per-ray origin heights (rdr_raytrace_epochs): the per-ray-height loop of
-//                         march_kernel with E cubes (at the end of this file).
-//   march_epochs_kernel   the light slice loop of march_kernel (raider_kernels.h) with E cubes: per sample the shared part -
-//                         the ray polynomials, the x / y cell search, the z window, the corner offset - runs once; then E corner-pair
-//                         gathers (independent of each other: the ILP the one-epoch marcher lacks) and E (wet, hydro) accumulators.
+//   march_epochs_kernel   march_kernel (raider_kernels.h) with E cubes, built from the same parts: the slice partition, the tile
+//                         mapping, the ray record and the no-check proof are march_kernel's own functions; per sample the shared
+//                         part - the ray polynomials, the x / y cell search, the z window, the corner offset - runs once; then E
+//                         corner-pair gathers (independent of each other: the ILP the one-epoch marcher lacks) and E (wet, hydro)
+//                         accumulators.  Its two level loops are march_kernel's two: the light slice loop (PR = false; a series of
+//                         height slices) and the per-ray-height loop (PR = true; rdr_raytrace_epochs with rays->hts).
 //
 // Per epoch the arithmetic is march_kernel's own: sample_finish_lerp on the same weights, the same trapezoid weights, the same
-// accumulation order - so epoch e's delays are bit for bit what rdr_raytrace_slices gives on cube e.  Generic rays (record field
+// accumulation order - so epoch e's delays are bit for bit what rdr_raytrace_slices / rdr_raytrace give on cube e.  Generic rays (record field
 // WS_SCALE == 0) are left to march_kernel<T2, true>, launched once per epoch on the same records.  The f64 LDS staging of
 // march_kernel (STAGED) is not carried over: with E gathers per sample in flight the direct loads are what the stacked loop needs.
 //
@@ -72,16 +73,23 @@ __device__ __forceinline__ void gather_corners_e(const CubeView<T2>& c, const Ep
     }
 }
 
-// Occupancy per (dtype, E), the highest at which the compiler's resource report shows no scratch (DESIGN.md "Time series"): at four
-// waves per SIMD f32 / E = 2 spills 48-80 B per lane, at three f32 / E = 4 48-112 B and f64 / E = 2 16-32 B.
-template <typename T2, int E>
-struct EpochWaves { static constexpr int value = (sizeof(T2) == 8 && E <= 2) ? 3 : 2; };
+// Occupancy per (dtype, E, PR): the highest at which the compiler's resource report shows no scratch (DESIGN.md "Time series", 5d).
+// Slice loop: at four waves per SIMD f32 / E = 2 spills 48-80 B per lane, at three f32 / E = 4 48-112 B and f64 / E = 2 16-32 B.
+// Per-ray-height loop: one step up f32 / E = 2 spills 64-100 B per lane, f32 / E = 4 88-96 B, f64 / E = 2 36-60 B; f64 / E = 4 needs
+// 8 B at two waves per SIMD on REGULAR grids (256 VGPRs), so it is built for one - and the driver does not use it by default (epoch_group).
+template <typename T2, int E, bool PR>
+struct EpochWaves {
+    static constexpr int value = PR ? (sizeof(T2) == 8 ? (E <= 2 ? 3 : 2) : (E <= 2 ? 2 : 1)) : ((sizeof(T2) == 8 && E <= 2) ? 3 : 2);
+};
 
 // GRID as in march_kernel: 1 REGULAR (exact axes, 32-bit offsets), 2 TABLES (nearly uniform axes, 32-bit offsets), 0 run-time flags.
+// PR as in march_kernel: per-ray origin heights (P.ht_ray; one slice) - REGULAR or run-time flags, the two the one-epoch per-ray-height
+// marcher is launched with.
 // Outputs: epoch e of slice-major ray index o at P.wet[e * estride + o] / P.hyd[e * estride + o].
-template <typename T2, int E, int GRID>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EpochWaves<T2, E>::value, EpochWaves<T2, E>::value)))
+template <typename T2, int E, int GRID, bool PR>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EpochWaves<T2, E, PR>::value, EpochWaves<T2, E, PR>::value)))
 void march_epochs_kernel(CubeView<T2> c_in, EpochCubes<T2, E> ev, RayParams P, int64_t estride) {
+    static_assert(!PR || GRID == 0 || GRID == 1, "per-ray heights: REGULAR or run-time flags");
     constexpr bool REGULAR = GRID == 1;
     CubeView<T2> c = c_in;
     if (REGULAR) { c.exact_y = 1; c.exact_x = 1; c.small = 1; }
@@ -98,73 +106,29 @@ void march_epochs_kernel(CubeView<T2> c_in, EpochCubes<T2, E> ev, RayParams P, i
         const int64_t tg = P.tile_begin + lt;
         const int sl = (int)(tg / P.tiles_per_slice);
         const int64_t t = tg - (int64_t)sl * P.tiles_per_slice;
-        if (sl != slice) {                                 // the slice's level table and partition: march_kernel's fill, verbatim
+        if (sl != slice) {                                 // the slice's level table and partition (packed records: the slice loop only)
             slice = sl;
             K = fill_levels(c.nz, m, P.hts ? P.hts[sl] : P.ht, P.zref);
-            int tz = threadIdx.x;
-            asm volatile("" : "+v"(tz));
-            if (tz == 0) m.K[1] = 0;
-            __syncthreads();
-            for (int k = tz; k < K; k += BLOCK) {
-                int np;
-                if (P.nparts_override) np = P.nparts_override[(int64_t)sl * MAX_LEVELS + k];
-                else {
-                    const double parts = ceil(__longlong_as_double((long long)P.maxlen_bits[(int64_t)sl * MAX_LEVELS + k]) / P.max_seg) + 1.0;
-                    np = (parts >= 1.0 && parts <= (double)MAX_NPARTS) ? (int)parts : -1;
-                }
-                if (np < 2 || np > MAX_NPARTS) {
-                    np = 2;
-                    atomicOr(P.flags + sl, 16);
-                    m.K[1] = 1;
-                }
-                m.np[k] = np;
-                m.step[k] = 1.0 / ((double)np - 1.0);
-                m.hs[k] = 0.5e-6 * m.step[k];
-                const int kzk = m.kz[k], last = c.nz - 1;
-                const int zb = max(window2_base(c.nz, kzk), 0);
-                LevelRec r;
-                r.xv = m.xv[k]; r.hs = m.hs[k]; r.step = m.step[k];
-                r.zmid = m.ax.ez[min(zb + 1, last)].x; r.r0 = m.ax.ez[zb].y; r.r1 = m.ax.ez[min(zb + 1, last)].y;
-                r.gk = m.ax.ez[kzk].x; r.rk = m.ax.ez[kzk].y;
-                r.npkz = np | (kzk << 17); r.pad[0] = r.pad[1] = r.pad[2] = 0;
-                m.lev[k] = r;
-                if (k == K - 1) { r.hs = 0.0; r.npkz = 2 | (kzk << 17); m.lev[K] = r; }
-            }
-            __syncthreads();
-            const int flags_in = P.flags[sl];
-            poison = (m.K[1] || (flags_in & (1 | 32))) ? qnan() : 0.0;
-            clamp_lo = !(flags_in & 4);
-            clamp_hi = !(flags_in & 8);
+            const SlicePartition part = fill_partition<!PR>(P, m, c.nz, sl, K);
+            poison = part.poison; clamp_lo = part.clamp_lo; clamp_hi = part.clamp_hi;
         }
         int tl = threadIdx.x;
         asm volatile("" : "+v"(tl));
         int64_t i; bool active;
-        if (P.origin_mode == 0) {
-            const int64_t ty = t / P.tiles_x, tx = t - ty * P.tiles_x;
-            const int64_t row = ty * TILE + (tl >> 4), col = tx * TILE + (tl & 15);
-            active = row < P.ny && col < P.nx;
-            i = row * P.nx + col;
-        } else {
-            i = t * BLOCK + tl;
-            active = i < P.n;
-        }
+        tile_ray(P, t, tl, i, active);
         const double* w = P.ws + (lt * BLOCK + tl);
         const int64_t ns = P.nslots;
         const double scale_rec = w[(int64_t)WS_SCALE * ns];
         const bool mine = !active || scale_rec != 0.0;     // light rays (and tile padding); generic rays: march_kernel<T2, true>
+        // per-ray heights: the ray's first level of the slice table, found exactly as pass 1 found it (idle lanes: none)
+        int k0 = 0; double lo_first = K > 0 ? m.lo[0] : 0.0;
+        if constexpr (PR) k0 = (active && mine) ? first_level(m.ax.ez, c.nz, m.lo, m.hi, m.kz, K, P.ht_ray[i], lo_first) : K;
         double acc_w[E], acc_h[E];
 #pragma unroll
         for (int e = 0; e < E; ++e) { acc_w[e] = 0.0; acc_h[e] = 0.0; }
         RayPoly q;
         double xc[PX];
-#pragma unroll
-        for (int n = 0; n < PN; ++n) {
-            q.h[n] = w[(int64_t)(WS_POLY_H + n) * ns];
-            q.lat[n] = w[(int64_t)(WS_POLY_LAT + n) * ns];
-            q.lon[n] = w[(int64_t)(WS_POLY_LON + n) * ns];
-        }
-#pragma unroll
-        for (int n = 0; n < PX; ++n) xc[n] = w[(int64_t)(WS_XPOLY + n) * ns];
+        load_ray_record(w, ns, q, xc);
         const double scale = scale_rec;
         const unsigned long long live = __builtin_amdgcn_ballot_w64(active && mine);
         auto finish = [&](const PendingSampleE<T2, E>& s, double wv) {
@@ -181,304 +145,151 @@ void march_epochs_kernel(CubeView<T2> c_in, EpochCubes<T2, E> ev, RayParams P, i
         };
         auto run = [&](auto nochk) {
             constexpr bool NC = decltype(nochk)::value;
-            typedef __attribute__((address_space(3))) const LevelRec LdsRec;
-            int la = (int)(size_t)m.lev;
-            asm volatile("" : "+v"(la));
-            const LdsRec* rec = (const LdsRec*)(size_t)(unsigned)la;
-            int npkz = __builtin_amdgcn_readfirstlane(rec->npkz);
-            int np = npkz & 0x1ffff, kz = npkz >> 17;
-            double hs = rec->hs;
-            double u_k = w[(int64_t)WS_U0 * ns];
-            double u_last = w[(int64_t)WS_U1 * ns];
-            double du = u_last - u_k;
-            if (K > 0) {                                   // the ray's very first sample (march_kernel: issue_top with MODE 1)
-                PendingSampleE<T2, E> s;
-                const double us = fma(0.0 * rec->step, du, u_k);
-                double ph = poly5(q.h, us);
-                const double plat = poly5(q.lat, us), plon = poly5(q.lon, us);
-                if (clamp_lo) { asm volatile("" ::: "memory"); ph = fmax(ph, c.z_lo); }
-                int iz;
-                window2_cell(m.ax.ez, c.nz, ph, window2_base(c.nz, kz - ((m.lo[0] <= m.ax.ez[kz].x) ? 1 : 0)), c.nz >= 4, iz, s.tz);
-                gather_corners_e<T2, E, true, NC>(c, ev, m.ax, plat, plon, iz, s);
-                finish(s, hs * fabs(du));
-            }
-#pragma unroll 1
-            for (int k = 0; k < K; ++k) {
-                const int zbase = window2_base(c.nz, kz);
-                const bool more = k + 1 < K;
-                const double w_mid = (2.0 * hs) * fabs(du);
-                if (np > 2) {
-                    const double step = rec->step, gk = rec->gk, rk = rec->rk;
-#pragma unroll 1
-                    for (int j = 1; j < np - 1; ++j) {
-                        PendingSampleE<T2, E> s;
-                        const double us = fma((double)j * step, du, u_k);
-                        const double ph = poly5(q.h, us), plat = poly5(q.lat, us), plon = poly5(q.lon, us);
-                        int iz = kz;
-                        s.tz = (ph - gk) * rk;
-                        if (!(s.tz >= 0.0) || !(s.tz <= 1.0)) cell_exact(m.ax.ez, c.nz, ph, iz, s.tz);   // rare
-                        gather_corners_e<T2, E, true, NC>(c, ev, m.ax, plat, plon, iz, s);
-                        finish(s, w_mid);
-                    }
-                }
-                PendingSampleE<T2, E> top;
-                {
-                    const double us = u_k + du;
+            if constexpr (PR) {
+                // The per-ray-height loop of march_kernel<T2, false, GRID, true> with E cubes.  The level schedule (k, j) stays
+                // slice-uniform; a lane joins it at its own first level k0 with its own first sample, the loop starts at the wave's
+                // lowest k0.  Per sample the polynomials, the z cell, cell_xy and the element offset run once, then E corner-pair
+                // gathers and E accumulator pairs.
+                // a level's top sample / the ray's first sample: the two-entry z window (sample_issue MODE 1)
+                auto issue_top = [&](double us, int zbase, bool floor_it, bool ceil_it, PendingSampleE<T2, E>& s) {
                     double ph = poly5(q.h, us);
                     const double plat = poly5(q.lat, us), plon = poly5(q.lon, us);
-                    if (clamp_hi && !more) { asm volatile("" ::: "memory"); ph = fmin(ph, c.z_hi); }
-                    const double d = ph - rec->zmid;
-                    int iz; bool ok;
-                    if (__builtin_expect((__builtin_amdgcn_ballot_w64(!(d >= 0.0)) & live) == 0ULL, 1)) {
-                        iz = zbase + 1;
-                        top.tz = d * rec->r1;
-                        ok = top.tz <= 1.0;
-                    } else {
-                        double ds = d;
-                        asm volatile("" : "+v"(ds));
-                        const bool up = ds >= 0.0;
-                        iz = zbase + (int)up;
-                        top.tz = fma(ds, up ? rec->r1 : rec->r0, up ? 0.0 : 1.0);
-                        ok = (top.tz >= 0.0) & (top.tz <= 1.0);
+                    if (floor_it) { asm volatile("" ::: "memory"); ph = fmax(ph, c.z_lo); }
+                    if (ceil_it) { asm volatile("" ::: "memory"); ph = fmin(ph, c.z_hi); }
+                    int iz;
+                    window2_cell(m.ax.ez, c.nz, ph, zbase, c.nz >= 4, iz, s.tz);
+                    gather_corners_e<T2, E, true, NC>(c, ev, m.ax, plat, plon, iz, s);
+                };
+                int kmin = k0;
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) kmin = min(kmin, __shfl_xor(kmin, off, 64));
+                kmin = __builtin_amdgcn_readfirstlane(kmin);
+                // every lane's FIRST sample (the bottom of its own first level) in one evaluation for the whole wave
+                const bool has = k0 < K;
+                const int kf = has ? k0 : 0;
+                double u_k = has ? w[(int64_t)WS_U0 * ns] : 0.0, u_last = has ? w[(int64_t)WS_U1 * ns] : 0.0;
+                double du = u_last - u_k;
+                if (K > 0) {
+                    const int kzf = m.kz[kf];
+                    PendingSampleE<T2, E> s;
+                    issue_top(fma(0.0 * m.step[kf], du, u_k), window2_base(c.nz, kzf - ((lo_first <= m.ax.ez[kzf].x) ? 1 : 0)), clamp_lo, false, s);
+                    if (has) finish(s, m.hs[kf] * fabs(du));
+                }
+#pragma unroll 1
+                for (int k = kmin; k < K; ++k) {
+                    const int np = __builtin_amdgcn_readfirstlane(m.np[k]);
+                    const int kz = __builtin_amdgcn_readfirstlane(m.kz[k]);
+                    const double step = m.step[k], hs = m.hs[k];
+                    const bool more = k + 1 < K;
+                    if (k >= k0) {
+                        const int zbase = window2_base(c.nz, kz);
+                        const double w_mid = (2.0 * hs) * fabs(du);
+#pragma unroll 1
+                        for (int j = 1; j < np - 1; ++j) {      // strictly inside model interval kz (sample_issue MODE 2)
+                            PendingSampleE<T2, E> s;
+                            const double us = fma((double)j * step, du, u_k);
+                            const double ph = poly5(q.h, us);
+                            const double plat = poly5(q.lat, us), plon = poly5(q.lon, us);
+                            const double2 e0 = m.ax.ez[kz];
+                            int iz = kz;
+                            s.tz = (ph - e0.x) * e0.y;
+                            if (!(s.tz >= 0.0) || !(s.tz <= 1.0)) cell_exact(m.ax.ez, c.nz, ph, iz, s.tz);   // rare
+                            gather_corners_e<T2, E, true, NC>(c, ev, m.ax, plat, plon, iz, s);
+                            finish(s, w_mid);
+                        }
+                        PendingSampleE<T2, E> top;
+                        issue_top(u_k + du, zbase, false, clamp_hi && !more, top);
+                        double du1 = 0.0;
+                        double w_top = hs * fabs(du);
+                        if (more) {
+                            const double t2 = poly7(xc, m.xv[k + 1]);
+                            du1 = t2 - u_last; u_last = t2;
+                            w_top = fma(m.hs[k + 1], fabs(du1), w_top);
+                        }
+                        finish(top, w_top);
+                        u_k += du; du = du1;
                     }
-                    if (!(ok & (c.nz >= 4))) cell_exact(m.ax.ez, c.nz, ph, iz, top.tz);                  // rare
-                    gather_corners_e<T2, E, true, NC>(c, ev, m.ax, plat, plon, iz, top);
                 }
-                const double t2 = poly7(xc, rec[1].xv);
-                const double du1 = t2 - u_last, hs1 = rec[1].hs;
-                u_last = t2;
-                const double w_top = fma(hs1, fabs(du1), hs * fabs(du));
-                npkz = __builtin_amdgcn_readfirstlane(rec[1].npkz);
-                finish(top, w_top);
-                u_k += du; du = du1; hs = hs1;
-                np = npkz & 0x1ffff; kz = npkz >> 17;
-                ++rec;
-            }
-        };
-        // the wave-wide no-check proof of march_kernel (bounds of the cell search from the polynomial coefficients)
-        bool lane_safe = false;
-        if (REGULAR) {
-            double u0r = w[(int64_t)WS_U0 * ns], u1r = w[(int64_t)WS_U1 * ns];
-            if (!active) {
-#pragma unroll
-                for (int n = 0; n < PN; ++n) { q.lat[n] = 0.0; q.lon[n] = 0.0; }
-                q.lat[0] = 0.5; q.lon[0] = 0.5;
-#pragma unroll
-                for (int n = 0; n < PX; ++n) xc[n] = 0.0;
-                u0r = 0.0; u1r = 0.0;
-            }
-            auto inside = [&](const double* cf, int n) {
-                const double r = 1.006 * (fabs(cf[1]) + fabs(cf[2]) + fabs(cf[3]) + fabs(cf[4]) + fabs(cf[5]));
-                return (cf[0] - r >= 0.0) & (cf[0] + r < (double)(n - 1));
-            };
-            double xs = 0.0;
-#pragma unroll
-            for (int n = 0; n < PX; ++n) xs += fabs(xc[n]);
-            lane_safe = mine && (fabs(u0r) <= 1.001) && (fabs(u1r) <= 1.001) && (xs <= 1.001) && inside(q.lat, c.ny) && inside(q.lon, c.nx);
-        }
-        if (REGULAR && __all(lane_safe)) run(std::integral_constant<bool, true>{});
-        else run(std::integral_constant<bool, false>{});
-        if (active && scale_rec != 0.0) {
-            const int64_t o = (int64_t)sl * P.n + i;
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const double aw = acc_w[e] * scale, ah = acc_h[e] * scale;
-                P.wet[e * estride + o] = aw + poison; P.hyd[e * estride + o] = ah + poison;
-            }
-        }
-    }
-}
-
-// ---- per-ray origin heights (rdr_raytrace_epochs) ------------------------------------------------------------------
-// march_epochs_pr_kernel: the per-ray-height loop of march_kernel<T2, false, GRID, true> with E cubes.  The level schedule (k, j) stays
-// slice-uniform; a lane joins it at its own first level k0 (first_level on P.ht_ray[i], as pass 1 found it) with its own first
-// sample, the loop starts at the wave's lowest k0.  Per sample the polynomials, the z cell, cell_xy and the element offset run once,
-// then E corner-pair gathers and E accumulator pairs: epoch e is bit for bit what march_kernel<..., PR> gives on cube e.
-// GRID: 1 REGULAR or 0 run-time flags - the two the one-epoch per-ray-height marcher is launched with.
-
-// Occupancy per (dtype, E): the highest at which the compiler's resource report shows no scratch.  One step up
-// f32 / E = 2 spills 64-100 B per lane, f32 / E = 4 88-96 B, f64 / E = 2 36-60 B; f64 / E = 4 needs 8 B at two waves per SIMD on
-// REGULAR grids (256 VGPRs), so it is built for one - and the driver does not use it by default (epochs_pr_group).
-template <typename T2, int E>
-struct EpochWavesPR { static constexpr int value = sizeof(T2) == 8 ? (E <= 2 ? 3 : 2) : (E <= 2 ? 2 : 1); };
-
-template <typename T2, int E, int GRID>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(EpochWavesPR<T2, E>::value, EpochWavesPR<T2, E>::value)))
-void march_epochs_pr_kernel(CubeView<T2> c_in, EpochCubes<T2, E> ev, RayParams P, int64_t estride) {
-    static_assert(GRID == 0 || GRID == 1, "per-ray heights: REGULAR or run-time flags");
-    constexpr bool REGULAR = GRID == 1;
-    CubeView<T2> c = c_in;
-    if (REGULAR) { c.exact_y = 1; c.exact_x = 1; c.small = 1; }
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const RaySmem m = carve_smem(smem_raw, c.ny, c.nx, c.nz, c.exact_y, c.exact_x);
-    fill_axes(c, m);
-    int K = 0, slice = -1;
-    double poison = 0.0;
-    bool clamp_lo = false, clamp_hi = false;
-    TileWalk walk(P.tile_count, P.tile_ctr, m.K + 2);
-    int64_t lt;
-    while (walk.next(P.tile_count, lt)) {
-        const int64_t tg = P.tile_begin + lt;
-        const int sl = (int)(tg / P.tiles_per_slice);
-        const int64_t t = tg - (int64_t)sl * P.tiles_per_slice;
-        if (sl != slice) {                                 // the slice's level table and partition: march_kernel's fill (no packed records)
-            slice = sl;
-            K = fill_levels(c.nz, m, P.hts ? P.hts[sl] : P.ht, P.zref);
-            int tz = threadIdx.x;
-            asm volatile("" : "+v"(tz));
-            if (tz == 0) m.K[1] = 0;
-            __syncthreads();
-            for (int k = tz; k < K; k += BLOCK) {
-                int np;
-                if (P.nparts_override) np = P.nparts_override[(int64_t)sl * MAX_LEVELS + k];
-                else {
-                    const double parts = ceil(__longlong_as_double((long long)P.maxlen_bits[(int64_t)sl * MAX_LEVELS + k]) / P.max_seg) + 1.0;
-                    np = (parts >= 1.0 && parts <= (double)MAX_NPARTS) ? (int)parts : -1;
+            } else {
+                // The light slice loop of march_kernel with E cubes (packed level records through one LDS address register).
+                typedef __attribute__((address_space(3))) const LevelRec LdsRec;
+                int la = (int)(size_t)m.lev;
+                asm volatile("" : "+v"(la));
+                const LdsRec* rec = (const LdsRec*)(size_t)(unsigned)la;
+                int npkz = __builtin_amdgcn_readfirstlane(rec->npkz);
+                int np = npkz & 0x1ffff, kz = npkz >> 17;
+                double hs = rec->hs;
+                double u_k = w[(int64_t)WS_U0 * ns];
+                double u_last = w[(int64_t)WS_U1 * ns];
+                double du = u_last - u_k;
+                if (K > 0) {                                   // the ray's very first sample (march_kernel: issue_top with MODE 1)
+                    PendingSampleE<T2, E> s;
+                    const double us = fma(0.0 * rec->step, du, u_k);
+                    double ph = poly5(q.h, us);
+                    const double plat = poly5(q.lat, us), plon = poly5(q.lon, us);
+                    if (clamp_lo) { asm volatile("" ::: "memory"); ph = fmax(ph, c.z_lo); }
+                    int iz;
+                    window2_cell(m.ax.ez, c.nz, ph, window2_base(c.nz, kz - ((m.lo[0] <= m.ax.ez[kz].x) ? 1 : 0)), c.nz >= 4, iz, s.tz);
+                    gather_corners_e<T2, E, true, NC>(c, ev, m.ax, plat, plon, iz, s);
+                    finish(s, hs * fabs(du));
                 }
-                if (np < 2 || np > MAX_NPARTS) {
-                    np = 2;
-                    atomicOr(P.flags + sl, 16);
-                    m.K[1] = 1;
-                }
-                m.np[k] = np;
-                m.step[k] = 1.0 / ((double)np - 1.0);
-                m.hs[k] = 0.5e-6 * m.step[k];
-            }
-            __syncthreads();
-            const int flags_in = P.flags[sl];
-            poison = (m.K[1] || (flags_in & (1 | 32))) ? qnan() : 0.0;
-            clamp_lo = !(flags_in & 4);
-            clamp_hi = !(flags_in & 8);
-        }
-        int tl = threadIdx.x;
-        asm volatile("" : "+v"(tl));
-        int64_t i; bool active;
-        if (P.origin_mode == 0) {
-            const int64_t ty = t / P.tiles_x, tx = t - ty * P.tiles_x;
-            const int64_t row = ty * TILE + (tl >> 4), col = tx * TILE + (tl & 15);
-            active = row < P.ny && col < P.nx;
-            i = row * P.nx + col;
-        } else {
-            i = t * BLOCK + tl;
-            active = i < P.n;
-        }
-        const double* w = P.ws + (lt * BLOCK + tl);
-        const int64_t ns = P.nslots;
-        const double scale_rec = w[(int64_t)WS_SCALE * ns];
-        const bool mine = !active || scale_rec != 0.0;     // light rays (and tile padding); generic rays: march_kernel<T2, true>
-        // the ray's first level of the slice table, found exactly as pass 1 found it (idle lanes: none)
-        double lo_first = K > 0 ? m.lo[0] : 0.0;
-        const int k0 = (active && mine) ? first_level(m.ax.ez, c.nz, m.lo, m.hi, m.kz, K, P.ht_ray[i], lo_first) : K;
-        double acc_w[E], acc_h[E];
-#pragma unroll
-        for (int e = 0; e < E; ++e) { acc_w[e] = 0.0; acc_h[e] = 0.0; }
-        RayPoly q;
-        double xc[PX];
-#pragma unroll
-        for (int n = 0; n < PN; ++n) {
-            q.h[n] = w[(int64_t)(WS_POLY_H + n) * ns];
-            q.lat[n] = w[(int64_t)(WS_POLY_LAT + n) * ns];
-            q.lon[n] = w[(int64_t)(WS_POLY_LON + n) * ns];
-        }
-#pragma unroll
-        for (int n = 0; n < PX; ++n) xc[n] = w[(int64_t)(WS_XPOLY + n) * ns];
-        const double scale = scale_rec;
-        auto finish = [&](const PendingSampleE<T2, E>& s, double wv) {
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                PendingSample<T2> one;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) one.v[j] = s.v[e][j];
-                one.ty = s.ty; one.tx = s.tx; one.tz = s.tz;
-                double vw, vh;
-                sample_finish_lerp(one, vw, vh);
-                acc_w[e] = fma(wv, vw, acc_w[e]); acc_h[e] = fma(wv, vh, acc_h[e]);
-            }
-        };
-        auto run = [&](auto nochk) {
-            constexpr bool NC = decltype(nochk)::value;
-            // a level's top sample / the ray's first sample: the two-entry z window (sample_issue MODE 1)
-            auto issue_top = [&](double us, int zbase, bool floor_it, bool ceil_it, PendingSampleE<T2, E>& s) {
-                double ph = poly5(q.h, us);
-                const double plat = poly5(q.lat, us), plon = poly5(q.lon, us);
-                if (floor_it) { asm volatile("" ::: "memory"); ph = fmax(ph, c.z_lo); }
-                if (ceil_it) { asm volatile("" ::: "memory"); ph = fmin(ph, c.z_hi); }
-                int iz;
-                window2_cell(m.ax.ez, c.nz, ph, zbase, c.nz >= 4, iz, s.tz);
-                gather_corners_e<T2, E, true, NC>(c, ev, m.ax, plat, plon, iz, s);
-            };
-            int kmin = k0;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) kmin = min(kmin, __shfl_xor(kmin, off, 64));
-            kmin = __builtin_amdgcn_readfirstlane(kmin);
-            // every lane's FIRST sample (the bottom of its own first level) in one evaluation for the whole wave
-            const bool has = k0 < K;
-            const int kf = has ? k0 : 0;
-            double u_k = has ? w[(int64_t)WS_U0 * ns] : 0.0, u_last = has ? w[(int64_t)WS_U1 * ns] : 0.0;
-            double du = u_last - u_k;
-            if (K > 0) {
-                const int kzf = m.kz[kf];
-                PendingSampleE<T2, E> s;
-                issue_top(fma(0.0 * m.step[kf], du, u_k), window2_base(c.nz, kzf - ((lo_first <= m.ax.ez[kzf].x) ? 1 : 0)), clamp_lo, false, s);
-                if (has) finish(s, m.hs[kf] * fabs(du));
-            }
 #pragma unroll 1
-            for (int k = kmin; k < K; ++k) {
-                const int np = __builtin_amdgcn_readfirstlane(m.np[k]);
-                const int kz = __builtin_amdgcn_readfirstlane(m.kz[k]);
-                const double step = m.step[k], hs = m.hs[k];
-                const bool more = k + 1 < K;
-                if (k >= k0) {
+                for (int k = 0; k < K; ++k) {
                     const int zbase = window2_base(c.nz, kz);
+                    const bool more = k + 1 < K;
                     const double w_mid = (2.0 * hs) * fabs(du);
+                    if (np > 2) {
+                        const double step = rec->step, gk = rec->gk, rk = rec->rk;
 #pragma unroll 1
-                    for (int j = 1; j < np - 1; ++j) {      // strictly inside model interval kz (sample_issue MODE 2)
-                        PendingSampleE<T2, E> s;
-                        const double us = fma((double)j * step, du, u_k);
-                        const double ph = poly5(q.h, us);
-                        const double plat = poly5(q.lat, us), plon = poly5(q.lon, us);
-                        const double2 e0 = m.ax.ez[kz];
-                        int iz = kz;
-                        s.tz = (ph - e0.x) * e0.y;
-                        if (!(s.tz >= 0.0) || !(s.tz <= 1.0)) cell_exact(m.ax.ez, c.nz, ph, iz, s.tz);   // rare
-                        gather_corners_e<T2, E, true, NC>(c, ev, m.ax, plat, plon, iz, s);
-                        finish(s, w_mid);
+                        for (int j = 1; j < np - 1; ++j) {
+                            PendingSampleE<T2, E> s;
+                            const double us = fma((double)j * step, du, u_k);
+                            const double ph = poly5(q.h, us), plat = poly5(q.lat, us), plon = poly5(q.lon, us);
+                            int iz = kz;
+                            s.tz = (ph - gk) * rk;
+                            if (!(s.tz >= 0.0) || !(s.tz <= 1.0)) cell_exact(m.ax.ez, c.nz, ph, iz, s.tz);   // rare
+                            gather_corners_e<T2, E, true, NC>(c, ev, m.ax, plat, plon, iz, s);
+                            finish(s, w_mid);
+                        }
                     }
                     PendingSampleE<T2, E> top;
-                    issue_top(u_k + du, zbase, false, clamp_hi && !more, top);
-                    double du1 = 0.0;
-                    double w_top = hs * fabs(du);
-                    if (more) {
-                        const double t2 = poly7(xc, m.xv[k + 1]);
-                        du1 = t2 - u_last; u_last = t2;
-                        w_top = fma(m.hs[k + 1], fabs(du1), w_top);
+                    {
+                        const double us = u_k + du;
+                        double ph = poly5(q.h, us);
+                        const double plat = poly5(q.lat, us), plon = poly5(q.lon, us);
+                        if (clamp_hi && !more) { asm volatile("" ::: "memory"); ph = fmin(ph, c.z_hi); }
+                        const double d = ph - rec->zmid;
+                        int iz; bool ok;
+                        if (__builtin_expect((__builtin_amdgcn_ballot_w64(!(d >= 0.0)) & live) == 0ULL, 1)) {
+                            iz = zbase + 1;
+                            top.tz = d * rec->r1;
+                            ok = top.tz <= 1.0;
+                        } else {
+                            double ds = d;
+                            asm volatile("" : "+v"(ds));
+                            const bool up = ds >= 0.0;
+                            iz = zbase + (int)up;
+                            top.tz = fma(ds, up ? rec->r1 : rec->r0, up ? 0.0 : 1.0);
+                            ok = (top.tz >= 0.0) & (top.tz <= 1.0);
+                        }
+                        if (!(ok & (c.nz >= 4))) cell_exact(m.ax.ez, c.nz, ph, iz, top.tz);                  // rare
+                        gather_corners_e<T2, E, true, NC>(c, ev, m.ax, plat, plon, iz, top);
                     }
+                    const double t2 = poly7(xc, rec[1].xv);
+                    const double du1 = t2 - u_last, hs1 = rec[1].hs;
+                    u_last = t2;
+                    const double w_top = fma(hs1, fabs(du1), hs * fabs(du));
+                    npkz = __builtin_amdgcn_readfirstlane(rec[1].npkz);
                     finish(top, w_top);
-                    u_k += du; du = du1;
+                    u_k += du; du = du1; hs = hs1;
+                    np = npkz & 0x1ffff; kz = npkz >> 17;
+                    ++rec;
                 }
             }
         };
-        // the wave-wide no-check proof of march_kernel (bounds of the cell search from the polynomial coefficients)
+        // the wave-wide no-check proof (lane_nocheck): bounds of the cell search from the polynomial coefficients
         bool lane_safe = false;
-        if (REGULAR) {
-            double u0r = w[(int64_t)WS_U0 * ns], u1r = w[(int64_t)WS_U1 * ns];
-            if (!active) {
-#pragma unroll
-                for (int n = 0; n < PN; ++n) { q.lat[n] = 0.0; q.lon[n] = 0.0; }
-                q.lat[0] = 0.5; q.lon[0] = 0.5;
-#pragma unroll
-                for (int n = 0; n < PX; ++n) xc[n] = 0.0;
-                u0r = 0.0; u1r = 0.0;
-            }
-            auto inside = [&](const double* cf, int n) {
-                const double r = 1.006 * (fabs(cf[1]) + fabs(cf[2]) + fabs(cf[3]) + fabs(cf[4]) + fabs(cf[5]));
-                return (cf[0] - r >= 0.0) & (cf[0] + r < (double)(n - 1));
-            };
-            double xs = 0.0;
-#pragma unroll
-            for (int n = 0; n < PX; ++n) xs += fabs(xc[n]);
-            lane_safe = mine && (fabs(u0r) <= 1.001) && (fabs(u1r) <= 1.001) && (xs <= 1.001) && inside(q.lat, c.ny) && inside(q.lon, c.nx);
-        }
+        if (REGULAR) lane_safe = lane_nocheck(w[(int64_t)WS_U0 * ns], w[(int64_t)WS_U1 * ns], active, mine, q, xc, c.ny, c.nx);
         if (REGULAR && __all(lane_safe)) run(std::integral_constant<bool, true>{});
         else run(std::integral_constant<bool, false>{});
         if (active && scale_rec != 0.0) {

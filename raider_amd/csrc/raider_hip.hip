@@ -2054,35 +2054,122 @@ static int launch_crossings(rdr_ctx* c, const rdr_cube* q, RayParams P, int64_t 
     return RDR_OK;
 }
 
+// The light pass-2 instantiation a cube takes (GRID of march_kernel / march_epochs_kernel): 1 REGULAR, 2 TABLES, 0 run-time flags.
+// Per-ray heights are built for REGULAR and run-time flags only.
+static int march_grid(const rdr_cube* q, bool per_ray) {
+    const bool small = make_view<float2>(q).small && (q->dtype == RDR_F32 || make_view<double2>(q).small);
+    if (!small) return 0;
+    if (q->exact[0] && q->exact[1]) return 1;
+    return (!per_ray && !q->exact[0] && !q->exact[1] && q->uni[0] && q->uni[1]) ? 2 : 0;
+}
+
+// generic-ray mop-up of pass 2 on the records of P, tile counters d_tilectr + 24 (zero_ctr: not yet zeroed); the kernel returns at once
+// when pass 1 found no generic ray
+static int launch_march_generic(rdr_ctx* c, const rdr_cube* q, RayParams P, dim3 G, dim3 B, size_t sm, bool zero_ctr) {
+    if (zero_ctr) HIPCHECK(c, hipMemsetAsync(c->d_tilectr + 24, 0, 8 * sizeof(int), c->stream));
+    P.tile_ctr = c->d_tilectr + 24;
+    hipError_t e;
+    if (q->dtype == RDR_F32) e = launch_lds(march_kernel<float2, true>, G, B, sm, c->stream, make_view<float2>(q), P, q->proj);
+    else e = launch_lds(march_kernel<double2, true>, G, B, sm, c->stream, make_view<double2>(q), P, q->proj);
+    if (e != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("march_kernel launch: ") + hipGetErrorString(e));
+    return RDR_OK;
+}
+
 static int launch_march(rdr_ctx* c, const rdr_cube* q, RayParams P, int64_t tb, int64_t tc, int64_t nslots_total = 0) {
     P.tile_begin = tb; P.tile_count = tc; P.nslots = nslots_total > 0 ? nslots_total : tc * BLOCK;
     static const int stage_f64 = []() { const char* e = std::getenv("RAIDER_HIP_F64_STAGE"); return e ? std::atoi(e) : 1; }();
     P.stage_f64 = stage_f64;
     const int g = ray_grid(c, tc, 8);
-    HIPCHECK(c, hipMemsetAsync(c->d_tilectr + 16, 0, 16 * sizeof(int), c->stream));
+    HIPCHECK(c, hipMemsetAsync(c->d_tilectr + 16, 0, 16 * sizeof(int), c->stream));     // (the mop-up's counters too)
     P.tile_ctr = c->d_tilectr + 16;
     const size_t sm = ray_smem(q);
     const dim3 G(g), B(BLOCK);
     hipError_t e = hipSuccess;
     {
         KTimer t(c, 1);
-        const auto v32 = make_view<float2>(q);
-        const bool small = v32.small && (q->dtype == RDR_F32 || make_view<double2>(q).small);
-        const int grid = !small ? 0 : (q->exact[0] && q->exact[1]) ? 1 : (!q->exact[0] && !q->exact[1] && q->uni[0] && q->uni[1]) ? 2 : 0;
-#define RDR_LAUNCH_M(T2, V) (P.ht_ray ? (grid == 1 ? launch_lds(march_kernel<T2, false, 1, true>, G, B, sm, c->stream, V, P, q->proj)   \
-                                                    : launch_lds(march_kernel<T2, false, 0, true>, G, B, sm, c->stream, V, P, q->proj)) \
-                             : grid == 1 ? launch_lds(march_kernel<T2, false, 1>, G, B, sm, c->stream, V, P, q->proj)   \
-                             : grid == 2 ? launch_lds(march_kernel<T2, false, 2>, G, B, sm, c->stream, V, P, q->proj) \
-                                         : launch_lds(march_kernel<T2, false, 0>, G, B, sm, c->stream, V, P, q->proj))
-        if (q->dtype == RDR_F32) e = RDR_LAUNCH_M(float2, v32);
-        else e = RDR_LAUNCH_M(double2, make_view<double2>(q));
+        const int grid = march_grid(q, P.ht_ray != nullptr);
+#define RDR_LAUNCH_M(T2) (P.ht_ray ? (grid == 1 ? launch_lds(march_kernel<T2, false, 1, true>, G, B, sm, c->stream, make_view<T2>(q), P, q->proj)   \
+                                                 : launch_lds(march_kernel<T2, false, 0, true>, G, B, sm, c->stream, make_view<T2>(q), P, q->proj)) \
+                          : grid == 1 ? launch_lds(march_kernel<T2, false, 1>, G, B, sm, c->stream, make_view<T2>(q), P, q->proj)   \
+                          : grid == 2 ? launch_lds(march_kernel<T2, false, 2>, G, B, sm, c->stream, make_view<T2>(q), P, q->proj) \
+                                      : launch_lds(march_kernel<T2, false, 0>, G, B, sm, c->stream, make_view<T2>(q), P, q->proj))
+        if (q->dtype == RDR_F32) e = RDR_LAUNCH_M(float2);
+        else e = RDR_LAUNCH_M(double2);
 #undef RDR_LAUNCH_M
     }
     if (e != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("march_kernel launch: ") + hipGetErrorString(e));
-    P.tile_ctr = c->d_tilectr + 24;
-    if (q->dtype == RDR_F32) e = launch_lds(march_kernel<float2, true>, G, B, sm, c->stream, make_view<float2>(q), P, q->proj);
-    else e = launch_lds(march_kernel<double2, true>, G, B, sm, c->stream, make_view<double2>(q), P, q->proj);
-    if (e != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("march_kernel launch: ") + hipGetErrorString(e));
+    return launch_march_generic(c, q, P, G, B, sm, false);
+}
+
+// epochs per stacked launch: 4, or RAIDER_HIP_EPOCHS_MAX = 1 / 2 / 4 (tools/bench_epochs.py compares them; 1 = the one-epoch march per epoch)
+static int epochs_max() {
+    const char* e = std::getenv("RAIDER_HIP_EPOCHS_MAX");
+    const int v = e ? std::atoi(e) : EPOCHS_MAX;
+    return v >= 4 ? 4 : v >= 2 ? 2 : 1;
+}
+
+// Epochs of the next stacked launch of a series with `left` epochs to go: 4, then 2, then 1 (engine.epoch_groups; 1: the one-epoch
+// kernel), capped by emax = epochs_max().  A per-ray-height series on f64 cubes goes in pairs - its E = 4 instantiation is spill-free
+// at one wave per SIMD only (EpochWaves; DESIGN.md 5d has the measurements) - unless RAIDER_HIP_EPOCHS_PR_F64_MAX = 1 / 2 / 4 says
+// otherwise (tools/bench_epochs.py compares them).
+static int epoch_group(int dtype, bool per_ray, int left, int emax) {
+    if (per_ray && dtype == RDR_F64) {
+        const char* env = std::getenv("RAIDER_HIP_EPOCHS_PR_F64_MAX");
+        emax = std::min(emax, env ? std::atoi(env) : 2);
+    }
+    return (left >= 4 && emax >= 4) ? 4 : (left >= 2 && emax >= 2) ? 2 : 1;
+}
+
+// the stacked light kernel of E epochs (grid: march_grid of the batch; per-ray heights from P.ht_ray)
+#define RDR_EPOCH_FN(T2, E, grid, pr) ((pr) ? ((grid) == 1 ? march_epochs_kernel<T2, E, 1, true> : march_epochs_kernel<T2, E, 0, true>) \
+                                            : (grid) == 1 ? march_epochs_kernel<T2, E, 1, false>                                         \
+                                            : (grid) == 2 ? march_epochs_kernel<T2, E, 2, false> : march_epochs_kernel<T2, E, 0, false>)
+
+template <typename T2, int E>
+static hipError_t launch_stacked(rdr_ctx* c, const rdr_cube* const* qs, int grid, const RayParams& P, int64_t estride, dim3 G, dim3 B, size_t sm) {
+    EpochCubes<T2, E> ev;
+    for (int j = 0; j < E; ++j) ev.v[j] = (const T2*)qs[j]->d_vals;
+    return launch_lds(RDR_EPOCH_FN(T2, E, grid, P.ht_ray != nullptr), G, B, sm, c->stream, make_view<T2>(qs[0]), ev, P, estride);
+}
+
+// pass 2 of D epochs over tiles [tb, tb+tc) on the records of ONE pass 1: groups of 4 / 2 epochs (epoch_group) take the stacked
+// marcher - its per-ray-height loop when the batch has per-ray heights (P.ht_ray; one slice) - plus the generic kernel once per epoch;
+// a last single epoch takes launch_march, whose instantiations the stacked ones match bit for bit.
+// P.wet / P.hyd: epoch 0's [nslices][n] block, epoch e's is estride doubles further.
+static int launch_march_epochs(rdr_ctx* c, const rdr_cube* const* qs, int D, RayParams P, int64_t tb, int64_t tc, int64_t estride) {
+    const rdr_cube* q = qs[0];
+    const int emax = epochs_max();
+    const bool per_ray = P.ht_ray != nullptr;
+    const int grid = march_grid(q, per_ray);
+    const int g = ray_grid(c, tc, 8);
+    const size_t sm = ray_smem(q);
+    const dim3 G(g), B(BLOCK);
+    for (int e = 0; e < D;) {
+        const int ge = epoch_group(q->dtype, per_ray, D - e, emax);
+        RayParams Pe = P;
+        Pe.wet = P.wet + (int64_t)e * estride; Pe.hyd = P.hyd + (int64_t)e * estride;
+        if (ge == 1) {
+            const int rc = launch_march(c, qs[e], Pe, tb, tc); if (rc) return rc;
+            ++e;
+            continue;
+        }
+        Pe.tile_begin = tb; Pe.tile_count = tc; Pe.nslots = tc * BLOCK;
+        HIPCHECK(c, hipMemsetAsync(c->d_tilectr + 16, 0, 8 * sizeof(int), c->stream));
+        Pe.tile_ctr = c->d_tilectr + 16;
+        hipError_t err = hipSuccess;
+        {
+            KTimer t(c, 1);
+            if (q->dtype == RDR_F32) err = ge == 4 ? launch_stacked<float2, 4>(c, qs + e, grid, Pe, estride, G, B, sm) : launch_stacked<float2, 2>(c, qs + e, grid, Pe, estride, G, B, sm);
+            else err = ge == 4 ? launch_stacked<double2, 4>(c, qs + e, grid, Pe, estride, G, B, sm) : launch_stacked<double2, 2>(c, qs + e, grid, Pe, estride, G, B, sm);
+        }
+        if (err != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("march_epochs_kernel launch: ") + hipGetErrorString(err));
+        for (int j = 0; j < ge; ++j) {                  // generic rays, epoch by epoch, on the same records and side buffer
+            RayParams Pj = Pe;
+            Pj.wet = Pe.wet + (int64_t)j * estride; Pj.hyd = Pe.hyd + (int64_t)j * estride;
+            const int rc = launch_march_generic(c, qs[e + j], Pj, G, B, sm, true); if (rc) return rc;
+        }
+        e += ge;
+    }
     return RDR_OK;
 }
 
@@ -2093,38 +2180,22 @@ int rdr_ray_kernel_attributes(rdr_ctx* c, const rdr_cube* q, int which, int32_t*
     if (!c || !q || which < 0 || which > 7) return fail(c, RDR_ERR_INVALID, "rdr_ray_kernel_attributes: bad argument");
     const void* fn = nullptr;
     const bool lcc = q->proj.kind == 1;
-    const bool pr = which == 2 || which == 3;      // 2 / 3: the per-ray-height instantiations of pass 1 / pass 2
-    if (which >= 6) {                              // 6 / 7: the stacked per-ray-height march (march_epochs_pr_kernel), E = 2 / 4
-        const auto v32 = make_view<float2>(q);
-        const bool small = v32.small && (q->dtype == RDR_F32 || make_view<double2>(q).small);
-        const bool regular = small && q->exact[0] && q->exact[1];
-#define RDR_EPOCH_PR_FN(T2, E) (regular ? (const void*)march_epochs_pr_kernel<T2, E, 1> : (const void*)march_epochs_pr_kernel<T2, E, 0>)
-        if (q->dtype == RDR_F32) fn = which == 6 ? RDR_EPOCH_PR_FN(float2, 2) : RDR_EPOCH_PR_FN(float2, 4);
-        else fn = which == 6 ? RDR_EPOCH_PR_FN(double2, 2) : RDR_EPOCH_PR_FN(double2, 4);
-#undef RDR_EPOCH_PR_FN
-    } else if (which >= 4) {                       // 4 / 5: the stacked time-series march (march_epochs_kernel), E = 2 / 4
-        const auto v32 = make_view<float2>(q);
-        const bool small = v32.small && (q->dtype == RDR_F32 || make_view<double2>(q).small);
-        const int grid = !small ? 0 : (q->exact[0] && q->exact[1]) ? 1 : (!q->exact[0] && !q->exact[1] && q->uni[0] && q->uni[1]) ? 2 : 0;
-#define RDR_EPOCH_FN(T2, E) (grid == 1 ? (const void*)march_epochs_kernel<T2, E, 1> : grid == 2 ? (const void*)march_epochs_kernel<T2, E, 2> : (const void*)march_epochs_kernel<T2, E, 0>)
-        if (q->dtype == RDR_F32) fn = which == 4 ? RDR_EPOCH_FN(float2, 2) : RDR_EPOCH_FN(float2, 4);
-        else fn = which == 4 ? RDR_EPOCH_FN(double2, 2) : RDR_EPOCH_FN(double2, 4);
-#undef RDR_EPOCH_FN
+    const bool pr = which == 2 || which == 3 || which >= 6;      // 2 / 3: the per-ray-height instantiations of pass 1 / pass 2; 6 / 7: of the stacked march
+    const int grid = march_grid(q, pr);
+    if (which >= 4) {                              // 4 / 5 (sliced), 6 / 7 (per-ray heights): the stacked march (march_epochs_kernel), E = 2 / 4
+        const bool four = (which & 1) != 0;
+        if (q->dtype == RDR_F32) fn = four ? (const void*)RDR_EPOCH_FN(float2, 4, grid, pr) : (const void*)RDR_EPOCH_FN(float2, 2, grid, pr);
+        else fn = four ? (const void*)RDR_EPOCH_FN(double2, 4, grid, pr) : (const void*)RDR_EPOCH_FN(double2, 2, grid, pr);
     } else if ((which & 1) == 0) {
         if (q->dtype == RDR_F32) fn = pr ? (lcc ? (const void*)crossings_kernel<float2, false, true, 1, true> : (const void*)crossings_kernel<float2, false, false, 1, true>)
                                          : (lcc ? (const void*)crossings_kernel<float2, false, true, 1> : (const void*)crossings_kernel<float2, false, false, 1>);
         else fn = pr ? (lcc ? (const void*)crossings_kernel<double2, false, true, 1, true> : (const void*)crossings_kernel<double2, false, false, 1, true>)
                      : (lcc ? (const void*)crossings_kernel<double2, false, true, 1> : (const void*)crossings_kernel<double2, false, false, 1>);
-    } else {
-        const auto v32 = make_view<float2>(q);
-        const bool small = v32.small && (q->dtype == RDR_F32 || make_view<double2>(q).small);
-        const int grid = !small ? 0 : (q->exact[0] && q->exact[1]) ? 1 : (!q->exact[0] && !q->exact[1] && q->uni[0] && q->uni[1]) ? 2 : 0;
-        if (pr) {
-            if (q->dtype == RDR_F32) fn = grid == 1 ? (const void*)march_kernel<float2, false, 1, true> : (const void*)march_kernel<float2, false, 0, true>;
-            else fn = grid == 1 ? (const void*)march_kernel<double2, false, 1, true> : (const void*)march_kernel<double2, false, 0, true>;
-        } else if (q->dtype == RDR_F32) fn = grid == 1 ? (const void*)march_kernel<float2, false, 1> : grid == 2 ? (const void*)march_kernel<float2, false, 2> : (const void*)march_kernel<float2, false, 0>;
-        else fn = grid == 1 ? (const void*)march_kernel<double2, false, 1> : grid == 2 ? (const void*)march_kernel<double2, false, 2> : (const void*)march_kernel<double2, false, 0>;
-    }
+    } else if (pr) {
+        if (q->dtype == RDR_F32) fn = grid == 1 ? (const void*)march_kernel<float2, false, 1, true> : (const void*)march_kernel<float2, false, 0, true>;
+        else fn = grid == 1 ? (const void*)march_kernel<double2, false, 1, true> : (const void*)march_kernel<double2, false, 0, true>;
+    } else if (q->dtype == RDR_F32) fn = grid == 1 ? (const void*)march_kernel<float2, false, 1> : grid == 2 ? (const void*)march_kernel<float2, false, 2> : (const void*)march_kernel<float2, false, 0>;
+    else fn = grid == 1 ? (const void*)march_kernel<double2, false, 1> : grid == 2 ? (const void*)march_kernel<double2, false, 2> : (const void*)march_kernel<double2, false, 0>;
     hipFuncAttributes a;
     HIPCHECK(c, hipFuncGetAttributes(&a, fn));
     if (vgprs) *vgprs = a.numRegs;
@@ -2356,11 +2427,14 @@ int rdr_ray_march(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, double ht, d
     return RDR_OK;
 }
 
-int rdr_raytrace(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, double ht, double zref, double max_seg, double* wet,
-                 double* hydro, int32_t* nparts_out, int32_t* flags_out) {
-    if (!c || !q || !wet || !hydro) return fail(c, RDR_ERR_INVALID, "rdr_raytrace: NULL argument");
-    note_use(c, q);
-    if (!(max_seg > 0)) return fail(c, RDR_ERR_INVALID, "rdr_raytrace: MAX_SEGMENT_LENGTH must be positive");
+// One batch of rays through D epoch cubes qs[] (epochs_check; D = 1: rdr_raytrace), per-ray heights (rays->hts) included: one pass 1
+// through ray_passes' workspace schedule, every chunk's pass 2 through launch_march_epochs.  Epoch e's delays are block e of [D][n];
+// nparts_out / flags_out are pass 1's, shared by every epoch.  The entries have checked their NULL arguments; `who` prefixes the rest.
+static int raytrace_impl(rdr_ctx* c, const char* who, const rdr_cube* const* qs, int32_t D, const rdr_rays* r, double ht, double zref,
+                         double max_seg, double* wet, double* hydro, int32_t* nparts_out, int32_t* flags_out) {
+    const rdr_cube* q = qs[0];
+    for (int32_t e = 0; e < D; ++e) note_use(c, qs[e]);
+    if (!(max_seg > 0)) return fail(c, RDR_ERR_INVALID, std::string(who) + ": MAX_SEGMENT_LENGTH must be positive");
     int rc = check_rays(c, r); if (rc) return rc;
     std::vector<double> lo, hi; std::vector<int> kz;
     const int K = levels_host(q->zs, ht, zref, lo, hi, kz);
@@ -2368,8 +2442,8 @@ int rdr_raytrace(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, double ht, do
     if (r->n == 0) return RDR_OK;
     HIPCHECK(c, hipSetDevice(c->device));
     RayParams P;
-    // large host-buffer batches with per-ray look vectors: overlap the PCIe transfers with the two passes (raytrace_pipelined)
-    bool pipelined = r->loc == RDR_HOST && r->n >= (1 << 21) && pipelining();
+    // one epoch, large host-buffer batches with per-ray look vectors: overlap the PCIe transfers with the two passes (raytrace_pipelined)
+    bool pipelined = D == 1 && r->loc == RDR_HOST && r->n >= (1 << 21) && pipelining();
     const bool los_chunks = pipelined && r->los_mode == RDR_LOS_VEC;
     const bool hts_chunks = pipelined && r->hts != nullptr;
     rdr_rays rr = *r;
@@ -2389,9 +2463,10 @@ int rdr_raytrace(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, double ht, do
         pipelined = false;
     }
     P.ht = ht; P.zref = zref; P.max_seg = max_seg;
+    const size_t bytes = (size_t)r->n * (size_t)D * 8;
     void *dw, *dh;
-    rc = stage_out(c, SLOT_OUT0, wet, (size_t)r->n * 8, r->loc, &dw); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT1, hydro, (size_t)r->n * 8, r->loc, &dh); if (rc) return rc;
+    rc = stage_out(c, SLOT_OUT0, wet, bytes, r->loc, &dw); if (rc) return rc;
+    rc = stage_out(c, SLOT_OUT1, hydro, bytes, r->loc, &dh); if (rc) return rc;
     P.wet = (double*)dw; P.hyd = (double*)dh;
     HIPCHECK(c, hipMemsetAsync(c->d_maxlen, 0, MAX_LEVELS * sizeof(unsigned long long), c->stream));
     HIPCHECK(c, hipMemsetAsync(c->d_flags, 0, sizeof(int), c->stream));
@@ -2403,11 +2478,11 @@ int rdr_raytrace(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, double ht, do
         rc = raytrace_pipelined(c, q, r, P, K, (double*)dl, (double*)dhts, (double*)dw, (double*)dh, wet, hydro); if (rc) return rc;
     } else {
         // one slice: pass 1 reduces AND stores the ray records when they all fit, pass 2 streams them back; else chunked
-        rc = ray_passes(c, q, P, K, P.ntiles, 1, ws_chunk_tiles(c, K), 1, true); if (rc) return rc;
-    }
-    if (!pipelined) {
-        rc = finish_out(c, wet, dw, (size_t)r->n * 8, r->loc); if (rc) return rc;
-        rc = finish_out(c, hydro, dh, (size_t)r->n * 8, r->loc); if (rc) return rc;
+        std::function<int(const RayParams&, int64_t, int64_t)> march;      // (one epoch: ray_passes' own launch_march)
+        if (D > 1) march = [&](const RayParams& Pm, int64_t tb, int64_t tc) { return launch_march_epochs(c, qs, D, Pm, tb, tc, (int64_t)r->n); };
+        rc = ray_passes(c, q, P, K, P.ntiles, 1, ws_chunk_tiles(c, K), 1, true, march); if (rc) return rc;
+        rc = finish_out(c, wet, dw, bytes, r->loc); if (rc) return rc;
+        rc = finish_out(c, hydro, dh, bytes, r->loc); if (rc) return rc;
     }
     const bool need_sync = r->loc == RDR_HOST || nparts_out || flags_out;
     if (need_sync) {
@@ -2423,6 +2498,12 @@ int rdr_raytrace(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, double ht, do
         return flags_to_status(c, f);
     }
     return RDR_OK;
+}
+
+int rdr_raytrace(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, double ht, double zref, double max_seg, double* wet,
+                 double* hydro, int32_t* nparts_out, int32_t* flags_out) {
+    if (!c || !q || !wet || !hydro) return fail(c, RDR_ERR_INVALID, "rdr_raytrace: NULL argument");
+    return raytrace_impl(c, "rdr_raytrace", &q, 1, r, ht, zref, max_seg, wet, hydro, nparts_out, flags_out);
 }
 
 // ---- height slices, and a time series of E weather epochs through one ray geometry (rdr_raytrace_slices[_epochs]) -----------------
@@ -2458,13 +2539,6 @@ static int epochs_check(rdr_ctx* c, const char* who, const rdr_cube* const* qs, 
     return RDR_OK;
 }
 
-// epochs per stacked launch: 4, or RAIDER_HIP_EPOCHS_MAX = 1 / 2 / 4 (tools/bench_epochs.py compares them; 1 = the one-epoch march per epoch)
-static int epochs_max() {
-    const char* e = std::getenv("RAIDER_HIP_EPOCHS_MAX");
-    const int v = e ? std::atoi(e) : EPOCHS_MAX;
-    return v >= 4 ? 4 : v >= 2 ? 2 : 1;
-}
-
 // ---- a date series at query points (rdr_interp3_project_epochs, rdr_point_delays_epochs) --------------------------------------------
 // The gather of D epochs that share one grid: `q` describes that grid (shape, axes, dtype), vals[e] is epoch e's value buffer.
 template <typename T2, int E>
@@ -2477,14 +2551,13 @@ static void launch_points_stacked(rdr_ctx* c, const rdr_cube* q, const void* con
                        (int)axes_fit_lds(q));
 }
 
-// groups of 4, then 2, then 1 epochs (engine.epoch_groups; RAIDER_HIP_EPOCHS_MAX caps the group).  dw / dh: epoch 0's block, epoch e's is
+// groups of 4, then 2, then 1 epochs (epoch_group).  dw / dh: epoch 0's block, epoch e's is
 // estride doubles further; Q.proj: epoch 0's divisors, epoch e's pstride doubles further (pstride 0: shared).
 static void launch_interp_epochs(rdr_ctx* c, const rdr_cube* q, const void* const* vals, int D, const PointQuery& Q, int64_t pstride, int64_t cnt, int64_t estride,
                                  double* dw, double* dh) {
     const int emax = epochs_max();
     for (int e = 0; e < D;) {
-        const int left = D - e;
-        const int ge = (left >= 4 && emax >= 4) ? 4 : (left >= 2 && emax >= 2) ? 2 : 1;
+        const int ge = epoch_group(q->dtype, false, D - e, emax);
         PointQuery Qe = Q;
         if (Qe.proj) Qe.proj += (int64_t)e * pstride;
         double* we = dw ? dw + (int64_t)e * estride : nullptr;
@@ -2631,129 +2704,6 @@ int rdr_point_delays_epochs(rdr_ctx* c, const rdr_cube* const* cubes, int32_t nc
     quiesce.armed = false;
     if (cube_has_nan) for (int e = 0; e < D; ++e) cube_has_nan[e] = nanw[(size_t)e] != 0;
     scratch_trim_point_delays(c);
-    return RDR_OK;
-}
-
-template <typename T2, int E>
-static hipError_t launch_stacked(rdr_ctx* c, const rdr_cube* const* qs, int grid, const RayParams& P, int64_t estride, dim3 G, dim3 B, size_t sm) {
-    EpochCubes<T2, E> ev;
-    for (int j = 0; j < E; ++j) ev.v[j] = (const T2*)qs[j]->d_vals;
-    const CubeView<T2> V = make_view<T2>(qs[0]);
-    return grid == 1 ? launch_lds(march_epochs_kernel<T2, E, 1>, G, B, sm, c->stream, V, ev, P, estride)
-         : grid == 2 ? launch_lds(march_epochs_kernel<T2, E, 2>, G, B, sm, c->stream, V, ev, P, estride)
-                     : launch_lds(march_epochs_kernel<T2, E, 0>, G, B, sm, c->stream, V, ev, P, estride);
-}
-
-// pass 2 of D epochs over tiles [tb, tb+tc) on the records of ONE pass 1: groups of 4 / 2 epochs take the stacked marcher (plus the
-// generic kernel once per epoch, which returns at once when pass 1 found no generic ray); a last single epoch takes launch_march.
-// P.wet / P.hyd: epoch 0's [nslices][n] block, epoch e's is estride doubles further.
-static int launch_march_epochs(rdr_ctx* c, const rdr_cube* const* qs, int D, RayParams P, int64_t tb, int64_t tc, int64_t estride) {
-    const rdr_cube* q = qs[0];
-    const int emax = epochs_max();
-    const auto v32 = make_view<float2>(q);
-    const bool small = v32.small && (q->dtype == RDR_F32 || make_view<double2>(q).small);
-    const int grid = !small ? 0 : (q->exact[0] && q->exact[1]) ? 1 : (!q->exact[0] && !q->exact[1] && q->uni[0] && q->uni[1]) ? 2 : 0;
-    const int g = ray_grid(c, tc, 8);
-    const size_t sm = ray_smem(q);
-    const dim3 G(g), B(BLOCK);
-    for (int e = 0; e < D;) {
-        const int left = D - e;
-        const int ge = (left >= 4 && emax >= 4) ? 4 : (left >= 2 && emax >= 2) ? 2 : 1;
-        RayParams Pe = P;
-        Pe.wet = P.wet + (int64_t)e * estride; Pe.hyd = P.hyd + (int64_t)e * estride;
-        if (ge == 1) {
-            const int rc = launch_march(c, qs[e], Pe, tb, tc); if (rc) return rc;
-            ++e;
-            continue;
-        }
-        Pe.tile_begin = tb; Pe.tile_count = tc; Pe.nslots = tc * BLOCK;
-        HIPCHECK(c, hipMemsetAsync(c->d_tilectr + 16, 0, 8 * sizeof(int), c->stream));
-        Pe.tile_ctr = c->d_tilectr + 16;
-        hipError_t err = hipSuccess;
-        {
-            KTimer t(c, 1);
-            if (q->dtype == RDR_F32) err = ge == 4 ? launch_stacked<float2, 4>(c, qs + e, grid, Pe, estride, G, B, sm) : launch_stacked<float2, 2>(c, qs + e, grid, Pe, estride, G, B, sm);
-            else err = ge == 4 ? launch_stacked<double2, 4>(c, qs + e, grid, Pe, estride, G, B, sm) : launch_stacked<double2, 2>(c, qs + e, grid, Pe, estride, G, B, sm);
-        }
-        if (err != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("march_epochs_kernel launch: ") + hipGetErrorString(err));
-        for (int j = 0; j < ge; ++j) {                  // generic rays, epoch by epoch, on the same records and side buffer
-            RayParams Pj = Pe;
-            Pj.wet = Pe.wet + (int64_t)j * estride; Pj.hyd = Pe.hyd + (int64_t)j * estride;
-            HIPCHECK(c, hipMemsetAsync(c->d_tilectr + 24, 0, 8 * sizeof(int), c->stream));
-            Pj.tile_ctr = c->d_tilectr + 24;
-            const rdr_cube* qj = qs[e + j];
-            if (q->dtype == RDR_F32) err = launch_lds(march_kernel<float2, true>, G, B, sm, c->stream, make_view<float2>(qj), Pj, qj->proj);
-            else err = launch_lds(march_kernel<double2, true>, G, B, sm, c->stream, make_view<double2>(qj), Pj, qj->proj);
-            if (err != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("march_kernel launch: ") + hipGetErrorString(err));
-        }
-        e += ge;
-    }
-    return RDR_OK;
-}
-
-// Epochs of the next stacked launch of a per-ray-height series (1: the one-epoch march on the shared pass 1).  f32 cubes: 4, 2, 1 as
-// the sliced series.  f64 cubes: pairs - the E = 4 instantiation is spill-free at one wave per SIMD only (EpochWavesPR; DESIGN.md 5d has
-// the measurements) - unless RAIDER_HIP_EPOCHS_PR_F64_MAX = 1 / 2 / 4 says otherwise (tools/bench_epochs.py compares them).
-// RAIDER_HIP_EPOCHS_MAX caps both.
-static int epochs_pr_group(int dtype, int left, int emax) {
-    const char* env = std::getenv("RAIDER_HIP_EPOCHS_PR_F64_MAX");
-    const int f64_max = env ? std::atoi(env) : 2;
-    if (dtype == RDR_F64) emax = std::min(emax, f64_max);
-    return (left >= 4 && emax >= 4) ? 4 : (left >= 2 && emax >= 2) ? 2 : 1;
-}
-
-template <typename T2, int E>
-static hipError_t launch_stacked_pr(rdr_ctx* c, const rdr_cube* const* qs, int grid, const RayParams& P, int64_t estride, dim3 G, dim3 B, size_t sm) {
-    EpochCubes<T2, E> ev;
-    for (int j = 0; j < E; ++j) ev.v[j] = (const T2*)qs[j]->d_vals;
-    const CubeView<T2> V = make_view<T2>(qs[0]);
-    return grid == 1 ? launch_lds(march_epochs_pr_kernel<T2, E, 1>, G, B, sm, c->stream, V, ev, P, estride)
-                     : launch_lds(march_epochs_pr_kernel<T2, E, 0>, G, B, sm, c->stream, V, ev, P, estride);
-}
-
-// launch_march_epochs for a batch with per-ray heights (P.ht_ray; one slice): the stacked groups take march_epochs_pr_kernel, a single
-// epoch launch_march (whose per-ray-height instantiation it is bit for bit).  A batch without them is launch_march_epochs' own.
-static int launch_march_epochs_pr(rdr_ctx* c, const rdr_cube* const* qs, int D, RayParams P, int64_t tb, int64_t tc, int64_t estride) {
-    if (!P.ht_ray) return launch_march_epochs(c, qs, D, P, tb, tc, estride);
-    const rdr_cube* q = qs[0];
-    const int emax = epochs_max();
-    const auto v32 = make_view<float2>(q);
-    const bool small = v32.small && (q->dtype == RDR_F32 || make_view<double2>(q).small);
-    const int grid = (small && q->exact[0] && q->exact[1]) ? 1 : 0;     // (launch_march's choice for per-ray heights)
-    const int g = ray_grid(c, tc, 8);
-    const size_t sm = ray_smem(q);
-    const dim3 G(g), B(BLOCK);
-    for (int e = 0; e < D;) {
-        const int ge = epochs_pr_group(q->dtype, D - e, emax);
-        RayParams Pe = P;
-        Pe.wet = P.wet + (int64_t)e * estride; Pe.hyd = P.hyd + (int64_t)e * estride;
-        if (ge == 1) {
-            const int rc = launch_march(c, qs[e], Pe, tb, tc); if (rc) return rc;
-            ++e;
-            continue;
-        }
-        Pe.tile_begin = tb; Pe.tile_count = tc; Pe.nslots = tc * BLOCK;
-        HIPCHECK(c, hipMemsetAsync(c->d_tilectr + 16, 0, 8 * sizeof(int), c->stream));
-        Pe.tile_ctr = c->d_tilectr + 16;
-        hipError_t err = hipSuccess;
-        {
-            KTimer t(c, 1);
-            if (q->dtype == RDR_F32) err = ge == 4 ? launch_stacked_pr<float2, 4>(c, qs + e, grid, Pe, estride, G, B, sm) : launch_stacked_pr<float2, 2>(c, qs + e, grid, Pe, estride, G, B, sm);
-            else err = ge == 4 ? launch_stacked_pr<double2, 4>(c, qs + e, grid, Pe, estride, G, B, sm) : launch_stacked_pr<double2, 2>(c, qs + e, grid, Pe, estride, G, B, sm);
-        }
-        if (err != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("march_epochs_pr_kernel launch: ") + hipGetErrorString(err));
-        for (int j = 0; j < ge; ++j) {                  // generic rays, epoch by epoch, on the same records and side buffer
-            RayParams Pj = Pe;
-            Pj.wet = Pe.wet + (int64_t)j * estride; Pj.hyd = Pe.hyd + (int64_t)j * estride;
-            HIPCHECK(c, hipMemsetAsync(c->d_tilectr + 24, 0, 8 * sizeof(int), c->stream));
-            Pj.tile_ctr = c->d_tilectr + 24;
-            const rdr_cube* qj = qs[e + j];
-            if (q->dtype == RDR_F32) err = launch_lds(march_kernel<float2, true>, G, B, sm, c->stream, make_view<float2>(qj), Pj, qj->proj);
-            else err = launch_lds(march_kernel<double2, true>, G, B, sm, c->stream, make_view<double2>(qj), Pj, qj->proj);
-            if (err != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("march_kernel launch: ") + hipGetErrorString(err));
-        }
-        e += ge;
-    }
     return RDR_OK;
 }
 
@@ -2963,54 +2913,14 @@ int rdr_raytrace_slices_epochs_to_cubes(rdr_ctx* c, const rdr_cube* const* cubes
     return raytrace_slices_to_cubes(c, who, cubes, ncubes, r, hts, nslices, los_per_slice, zref, max_seg, K_out, nparts_out, ld, flags_out, out);
 }
 
-// rdr_raytrace for D epoch cubes on ONE ray batch, per-ray heights (rays->hts) included: one pass 1 through ray_passes' workspace
-// schedule, every chunk's pass 2 through launch_march_epochs_pr.  Epoch e's delays are block e of [D][n]; nparts_out / flags_out are
-// pass 1's, shared by every epoch.  D = 1 is rdr_raytrace itself (with its pipelined host upload).
+// rdr_raytrace for D epoch cubes on ONE ray batch (raytrace_impl).  D = 1 is rdr_raytrace itself (with its pipelined host upload).
 int rdr_raytrace_epochs(rdr_ctx* c, const rdr_cube* const* cubes, int32_t ncubes, const rdr_rays* r, double ht, double zref, double max_seg,
                         double* wet, double* hydro, int32_t* nparts_out, int32_t* flags_out) {
     static const char* who = "rdr_raytrace_epochs";
     int rc = epochs_check(c, who, cubes, ncubes); if (rc) return rc;
     if (!wet || !hydro) return fail(c, RDR_ERR_INVALID, std::string(who) + ": NULL argument");
     if (ncubes == 1) return rdr_raytrace(c, cubes[0], r, ht, zref, max_seg, wet, hydro, nparts_out, flags_out);
-    const rdr_cube* q = cubes[0];
-    for (int32_t e = 0; e < ncubes; ++e) note_use(c, cubes[e]);
-    if (!(max_seg > 0)) return fail(c, RDR_ERR_INVALID, std::string(who) + ": MAX_SEGMENT_LENGTH must be positive");
-    rc = check_rays(c, r); if (rc) return rc;
-    std::vector<double> lo, hi; std::vector<int> kz;
-    const int K = levels_host(q->zs, ht, zref, lo, hi, kz);
-    if (K == 0) return fail(c, RDR_ERR_NO_LEVELS, "no weather-model interval contributes to the ray integral (build_ray -> None)");
-    if (r->n == 0) return RDR_OK;
-    HIPCHECK(c, hipSetDevice(c->device));
-    RayParams P;
-    rc = stage_rays(c, r, P); if (rc) return rc;
-    P.ht = ht; P.zref = zref; P.max_seg = max_seg;
-    const size_t total = (size_t)r->n * (size_t)ncubes;
-    void *dw, *dh;
-    rc = stage_out(c, SLOT_OUT0, wet, total * 8, r->loc, &dw); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT1, hydro, total * 8, r->loc, &dh); if (rc) return rc;
-    P.wet = (double*)dw; P.hyd = (double*)dh;
-    HIPCHECK(c, hipMemsetAsync(c->d_maxlen, 0, MAX_LEVELS * sizeof(unsigned long long), c->stream));
-    HIPCHECK(c, hipMemsetAsync(c->d_flags, 0, sizeof(int), c->stream));
-    c->wsig.valid = false;
-    rc = ray_passes(c, q, P, K, P.ntiles, 1, ws_chunk_tiles(c, K), 1, true,
-                    [&](const RayParams& Pm, int64_t tb, int64_t tc) { return launch_march_epochs_pr(c, cubes, ncubes, Pm, tb, tc, (int64_t)r->n); });
-    if (rc) return rc;
-    rc = finish_out(c, wet, dw, total * 8, r->loc); if (rc) return rc;
-    rc = finish_out(c, hydro, dh, total * 8, r->loc); if (rc) return rc;
-    const bool need_sync = r->loc == RDR_HOST || nparts_out || flags_out;
-    if (need_sync) {
-        std::vector<double> ml(K);
-        int f = 0, nslow = 0;
-        HIPCHECK(c, hipMemcpyAsync(ml.data(), c->d_maxlen, (size_t)K * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHECK(c, hipMemcpyAsync(&f, c->d_flags, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHECK(c, hipMemcpyAsync(&nslow, c->d_nslow, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHECK(c, hipStreamSynchronize(c->stream));
-        c->last_nslow = nslow;
-        if (nparts_out) rdr_nparts(ml.data(), K, max_seg, nparts_out);
-        if (flags_out) *flags_out = f;
-        return flags_to_status(c, f);
-    }
-    return RDR_OK;
+    return raytrace_impl(c, who, cubes, ncubes, r, ht, zref, max_seg, wet, hydro, nparts_out, flags_out);
 }
 
 int rdr_top_of_atmosphere(rdr_ctx* c, const double* xyz, const double* los, int64_t n, double h, const double* factor, double* pos, int loc) {

@@ -1108,6 +1108,119 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
     }
 }
 
+// ---- pass 2: the parts march_kernel and march_epochs_kernel (epoch_kernels.h) share ---------------------------------
+// What a slice's partition decides for every ray of the slice.
+struct SlicePartition {
+    double poison;          // NaN when the partition is undefined, else 0: added to every output of the slice
+    bool clamp_lo, clamp_hi;
+};
+
+// Integration partition of slice sl, after fill_levels (workgroup-uniform; called by every thread).  REC: also the packed records
+// of the light slice loops (the per-ray-height loops and the generic kernel read the separate arrays).
+template <bool REC>
+__device__ __forceinline__ SlicePartition fill_partition(const RayParams& P, const RaySmem& m, int nz, int sl, int K) {
+    int tz = threadIdx.x;
+    asm volatile("" : "+v"(tz));                   // (opaque: nothing derived from it is hoisted out of the tile loop and spilled)
+    if (tz == 0) m.K[1] = 0;
+    __syncthreads();
+    for (int k = tz; k < K; k += BLOCK) {
+        int np;
+        if (P.nparts_override) np = P.nparts_override[(int64_t)sl * MAX_LEVELS + k];
+        else {
+            const double parts = ceil(__longlong_as_double((long long)P.maxlen_bits[(int64_t)sl * MAX_LEVELS + k]) / P.max_seg) + 1.0;   // delay.py:283
+            np = (parts >= 1.0 && parts <= (double)MAX_NPARTS) ? (int)parts : -1;
+        }
+        if (np < 2 || np > MAX_NPARTS) {      // diverged lengths (e.g. look vectors far from unit length): refuse to loop over them
+            np = 2;
+            atomicOr(P.flags + sl, 16);       // RDR_FLAG_DIVERGED
+            m.K[1] = 1;
+        }
+        m.np[k] = np;
+        m.step[k] = 1.0 / ((double)np - 1.0);                    // np.linspace(0,1,np) (delay.py:287)
+        m.hs[k] = 0.5e-6 * m.step[k];                            // delay.py:314-315: end points get half of L*1e-6/(np-1)
+        if constexpr (REC) {                                     // the slice loop's packed record of the level
+            const int kzk = m.kz[k], last = nz - 1;
+            const int zb = max(window2_base(nz, kzk), 0);        // (nz = 2: the window is never trusted, only in-range reads matter)
+            LevelRec r;
+            r.xv = m.xv[k]; r.hs = m.hs[k]; r.step = m.step[k];
+            r.zmid = m.ax.ez[min(zb + 1, last)].x; r.r0 = m.ax.ez[zb].y; r.r1 = m.ax.ez[min(zb + 1, last)].y;
+            r.gk = m.ax.ez[kzk].x; r.rk = m.ax.ez[kzk].y;
+            r.npkz = np | (kzk << 17); r.pad[0] = r.pad[1] = r.pad[2] = 0;
+            m.lev[k] = r;
+            // one record past the last level (K <= nz-1): the "next level" of the last one repeats its top abscissa with weight 0,
+            // so the loop computes du1 = X(v) - X(v) = 0 and adds 0 * 0 to the top weight instead of branching on `more`
+            if (k == K - 1) { r.hs = 0.0; r.npkz = 2 | (kzk << 17); m.lev[K] = r; }
+        }
+    }
+    __syncthreads();
+    const int flags_in = P.flags[sl];
+    SlicePartition s;
+    // Every output of the slice is NaN when its partition is undefined: diverged lengths, or a NaN ray length anywhere in
+    // the slice - ndarray.max poisons nParts and the reference raises (delay.py:283).  The synchronous entry points raise
+    // the same error; a caller of the asynchronous ones (device arrays, no host round trip) gets NaN, never a finite
+    // delay computed with a partition the reference does not define.
+    s.poison = (m.K[1] || (flags_in & (1 | 32))) ? qnan() : 0.0;      // (32: a per-ray height below the slice table's)
+    s.clamp_lo = !(flags_in & 4);               // ALL first samples below zmin  (delay.py:306-307)
+    s.clamp_hi = !(flags_in & 8);               // ALL last samples above zmax   (delay.py:310-311)
+    return s;
+}
+
+// Thread tl of tile t (within its slice) -> ray i of the batch; active: the ray exists (false: tile padding).
+__device__ __forceinline__ void tile_ray(const RayParams& P, int64_t t, int tl, int64_t& i, bool& active) {
+    if (P.origin_mode == 0) {
+        const int64_t ty = t / P.tiles_x, tx = t - ty * P.tiles_x;
+        const int64_t row = ty * TILE + (tl >> 4), col = tx * TILE + (tl & 15);
+        active = row < P.ny && col < P.nx;
+        i = row * P.nx + col;
+    } else {
+        i = t * BLOCK + tl;
+        active = i < P.n;
+    }
+}
+
+// A light ray's record (w: the ray's slot of the workspace, ns: its field stride): the three ray polynomials and the crossing
+// polynomial.  The level crossings come from the latter as the loop reaches them (7 FMAs, no global loads inside the loop besides
+// the gathers, so the only memory waits are on a sample's own corners).
+__device__ __forceinline__ void load_ray_record(const double* w, int64_t ns, RayPoly& q, double (&xc)[PX]) {
+#pragma unroll
+    for (int n = 0; n < PN; ++n) {
+        q.h[n] = w[(int64_t)(WS_POLY_H + n) * ns];
+        q.lat[n] = w[(int64_t)(WS_POLY_LAT + n) * ns];
+        q.lon[n] = w[(int64_t)(WS_POLY_LON + n) * ns];
+    }
+#pragma unroll
+    for (int n = 0; n < PX; ++n) xc[n] = w[(int64_t)(WS_XPOLY + n) * ns];
+}
+
+// The no-check proof of a lane (REGULAR grids; the kernels take it wave-wide: __all); u0r, u1r: fields WS_U0, WS_U1 of its record,
+// passed by value (loaded inside, the per-ray-height instantiations allocate registers differently: profiles/r15_march_fold_regs.txt).
+// Bounds of the horizontal cell search, decided ONCE per wave from the polynomial coefficients.  Every sample's ray parameter lies between the ray's crossings: the two of the
+// first level (u0, u1 of the record) and X(v_k), |v_k| <= 1, whose magnitude is at most sum |x_k|.  So when |u0|, |u1| and
+// sum |x_k| are all <= 1.001 (the crossings sit inside the fit range [-1, 1] by construction; diverged or non-finite rays fail this),
+// every sample has |u| <= 1.001 and p(u) lies within c0 +- 1.006 sum_{k>=1} |c_k| (1.001^5 < 1.006).  When that interval is inside
+// [0, n-1) for the index-space lat AND lon polynomials of every ray of the wave, no gather can leave the cube and the per-sample
+// bounds tests (4 compares + the rare-path plumbing) are compiled out of the loop.  Lanes of tile padding get a harmless in-range
+// polynomial (written into q / xc here); a wave holding a generic ray (whose record is not a polynomial), a diverged ray or a ray
+// near the cube's edge keeps the checked loop.
+__device__ __forceinline__ bool lane_nocheck(double u0r, double u1r, bool active, bool mine, RayPoly& q, double (&xc)[PX], int ny, int nx) {
+    if (!active) {
+#pragma unroll
+        for (int n = 0; n < PN; ++n) { q.lat[n] = 0.0; q.lon[n] = 0.0; }
+        q.lat[0] = 0.5; q.lon[0] = 0.5;
+#pragma unroll
+        for (int n = 0; n < PX; ++n) xc[n] = 0.0;
+        u0r = 0.0; u1r = 0.0;
+    }
+    auto inside = [&](const double* cf, int n) {
+        const double r = 1.006 * (fabs(cf[1]) + fabs(cf[2]) + fabs(cf[3]) + fabs(cf[4]) + fabs(cf[5]));
+        return (cf[0] - r >= 0.0) & (cf[0] + r < (double)(n - 1));
+    };
+    double xs = 0.0;
+#pragma unroll
+    for (int n = 0; n < PX; ++n) xs += fabs(xc[n]);
+    return (mine || !active) && (fabs(u0r) <= 1.001) && (fabs(u1r) <= 1.001) && (xs <= 1.001) && inside(q.lat, ny) && inside(q.lon, nx);
+}
+
 // ---- pass 2: trapezoid integration of both fields along every ray (delay.py:285-323) -------------------------------
 // SLOW as in crossings_kernel: <false> integrates the classified-fast rays with the light geodesy, <true> the rest
 // with the generic one (and returns immediately when there are none).
@@ -1148,62 +1261,14 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
         if (sl != slice) {                                 // (workgroup-uniform) the slice's level table and integration partition
             slice = sl;
             K = fill_levels(c.nz, m, P.hts ? P.hts[sl] : P.ht, P.zref);
-            int tz = threadIdx.x;
-            asm volatile("" : "+v"(tz));                   // (opaque: nothing derived from it is hoisted out of the tile loop and spilled)
-            if (tz == 0) m.K[1] = 0;
-            __syncthreads();
-            for (int k = tz; k < K; k += BLOCK) {
-                int np;
-                if (P.nparts_override) np = P.nparts_override[(int64_t)sl * MAX_LEVELS + k];
-                else {
-                    const double parts = ceil(__longlong_as_double((long long)P.maxlen_bits[(int64_t)sl * MAX_LEVELS + k]) / P.max_seg) + 1.0;   // delay.py:283
-                    np = (parts >= 1.0 && parts <= (double)MAX_NPARTS) ? (int)parts : -1;
-                }
-                if (np < 2 || np > MAX_NPARTS) {      // diverged lengths (e.g. look vectors far from unit length): refuse to loop over them
-                    np = 2;
-                    atomicOr(P.flags + sl, 16);       // RDR_FLAG_DIVERGED
-                    m.K[1] = 1;
-                }
-                m.np[k] = np;
-                m.step[k] = 1.0 / ((double)np - 1.0);                    // np.linspace(0,1,np) (delay.py:287)
-                m.hs[k] = 0.5e-6 * m.step[k];                            // delay.py:314-315: end points get half of L*1e-6/(np-1)
-                if constexpr (!SLOW && !PR) {                            // the slice loop's packed record of the level
-                    const int kzk = m.kz[k], last = c.nz - 1;
-                    const int zb = max(window2_base(c.nz, kzk), 0);      // (nz = 2: the window is never trusted, only in-range reads matter)
-                    LevelRec r;
-                    r.xv = m.xv[k]; r.hs = m.hs[k]; r.step = m.step[k];
-                    r.zmid = m.ax.ez[min(zb + 1, last)].x; r.r0 = m.ax.ez[zb].y; r.r1 = m.ax.ez[min(zb + 1, last)].y;
-                    r.gk = m.ax.ez[kzk].x; r.rk = m.ax.ez[kzk].y;
-                    r.npkz = np | (kzk << 17); r.pad[0] = r.pad[1] = r.pad[2] = 0;
-                    m.lev[k] = r;
-                    // one record past the last level (K <= nz-1): the "next level" of the last one repeats its top abscissa with weight 0,
-                    // so the loop computes du1 = X(v) - X(v) = 0 and adds 0 * 0 to the top weight instead of branching on `more`
-                    if (k == K - 1) { r.hs = 0.0; r.npkz = 2 | (kzk << 17); m.lev[K] = r; }
-                }
-            }
-            __syncthreads();
-            const int flags_in = P.flags[sl];
-            // Every output of the slice is NaN when its partition is undefined: diverged lengths, or a NaN ray length anywhere in
-            // the slice - ndarray.max poisons nParts and the reference raises (delay.py:283).  The synchronous entry points raise
-            // the same error; a caller of the asynchronous ones (device arrays, no host round trip) gets NaN, never a finite
-            // delay computed with a partition the reference does not define.
-            poison = (m.K[1] || (flags_in & (1 | 32))) ? qnan() : 0.0;      // (32: a per-ray height below the slice table's)
-            clamp_lo = !(flags_in & 4);               // ALL first samples below zmin  (delay.py:306-307)
-            clamp_hi = !(flags_in & 8);               // ALL last samples above zmax   (delay.py:310-311)
+            const SlicePartition part = fill_partition<!SLOW && !PR>(P, m, c.nz, sl, K);
+            poison = part.poison; clamp_lo = part.clamp_lo; clamp_hi = part.clamp_hi;
             clamp_any = clamp_lo | clamp_hi;
         }
         int tl = threadIdx.x;
         asm volatile("" : "+v"(tl));                       // per-tile opaque copy of the thread index (see crossings_kernel)
         int64_t i; bool active;
-        if (P.origin_mode == 0) {
-            const int64_t ty = t / P.tiles_x, tx = t - ty * P.tiles_x;
-            const int64_t row = ty * TILE + (tl >> 4), col = tx * TILE + (tl & 15);
-            active = row < P.ny && col < P.nx;
-            i = row * P.nx + col;
-        } else {
-            i = t * BLOCK + tl;
-            active = i < P.n;
-        }
+        tile_ray(P, t, tl, i, active);
         const double* w = P.ws + (lt * BLOCK + tl);
         const int64_t ns = P.nslots;
         const double scale_rec = w[(int64_t)WS_SCALE * ns];         // light ray: ray length per unit of u (> 0 or NaN); generic ray: 0
@@ -1224,16 +1289,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
             // plus its top sample.  Latency is hidden by the four waves per SIMD, not by batching samples inside a lane.
             RayPoly q;
             double xc[PX];
-#pragma unroll
-            for (int n = 0; n < PN; ++n) {
-                q.h[n] = w[(int64_t)(WS_POLY_H + n) * ns];
-                q.lat[n] = w[(int64_t)(WS_POLY_LAT + n) * ns];
-                q.lon[n] = w[(int64_t)(WS_POLY_LON + n) * ns];
-            }
-            // The level crossings come from the ray's crossing polynomial as the loop reaches them (7 FMAs, no global loads
-            // inside the loop besides the gathers, so the only memory waits are on a sample's own corners).
-#pragma unroll
-            for (int n = 0; n < PX; ++n) xc[n] = w[(int64_t)(WS_XPOLY + n) * ns];
+            load_ray_record(w, ns, q, xc);
             const double scale = scale_rec;
             // MODE 1: a level's top sample / the ray's first sample; MODE 2: a sample strictly inside its model interval
             // lanes whose samples count: a lane of tile padding or a generic ray (its record is not a polynomial) computes garbage that is
@@ -1392,35 +1448,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
             }
             }   // (slice loop)
             };
-            // Bounds of the horizontal cell search, decided ONCE per wave from the polynomial coefficients.  Every sample's ray
-            // parameter lies between the ray's crossings: the two of the first level (u0, u1 of the record) and X(v_k), |v_k| <= 1,
-            // whose magnitude is at most sum |x_k|.  So when |u0|, |u1| and sum |x_k| are all <= 1.001 (the crossings sit inside
-            // the fit range [-1, 1] by construction; diverged or non-finite rays fail this), every sample has |u| <= 1.001 and
-            // p(u) lies within c0 +- 1.006 sum_{k>=1} |c_k| (1.001^5 < 1.006).  When that interval is inside [0, n-1) for the
-            // index-space lat AND lon polynomials of every ray of the wave, no gather can leave the cube and the per-sample bounds
-            // tests (4 compares + the rare-path plumbing) are compiled out of the loop.  Lanes of tile padding get a harmless
-            // in-range polynomial; a wave holding a generic ray (whose record is not a polynomial), a diverged ray or a ray near
-            // the cube's edge keeps the checked loop.
+            // the wave-wide no-check proof (lane_nocheck): bounds of the cell search from the polynomial coefficients
             bool lane_safe = false;
-            if (REGULAR) {
-                double u0r = w[(int64_t)WS_U0 * ns], u1r = w[(int64_t)WS_U1 * ns];
-                if (!active) {
-#pragma unroll
-                    for (int n = 0; n < PN; ++n) { q.lat[n] = 0.0; q.lon[n] = 0.0; }
-                    q.lat[0] = 0.5; q.lon[0] = 0.5;
-#pragma unroll
-                    for (int n = 0; n < PX; ++n) xc[n] = 0.0;
-                    u0r = 0.0; u1r = 0.0;
-                }
-                auto inside = [&](const double* cf, int n) {
-                    const double r = 1.006 * (fabs(cf[1]) + fabs(cf[2]) + fabs(cf[3]) + fabs(cf[4]) + fabs(cf[5]));
-                    return (cf[0] - r >= 0.0) & (cf[0] + r < (double)(n - 1));
-                };
-                double xs = 0.0;
-#pragma unroll
-                for (int n = 0; n < PX; ++n) xs += fabs(xc[n]);
-                lane_safe = (mine || !active) && (fabs(u0r) <= 1.001) && (fabs(u1r) <= 1.001) && (xs <= 1.001) && inside(q.lat, c.ny) && inside(q.lon, c.nx);
-            }
+            if (REGULAR) lane_safe = lane_nocheck(w[(int64_t)WS_U0 * ns], w[(int64_t)WS_U1 * ns], active, mine, q, xc, c.ny, c.nx);
             // ---- f64 cubes: the level's footprint through LDS --------------------------------------------------------------------
             // An f64 cube doubles the bytes of every gather (4 x 32 B per lane and sample): the instantiation is bound by the vector L1's
             // 64 B/clk return path, not by instruction issue (6.8 against 5.0 ms per 16 M rays, round 3).  But the 64 rays of a wave

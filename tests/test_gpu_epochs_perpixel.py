@@ -1,6 +1,6 @@
 """GPU: a time series of weather epochs through ONE ray batch with per-ray origin heights (rdr_raytrace_epochs,
 raider_amd.raytrace_epochs) - a SAR scene on a DEM traced for every date.  Pass 1 runs once, pass 2 marches up to four epochs together
-(march_epochs_pr_kernel); pinned as
+(the per-ray-height loop of march_epochs_kernel); pinned as
   * bit for bit what Cube.raytrace gives per epoch: every group pattern (D = 1 .. 6), f32 and f64 cubes, every input form, conic and
     polar-stereographic cubes, generic rays, the chunked workspace schedule, device arrays;
   * the oracle's per-pixel restatement (oracle_c.build_cube_ray_per_pixel) to 1e-9 m with the same partition.
@@ -308,8 +308,9 @@ def test_refusals(R, scene, cubes32):
 
 
 def test_stacked_kernels_are_loaded_without_scratch(R, cubes32, cubes64):
-    """the resource report of DESIGN 5d, read from the loaded code object: no scratch at the chosen occupancy"""
+    """the resource report of DESIGN "Time series" / 5d, read from the loaded code object: no scratch at the chosen occupancy, in the
+    sliced stacked kernels (4, 5) and the per-ray-height ones (6, 7)"""
     for cubes in (cubes32, cubes64):
-        for which in (6, 7):
+        for which in (4, 5, 6, 7):
             a = cubes[0].ray_kernel_attributes(which)
             assert a['scratch'] == 0 and a['vgpr'] > 0, (which, a)
