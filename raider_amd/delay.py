@@ -169,6 +169,13 @@ def _with_model_crs(cube, model_crs):
     return (cube if same else cube.view(want)), want is not None
 
 
+def _pointwise_cube(cube, model_crs):
+    """The cube a ray trace of THIS call marches through (_with_model_crs), or None when the model is on neither a lon/lat grid nor
+    one the kernels project to (Lambert conformal conic, polar stereographic)."""
+    cube, projected = _with_model_crs(cube, model_crs)
+    return cube if (projected or _is_4326(model_crs)) else None
+
+
 # ------------------------------------------------------------------------------------------------
 # small containers (the AOI / Dataset providers themselves are outside the hot path, SURVEY.md §2 row 9)
 # ------------------------------------------------------------------------------------------------
@@ -348,6 +355,49 @@ def _model_prelude(weather_model_file, aoi, height_levels, zref):
     return var, wm_proj, height_levels, zref
 
 
+# ---- the rules the per-date point branch (_point_branch_on_device) and the series planners share, each written once ---------------
+def _query_points(lats, lons, hgts, out_proj):
+    """The query points of a points AOI (its readLL() and readZ()) in the output CRS, as the arguments of Cube.interp_project /
+    point_delays: three arrays, or one packed [..., 3] array."""
+    # transformPoints(4326 -> 4326) is the identity stack: the three arrays go up as they are
+    return (lats, lons, hgts) if _is_4326(out_proj) else (transformPoints(lats, lons, hgts, 4326, out_proj),)
+
+
+def _slice_budget():
+    """Bytes a batch of height slices may hold on the device (_slice_batches): RAIDER_HIP_SLICE_BUDGET_BYTES, default 8 GiB."""
+    return int(os.environ.get('RAIDER_HIP_SLICE_BUDGET_BYTES', 8 << 30))
+
+
+def _device_takes_grid(xpts, ypts, zpts):
+    """Whether the device routes of a point job take (xpts, ypts, zpts: float64 arrays) as their intermediate grid: 1-D heights, at
+    least 2 nodes per axis, at most 512 heights, axes of at most 100000 nodes in sum, strictly monotonic heights (scipy's grid rule:
+    the host sequence raises what it raises)."""
+    if zpts.ndim != 1 or min(xpts.size, ypts.size, zpts.size) < 2 or zpts.size > 512 or xpts.size + ypts.size + zpts.size > 100000:
+        return False
+    dz = np.diff(zpts)
+    return bool(np.all(dz > 0) or np.all(dz < 0))
+
+
+def _total_cube(weather_model_file, wm_proj, crs):
+    """(the total-delay cube a zenith / projected point job builds its intermediate cube from, `grid` of Cube.point_delays), or None
+    when the output CRS is neither the model's, nor lon/lat, nor a UTM / conic CRS (grid_projection)."""
+    grid = None if (_is_4326(crs) or _same_crs(wm_proj, crs)) else grid_projection(crs)
+    cube = getInterpolators(weather_model_file, 'total')[0].cube
+    if _same_crs(wm_proj, crs) and (cube.projection is None or _is_4326(wm_proj)):
+        cube, _ = _with_model_crs(cube, 4326)                         # grid nodes already in the model's coordinates: nothing to project
+    elif _is_4326(crs):
+        cube, projected = _with_model_crs(cube, wm_proj)
+        if not projected:
+            return None
+    elif grid is not None:                                            # a UTM / conic grid: rdr_point_delays_grid
+        cube, projected = _with_model_crs(cube, 4326 if _is_4326(wm_proj) else wm_proj)
+        if not (projected or _is_4326(wm_proj)):
+            return None
+    else:
+        return None
+    return cube, grid
+
+
 def tropo_delay(datetime, weather_model_file, aoi, los, height_levels=None, out_proj=4326, zref=None):
     """delay.py:35-130: ZTD, projected STD, or ray-traced STD on an AOI.
 
@@ -374,8 +424,7 @@ def tropo_delay(datetime, weather_model_file, aoi, los, height_levels=None, out_
         los.setPoints(lats, lons, hgts)
         proj = los._divisor_source() if hasattr(los, '_divisor_source') else False
     kw = {} if not proj else ({'inc': proj[1]} if proj[0] == 'inc' else {'divisor': proj[1]})
-    # transformPoints(4326 -> 4326) is the identity stack: the three arrays go up as they are
-    pts = (lats, lons, hgts) if _is_4326(out_proj) else (transformPoints(lats, lons, hgts, 4326, out_proj),)
+    pts = _query_points(lats, lons, hgts, out_proj)
     res = _point_branch_on_device(weather_model_file, wm_proj, aoi, height_levels, los, crs, zref, var, pts, kw)
     if res is None:
         # jobs the device route does not take (an output CRS that is neither the model's, nor lon/lat, nor a UTM / conic CRS, a one-node
@@ -448,8 +497,8 @@ def _series_plan(datetime, weather_model_file, aoi, los, height_levels, out_proj
     cube, fields = _cube_of([ifWet, ifHydro])
     if list(fields) != [0, 1]:
         return None
-    cube, projected = _with_model_crs(cube, wm_proj)
-    if not (projected or _is_4326(wm_proj)):
+    cube = _pointwise_cube(cube, wm_proj)
+    if cube is None:
         return None                                                    # (tropo_delay raises NotImplementedError itself)
     if route == 'cube':
         zpts = np.array(height_levels)
@@ -457,10 +506,7 @@ def _series_plan(datetime, weather_model_file, aoi, los, height_levels, out_proj
             return None
     else:
         zpts = np.array(height_levels, dtype=np.float64)
-        if zpts.ndim != 1 or min(xpts.size, ypts.size, zpts.size) < 2 or zpts.size > 512 or xpts.size + ypts.size + zpts.size > 100000:
-            return None
-        dz = np.diff(zpts)
-        if not (np.all(dz > 0) or np.all(dz < 0)):
+        if not _device_takes_grid(xpts, ypts, zpts):
             return None
     return dict(cube=cube, zpts=zpts, zref=zref, xpts=xpts, ypts=ypts, axes=(aoi.xpts, aoi.ypts), src=weather_model_file)
 
@@ -495,36 +541,56 @@ def _stacked_cube(plans, datetimes, los, crs):
     return res
 
 
-def _stacked_points(plans, los, aoi, out_proj):
-    """_point_branch_on_device for every planned date: the intermediate cubes of all dates from one series call, then the gather
-    per date: [(wetDelay, hydroDelay)], or None when the batch does not fit (the dates then go one by one)."""
-    from .engine import raytrace_slices_epochs_to_cubes
-    p0 = plans[0]
-    xpts, ypts, zpts, zref = p0['xpts'], p0['ypts'], p0['zpts'], p0['zref']
-    D = len(plans)
-    if xpts.size * ypts.size * zpts.size * (64 + 16 * D) > int(os.environ.get('RAIDER_HIP_SLICE_BUDGET_BYTES', 8 << 30)):
-        return None
-    lats, lons = aoi.readLL()
-    hgts = aoi.readZ()
-    pts = (lats, lons, hgts) if _is_4326(out_proj) else (transformPoints(lats, lons, hgts, 4326, out_proj),)
-    from ._lib import DeviceOutOfMemory
-    cubes = [p['cube'] for p in plans]
-    try:
-        rays = los.ray_batch_slices(xpts, ypts, zpts, **_ray_crs_kw(out_proj))
-        dcubes, K, _nparts, flags = raytrace_slices_epochs_to_cubes(cubes, rays, zpts, zref, 1000.0)
-    except (MemoryError, RuntimeError) as exc:
-        if not (isinstance(exc, DeviceOutOfMemory) or type(exc).__name__ == 'OutOfMemoryError'):
-            raise
-        logger.info(f'the series did not fit the device in one piece ({exc}); continuing date by date')
-        return None
-    _raise_slice_failures(K, flags[0], zpts, zpts[-1])
-    res = []
-    for dc in dcubes:
-        wet, hyd = dc.interp_project(*pts)
-        if dc.has_nan():
-            logger.critical('There are missing delay values. Check your inputs.')
-        res.append((wet, hyd))
+def _run_series(datetimes, files, aoi, los, height_levels, out_proj, zref, route, plan, run):
+    """The driver of both series entries: [tropo_delay(t, f, aoi, los, height_levels, out_proj, zref) for t, f in zip(datetimes, files)]
+    as a SeriesResult, the dates that can share one library call taken out of the loop.
+    route(aoi, los, out_proj): the entry's stacked route, or None (every date goes per date), looked up for two dates or more: a single
+    date goes per date without it and without a plan;
+    plan(t, f, aoi, los, height_levels, out_proj, zref, route): what that date would hand the stacked call, or None when it goes per date;
+    run(route, plans, datetimes, aoi, los, out_proj): the results of the stacking dates (stacking_dates) in their order, or None when the
+    call does not fit the device.  Planning runs in date order and stops at the first exception: that date raises it again in its own
+    tropo_delay call below, after the dates before it."""
+    datetimes = list(datetimes)
+    files = list(files)
+    if len(datetimes) != len(files):
+        raise ValueError(f'{len(datetimes)} dates but {len(files)} weather model files')
+    route = route(aoi, los, out_proj) if len(files) > 1 else None
+    stacked = {}
+    if route is not None:
+        plans = {}
+        for i, (t, f) in enumerate(zip(datetimes, files)):
+            try:
+                plans[i] = plan(t, f, aoi, los, height_levels, out_proj, zref, route)
+            except Exception:
+                break                                                  # this date raises in its own tropo_delay call, in date order
+        idx = stacking_dates(plans)
+        if idx:
+            try:
+                out = run(route, [plans[i] for i in idx], [datetimes[i] for i in idx], aoi, los, out_proj)
+            except Exception as exc:
+                # what the per-date calls share they raise again below, in date order; a refusal of the stacked call alone must not pass
+                # unseen, so it is logged
+                logger.warning(f'the stacked point series failed ({type(exc).__name__}: {exc}); continuing date by date')
+                out = None
+            if out is not None:
+                stacked = dict(zip(idx, out))
+    res = SeriesResult()
+    res.routes = []
+    for i, (t, f) in enumerate(zip(datetimes, files)):
+        if i in stacked:
+            res.append(stacked[i]); res.routes.append('stacked')
+        else:
+            res.append(tropo_delay(t, f, aoi, los, height_levels, out_proj, zref)); res.routes.append('per-date')
     return res
+
+
+def _run_stacked(route, plans, datetimes, aoi, los, out_proj):
+    """The one stacked call of a route (stacked_route: 'cube' / 'points'; point_series_route: 'delays' / 'rays')."""
+    if route == 'cube':
+        return _stacked_cube(plans, datetimes, los, out_proj)
+    if route == 'delays':
+        return _stacked_point_delays(plans, aoi, out_proj)
+    return _stacked_point_rays(plans, los, aoi, out_proj)
 
 
 def tropo_delay_series(datetimes, weather_model_files, aoi, los, height_levels=None, out_proj=4326, zref=None):
@@ -534,48 +600,11 @@ def tropo_delay_series(datetimes, weather_model_files, aoi, los, height_levels=N
 
     A ray-traced LOS on a lon/lat, UTM or conic output grid (cube AOI) or through the station branch (points AOI) traces every date whose model
     grid matches the first such date's (shape, dtype, axes, CRS) in one library call: pass 1 (ray polynomials, crossings, the slice
-    partition) once, pass 2 for up to four dates together (rdr_raytrace_slices_epochs).  Everything else - zenith and projected lines
-    of sight, the host fallbacks, dates on another grid, a single date - is one tropo_delay per date."""
-    datetimes = list(datetimes)
-    files = list(weather_model_files)
-    if len(datetimes) != len(files):
-        raise ValueError(f'{len(datetimes)} dates but {len(files)} weather model files')
-    route = stacked_route(aoi, los, out_proj) if len(files) > 1 else None
-    stacked = {}
-    if route is not None:
-        plans = {}
-        for i, (t, f) in enumerate(zip(datetimes, files)):
-            try:
-                p = _series_plan(t, f, aoi, los, height_levels, out_proj, zref, route)
-            except Exception:
-                break                                                  # this date raises in its own tropo_delay call, in date order
-            if p is None:
-                continue
-            first = next(iter(plans.values()), None)
-            if first is not None and (epochs_compatible(first['cube'], p['cube']) is not None or not np.array_equal(first['zpts'], p['zpts']) or
-                                      first['zref'] != p['zref']):
-                continue
-            plans[i] = p
-        if len(plans) > 1:
-            idx = sorted(plans)
-            try:
-                if route == 'cube':
-                    out = _stacked_cube([plans[i] for i in idx], [datetimes[i] for i in idx], los, out_proj)
-                else:
-                    out = _stacked_points([plans[i] for i in idx], los, aoi, out_proj)
-            except Exception:
-                out = None                                             # (the per-date calls below raise it again, in date order)
-            if out is not None:
-                stacked = dict(zip(idx, out))
-    res = SeriesResult()
-    routes = []
-    for i, (t, f) in enumerate(zip(datetimes, files)):
-        if i in stacked:
-            res.append(stacked[i]); routes.append('stacked')
-        else:
-            res.append(tropo_delay(t, f, aoi, los, height_levels, out_proj, zref)); routes.append('per-date')
-    res.routes = routes
-    return res
+    partition) once, pass 2 for up to four dates together (rdr_raytrace_slices_epochs); the station branch then gathers all its dates in
+    one pass, exactly as tropo_delay_point_series does (_stacked_point_rays).  Everything else - zenith and projected lines of sight
+    (tropo_delay_point_series stacks those at query points), the host fallbacks, dates on another grid, a single date - is one
+    tropo_delay per date; a stacked call that raises is logged at WARNING level and its dates go per date too."""
+    return _run_series(datetimes, weather_model_files, aoi, los, height_levels, out_proj, zref, stacked_route, _series_plan, _run_stacked)
 
 
 # ---- a date series at query points: every line of sight, one gather pass for all dates ---------------------------------------------
@@ -639,27 +668,10 @@ def _point_series_plan(datetime, weather_model_file, aoi, los, height_levels, ou
     zpts = np.array(height_levels, dtype=np.float64)
     _ensure_output_grid(aoi, src, crs)
     xpts, ypts = np.asarray(aoi.xpts, dtype=np.float64), np.asarray(aoi.ypts, dtype=np.float64)
-    if zpts.ndim != 1 or min(xpts.size, ypts.size, zpts.size) < 2 or zpts.size > 512 or xpts.size + ypts.size + zpts.size > 100000:
+    chosen = _total_cube(src, wm_proj, crs) if _device_takes_grid(xpts, ypts, zpts) else None
+    if chosen is None:
         return None
-    dz = np.diff(zpts)
-    if not (np.all(dz > 0) or np.all(dz < 0)):
-        return None
-    # the cube choice of _point_branch_on_device
-    grid = None if (_is_4326(crs) or _same_crs(wm_proj, crs)) else grid_projection(crs)
-    ifWet, ifHydro = getInterpolators(src, 'total')
-    cube = ifWet.cube
-    if _same_crs(wm_proj, crs) and (cube.projection is None or _is_4326(wm_proj)):
-        cube, _ = _with_model_crs(cube, 4326)
-    elif _is_4326(crs):
-        cube, projected = _with_model_crs(cube, wm_proj)
-        if not projected:
-            return None
-    elif grid is not None:
-        cube, projected = _with_model_crs(cube, 4326 if _is_4326(wm_proj) else wm_proj)
-        if not (projected or _is_4326(wm_proj)):
-            return None
-    else:
-        return None
+    cube, grid = chosen
     gridkey = None if grid is None else (int(grid[0]), np.asarray(grid[1], dtype=np.float64).tobytes())
     return dict(cube=cube, zpts=zpts, zref=zref, xpts=xpts, ypts=ypts, grid=grid, gridkey=gridkey, div=div, divkind=None if div is None else div[0])
 
@@ -679,6 +691,8 @@ def _series_divisor(plans, shape):
 
 
 def _device_oom(exc):
+    """Out of DEVICE memory: RDR_ERR_OOM arrives as _lib.DeviceOutOfMemory (a MemoryError), torch's allocator raises
+    torch.OutOfMemoryError (a RuntimeError)."""
     from ._lib import DeviceOutOfMemory
     return isinstance(exc, DeviceOutOfMemory) or type(exc).__name__ == 'OutOfMemoryError'
 
@@ -689,8 +703,7 @@ def _stacked_point_delays(plans, aoi, out_proj):
     from .engine import point_delays_epochs
     p0 = plans[0]
     lats, lons = aoi.readLL()
-    hgts = aoi.readZ()
-    pts = (lats, lons, hgts) if _is_4326(out_proj) else (transformPoints(lats, lons, hgts, 4326, out_proj),)
+    pts = _query_points(lats, lons, aoi.readZ(), out_proj)
     kw = _series_divisor(plans, np.shape(lats))
     cubes = [p['cube'] for p in plans]
     try:
@@ -713,16 +726,17 @@ def _stacked_point_delays(plans, aoi, out_proj):
 
 
 def _stacked_point_rays(plans, los, aoi, out_proj):
-    """_stacked_points with ONE gather over the D delay cubes (rdr_interp3_project_epochs) instead of one per date."""
+    """The ray-traced point branch (_point_branch_on_device) of every planned date, for both series entries: the intermediate delay
+    cubes of all dates from one series trace, then ONE gather over them (rdr_interp3_project_epochs; measured 3.8 ms of an 85 ms
+    call faster than a gather per date at 8 dates and 10^6 stations, NOTES.md): [(wetDelay, hydroDelay)], or None when the batch does
+    not fit (the dates then go one by one)."""
     from .engine import interp_project_epochs, raytrace_slices_epochs_to_cubes
     p0 = plans[0]
     xpts, ypts, zpts, zref = p0['xpts'], p0['ypts'], p0['zpts'], p0['zref']
     D = len(plans)
-    if xpts.size * ypts.size * zpts.size * (64 + 16 * D) > int(os.environ.get('RAIDER_HIP_SLICE_BUDGET_BYTES', 8 << 30)):
+    if xpts.size * ypts.size * zpts.size * (64 + 16 * D) > _slice_budget():
         return None
-    lats, lons = aoi.readLL()
-    hgts = aoi.readZ()
-    pts = (lats, lons, hgts) if _is_4326(out_proj) else (transformPoints(lats, lons, hgts, 4326, out_proj),)
+    pts = _query_points(*aoi.readLL(), aoi.readZ(), out_proj)
     cubes = [p['cube'] for p in plans]
     try:
         rays = los.ray_batch_slices(xpts, ypts, zpts, **_ray_crs_kw(out_proj))
@@ -755,45 +769,14 @@ def tropo_delay_point_series(datetimes, weather_model_files, aoi, los, height_le
 
     The planning pass runs every date's prelude (file, CRS, heights, zref, the line of sight's setTime / setPoints); a date that then
     goes per date runs it again inside tropo_delay, so its non-critical prelude log lines (a missing CRS, zref forced to the model top)
-    appear twice.  The host arrays of the points take the stacked gather (measured 1.9-2.2 x faster per date)."""
-    datetimes = list(datetimes)
-    files = list(weather_model_files)
-    if len(datetimes) != len(files):
-        raise ValueError(f'{len(datetimes)} dates but {len(files)} weather model files')
-    if _is_cube_aoi(aoi):
+    appear twice.  The host arrays of the points take the stacked gather (measured 1.9-2.2 x faster per date).
+
+    The driver is tropo_delay_series' (_run_series); only the route lookup differs.  A ray-traced line of sight takes the same plan and
+    the same stacked call from either entry."""
+    datetimes, files = list(datetimes), list(weather_model_files)
+    if len(datetimes) == len(files) and _is_cube_aoi(aoi):             # (a count mismatch comes first: the driver raises it)
         raise ValueError('tropo_delay_point_series takes a points AOI; tropo_delay_series takes cube AOIs')
-    route = point_series_route(aoi, los, out_proj) if len(files) > 1 else None
-    stacked = {}
-    if route is not None:
-        plans = {}
-        for i, (t, f) in enumerate(zip(datetimes, files)):
-            try:
-                plans[i] = _point_series_plan(t, f, aoi, los, height_levels, out_proj, zref, route)
-            except Exception:
-                break                                                  # this date raises in its own tropo_delay call, in date order
-        idx = stacking_dates(plans)
-        if idx:
-            try:
-                if route == 'delays':
-                    out = _stacked_point_delays([plans[i] for i in idx], aoi, out_proj)
-                else:
-                    out = _stacked_point_rays([plans[i] for i in idx], los, aoi, out_proj)
-            except Exception as exc:
-                # what the per-date calls share they raise again below, in date order; a refusal of the stacked call alone must not pass
-                # unseen, so it is logged
-                logger.warning(f'the stacked point series failed ({type(exc).__name__}: {exc}); continuing date by date')
-                out = None
-            if out is not None:
-                stacked = dict(zip(idx, out))
-    res = SeriesResult()
-    routes = []
-    for i, (t, f) in enumerate(zip(datetimes, files)):
-        if i in stacked:
-            res.append(stacked[i]); routes.append('stacked')
-        else:
-            res.append(tropo_delay(t, f, aoi, los, height_levels, out_proj, zref)); routes.append('per-date')
-    res.routes = routes
-    return res
+    return _run_series(datetimes, files, aoi, los, height_levels, out_proj, zref, point_series_route, _point_series_plan, _run_stacked)
 
 
 class _Result(list):
@@ -832,8 +815,7 @@ def _slice_batches(xpts, ypts, zpts, bytes_per_ray, trace, what=''):
     8 GiB), at most 512; a batch the device still cannot hold is halved until it fits.  Returns nan_out.any(axis=-1) over all batches:
     what np.isnan(result).any() would find (delay.py:187), per date."""
     n_per = max(1, xpts.size * ypts.size)
-    budget = int(os.environ.get('RAIDER_HIP_SLICE_BUDGET_BYTES', 8 << 30))
-    chunk = int(min(512, max(1, budget // (n_per * bytes_per_ray))))
+    chunk = int(min(512, max(1, _slice_budget() // (n_per * bytes_per_ray))))
     any_nan = False
     s0 = 0
     while s0 < zpts.size:
@@ -842,9 +824,9 @@ def _slice_batches(xpts, ypts, zpts, bytes_per_ray, trace, what=''):
         try:
             K, flags, nan_out = trace(s0, zz)
         except (MemoryError, RuntimeError) as exc:
-            # out of DEVICE memory, told by status / class, not by the wording of a message: RDR_ERR_OOM arrives as
-            # _lib.DeviceOutOfMemory (a MemoryError), torch's allocator raises torch.OutOfMemoryError (a RuntimeError)
-            if chunk == 1 or not (isinstance(exc, MemoryError) or type(exc).__name__ == 'OutOfMemoryError'):
+            # out of DEVICE memory, told by status / class, not by the wording of a message (_device_oom); any other MemoryError
+            # halves the batch as well
+            if chunk == 1 or not (isinstance(exc, MemoryError) or _device_oom(exc)):
                 raise
             chunk = max(1, chunk // 2)                                 # the device could not hold the batch: smaller ones
             logger.info(f'slice batch did not fit the device ({exc}); continuing with {chunk} slices per call')
@@ -883,41 +865,25 @@ def _point_branch_on_device(weather_model_file, wm_proj, aoi, heights, los, crs,
         weather_model_file = _loaded
     _ensure_output_grid(aoi, weather_model_file, crs)
     xpts, ypts = np.asarray(aoi.xpts, dtype=np.float64), np.asarray(aoi.ypts, dtype=np.float64)
-    if zpts.ndim != 1 or min(xpts.size, ypts.size, zpts.size) < 2 or zpts.size > 512 or xpts.size + ypts.size + zpts.size > 100000:
+    if not _device_takes_grid(xpts, ypts, zpts):
         return None
-    dz = np.diff(zpts)
-    if not (np.all(dz > 0) or np.all(dz < 0)):
-        return None                                                    # (scipy's grid rule: the host sequence raises what it raises)
-    from ._lib import DeviceOutOfMemory
-    grid = None if (_is_4326(crs) or _same_crs(wm_proj, crs)) else grid_projection(crs)
     ray_kw = _ray_crs_kw(crs)
     try:
         if los.is_Zenith() or los.is_Projected():
-            ifWet, ifHydro = getInterpolators(weather_model_file, 'total')
-            cube = ifWet.cube
-            if _same_crs(wm_proj, crs) and (cube.projection is None or _is_4326(wm_proj)):
-                cube, _ = _with_model_crs(cube, 4326)                     # grid nodes already in the model's coordinates: nothing to project
-            elif _is_4326(crs):
-                cube, projected = _with_model_crs(cube, wm_proj)
-                if not projected:
-                    return None
-            elif grid is not None:                                        # a UTM / conic grid: rdr_point_delays_grid
-                cube, projected = _with_model_crs(cube, 4326 if _is_4326(wm_proj) else wm_proj)
-                if not (projected or _is_4326(wm_proj)):
-                    return None
-            else:
+            chosen = _total_cube(weather_model_file, wm_proj, crs)
+            if chosen is None:
                 return None
+            cube, grid = chosen
             wet, hyd, has_nan = cube.point_delays(xpts, ypts, zpts, *pts, grid=grid, **kw)
         else:
             if ray_kw is None or not hasattr(los, 'ray_batch_slices'):
                 return None
-            ifWet, ifHydro = getInterpolators(weather_model_file, kind='pointwise')
-            cube, projected = _with_model_crs(ifWet.cube, wm_proj)
-            if not (projected or _is_4326(wm_proj)):
+            cube = _pointwise_cube(getInterpolators(weather_model_file, kind='pointwise')[0].cube, wm_proj)
+            if cube is None:
                 return None
             # the whole intermediate cube in one batch only when it fits the slice budget of _build_cube_ray (64 B per ray and slice on
             # the device next to the 16 B per cell of the cube itself); larger jobs take the chunked host sequence
-            if xpts.size * ypts.size * zpts.size * 80 > int(os.environ.get('RAIDER_HIP_SLICE_BUDGET_BYTES', 8 << 30)):
+            if xpts.size * ypts.size * zpts.size * 80 > _slice_budget():
                 return None
             rays = los.ray_batch_slices(xpts, ypts, zpts, **ray_kw)
             dcube, K, _nparts, flags = cube.raytrace_slices_to_cube(rays, zpts, zref, 1000.0)
@@ -925,10 +891,9 @@ def _point_branch_on_device(weather_model_file, wm_proj, aoi, heights, los, crs,
             wet, hyd = dcube.interp_project(*pts, **kw)
             has_nan = dcube.has_nan()                                      # (asked AFTER the gather: the cube was made without a host synchronisation)
     except (MemoryError, RuntimeError) as exc:
-        # out of DEVICE memory (RDR_ERR_OOM -> _lib.DeviceOutOfMemory, a MemoryError; torch's allocator: torch.OutOfMemoryError, a
-        # RuntimeError): the one-call route holds the whole intermediate cube; the host sequence builds it in chunks that are halved
-        # until they fit (_build_cube_ray), so the job still completes - as it did before the cube stayed on the device
-        if not (isinstance(exc, DeviceOutOfMemory) or type(exc).__name__ == 'OutOfMemoryError'):
+        # out of DEVICE memory: the one-call route holds the whole intermediate cube; the host sequence builds it in chunks that are
+        # halved until they fit (_build_cube_ray), so the job still completes - as it did before the cube stayed on the device
+        if not _device_oom(exc):
             raise
         logger.info(f'the point branch did not fit the device in one piece ({exc}); continuing with the chunked sequence')
         try:
@@ -1020,8 +985,8 @@ def _build_cube_ray(xpts, ypts, zpts, los, model_crs, pts_crs, interpolators, ou
     pass 1 = build_ray's per-level ray lengths reduced to the slice maximum (-> nParts, delay.py:283),
     pass 2 = Newton level intersections + ECEF->geodetic + trilinear gather + trapezoid, per ray."""
     cube, fields = _cube_of(interpolators)
-    cube, projected = _with_model_crs(cube, model_crs)     # (never modifies a shared cube: a view with THIS call's model CRS)
-    if not (projected or _is_4326(model_crs)):
+    cube = _pointwise_cube(cube, model_crs)                # (never modifies a shared cube: a view with THIS call's model CRS)
+    if cube is None:
         raise NotImplementedError('ray tracing needs the weather cube on an EPSG:4326 lat/lon grid, a Lambert-conformal-conic grid '
                                   f'(HRRR) or a polar-stereographic grid (HRRR-AK); got {model_crs!r}')
     xpts = np.asarray(xpts, dtype=np.float64)

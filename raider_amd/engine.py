@@ -27,6 +27,36 @@ def _dev_f64(t, what, numel=None):
     return t
 
 
+def _dev_points(ctx, y, x, z, inc, divisor):
+    """(shape, n) of device-resident query points - three float64 tensors of one shape, or y = one packed [..., 3] - after the checks
+    every point call makes; the call then runs on torch's current stream."""
+    if inc is not None and divisor is not None:
+        raise ValueError('give inc= or divisor=, not both')
+    ctx.adopt_torch_stream(y)
+    if x is None:
+        if y.shape[-1] != 3:
+            raise ValueError(f'The requested sample points xi have dimension {y.shape[-1]} but this RegularGridInterpolator has dimension 3')
+        _dev_f64(y, 'pts')
+        return tuple(y.shape[:-1]), y.numel() // 3
+    n = y.numel()
+    for t, what in ((y, 'y'), (x, 'x'), (z, 'z')):
+        _dev_f64(t, what, n)
+    return tuple(y.shape), n
+
+
+def _delay_outputs(rays, out, lead=()):
+    """(wet, hydro) a ray call writes: `out`, else torch tensors on the rays' device, else page-locked host arrays (large batches:
+    recycled results, _pinned.py) of shape lead + rays.shape (lead: () for one cube, (D,) / (D, S) for a series / its slices)."""
+    if out is not None:
+        return out
+    shape = tuple(lead) + tuple(rays.shape)
+    if rays._torch_device is not None:
+        import torch
+        wet = torch.empty(shape, dtype=torch.float64, device=rays._torch_device)
+        return wet, torch.empty_like(wet)
+    return _pinned.empty(shape), _pinned.empty(shape)
+
+
 class Cube:
     """Both fields of one processed weather model on the GPU, with scipy-RGI semantics.
 
@@ -244,18 +274,7 @@ class Cube:
         if _is_dev(y):
             # device-resident points (three float64 tensors of one shape, or one packed [..., 3]): nothing crosses PCIe, the call is asynchronous
             import torch
-            if inc is not None and divisor is not None:
-                raise ValueError('give inc= or divisor=, not both')
-            self.ctx.adopt_torch_stream(y)
-            if x is None:
-                if y.shape[-1] != 3:
-                    raise ValueError(f'The requested sample points xi have dimension {y.shape[-1]} but this RegularGridInterpolator has dimension 3')
-                shape, n = tuple(y.shape[:-1]), y.numel() // 3
-                _dev_f64(y, 'pts')
-            else:
-                shape, n = tuple(y.shape), y.numel()
-                for t, what in ((y, 'y'), (x, 'x'), (z, 'z')):
-                    _dev_f64(t, what, n)
+            shape, n = _dev_points(self.ctx, y, x, z, inc, divisor)
             mode, parr, inc0 = 0, None, 0.0
             arr = inc if inc is not None else divisor
             if arr is not None:
@@ -435,20 +454,7 @@ class Cube:
         nparts/flags are None when want_nparts is False (fully asynchronous for device arrays).
         A batch with per-ray origin heights (Rays.grid(..., hts=...)) takes ht=None; nparts then has one entry per level of the
         table built for the LOWEST ray (ray_levels(rays.ht_min, zref))."""
-        rays.adopt_stream(self.ctx)
-        ht = rays.table_height(ht)
-        wet, hyd = out if out is not None else rays.empty_outputs()
-        rays.check_outputs(wet, hyd)
-        if want_nparts:
-            K = len(self.ray_levels(ht, zref)[0])
-            nparts = np.zeros(K, dtype=np.int32)
-            flags = C.c_int32()
-            check(self.ctx.lib.rdr_raytrace(self.ctx.handle, self.handle, C.byref(rays.struct), float(ht), float(zref), float(max_seg),
-                                            ptr(wet), ptr(hyd), ptr(nparts), C.byref(flags)), self.ctx.handle)
-            return wet, hyd, nparts, flags.value
-        check(self.ctx.lib.rdr_raytrace(self.ctx.handle, self.handle, C.byref(rays.struct), float(ht), float(zref), float(max_seg),
-                                        ptr(wet), ptr(hyd), None, None), self.ctx.handle)
-        return wet, hyd, None, None
+        return _trace_batch(self, self.ctx.lib.rdr_raytrace, (self.handle,), (), rays, ht, zref, max_seg, out, want_nparts)
 
     def raytrace_slices(self, rays, hts, zref, max_seg=1000.0, out=None, want_partition=True, want_nan=False):
         """The height loop of _build_cube_ray (delay.py:256-323) in one launch pair: every slice hts[s] of the same origins is
@@ -506,20 +512,31 @@ def _partition_outputs(lead, S, ld):
     return np.zeros(S, dtype=np.int32), np.zeros((S, ld), dtype=np.int32), np.zeros(lead + (S,), dtype=np.int32)
 
 
+def _trace_batch(cube, fn, cube_args, lead, rays, ht, zref, max_seg, out, want_nparts):
+    """rdr_raytrace[_epochs] (`fn`, cube arguments `cube_args`; `cube`: the one cube, or the first of the series - its context and
+    level table) on ONE ray batch into outputs of shape lead + rays.shape: (wet, hydro, nparts[K], flags) of pass 1, the last two
+    None when want_nparts is False (fully asynchronous for device arrays)."""
+    ctx = cube.ctx
+    rays.adopt_stream(ctx)
+    ht = rays.table_height(ht)
+    wet, hyd = _delay_outputs(rays, out, lead)
+    rays.check_outputs(wet, hyd, slices=int(np.prod(lead)))
+    args = (ctx.handle, *cube_args, C.byref(rays.struct), float(ht), float(zref), float(max_seg), ptr(wet), ptr(hyd))
+    if not want_nparts:
+        check(fn(*args, None, None), ctx.handle)
+        return wet, hyd, None, None
+    nparts = np.zeros(len(cube.ray_levels(ht, zref)[0]), dtype=np.int32)
+    flags = C.c_int32()
+    check(fn(*args, ptr(nparts), C.byref(flags)), ctx.handle)
+    return wet, hyd, nparts, flags.value
+
+
 def _trace_slices(ctx, fn, cube_args, lead, ld, rays, hts, zref, max_seg, out, want_partition, want_nan):
     """rdr_raytrace_slices[_epochs] (`fn`, cube arguments `cube_args`) into outputs of shape lead + (S,) + rays.shape: `out`, torch
     tensors on the rays' device or page-locked host arrays.  RDR_FLAG_NAN_OUTPUT (np.isnan(result).any() per slice, scanned on the
     device before the download) is reported apart from the partition flags, which stay what rdr_raytrace returns for the slice."""
     S = hts.size
-    shape = lead + (S,) + tuple(rays.shape)
-    if out is not None:
-        wet, hyd = out
-    elif rays._torch_device is not None:
-        import torch
-        wet = torch.empty(shape, dtype=torch.float64, device=rays._torch_device)
-        hyd = torch.empty_like(wet)
-    else:
-        wet = _pinned.empty(shape); hyd = _pinned.empty(shape)
+    wet, hyd = _delay_outputs(rays, out, lead + (S,))
     rays.check_outputs(wet, hyd, slices=S * int(np.prod(lead)))
     args = (ctx.handle, *cube_args, C.byref(rays.struct), ptr(hts), S, int(rays.slices > 0), float(zref), float(max_seg), ptr(wet), ptr(hyd))
     if not want_partition:
@@ -543,14 +560,19 @@ def _trace_slices_to_cubes(ctx, fn, cube_args, lead, ld, rays, hts, zref, max_se
     return [Cube._from_handle(ctx, C.c_void_p(h)) for h in hs], K, nparts, flags
 
 
-def _epoch_args(cubes, rays, hts):
-    """(cubes, ctx, (C array of handles, D), hts) of a time-series call; the cubes' compatibility is checked by the library."""
+def _series_cubes(cubes, none='a series needs at least one epoch cube'):
+    """(cubes as a list, their context, C array of their handles) of a series call; the cubes' compatibility is checked by the library."""
     cubes = list(cubes)
     if not cubes:
-        raise ValueError('a series needs at least one epoch cube')
-    ctx = cubes[0].ctx
+        raise ValueError(none)
+    return cubes, cubes[0].ctx, (C.c_void_p * len(cubes))(*[c.handle for c in cubes])
+
+
+def _epoch_args(cubes, rays, hts):
+    """(cubes, ctx, (C array of handles, D), hts) of a sliced time-series call."""
+    cubes, ctx, handles = _series_cubes(cubes)
     hts = _slice_heights(ctx, rays, hts, 'per-ray heights (rays.hts) are not supported in a series')
-    return cubes, ctx, ((C.c_void_p * len(cubes))(*[c.handle for c in cubes]), len(cubes)), hts
+    return cubes, ctx, (handles, len(cubes)), hts
 
 
 def raytrace_slices_epochs(cubes, rays, hts, zref, max_seg=1000.0, out=None, want_partition=True, want_nan=False):
@@ -578,34 +600,10 @@ def raytrace_epochs(cubes, rays, ht, zref, max_seg=1000.0, out=None, want_nparts
     date.  Pass 1 runs once, pass 2 marches up to four epochs together; epoch e's delays are bit for bit
     cubes[e].raytrace(rays, ht, zref)'s.  Returns (wet[D, ...], hydro[D, ...], nparts[K], flags) - nparts and flags belong to pass
     1 and are shared by every epoch; they are None when want_nparts is False (fully asynchronous for device arrays)."""
-    cubes = list(cubes)
-    if not cubes:
-        raise ValueError('raytrace_epochs needs at least one epoch cube')
+    cubes, ctx, handles = _series_cubes(cubes, 'raytrace_epochs needs at least one epoch cube')
     if rays.slices > 0:
         raise ValueError('raytrace_epochs takes ONE batch: these rays carry look vectors for height slices (use raytrace_slices_epochs)')
-    ctx = cubes[0].ctx
-    rays.adopt_stream(ctx)
-    ht = rays.table_height(ht)
-    D = len(cubes)
-    shape = (D,) + tuple(rays.shape)
-    if out is not None:
-        wet, hyd = out
-    elif rays._torch_device is not None:
-        import torch
-        wet = torch.empty(shape, dtype=torch.float64, device=rays._torch_device)
-        hyd = torch.empty_like(wet)
-    else:
-        wet = _pinned.empty(shape); hyd = _pinned.empty(shape)
-    rays.check_outputs(wet, hyd, slices=D)
-    handles = (C.c_void_p * D)(*[c.handle for c in cubes])
-    args = (ctx.handle, handles, D, C.byref(rays.struct), float(ht), float(zref), float(max_seg), ptr(wet), ptr(hyd))
-    if not want_nparts:
-        check(ctx.lib.rdr_raytrace_epochs(*args, None, None), ctx.handle)
-        return wet, hyd, None, None
-    nparts = np.zeros(len(cubes[0].ray_levels(ht, zref)[0]), dtype=np.int32)
-    flags = C.c_int32()
-    check(ctx.lib.rdr_raytrace_epochs(*args, ptr(nparts), C.byref(flags)), ctx.handle)
-    return wet, hyd, nparts, flags.value
+    return _trace_batch(cubes[0], ctx.lib.rdr_raytrace_epochs, (handles, len(cubes)), (len(cubes),), rays, ht, zref, max_seg, out, want_nparts)
 
 
 def _series_proj_args(D, n, shape, inc, divisor):
@@ -627,13 +625,6 @@ def _series_proj_args(D, n, shape, inc, divisor):
     return mode, f64(np.broadcast_to(a, shape)).reshape(-1), 0, 0.0
 
 
-def _series_cubes(cubes):
-    cubes = list(cubes)
-    if not cubes:
-        raise ValueError('a series needs at least one epoch cube')
-    return cubes, cubes[0].ctx, (C.c_void_p * len(cubes))(*[c.handle for c in cubes])
-
-
 def interp_project_epochs(cubes, y, x=None, z=None, inc=None, divisor=None):
     """Cube.interp_project at ONE point set on D cubes of one grid (same shape, dtype, axes and projection) - a date series at
     stations or pixels - in one call (rdr_interp3_project_epochs): the points go up once, the cell search and the weights are made
@@ -646,18 +637,7 @@ def interp_project_epochs(cubes, y, x=None, z=None, inc=None, divisor=None):
     D = len(cubes)
     if _is_dev(y):
         import torch
-        if inc is not None and divisor is not None:
-            raise ValueError('give inc= or divisor=, not both')
-        ctx.adopt_torch_stream(y)
-        if x is None:
-            if y.shape[-1] != 3:
-                raise ValueError(f'The requested sample points xi have dimension {y.shape[-1]} but this RegularGridInterpolator has dimension 3')
-            shape, n = tuple(y.shape[:-1]), y.numel() // 3
-            _dev_f64(y, 'pts')
-        else:
-            shape, n = tuple(y.shape), y.numel()
-            for t, what in ((y, 'y'), (x, 'x'), (z, 'z')):
-                _dev_f64(t, what, n)
+        shape, n = _dev_points(ctx, y, x, z, inc, divisor)
         arr = inc if inc is not None else divisor
         if arr is not None and _is_dev(arr):
             mode, inc0 = (1 if inc is not None else 3), 0.0
@@ -906,11 +886,7 @@ class Rays:
             ctx.set_stream(-1)
 
     def empty_outputs(self):
-        if self._torch_device is not None:
-            import torch
-            return (torch.empty(self.shape, dtype=torch.float64, device=self._torch_device),
-                    torch.empty(self.shape, dtype=torch.float64, device=self._torch_device))
-        return _pinned.empty(tuple(self.shape)), _pinned.empty(tuple(self.shape))       # (large batches: recycled page-locked results)
+        return _delay_outputs(self, None)
 
     def look_vectors(self, ctx=None):
         ctx = ctx or Context.default()

@@ -213,7 +213,18 @@ def test_stations_take_the_stacked_route(caplog):
     rng = np.random.default_rng(3)
     la = rng.uniform(32.0, 34.0, 300); lo = rng.uniform(-119.0, -116.0, 300); hg = rng.uniform(0.0, 900.0, 300)
     xp = np.linspace(-119.5, -115.5, 31); yp = np.linspace(34.5, 31.5, 27)
-    _series_vs_loop(files, lambda: PointsAOI(la, lo, hg, xp, yp), Raytracing(inc=39.0, heading=-167.9), [0.0, 500.0, 1500.0, 3000.0], caplog)
+    los, hl = Raytracing(inc=39.0, heading=-167.9), [0.0, 500.0, 1500.0, 3000.0]
+    ser = _series_vs_loop(files, lambda: PointsAOI(la, lo, hg, xp, yp), los, hl, caplog)
+    # tropo_delay_point_series runs the same stacked call (_stacked_point_rays): the same bytes per date - the NaNs of the holed date
+    # where they are - and the same routes
+    from raider_amd.delay import tropo_delay_point_series
+    dates = [dt.datetime(2020, 1, 1) + dt.timedelta(days=12 * i) for i in range(len(files))]
+    pser = tropo_delay_point_series(dates, files, PointsAOI(la, lo, hg, xp, yp), los, hl)
+    assert len(pser) == len(ser) == 4 and pser.routes == ser.routes
+    for a, b in zip(ser, pser):
+        for u, v in zip(a, b):
+            u, v = np.asarray(u), np.asarray(v)
+            assert u.shape == v.shape == (300,) and u.dtype == v.dtype == np.float64 and u.tobytes() == v.tobytes()
 
 
 def test_fallbacks_route_per_date(caplog):

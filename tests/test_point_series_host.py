@@ -114,3 +114,100 @@ def test_the_cube_series_routes_have_not_moved():
                 assert series_route(aoi, los, crs) is None and stacked_route(aoi, los, crs) is None
     assert series_route(grid, ray, 4326) == 'cube' and series_route(pts, ray, 4326) == 'points' and series_route(grid, ray, 32611) is None
     assert stacked_route(grid, ray, 32611) == 'cube' and stacked_route(pts, ray, LCC) == 'points' and stacked_route(pts, ray, OBLIQUE) is None
+
+
+def test_the_shared_series_driver(monkeypatch, caplog):
+    """_run_series, the skeleton under tropo_delay_series and tropo_delay_point_series, with stub planners and stacked calls: which
+    dates are planned, which stack, and that everything else - a failed stacked call included - is one tropo_delay per date, in date
+    order."""
+    import logging
+    from raider_amd import delay as D
+    events = []
+
+    def fake_tropo_delay(t, f, aoi, los, height_levels=None, out_proj=4326, zref=None):
+        events.append(('tropo_delay', t))
+        if isinstance(f, Exception):
+            raise f
+        return 'per-date', t
+    monkeypatch.setattr(D, 'tropo_delay', fake_tropo_delay)
+
+    def drive(files, run='ok', route='rays'):
+        """files: per date a plan dict, None (the route refuses the date) or an exception (its prelude raises)"""
+        def plan(t, f, aoi, los, height_levels, out_proj, zref, r):
+            assert (aoi, los, height_levels, out_proj, zref, r) == ('aoi', 'los', 'hl', 4326, 'zref', route)
+            events.append(('plan', t))
+            if isinstance(f, Exception):
+                raise f
+            return f
+
+        def stacked_call(r, plans, dates, aoi, los, out_proj):
+            assert (r, aoi, los, out_proj) == (route, 'aoi', 'los', 4326) and plans == [files[t] for t in dates]
+            events.append(('run', list(dates)))
+            if isinstance(run, Exception):
+                raise run
+            return None if run is None else [('stacked', t) for t in dates]
+        del events[:]
+        return D._run_series(range(len(files)), files, 'aoi', 'los', 'hl', 4326, 'zref', lambda aoi, los, out_proj: route, plan, stacked_call)
+
+    def per_date(ts):
+        return [('tropo_delay', t) for t in ts]
+
+    def plans(ts):
+        return [('plan', t) for t in ts]
+
+    for n_dates, n_files in ((2, 1), (0, 3)):                          # the text both entries raise today
+        with pytest.raises(ValueError, match=f'^{n_dates} dates but {n_files} weather model files$'):
+            D._run_series(range(n_dates), ['f'] * n_files, 'aoi', 'los', 'hl', 4326, 'zref', lambda *a: 'rays', None, None)
+    # a single date, or no stacked route: per date, nothing is planned - and for a single date (or none) the route is not even looked up
+    res = drive([_plan()])
+    assert isinstance(res, D.SeriesResult) and res == [('per-date', 0)] and res.routes == ['per-date'] and events == per_date([0])
+    for n in (0, 1):
+        res = D._run_series(range(n), ['f'] * n, 'aoi', 'los', 'hl', 4326, 'zref', lambda *a: 1 / 0, None, None)
+        assert res == [('per-date', t) for t in range(n)] and res.routes == ['per-date'] * n
+    res = drive([_plan(), _plan()], route=None)
+    assert res == [('per-date', 0), ('per-date', 1)] and res.routes == ['per-date'] * 2 and events == per_date([0, 1])
+    # every plan agrees: one stacked call, tropo_delay is never called
+    res = drive([_plan(), _plan(), _plan()])
+    assert res == [('stacked', 0), ('stacked', 1), ('stacked', 2)] and res.routes == ['stacked'] * 3
+    assert events == plans([0, 1, 2]) + [('run', [0, 1, 2])]
+    # a date the route refuses and one that disagrees with the first planned date go per date, the rest stack; results in date order
+    res = drive([_plan(), None, _plan(zref=14000.0), _plan()])
+    assert res == [('stacked', 0), ('per-date', 1), ('per-date', 2), ('stacked', 3)]
+    assert res.routes == ['stacked', 'per-date', 'per-date', 'stacked']
+    assert events == plans([0, 1, 2, 3]) + [('run', [0, 3])] + per_date([1, 2])
+    res = drive([_plan(), _plan(_cube(z0=1.0))])                        # fewer than two agree: no stacked call at all
+    assert res.routes == ['per-date'] * 2 and events == plans([0, 1]) + per_date([0, 1])
+    # the plan of date 2 raises: planning stops there, dates 0 and 1 still stack, and date 2's exception comes out of ITS tropo_delay
+    # call - after the stacked call, and before date 3 is touched at all
+    boom = KeyError('wet_total')
+    with pytest.raises(KeyError) as exc:
+        drive([_plan(), _plan(), boom, _plan()])
+    assert exc.value is boom
+    assert events == plans([0, 1, 2]) + [('run', [0, 1])] + per_date([2])
+    with pytest.raises(KeyError):                                      # ... and after the per-date dates before it, in date order
+        drive([_plan(), None, _plan(), boom])
+    assert events == plans([0, 1, 2, 3]) + [('run', [0, 2])] + per_date([1, 3])
+    with pytest.raises(KeyError):                                      # fewer than two planned before it: nothing stacks
+        drive([_plan(), boom, _plan()])
+    assert events == plans([0, 1]) + per_date([0, 1])
+    # a date whose plan raised but whose tropo_delay call then succeeds is a per-date result like any other, and so are the dates after it
+    flaky = RuntimeError('only while planning')
+    files = [_plan(), _plan(), flaky, _plan()]
+    monkeypatch.setattr(D, 'tropo_delay', lambda t, f, *a, **k: events.append(('tropo_delay', t)) or ('per-date', t))
+    res = drive(files)
+    assert res == [('stacked', 0), ('stacked', 1), ('per-date', 2), ('per-date', 3)] and res.routes == ['stacked', 'stacked', 'per-date', 'per-date']
+    assert events == plans([0, 1, 2]) + [('run', [0, 1])] + per_date([2, 3])
+    # the stacked call does not fit (None): every date goes per date, silently
+    with caplog.at_level(logging.WARNING, logger=D.logger.name):
+        caplog.clear()
+        res = drive([_plan(), _plan(), _plan()], run=None)
+        assert res == [('per-date', t) for t in range(3)] and res.routes == ['per-date'] * 3
+        assert events == plans([0, 1, 2]) + [('run', [0, 1, 2])] + per_date([0, 1, 2])
+        assert [r for r in caplog.records if r.levelno >= logging.WARNING] == []
+        # the stacked call raises: the same fallback, and ONE warning that names the exception
+        res = drive([_plan(), _plan(), _plan()], run=ValueError('geo2rdr did not converge'))
+        assert res == [('per-date', t) for t in range(3)] and res.routes == ['per-date'] * 3
+        assert events == plans([0, 1, 2]) + [('run', [0, 1, 2])] + per_date([0, 1, 2])
+        warned = [r for r in caplog.records if r.levelno >= logging.WARNING]
+        assert len(warned) == 1 and warned[0].levelno == logging.WARNING
+        assert warned[0].getMessage() == 'the stacked point series failed (ValueError: geo2rdr did not converge); continuing date by date'
