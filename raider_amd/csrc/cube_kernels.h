@@ -785,6 +785,9 @@ __global__ __launch_bounds__(256) void build_cube_kernel(const T2* __restrict__ 
                     emit(std::false_type{}, kb + u, v[u]);
                 }
             }
+            // every wave has read this tile's s_fp before thread 0 resets it for the next one (a staged tile has its round barrier in
+            // between; here a late wave could see fy0 / fx0 reset, ncol wrap into (0, BUILD_NCOL_MAX] and take the staged branch alone)
+            __syncthreads();
         }
     }
 }
