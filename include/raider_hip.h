@@ -41,6 +41,7 @@ extern "C" {
 
 #define RDR_F32 0
 #define RDR_F64 1
+#define RDR_I16 2 /* int16 elements: rasters only (rdr_raster_sample / rdr_raster_bounds; a DEM in its file type) */
 #define RDR_BYTESWAPPED 0x100 /* or-ed into the dtype of rdr_cube_create: the source fields are in the OTHER byte order than the host
                                * (a NetCDF-3 file is big-endian) - swapped on the device while packing, so a file mapping is uploaded as is */
 #define RDR_HOST 0
@@ -545,6 +546,23 @@ int rdr_interp_along_axis(rdr_ctx* ctx, const double* points, const double* valu
 int64_t rdr_make_points_count(double max_len, double step);
 int rdr_make_points(rdr_ctx* ctx, double max_len, const double* sp, const double* slv, int64_t nrays,
                     double step, double* out, int loc);
+
+/* ---- georeferenced rasters: AOI bounds and DEM heights (llreader.py, interpolator.py:133-184) -----------------------------------
+ * rdr_raster_sample = interpolateDEM / interpolate_elevation: a north-up raster[height][width] of dtype RDR_I16 / RDR_F32 / RDR_F64
+ * with GDAL geotransform gt6 (HOST; gt6[2] == gt6[4] == 0, gt6[1] and gt6[5] non-zero of either sign) sampled at (x[i], y[i]) in the
+ * raster's CRS.  method 0 = nearest: the pixel whose cell holds the point, col = floor((x - gt0) / gt1), row = floor((y - gt3) / gt5)
+ * in f64 - rasterio.transform.rowcol's default (interpolator.py:173); NaN where row / col fall outside or a coordinate is NaN.
+ * method 1 = bilinear on pixel-centre coordinates (da_dem.interp(y=, x=), interpolator.py:149) with scipy's cell rule and sum
+ * order; NaN outside the hull of the centres, the last centre inside; needs two pixels per axis.  has_nodata: a raster value equal
+ * to `nodata` counts as NaN (the reference passes no-data values through: has_nodata = 0).  raster, x, y and out live at `loc`.
+ * RDR_ERR_INVALID: NULL, height / width / n <= 0, an unknown dtype / method / loc, a rotated or degenerate geotransform. */
+int rdr_raster_sample(rdr_ctx* ctx, const void* raster, int dtype, int64_t height, int64_t width, const double* gt6, const double* x,
+                      const double* y, int64_t n, int method, int has_nodata, double nodata, double* out, int loc);
+/* The statistics bounds_from_latlon_rasters takes from rio_stats (llreader.py:397-420, utilFcns.py:213-241) for one raster or two of
+ * equal length (b may be NULL) in one pass: out6 = {min a, max a, valid a, min b, max b, valid b}, valid = elements that are neither
+ * NaN nor (has_nodata) equal to `nodata`, as a double; min / max are NaN where valid is 0 (and for a NULL b).  Minima and maxima are
+ * exact and no floating-point atomics are used: the same bytes on every run.  a, b and out6 live at `loc`. */
+int rdr_raster_bounds(rdr_ctx* ctx, const void* a, const void* b, int dtype, int64_t n, int has_nodata, double nodata, double* out6, int loc);
 
 #ifdef __cplusplus
 }

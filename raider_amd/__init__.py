@@ -9,5 +9,6 @@ __version__ = '0.1.0'
 from ._lib import Context, NoLevels, load as load_library  # noqa: F401
 from .engine import (Cube, Rays, grid_geodetic, interp_project_epochs, nparts_from_maxlen, point_delays_epochs, raytrace_epochs,  # noqa: F401
                      raytrace_slices_epochs, raytrace_slices_epochs_to_cubes)
+from .llreader import AOI, BoundingBox, GeocodedFile, Geocube, RasterRDR, StationFile, bounds_from_csv, bounds_from_latlon_rasters  # noqa: F401
 from .time_interp import (DatetimeFailed, NoWeatherModelData, WrongNumberOfFiles, combine_weather_files, get_dt, get_nearest_wmtimes,  # noqa: F401
                           get_weights_time_interp, getWeatherFile, round_date, round_time, tropo_delay_interp, tropo_delay_interp_series)

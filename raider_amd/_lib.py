@@ -15,7 +15,8 @@ LIB_PATH = Path(os.environ.get('RAIDER_HIP_LIB', _HERE / 'libraider_hip.so'))
 
 RDR_OK = 0
 RDR_ERR_INVALID, RDR_ERR_HIP, RDR_ERR_NODEVICE, RDR_ERR_ALL_NAN, RDR_ERR_NO_LEVELS, RDR_ERR_NAN_LENGTH, RDR_ERR_OOM = -1, -2, -3, -4, -5, -6, -7
-RDR_F32, RDR_F64 = 0, 1
+RDR_F32, RDR_F64, RDR_I16 = 0, 1, 2
+RASTER_NEAREST, RASTER_LINEAR = 0, 1
 RDR_BYTESWAPPED = 0x100
 RDR_HOST, RDR_DEVICE = 0, 1
 ORIGIN_GRID, ORIGIN_LLH, ORIGIN_XYZ = 0, 1, 2
@@ -145,6 +146,8 @@ SYMBOLS = [
     ('rdr_interp_along_axis', C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, C.c_int, C.c_double, _VP, C.c_int]),
     ('rdr_make_points_count', C.c_int64, [C.c_double, C.c_double]),
     ('rdr_make_points', C.c_int, [_VP, C.c_double, _VP, _VP, C.c_int64, C.c_double, _VP, C.c_int]),
+    ('rdr_raster_sample', C.c_int, [_VP, _VP, C.c_int, C.c_int64, C.c_int64, _VP, _VP, _VP, C.c_int64, C.c_int, C.c_int, C.c_double, _VP, C.c_int]),
+    ('rdr_raster_bounds', C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int64, C.c_int, C.c_double, _VP, C.c_int]),
 ]
 
 

@@ -335,6 +335,7 @@ static hipError_t launch_lds(void (*kern)(KArgs...), dim3 g, dim3 b, size_t sm, 
 #include "native_kernels.h"
 #include "proj_kernels.h"
 #include "epoch_kernels.h"
+#include "raster_kernels.h"
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -3408,3 +3409,80 @@ int rdr_make_points(rdr_ctx* c, double max_len, const double* sp, const double* 
     return RDR_OK;
 }
 
+
+// ---- georeferenced rasters (raster_kernels.h): DEM sampling and lat / lon raster bounds ---------------------------------------------
+static int raster_elem_size(int dtype) { return dtype == RDR_I16 ? 2 : dtype == RDR_F32 ? 4 : dtype == RDR_F64 ? 8 : 0; }
+
+template <typename T>
+static void launch_raster_sample(rdr_ctx* c, int method, const void* raster, const RasterGeo& g, const double* x, const double* y, int64_t n,
+                                 int has_nodata, double nodata, double* out) {
+    const dim3 G(grid_for(n, 256, c->num_cus * 8)), B(256);
+    KTimer t(c, 2);
+    if (method == RASTER_NEAREST)
+        hipLaunchKernelGGL((raster_sample_kernel<T, RASTER_NEAREST>), G, B, 0, c->stream, (const T*)raster, g, x, y, n, has_nodata, nodata, out);
+    else
+        hipLaunchKernelGGL((raster_sample_kernel<T, RASTER_LINEAR>), G, B, 0, c->stream, (const T*)raster, g, x, y, n, has_nodata, nodata, out);
+}
+
+int rdr_raster_sample(rdr_ctx* c, const void* raster, int dtype, int64_t height, int64_t width, const double* gt6, const double* x,
+                      const double* y, int64_t n, int method, int has_nodata, double nodata, double* out, int loc) {
+    if (!c || !raster || !gt6 || !x || !y || !out) return fail(c, RDR_ERR_INVALID, "rdr_raster_sample: NULL argument");
+    const int esize = raster_elem_size(dtype);
+    if (!esize) return fail(c, RDR_ERR_INVALID, "rdr_raster_sample: dtype must be RDR_I16, RDR_F32 or RDR_F64");
+    if (height <= 0 || width <= 0 || height > ((int64_t)1 << 31) || width > ((int64_t)1 << 31) || height * width > ((int64_t)1 << 40))
+        return fail(c, RDR_ERR_INVALID, "rdr_raster_sample: the raster needs positive sizes (at most 2^40 pixels)");
+    if (n <= 0) return fail(c, RDR_ERR_INVALID, "rdr_raster_sample: the point count must be positive");
+    if (method != RASTER_NEAREST && method != RASTER_LINEAR) return fail(c, RDR_ERR_INVALID, "rdr_raster_sample: method must be 0 (nearest) or 1 (linear)");
+    if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, "rdr_raster_sample: loc must be RDR_HOST or RDR_DEVICE");
+    for (int i = 0; i < 6; ++i)
+        if (!std::isfinite(gt6[i])) return fail(c, RDR_ERR_INVALID, "rdr_raster_sample: the geotransform is not finite");
+    if (gt6[1] == 0.0 || gt6[5] == 0.0) return fail(c, RDR_ERR_INVALID, "rdr_raster_sample: the geotransform has a zero pixel size");
+    if (gt6[2] != 0.0 || gt6[4] != 0.0) return fail(c, RDR_ERR_INVALID, "rdr_raster_sample: rotated geotransforms are not supported (north-up rasters only)");
+    if (method == RASTER_LINEAR && (height < 2 || width < 2)) return fail(c, RDR_ERR_INVALID, "rdr_raster_sample: linear sampling needs two pixels per axis");
+    HIPCHECK(c, hipSetDevice(c->device));
+    const RasterGeo g{height, width, gt6[0], gt6[1], gt6[3], gt6[5]};
+    const void *dr, *dx, *dy; void* dout;
+    int rc = stage_in(c, SLOT_IN0, raster, (size_t)(height * width) * esize, loc, &dr); if (rc) return rc;
+    rc = stage_in(c, SLOT_IN1, x, (size_t)n * 8, loc, &dx); if (rc) return rc;
+    rc = stage_in(c, SLOT_IN2, y, (size_t)n * 8, loc, &dy); if (rc) return rc;
+    rc = stage_out(c, SLOT_OUT0, out, (size_t)n * 8, loc, &dout); if (rc) return rc;
+    if (dtype == RDR_I16) launch_raster_sample<int16_t>(c, method, dr, g, (const double*)dx, (const double*)dy, n, has_nodata != 0, nodata, (double*)dout);
+    else if (dtype == RDR_F32) launch_raster_sample<float>(c, method, dr, g, (const double*)dx, (const double*)dy, n, has_nodata != 0, nodata, (double*)dout);
+    else launch_raster_sample<double>(c, method, dr, g, (const double*)dx, (const double*)dy, n, has_nodata != 0, nodata, (double*)dout);
+    HIPCHECK(c, hipGetLastError());
+    rc = finish_out(c, out, dout, (size_t)n * 8, loc); if (rc) return rc;
+    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return RDR_OK;
+}
+
+template <typename T>
+static void launch_raster_bounds(rdr_ctx* c, int grid, const void* a, const void* b, int64_t n, int has_nodata, double nodata, double* partial) {
+    hipLaunchKernelGGL(raster_bounds_kernel<T>, dim3(grid), dim3(256), 0, c->stream, (const T*)a, (const T*)b, n, has_nodata, nodata, partial);
+}
+
+int rdr_raster_bounds(rdr_ctx* c, const void* a, const void* b, int dtype, int64_t n, int has_nodata, double nodata, double* out6, int loc) {
+    if (!c || !a || !out6) return fail(c, RDR_ERR_INVALID, "rdr_raster_bounds: NULL argument");
+    const int esize = raster_elem_size(dtype);
+    if (!esize) return fail(c, RDR_ERR_INVALID, "rdr_raster_bounds: dtype must be RDR_I16, RDR_F32 or RDR_F64");
+    if (n <= 0 || n > ((int64_t)1 << 40)) return fail(c, RDR_ERR_INVALID, "rdr_raster_bounds: the element count must be positive (at most 2^40)");
+    if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, "rdr_raster_bounds: loc must be RDR_HOST or RDR_DEVICE");
+    HIPCHECK(c, hipSetDevice(c->device));
+    const void *da, *db; void *dpart, *dout;
+    int rc = stage_in(c, SLOT_IN0, a, (size_t)n * esize, loc, &da); if (rc) return rc;
+    rc = stage_in(c, SLOT_IN1, b, (size_t)n * esize, loc, &db); if (rc) return rc;
+    // one lane takes 16 bytes per step; the grid is sized from the compute-unit count and strides over the rest
+    const int grid = grid_for((n * esize + 15) / 16, 256, c->num_cus * 8);
+    rc = ensure(c, SLOT_AUX, (size_t)grid * 6 * 8, &dpart); if (rc) return rc;
+    rc = stage_out(c, SLOT_OUT0, out6, 6 * 8, loc, &dout); if (rc) return rc;
+    {
+        KTimer t(c, 3);
+        if (dtype == RDR_I16) launch_raster_bounds<int16_t>(c, grid, da, db, n, has_nodata != 0, nodata, (double*)dpart);
+        else if (dtype == RDR_F32) launch_raster_bounds<float>(c, grid, da, db, n, has_nodata != 0, nodata, (double*)dpart);
+        else launch_raster_bounds<double>(c, grid, da, db, n, has_nodata != 0, nodata, (double*)dpart);
+        hipLaunchKernelGGL(raster_bounds_final_kernel, dim3(1), dim3(256), 0, c->stream, (const double*)dpart, grid, (double*)dout);
+    }
+    HIPCHECK(c, hipGetLastError());
+    rc = finish_out(c, out6, dout, 6 * 8, loc); if (rc) return rc;
+    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return RDR_OK;
+}

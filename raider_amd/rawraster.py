@@ -11,7 +11,9 @@ ISCE's products is a headerless binary array described by a side-car:
 
 `rio_open` prefers `<file>.vrt` when it exists; so does this reader.  GeoTIFF, NetCDF sub-datasets and everything else GDAL
 reads are NOT handled here (rasterio is used for them when it is installed).  Returns what rasterio returns: `read()` gives
-(bands, rows, cols) in the file's element type; `profile` carries width / height / count / dtype / nodata."""
+(bands, rows, cols) in the file's element type; `profile` carries width / height / count / dtype / nodata and, where the side-car
+names them, `transform` (GDAL's six numbers, from the VRT's <GeoTransform> or the ENVI header's `map info`) and `crs` (an EPSG code or a
+PROJ-style dict, from the VRT's <SRS> or the `map info` datum / UTM zone); a raster without either keeps None."""
 import re
 import xml.etree.ElementTree as ET
 from pathlib import Path
@@ -47,6 +49,54 @@ def _envi_header(path):
     nd = kv.get('data ignore value')
     meta['nodata'] = float(nd) if nd not in (None, '') else None
     return meta
+
+
+def _envi_georef(hdr_path):
+    """(geotransform, crs) of an ENVI header's `map info = {projection, tie x, tie y, easting, northing, dx, dy, ...}` - geographic
+    lat/lon and UTM, the two spellings write_envi writes (the tie pixel is 1-based; rows run southwards); (None, None) without one."""
+    txt = re.sub(r'\{[^}]*\}', lambda m: m.group(0).replace('\n', ' '), Path(hdr_path).read_text(errors='replace'))
+    m = re.search(r'^\s*map info\s*=\s*\{([^}]*)\}', txt, flags=re.M | re.I)
+    if not m:
+        return None, None
+    f = [t.strip() for t in m.group(1).split(',')]
+    try:
+        px, py, x0, y0, dx, dy = (float(t) for t in f[1:7])
+    except ValueError:
+        return None, None
+    gt = (x0 if px == 1.0 else x0 - (px - 1.0) * dx, dx, 0.0, y0 if py == 1.0 else y0 + (py - 1.0) * dy, 0.0, -dy)
+    kind = f[0].lower()
+    crs = None
+    if kind.startswith('geographic'):
+        crs = 4326
+    elif kind == 'utm' and len(f) >= 9 and f[7].isdigit():
+        crs = (32700 if f[8].lower().startswith('s') else 32600) + int(f[7])
+    return gt, crs
+
+
+def _vrt_georef(vrt_path):
+    """(geotransform, crs) of a VRT's <GeoTransform> / <SRS> elements; None where the element is absent."""
+    try:
+        root = ET.parse(vrt_path).getroot()
+    except ET.ParseError:
+        return None, None
+    gt = crs = None
+    txt = root.findtext('GeoTransform')
+    if txt:
+        vals = tuple(float(t) for t in txt.split(','))
+        if len(vals) == 6:
+            gt = vals
+    srs = (root.findtext('SRS') or '').strip()
+    if srs:
+        m = re.fullmatch(r'EPSG:(\d+)', srs, flags=re.I)
+        if m:
+            crs = int(m.group(1))
+        else:
+            from .crs import crs_from_wkt
+            try:
+                crs = crs_from_wkt(srs)
+            except ValueError:
+                crs = srs
+    return gt, crs
 
 
 def _read_envi(data_path, hdr_path):
@@ -149,18 +199,19 @@ class RawRaster:
         path = Path(path)
         if not path.exists():
             raise FileNotFoundError(f'{path}: No such file or directory')
-        if path.suffix.lower() == '.vrt':
-            self._data, self.nodatavals = _read_vrt(path)
-        elif Path(str(path) + '.vrt').exists():
-            self._data, self.nodatavals = _read_vrt(Path(str(path) + '.vrt'))
+        vrt = path if path.suffix.lower() == '.vrt' else Path(str(path) + '.vrt')
+        if vrt.exists():
+            self._data, self.nodatavals = _read_vrt(vrt)
+            gt, crs = _vrt_georef(vrt)
         else:
             hdr = _find_envi_header(path)
             if hdr is None or path.suffix.lower() == '.hdr':
                 raise NotARawRaster(f'{path}: no .vrt or ENVI .hdr beside it (GeoTIFF / NetCDF rasters need rasterio)')
             self._data, self.nodatavals = _read_envi(path, hdr)
+            gt, crs = _envi_georef(hdr)
         self.nodatavals = tuple(self.nodatavals)
         n, h, w = self._data.shape
-        self.profile = dict(driver='RAW', dtype=str(self._data.dtype), nodata=self.nodatavals[0], width=w, height=h, count=n, crs=None, transform=None)
+        self.profile = dict(driver='RAW', dtype=str(self._data.dtype), nodata=self.nodatavals[0], width=w, height=h, count=n, crs=crs, transform=gt)
         self.count, self.height, self.width = n, h, w
 
     def read(self, band=None):

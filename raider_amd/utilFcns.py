@@ -188,3 +188,91 @@ def writeDelays(aoi, wetDelay, hydroDelay, wet_path, hydro_path=None, outformat=
     gt = aoi.geotransform() if hasattr(aoi, 'geotransform') else None
     writeArrayToRaster(wetDelay, Path(wet_path), noDataValue=ndv, fmt=outformat or 'ENVI', proj=proj, gt=gt)
     writeArrayToRaster(hydroDelay, Path(hydro_path), noDataValue=ndv, fmt=outformat or 'ENVI', proj=proj, gt=gt)
+
+
+# ---- what llreader.py takes from utilFcns: bounding boxes and raster metadata (utilFcns.py:140-161, 213-254, 586-630) -----------
+def get_file_and_band(filestr):
+    """utilFcns.py:244-254: `file;band` -> (Path, band), band 1 without a suffix."""
+    from pathlib import Path
+    parts = filestr.split(';')
+    if len(parts) == 1:
+        return Path(filestr.strip()), 1
+    elif len(parts) == 2:
+        return Path(parts[0].strip()), int(parts[1].strip())
+    else:
+        raise ValueError(f'Cannot interpret {filestr} as valid filename')
+
+
+def clip_bbox(bbox, spacing):
+    """utilFcns.py:623-630: clip box to multiple of spacing (outwards)."""
+    return [
+        np.floor(bbox[0] / spacing) * spacing,
+        np.ceil(bbox[1] / spacing) * spacing,
+        np.floor(bbox[2] / spacing) * spacing,
+        np.ceil(bbox[3] / spacing) * spacing,
+    ]
+
+
+def transform_bbox(snwe_in, dest_crs=4326, src_crs=4326, buffer=100.0):
+    """utilFcns.py:586-620: SNWE box in `src_crs` -> SNWE box in `dest_crs`: the identity for equal CRSs, else the extremes of an
+    11 x 11 mesh over the box grown by `buffer` metres (1e-5 degrees per metre for a lon / lat source), taken through transformPoints -
+    so for the CRSs that function has built in (anything else needs pyproj there, as in the reference)."""
+    from .delay import _is_4326, _same_crs, transformPoints
+    if _is_4326(src_crs):
+        buffer = buffer / 1.0e5
+    if _same_crs(dest_crs, src_crs):
+        return snwe_in
+    xs = np.linspace(snwe_in[2] - buffer, snwe_in[3] + buffer, num=11)
+    ys = np.linspace(snwe_in[0] - buffer, snwe_in[1] + buffer, num=11)
+    X, Y = np.meshgrid(xs, ys)
+    out = transformPoints(Y, X, np.zeros_like(X), src_crs, dest_crs)
+    yy, xx = out[..., 0], out[..., 1]
+    return [np.nanmin(yy), np.nanmax(yy), np.nanmin(xx), np.nanmax(xx)]
+
+
+def rio_profile(path):
+    """utilFcns.py:140-151: the profile of a raster (`<path>.vrt` preferred)."""
+    from pathlib import Path
+    from .rawraster import open_raster
+    path = Path(path)
+    if path.name.startswith('S1-GUNW'):
+        raise NotImplementedError('GUNW sub-datasets are read by raider_amd.gunw, not as rasters')
+    vrt = Path(f'{path}.vrt')
+    with open_raster(vrt if vrt.exists() else path) as src:
+        return src.profile
+
+
+def _gdal_transform(profile):
+    gt = profile.get('transform')
+    if gt is None:
+        raise ValueError('the raster carries no geotransform')
+    return tuple(gt.to_gdal()) if hasattr(gt, 'to_gdal') else tuple(gt)
+
+
+def rio_extents(profile):
+    """utilFcns.py:154-161: SNWE of a profile - the coordinates of the first and the last pixel's upper-left corner, as the reference
+    computes them."""
+    gt = _gdal_transform(profile)
+    xSize = profile['width']
+    ySize = profile['height']
+    W, E = gt[0], gt[0] + (xSize - 1) * gt[1] + (ySize - 1) * gt[2]
+    N, S = gt[3], gt[3] + (xSize - 1) * gt[4] + (ySize - 1) * gt[5]
+    return S, N, W, E
+
+
+def rio_stats(path, band=1):
+    """utilFcns.py:213-241: (stats, CRS, geotransform) of one band.  stats has .min / .max / .count over the valid pixels (neither NaN
+    nor the band's no-data value), reduced on the device (rdr_raster_bounds) - what the reference's callers read of GDAL's
+    statistics; the CRS is 4326 when the file names none (the assumption bounds_from_latlon_rasters makes); the geotransform is None
+    for a raster without one."""
+    from collections import namedtuple
+    from pathlib import Path
+    from .interpolator import raster_bounds
+    from .rawraster import rio_open as _rio_open
+    data, profile = _rio_open(Path(path), band=band)
+    (lo, hi, count), _ = raster_bounds(data, None, nodata=profile.get('nodata'))
+    gt = profile.get('transform')
+    if gt is not None:
+        gt = _gdal_transform(profile)
+    crs = profile.get('crs')
+    return namedtuple('Statistics', 'min max count')(lo, hi, count), (4326 if crs is None else crs), gt
