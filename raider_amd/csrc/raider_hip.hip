@@ -2012,6 +2012,31 @@ static bool pass1_skip_on() {
     return on != 0;
 }
 
+// ---- one selector per kernel family: the instantiation a launcher launches IS the one rdr_ray_kernel_attributes reports -------------
+// the light pass-1 kernel; om: the input form of the batch (crossings_kernel's OM: 1 GRID + look vectors, 2 GRID + incidence, 0 the rest)
+template <typename T2>
+static auto crossings_fn(bool lcc, int om, bool per_ray) -> void (*)(CubeView<T2>, RayParams, LccParams) {
+#define RDR_X(LCC_, OM_) (per_ray ? crossings_kernel<T2, false, LCC_, OM_, true> : crossings_kernel<T2, false, LCC_, OM_, false>)
+#define RDR_X_OM(LCC_) (om == 1 ? RDR_X(LCC_, 1) : om == 2 ? RDR_X(LCC_, 2) : RDR_X(LCC_, 0))
+    return lcc ? RDR_X_OM(true) : RDR_X_OM(false);
+#undef RDR_X_OM
+#undef RDR_X
+}
+
+// the light pass-2 kernel of one cube (grid: march_grid; per-ray heights are built for REGULAR and run-time flags only)
+template <typename T2>
+static auto march_fn(int grid, bool per_ray) -> void (*)(CubeView<T2>, RayParams, LccParams) {
+    if (per_ray) return grid == 1 ? march_kernel<T2, false, 1, true> : march_kernel<T2, false, 0, true>;
+    return grid == 1 ? march_kernel<T2, false, 1> : grid == 2 ? march_kernel<T2, false, 2> : march_kernel<T2, false, 0>;
+}
+
+// the stacked light pass-2 kernel of E epochs (grid, per_ray as in march_fn)
+template <typename T2, int E>
+static auto march_epochs_fn(int grid, bool per_ray) -> void (*)(CubeView<T2>, EpochCubes<T2, E>, RayParams, int64_t) {
+    if (per_ray) return grid == 1 ? march_epochs_kernel<T2, E, 1, true> : march_epochs_kernel<T2, E, 0, true>;
+    return grid == 1 ? march_epochs_kernel<T2, E, 1, false> : grid == 2 ? march_epochs_kernel<T2, E, 2, false> : march_epochs_kernel<T2, E, 0, false>;
+}
+
 static int launch_crossings(rdr_ctx* c, const rdr_cube* q, RayParams P, int64_t tb, int64_t tc, int64_t nslots_total = 0, bool reset_nslow = true) {
     P.tile_begin = tb; P.tile_count = tc; P.nslots = nslots_total > 0 ? nslots_total : tc * BLOCK;
     // the lon/lat slice instantiations may skip the level loop per wave; their two tables lie behind the common LDS layout and are
@@ -2038,13 +2063,8 @@ static int launch_crossings(rdr_ctx* c, const rdr_cube* q, RayParams P, int64_t 
         // input form of the batch, fixed at compile time for the two hot ones (crossings_kernel's OM parameter)
         const int om = P.origin_mode != RDR_ORIGIN_GRID ? 0 : (P.los_mode == RDR_LOS_VEC ? 1 : 2);
         const dim3 G(g), B(BLOCK);
-#define RDR_LAUNCH_X(T2, LCC_, OM_) e = (P.ht_ray ? launch_lds(crossings_kernel<T2, false, LCC_, OM_, true>, G, B, sm_light, c->stream, make_view<T2>(q), P, q->proj) \
-                                                  : launch_lds(crossings_kernel<T2, false, LCC_, OM_, false>, G, B, sm_light, c->stream, make_view<T2>(q), P, q->proj))
-#define RDR_LAUNCH_X_OM(T2, LCC_) do { if (om == 1) RDR_LAUNCH_X(T2, LCC_, 1); else if (om == 2) RDR_LAUNCH_X(T2, LCC_, 2); else RDR_LAUNCH_X(T2, LCC_, 0); } while (0)
-        if (q->dtype == RDR_F32) { if (lcc) RDR_LAUNCH_X_OM(float2, true); else RDR_LAUNCH_X_OM(float2, false); }
-        else { if (lcc) RDR_LAUNCH_X_OM(double2, true); else RDR_LAUNCH_X_OM(double2, false); }
-#undef RDR_LAUNCH_X_OM
-#undef RDR_LAUNCH_X
+        e = q->dtype == RDR_F32 ? launch_lds(crossings_fn<float2>(lcc, om, P.ht_ray != nullptr), G, B, sm_light, c->stream, make_view<float2>(q), P, q->proj)
+                                : launch_lds(crossings_fn<double2>(lcc, om, P.ht_ray != nullptr), G, B, sm_light, c->stream, make_view<double2>(q), P, q->proj);
     }
     if (e != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("crossings_kernel launch: ") + hipGetErrorString(e));
     // generic-geodesy mop-up of the rays the classification rejected (returns at once when there are none)
@@ -2088,15 +2108,10 @@ static int launch_march(rdr_ctx* c, const rdr_cube* q, RayParams P, int64_t tb, 
     hipError_t e = hipSuccess;
     {
         KTimer t(c, 1);
-        const int grid = march_grid(q, P.ht_ray != nullptr);
-#define RDR_LAUNCH_M(T2) (P.ht_ray ? (grid == 1 ? launch_lds(march_kernel<T2, false, 1, true>, G, B, sm, c->stream, make_view<T2>(q), P, q->proj)   \
-                                                 : launch_lds(march_kernel<T2, false, 0, true>, G, B, sm, c->stream, make_view<T2>(q), P, q->proj)) \
-                          : grid == 1 ? launch_lds(march_kernel<T2, false, 1>, G, B, sm, c->stream, make_view<T2>(q), P, q->proj)   \
-                          : grid == 2 ? launch_lds(march_kernel<T2, false, 2>, G, B, sm, c->stream, make_view<T2>(q), P, q->proj) \
-                                      : launch_lds(march_kernel<T2, false, 0>, G, B, sm, c->stream, make_view<T2>(q), P, q->proj))
-        if (q->dtype == RDR_F32) e = RDR_LAUNCH_M(float2);
-        else e = RDR_LAUNCH_M(double2);
-#undef RDR_LAUNCH_M
+        const bool per_ray = P.ht_ray != nullptr;
+        const int grid = march_grid(q, per_ray);
+        e = q->dtype == RDR_F32 ? launch_lds(march_fn<float2>(grid, per_ray), G, B, sm, c->stream, make_view<float2>(q), P, q->proj)
+                                : launch_lds(march_fn<double2>(grid, per_ray), G, B, sm, c->stream, make_view<double2>(q), P, q->proj);
     }
     if (e != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("march_kernel launch: ") + hipGetErrorString(e));
     return launch_march_generic(c, q, P, G, B, sm, false);
@@ -2121,16 +2136,12 @@ static int epoch_group(int dtype, bool per_ray, int left, int emax) {
     return (left >= 4 && emax >= 4) ? 4 : (left >= 2 && emax >= 2) ? 2 : 1;
 }
 
-// the stacked light kernel of E epochs (grid: march_grid of the batch; per-ray heights from P.ht_ray)
-#define RDR_EPOCH_FN(T2, E, grid, pr) ((pr) ? ((grid) == 1 ? march_epochs_kernel<T2, E, 1, true> : march_epochs_kernel<T2, E, 0, true>) \
-                                            : (grid) == 1 ? march_epochs_kernel<T2, E, 1, false>                                         \
-                                            : (grid) == 2 ? march_epochs_kernel<T2, E, 2, false> : march_epochs_kernel<T2, E, 0, false>)
-
+// the stacked light kernel of E epochs on the cubes qs[0..E) (grid: march_grid of the batch; per-ray heights from P.ht_ray)
 template <typename T2, int E>
 static hipError_t launch_stacked(rdr_ctx* c, const rdr_cube* const* qs, int grid, const RayParams& P, int64_t estride, dim3 G, dim3 B, size_t sm) {
     EpochCubes<T2, E> ev;
     for (int j = 0; j < E; ++j) ev.v[j] = (const T2*)qs[j]->d_vals;
-    return launch_lds(RDR_EPOCH_FN(T2, E, grid, P.ht_ray != nullptr), G, B, sm, c->stream, make_view<T2>(qs[0]), ev, P, estride);
+    return launch_lds(march_epochs_fn<T2, E>(grid, P.ht_ray != nullptr), G, B, sm, c->stream, make_view<T2>(qs[0]), ev, P, estride);
 }
 
 // pass 2 of D epochs over tiles [tb, tb+tc) on the records of ONE pass 1: groups of 4 / 2 epochs (epoch_group) take the stacked
@@ -2183,20 +2194,12 @@ int rdr_ray_kernel_attributes(rdr_ctx* c, const rdr_cube* q, int which, int32_t*
     const bool lcc = q->proj.kind == 1;
     const bool pr = which == 2 || which == 3 || which >= 6;      // 2 / 3: the per-ray-height instantiations of pass 1 / pass 2; 6 / 7: of the stacked march
     const int grid = march_grid(q, pr);
+    const bool f32 = q->dtype == RDR_F32;
     if (which >= 4) {                              // 4 / 5 (sliced), 6 / 7 (per-ray heights): the stacked march (march_epochs_kernel), E = 2 / 4
-        const bool four = (which & 1) != 0;
-        if (q->dtype == RDR_F32) fn = four ? (const void*)RDR_EPOCH_FN(float2, 4, grid, pr) : (const void*)RDR_EPOCH_FN(float2, 2, grid, pr);
-        else fn = four ? (const void*)RDR_EPOCH_FN(double2, 4, grid, pr) : (const void*)RDR_EPOCH_FN(double2, 2, grid, pr);
-    } else if ((which & 1) == 0) {
-        if (q->dtype == RDR_F32) fn = pr ? (lcc ? (const void*)crossings_kernel<float2, false, true, 1, true> : (const void*)crossings_kernel<float2, false, false, 1, true>)
-                                         : (lcc ? (const void*)crossings_kernel<float2, false, true, 1> : (const void*)crossings_kernel<float2, false, false, 1>);
-        else fn = pr ? (lcc ? (const void*)crossings_kernel<double2, false, true, 1, true> : (const void*)crossings_kernel<double2, false, false, 1, true>)
-                     : (lcc ? (const void*)crossings_kernel<double2, false, true, 1> : (const void*)crossings_kernel<double2, false, false, 1>);
-    } else if (pr) {
-        if (q->dtype == RDR_F32) fn = grid == 1 ? (const void*)march_kernel<float2, false, 1, true> : (const void*)march_kernel<float2, false, 0, true>;
-        else fn = grid == 1 ? (const void*)march_kernel<double2, false, 1, true> : (const void*)march_kernel<double2, false, 0, true>;
-    } else if (q->dtype == RDR_F32) fn = grid == 1 ? (const void*)march_kernel<float2, false, 1> : grid == 2 ? (const void*)march_kernel<float2, false, 2> : (const void*)march_kernel<float2, false, 0>;
-    else fn = grid == 1 ? (const void*)march_kernel<double2, false, 1> : grid == 2 ? (const void*)march_kernel<double2, false, 2> : (const void*)march_kernel<double2, false, 0>;
+        if ((which & 1) != 0) fn = f32 ? (const void*)march_epochs_fn<float2, 4>(grid, pr) : (const void*)march_epochs_fn<double2, 4>(grid, pr);
+        else fn = f32 ? (const void*)march_epochs_fn<float2, 2>(grid, pr) : (const void*)march_epochs_fn<double2, 2>(grid, pr);
+    } else if ((which & 1) == 0) fn = f32 ? (const void*)crossings_fn<float2>(lcc, 1, pr) : (const void*)crossings_fn<double2>(lcc, 1, pr);
+    else fn = f32 ? (const void*)march_fn<float2>(grid, pr) : (const void*)march_fn<double2>(grid, pr);
     hipFuncAttributes a;
     HIPCHECK(c, hipFuncGetAttributes(&a, fn));
     if (vgprs) *vgprs = a.numRegs;

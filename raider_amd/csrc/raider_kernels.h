@@ -6,6 +6,8 @@
 //   toa_newton / _t            getTopOfAtmosphere [losreader.py:706-733] (materialising API kernels / generic ray kernels)
 //   crossings_kernel           pass 1: build_ray [losreader.py:772-835] -> per-level batch maximum of the ray length
 //                              (delay.py:283) + NaN / z-clamp flags (delay.py:279,306-311) + the ray records for pass 2
+//   march_slice_levels /       pass 2: the two level loops of the light rays over E cubes on one ray geometry, called by
+//   march_ray_height_levels    march_kernel (E = 1) and by march_epochs_kernel (epoch_kernels.h, E epochs of a date series)
 //   march_kernel               pass 2: the trapezoid of _build_cube_ray [delay.py:285-323]
 //
 // Design notes (MI355X):
@@ -211,50 +213,65 @@ __device__ __forceinline__ void cell_xy(const double2* e, int n, double v, doubl
 // One trilinear sample in two halves, so that several samples' gathers can be in flight together:
 //   sample_issue : cell search on the three axes, address, the four 16-byte (32-byte for f64 cubes) corner-pair loads
 //   sample_finish: weights, f32->f64 conversion, the 16 FMAs                    (weights/corner order: _rgi.py:490-498)
-template <typename T2>
+// E samples that share their cell and weights - one set of corners per weather epoch of a series (epoch_kernels.h); E = 1: one cube.
+template <typename T2, int E = 1>
 struct PendingSample {
-    T2 v[8];              // corners in (y,x,z) lexicographic order
+    T2 v[E][8];           // per epoch: corners in (y,x,z) lexicographic order
     double ty, tx, tz;
 };
 
-// The horizontal half of a sample: cell search on x / y (cell_xy), the element offset of corner (iy, ix, iz) and the four 16-byte (32-byte
-// for f64 cubes) corner-pair loads.  iz may be slice-uniform (a scalar) or per lane.
-template <typename T2, bool IDX, bool NOCHECK>
-__device__ __forceinline__ void gather_corners(const CubeView<T2>& c, const AxisTabs& m, double y, double x, int iz, PendingSample<T2>& s) {
+// The value pointers of E cubes of one shape (a kernel argument of the stacked kernels); E = 1: the cube's own c.v.
+template <typename T2, int E>
+struct EpochCubes { const T2* v[E]; };
+
+// The horizontal half of a sample: cell search on x / y (cell_xy) and the element offset of corner (iy, ix, iz), both once, then per
+// cube the four 16-byte (32-byte for f64 cubes) corner-pair loads - E x 4 independent loads.  iz may be slice-uniform (a scalar) or
+// per lane.
+template <typename T2, int E, bool IDX, bool NOCHECK>
+__device__ __forceinline__ void gather_corners(const CubeView<T2>& c, const EpochCubes<T2, E>& ev, const AxisTabs& m, double y, double x, int iz,
+                                               PendingSample<T2, E>& s) {
     int iy, ix;
     cell_xy<IDX, NOCHECK>(m.ey, c.ny, y, c.y_lo, c.y_hi, c.inv_dy, c.exact_y, c.uni_y, iy, s.ty);
     cell_xy<IDX, NOCHECK>(m.ex, c.nx, x, c.x_lo, c.x_hi, c.inv_dx, c.exact_x, c.uni_x, ix, s.tx);
-    const T2 *p00, *p01, *p10, *p11;
     if (c.small) {              // one 32-bit element offset against four uniform row bases
         // (iy nx + ix) as ONE full-rate v_mad_u32_u24: left to itself the compiler picks v_mad_u64_u32, a quarter-rate instruction
         // that holds the vector ALU for four issue slots
         unsigned col;
         asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(col) : "v"((unsigned)iy), "s"((unsigned)c.nx), "v"((unsigned)ix));
         const unsigned off = (__umul24(col, (unsigned)c.nz) + (unsigned)iz) * (unsigned)sizeof(T2);
-        const char* b = reinterpret_cast<const char*>(c.v);
         const size_t rowx = (size_t)c.nz * sizeof(T2), rowy = (size_t)c.nx * rowx;
-        p00 = reinterpret_cast<const T2*>(b + off);
-        p01 = reinterpret_cast<const T2*>(b + rowx + off);
-        p10 = reinterpret_cast<const T2*>(b + rowy + off);
-        p11 = reinterpret_cast<const T2*>(b + rowy + rowx + off);
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const char* b = reinterpret_cast<const char*>(ev.v[e]);
+            const T2* p00 = reinterpret_cast<const T2*>(b + off);
+            const T2* p01 = reinterpret_cast<const T2*>(b + rowx + off);
+            const T2* p10 = reinterpret_cast<const T2*>(b + rowy + off);
+            const T2* p11 = reinterpret_cast<const T2*>(b + rowy + rowx + off);
+            s.v[e][0] = p00[0]; s.v[e][1] = p00[1];
+            s.v[e][2] = p01[0]; s.v[e][3] = p01[1];
+            s.v[e][4] = p10[0]; s.v[e][5] = p10[1];
+            s.v[e][6] = p11[0]; s.v[e][7] = p11[1];
+        }
     } else {
-        p00 = c.v + ((int64_t)iy * c.nx + ix) * c.nz + iz;
-        p01 = p00 + c.nz;
-        p10 = p00 + (int64_t)c.nx * c.nz;
-        p11 = p10 + c.nz;
+        const int64_t o00 = ((int64_t)iy * c.nx + ix) * c.nz + iz, o01 = o00 + c.nz;
+        const int64_t o10 = o00 + (int64_t)c.nx * c.nz, o11 = o10 + c.nz;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const T2* p = ev.v[e];
+            s.v[e][0] = p[o00]; s.v[e][1] = p[o00 + 1];
+            s.v[e][2] = p[o01]; s.v[e][3] = p[o01 + 1];
+            s.v[e][4] = p[o10]; s.v[e][5] = p[o10 + 1];
+            s.v[e][6] = p[o11]; s.v[e][7] = p[o11 + 1];
+        }
     }
-    s.v[0] = p00[0]; s.v[1] = p00[1];
-    s.v[2] = p01[0]; s.v[3] = p01[1];
-    s.v[4] = p10[0]; s.v[5] = p10[1];
-    s.v[6] = p11[0]; s.v[7] = p11[1];
 }
 
 // MODE 0: generic kernels (three-entry z window).  MODE 1 (light march loop, a level's TOP sample or the ray's first sample):
 // index-space x / y on exact axes, two-entry z window.  MODE 2 (light march loop, a sample strictly INSIDE model interval kz):
 // its z cell is kz itself, one table entry, no select.  Any sample whose weight leaves [0,1] takes the exact search.
-template <typename T2, int MODE = 0, bool NOCHECK = false>
-__device__ __forceinline__ void sample_issue(const CubeView<T2>& c, const AxisTabs& m, double y, double x, double z, int kz,
-                                             PendingSample<T2>& s) {
+template <typename T2, int MODE = 0, bool NOCHECK = false, int E = 1>
+__device__ __forceinline__ void sample_issue(const CubeView<T2>& c, const EpochCubes<T2, E>& ev, const AxisTabs& m, double y, double x, double z, int kz,
+                                             PendingSample<T2, E>& s) {
     const double2* ez = m.ez;
     int iz;
     if (MODE == 2) {
@@ -264,36 +281,45 @@ __device__ __forceinline__ void sample_issue(const CubeView<T2>& c, const AxisTa
         if (!(s.tz >= 0.0) || !(s.tz <= 1.0)) cell_exact(ez, c.nz, z, iz, s.tz);   // rare
     } else if (MODE == 1) window2_cell(ez, c.nz, z, kz, c.nz >= 4, iz, s.tz);
     else window_cell(ez, c.nz, z, kz, c.nz >= 4, iz, s.tz);
-    gather_corners<T2, MODE != 0, NOCHECK>(c, m, y, x, iz, s);
+    gather_corners<T2, E, MODE != 0, NOCHECK>(c, ev, m, y, x, iz, s);
+}
+
+// one cube: its own values
+template <typename T2, int MODE = 0, bool NOCHECK = false>
+__device__ __forceinline__ void sample_issue(const CubeView<T2>& c, const AxisTabs& m, double y, double x, double z, int kz, PendingSample<T2>& s) {
+    sample_issue<T2, MODE, NOCHECK, 1>(c, EpochCubes<T2, 1>{{c.v}}, m, y, x, z, kz, s);
 }
 
 // Generic kernels: scipy's own summation order, weight = ((1*wy)*wx)*wz over the corners in lexicographic order (_rgi.py:490-498).
-template <typename T2>
-__device__ __forceinline__ void sample_finish(const PendingSample<T2>& s, double& wet, double& hyd) {
+// (e: the epoch of the sample set, here and in sample_finish_lerp)
+template <typename T2, int E>
+__device__ __forceinline__ void sample_finish(const PendingSample<T2, E>& s, double& wet, double& hyd, int e = 0) {
+    const T2* v = s.v[e];
     const double wy0 = 1.0 - s.ty, wx0 = 1.0 - s.tx, wz0 = 1.0 - s.tz;
     const double a00 = wy0 * wx0, a01 = wy0 * s.tx, a10 = s.ty * wx0, a11 = s.ty * s.tx;
     double sw = 0.0, sh = 0.0, k;
-    k = a00 * wz0;  sw = fma((double)s.v[0].x, k, sw); sh = fma((double)s.v[0].y, k, sh);
-    k = a00 * s.tz; sw = fma((double)s.v[1].x, k, sw); sh = fma((double)s.v[1].y, k, sh);
-    k = a01 * wz0;  sw = fma((double)s.v[2].x, k, sw); sh = fma((double)s.v[2].y, k, sh);
-    k = a01 * s.tz; sw = fma((double)s.v[3].x, k, sw); sh = fma((double)s.v[3].y, k, sh);
-    k = a10 * wz0;  sw = fma((double)s.v[4].x, k, sw); sh = fma((double)s.v[4].y, k, sh);
-    k = a10 * s.tz; sw = fma((double)s.v[5].x, k, sw); sh = fma((double)s.v[5].y, k, sh);
-    k = a11 * wz0;  sw = fma((double)s.v[6].x, k, sw); sh = fma((double)s.v[6].y, k, sh);
-    k = a11 * s.tz; sw = fma((double)s.v[7].x, k, sw); sh = fma((double)s.v[7].y, k, sh);
+    k = a00 * wz0;  sw = fma((double)v[0].x, k, sw); sh = fma((double)v[0].y, k, sh);
+    k = a00 * s.tz; sw = fma((double)v[1].x, k, sw); sh = fma((double)v[1].y, k, sh);
+    k = a01 * wz0;  sw = fma((double)v[2].x, k, sw); sh = fma((double)v[2].y, k, sh);
+    k = a01 * s.tz; sw = fma((double)v[3].x, k, sw); sh = fma((double)v[3].y, k, sh);
+    k = a10 * wz0;  sw = fma((double)v[4].x, k, sw); sh = fma((double)v[4].y, k, sh);
+    k = a10 * s.tz; sw = fma((double)v[5].x, k, sw); sh = fma((double)v[5].y, k, sh);
+    k = a11 * wz0;  sw = fma((double)v[6].x, k, sw); sh = fma((double)v[6].y, k, sh);
+    k = a11 * s.tz; sw = fma((double)v[7].x, k, sw); sh = fma((double)v[7].y, k, sh);
     wet = sw; hyd = sh;
 }
 
 // Light march loop: the same trilinear interpolant in nested-lerp form, a + t (b - a) along z, then x, then y: 7 lerps of
 // (sub, fma) per field = 28 instructions instead of the 31 of the weight-product form (the f32 -> f64 conversions are exact, so
 // the two forms agree to a few ulp of the interpolated value; the parity tests hold 1e-9 m on the integrated delay).
-template <typename T2>
-__device__ __forceinline__ void sample_finish_lerp(const PendingSample<T2>& s, double& wet, double& hyd) {
+template <typename T2, int E>
+__device__ __forceinline__ void sample_finish_lerp(const PendingSample<T2, E>& s, double& wet, double& hyd, int e = 0) {
+    const T2* v = s.v[e];
     auto lerp = [](double a, double b, double t) { return fma(t, b - a, a); };
-    const double w00 = lerp((double)s.v[0].x, (double)s.v[1].x, s.tz), h00 = lerp((double)s.v[0].y, (double)s.v[1].y, s.tz);
-    const double w01 = lerp((double)s.v[2].x, (double)s.v[3].x, s.tz), h01 = lerp((double)s.v[2].y, (double)s.v[3].y, s.tz);
-    const double w10 = lerp((double)s.v[4].x, (double)s.v[5].x, s.tz), h10 = lerp((double)s.v[4].y, (double)s.v[5].y, s.tz);
-    const double w11 = lerp((double)s.v[6].x, (double)s.v[7].x, s.tz), h11 = lerp((double)s.v[6].y, (double)s.v[7].y, s.tz);
+    const double w00 = lerp((double)v[0].x, (double)v[1].x, s.tz), h00 = lerp((double)v[0].y, (double)v[1].y, s.tz);
+    const double w01 = lerp((double)v[2].x, (double)v[3].x, s.tz), h01 = lerp((double)v[2].y, (double)v[3].y, s.tz);
+    const double w10 = lerp((double)v[4].x, (double)v[5].x, s.tz), h10 = lerp((double)v[4].y, (double)v[5].y, s.tz);
+    const double w11 = lerp((double)v[6].x, (double)v[7].x, s.tz), h11 = lerp((double)v[6].y, (double)v[7].y, s.tz);
     const double w0 = lerp(w00, w01, s.tx), h0 = lerp(h00, h01, s.tx);
     const double w1 = lerp(w10, w11, s.tx), h1 = lerp(h10, h11, s.tx);
     wet = lerp(w0, w1, s.ty); hyd = lerp(h0, h1, s.ty);
@@ -1221,6 +1247,188 @@ __device__ __forceinline__ bool lane_nocheck(double u0r, double u1r, bool active
     return (mine || !active) && (fabs(u0r) <= 1.001) && (fabs(u1r) <= 1.001) && (xs <= 1.001) && inside(q.lat, ny) && inside(q.lon, nx);
 }
 
+// ---- pass 2: the two level loops of the light rays, for E cubes on one ray geometry ----------------------------------
+// march_kernel runs them with E = 1 on its own cube, march_epochs_kernel (epoch_kernels.h) with the E epochs of a stacked launch: per
+// sample the ray polynomials, the cell searches, the z window and the corner offset run once, then E corner-pair gathers (independent of
+// each other) and E (wet, hydro) accumulators.  Per epoch the instructions and their operands do not depend on E, which is why epoch e of
+// a series is bit for bit the one-cube call on cube e.
+// Every distinct sample point of the ray once, level by level.  The sample schedule (level k, fraction j/(np-1)) is the same for every
+// ray of the slice, so the loop counters live in scalar registers.  A sample shared by two segments (top of k = bottom of k+1,
+// losreader.py:811-812) is evaluated once and carries both trapezoid end weights; a level is its interior samples (usually none or one)
+// plus its top sample.  Latency is hidden by the waves per SIMD (and the E gathers), not by batching samples inside a lane.
+
+// A level's top sample or the ray's first sample (sample_issue MODE 1) at ray parameter us.
+template <typename T2, int E, bool NC>
+__device__ __forceinline__ void issue_top(const CubeView<T2>& c, const EpochCubes<T2, E>& ev, const RaySmem& m, const RayPoly& q, double us, int zbase,
+                                          bool floor_it, bool ceil_it, PendingSample<T2, E>& s) {
+    double ph = poly5(q.h, us);
+    const double plat = poly5(q.lat, us), plon = poly5(q.lon, us);       // delay.py:295 through the ray polynomials
+    // all-pixels z-clamp of the very first / very last sample (delay.py:306-311): when it applies every pixel is
+    // below (above) the cube, so "set to zmin" == max(ph, zmin).  Slice-uniform conditions: real (scalar) branches,
+    // so the two samples of a ray they can apply to are the only ones that pay for them.
+    if (floor_it) { asm volatile("" ::: "memory"); ph = fmax(ph, c.z_lo); }
+    if (ceil_it) { asm volatile("" ::: "memory"); ph = fmin(ph, c.z_hi); }
+    sample_issue<T2, 1, NC, E>(c, ev, m.ax, plat, plon, ph, zbase, s);   // delay.py:298,319
+}
+
+// The E values of a sample set into the E accumulator pairs with trapezoid weight wv.  (The epoch index is a template argument, not a
+// loop counter: the sample set is split into registers before any loop is unrolled, which the E = 1 instantiations need to come out
+// as march_kernel's hand-written loops did - profiles/r16_loop_fold_regs.txt.)
+template <typename T2, int E, int e = 0>
+__device__ __forceinline__ void finish_into(const PendingSample<T2, E>& s, double wv, double* acc_w, double* acc_h) {
+    double vw, vh;
+    sample_finish_lerp(s, vw, vh, e);
+    acc_w[e] = fma(wv, vw, acc_w[e]); acc_h[e] = fma(wv, vh, acc_h[e]);          // delay.py:323
+    if constexpr (e + 1 < E) finish_into<T2, E, e + 1>(s, wv, acc_w, acc_h);
+}
+
+// The slice loop: every ray of the slice starts at the slice's height.  u0, u1: fields WS_U0, WS_U1 of the ray's record (the crossings
+// of its first level); live: the lanes whose samples count - a lane of tile padding or a generic ray (its record is not a polynomial)
+// computes garbage that is never stored, and must not decide a wave-uniform branch.  Adds into acc_w[E], acc_h[E] (per unit of u).
+template <typename T2, int E, bool NC>
+__device__ __forceinline__ void march_slice_levels(const CubeView<T2>& c, const EpochCubes<T2, E>& ev, const RaySmem& m, const RayPoly& q, const double (&xc)[PX],
+                                                   double u0, double u1, int K, bool clamp_lo, bool clamp_hi, unsigned long long live,
+                                                   double* acc_w, double* acc_h) {
+    // Everything slice-uniform about a level comes from its packed LDS record through ONE address register (la + fixed offsets).
+    typedef __attribute__((address_space(3))) const LevelRec LdsRec;
+    int la = (int)(size_t)m.lev;                                             // LDS byte address of record 0 (a 32-bit LDS pointer)
+    asm volatile("" : "+v"(la));                                             // (a VGPR once, not a v_mov per read)
+    const LdsRec* rec = (const LdsRec*)(size_t)(unsigned)la;
+    int npkz = __builtin_amdgcn_readfirstlane(rec->npkz);
+    int np = npkz & 0x1ffff, kz = npkz >> 17;                                // np >= 2 (fill_partition)
+    double hs = rec->hs;
+    double u_k = u0;
+    double u_last = u1;
+    double du = u_last - u_k;
+    // the ray's very first sample is the BOTTOM of its segment: when that is a model node (origin at or below it), the
+    // two-entry z window must start one interval lower
+    if (K > 0) {
+        PendingSample<T2, E> s;
+        issue_top<T2, E, NC>(c, ev, m, q, fma(0.0 * rec->step, du, u_k), window2_base(c.nz, kz - ((m.lo[0] <= m.ax.ez[kz].x) ? 1 : 0)), clamp_lo, false, s);
+        finish_into(s, hs * fabs(du), acc_w, acc_h);
+    }
+#pragma unroll 1
+    for (int k = 0; k < K; ++k) {
+        const int zbase = window2_base(c.nz, kz);                            // first table entry of the two-entry z window
+        const bool more = k + 1 < K;
+        // trapezoid weights per unit of u (delay.py:314-315): interior samples, and the top one with both its segments.  The weight is the
+        // segment's LENGTH (a norm, losreader.py:821): |du| - an origin above zref in zref's model interval walks its one segment downwards
+        const double w_mid = (2.0 * hs) * fabs(du);
+        if (np > 2) {
+            const double step = rec->step, gk = rec->gk, rk = rec->rk;
+#pragma unroll 1
+            for (int j = 1; j < np - 1; ++j) {                               // low + frac * (high - low), delay.py:292
+                PendingSample<T2, E> s;
+                const double us = fma((double)j * step, du, u_k);
+                const double ph = poly5(q.h, us), plat = poly5(q.lat, us), plon = poly5(q.lon, us);
+                int iz = kz;                                                 // strictly inside model interval kz: one table entry, no select
+                s.tz = (ph - gk) * rk;
+                if (!(s.tz >= 0.0) || !(s.tz <= 1.0)) cell_exact(m.ax.ez, c.nz, ph, iz, s.tz);   // rare
+                gather_corners<T2, E, true, NC>(c, ev, m.ax, plat, plon, iz, s);
+                finish_into(s, w_mid, acc_w, acc_h);
+            }
+        }
+        // top sample: its gathers are issued first, the next level's crossing (7 FMAs that need no memory) is computed
+        // while they are in flight, then the sample is finished with the weight of both its segments
+        PendingSample<T2, E> top;
+        {
+            const double us = u_k + du;                                      // fraction exactly 1.0, as np.linspace returns it
+            double ph = poly5(q.h, us);
+            const double plat = poly5(q.lat, us), plon = poly5(q.lon, us);   // delay.py:295 through the ray polynomials
+            if (clamp_hi && !more) { asm volatile("" ::: "memory"); ph = fmin(ph, c.z_hi); }      // delay.py:310-311 (slice-uniform branch)
+            // z cell: the top sits on node g[zbase+1] within the residual of the three-iteration crossing - ABOVE it for every ray
+            // whose zenith angle falls with height (profiles/r06_nodetop_ab.txt).  When no live lane of the wave is below the node
+            // (one compare + a scalar test) the cell index is the scalar zbase+1 and the weight one multiplication; otherwise the
+            // per-lane two-entry window.  Same values either way.
+            const double d = ph - rec->zmid;
+            int iz; bool ok;
+            if (__builtin_expect((__builtin_amdgcn_ballot_w64(!(d >= 0.0)) & live) == 0ULL, 1)) {
+                iz = zbase + 1;
+                top.tz = d * rec->r1;
+                ok = top.tz <= 1.0;                                                                // (idle lanes: NaN)
+            } else {
+                double ds = d;
+                asm volatile("" : "+v"(ds));                                                       // (nothing of this block is hoisted into the fast path)
+                const bool up = ds >= 0.0;
+                iz = zbase + (int)up;
+                top.tz = fma(ds, up ? rec->r1 : rec->r0, up ? 0.0 : 1.0);
+                ok = (top.tz >= 0.0) & (top.tz <= 1.0);
+            }
+            if (!(ok & (c.nz >= 4))) cell_exact(m.ax.ez, c.nz, ph, iz, top.tz);                  // rare
+            gather_corners<T2, E, true, NC>(c, ev, m.ax, plat, plon, iz, top);                   // delay.py:298,319
+        }
+        // (the record after the last level: same abscissa, weight 0 - see fill_partition)
+        const double t2 = poly7(xc, rec[1].xv);
+        const double du1 = t2 - u_last, hs1 = rec[1].hs;
+        u_last = t2;
+        const double w_top = fma(hs1, fabs(du1), hs * fabs(du));
+        npkz = __builtin_amdgcn_readfirstlane(rec[1].npkz);
+        finish_into(top, w_top, acc_w, acc_h);
+        u_k += du; du = du1; hs = hs1;
+        np = npkz & 0x1ffff; kz = npkz >> 17;
+        ++rec;
+    }
+}
+
+// The per-ray-height loop (P.ht_ray): the level schedule (k, j) stays slice-uniform - scalar loop counters, the partition
+// of the slice - and a lane joins it at its own first level k0 (first_level; K: none) with its own first sample; until then it idles
+// (execution mask).  The loop starts at the wave's lowest k0.  Same arithmetic per sample as the slice loop, so that equal heights give
+// the slice kernel's delays bit for bit.  lo_first: the bottom of the lane's first level.
+// (K by reference, as the kernels' own loops read it: by value the compiler allocates the registers of the REGULAR f32 instantiation
+// differently - 16 B of scratch instead of 24 - and this is a fold, not a tuning: profiles/r16_loop_fold_regs.txt.)
+template <typename T2, int E, bool NC>
+__device__ __forceinline__ void march_ray_height_levels(const CubeView<T2>& c, const EpochCubes<T2, E>& ev, const RaySmem& m, const RayPoly& q, const double (&xc)[PX],
+                                                        double u0, double u1, const int& K, int k0, double lo_first, bool clamp_lo, bool clamp_hi,
+                                                        double* acc_w, double* acc_h) {
+    int kmin = k0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) kmin = min(kmin, __shfl_xor(kmin, off, 64));
+    kmin = __builtin_amdgcn_readfirstlane(kmin);
+    // every lane's FIRST sample (the bottom of its own first level) in one evaluation for the whole wave - per-lane level
+    // constants from LDS - instead of once per distinct k0 inside the loop (a DEM tile has a dozen of those)
+    const bool has = k0 < K;
+    const int kf = has ? k0 : 0;
+    double u_k = has ? u0 : 0.0, u_last = has ? u1 : 0.0;
+    double du = u_last - u_k;
+    if (K > 0) {
+        const int kzf = m.kz[kf];
+        PendingSample<T2, E> s;
+        issue_top<T2, E, NC>(c, ev, m, q, fma(0.0 * m.step[kf], du, u_k), window2_base(c.nz, kzf - ((lo_first <= m.ax.ez[kzf].x) ? 1 : 0)), clamp_lo, false, s);
+        if (has) finish_into(s, m.hs[kf] * fabs(du), acc_w, acc_h);
+    }
+#pragma unroll 1
+    for (int k = kmin; k < K; ++k) {
+        const int np = __builtin_amdgcn_readfirstlane(m.np[k]);
+        const int kz = __builtin_amdgcn_readfirstlane(m.kz[k]);
+        const double step = m.step[k], hs = m.hs[k];
+        const bool more = k + 1 < K;
+        if (k >= k0) {
+            const int zbase = window2_base(c.nz, kz);
+            const double w_mid = (2.0 * hs) * fabs(du);
+#pragma unroll 1
+            for (int j = 1; j < np - 1; ++j) {          // strictly inside model interval kz (sample_issue MODE 2)
+                PendingSample<T2, E> s;
+                const double us = fma((double)j * step, du, u_k);
+                const double ph = poly5(q.h, us);
+                const double plat = poly5(q.lat, us), plon = poly5(q.lon, us);
+                sample_issue<T2, 2, NC, E>(c, ev, m.ax, plat, plon, ph, kz, s);
+                finish_into(s, w_mid, acc_w, acc_h);
+            }
+            PendingSample<T2, E> top;
+            issue_top<T2, E, NC>(c, ev, m, q, u_k + du, zbase, false, clamp_hi && !more, top);
+            double du1 = 0.0;
+            double w_top = hs * fabs(du);
+            if (more) {
+                const double t2 = poly7(xc, m.xv[k + 1]);
+                du1 = t2 - u_last; u_last = t2;
+                w_top = fma(m.hs[k + 1], fabs(du1), w_top);
+            }
+            finish_into(top, w_top, acc_w, acc_h);
+            u_k += du; du = du1;
+        }
+    }
+}
+
 // ---- pass 2: trapezoid integration of both fields along every ray (delay.py:285-323) -------------------------------
 // SLOW as in crossings_kernel: <false> integrates the classified-fast rays with the light geodesy, <true> the rest
 // with the generic one (and returns immediately when there are none).
@@ -1282,175 +1490,22 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
             if (per_ray) k0 = (active && mine) ? first_level(m.ax.ez, c.nz, m.lo, m.hi, m.kz, K, P.ht_ray[i], lo_first) : K;
         }
         if constexpr (!SLOW) {
-            // ---- light rays: every distinct sample point of the ray once, level by level --------------------------------
-            // The sample schedule (level k, fraction j/(np-1)) is the same for every ray of the slice, so the loop counters
-            // live in scalar registers.  A sample shared by two segments (top of k = bottom of k+1, losreader.py:811-812) is
-            // evaluated once and carries both trapezoid end weights; a level is its interior samples (usually none or one)
-            // plus its top sample.  Latency is hidden by the four waves per SIMD, not by batching samples inside a lane.
+            // ---- light rays: the two level loops above, on this one cube ------------------------------------------------
             RayPoly q;
             double xc[PX];
             load_ray_record(w, ns, q, xc);
             const double scale = scale_rec;
-            // MODE 1: a level's top sample / the ray's first sample; MODE 2: a sample strictly inside its model interval
-            // lanes whose samples count: a lane of tile padding or a generic ray (its record is not a polynomial) computes garbage that is
-            // never stored, and must not decide a wave-uniform branch
+            const double u0r = w[(int64_t)WS_U0 * ns], u1r = w[(int64_t)WS_U1 * ns];
+            const EpochCubes<T2, 1> one{{c.v}};
             const unsigned long long live = __builtin_amdgcn_ballot_w64(active && mine);
             auto run = [&](auto nochk) {
-            constexpr bool NC = decltype(nochk)::value;
-            auto issue_top = [&](double us, int zbase, bool floor_it, bool ceil_it, PendingSample<T2>& s) {
-                double ph = poly5(q.h, us);
-                const double plat = poly5(q.lat, us), plon = poly5(q.lon, us);       // delay.py:295 through the ray polynomials
-                // all-pixels z-clamp of the very first / very last sample (delay.py:306-311): when it applies every pixel is
-                // below (above) the cube, so "set to zmin" == max(ph, zmin).  Slice-uniform conditions: real (scalar) branches,
-                // so the two samples of a ray they can apply to are the only ones that pay for them.
-                if (floor_it) { asm volatile("" ::: "memory"); ph = fmax(ph, c.z_lo); }
-                if (ceil_it) { asm volatile("" ::: "memory"); ph = fmin(ph, c.z_hi); }
-                sample_issue<T2, 1, NC>(c, m.ax, plat, plon, ph, zbase, s);              // delay.py:298,319
-            };
-            auto issue_mid = [&](double us, int kz_, PendingSample<T2>& s) {
-                const double ph = poly5(q.h, us);
-                const double plat = poly5(q.lat, us), plon = poly5(q.lon, us);
-                sample_issue<T2, 2, NC>(c, m.ax, plat, plon, ph, kz_, s);
-            };
-            auto finish = [&](const PendingSample<T2>& s, double wv) {
-                double vw, vh;
-                sample_finish_lerp(s, vw, vh);
-                acc_w = fma(wv, vw, acc_w); acc_h = fma(wv, vh, acc_h);              // delay.py:323
-            };
-            if constexpr (PR) {
-                // Per-ray heights: the level schedule (k, j) stays slice-uniform - scalar loop counters, the partition of the slice - and a
-                // lane joins it at its own first level k0 with its own first sample; until then it idles (execution mask).  The loop
-                // starts at the wave's lowest k0.  Same arithmetic per sample as the slice loop below, so that equal heights give the
-                // slice kernel's delays bit for bit.
-                int kmin = k0;
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) kmin = min(kmin, __shfl_xor(kmin, off, 64));
-                kmin = __builtin_amdgcn_readfirstlane(kmin);
-                // every lane's FIRST sample (the bottom of its own first level) in one evaluation for the whole wave - per-lane level
-                // constants from LDS - instead of once per distinct k0 inside the loop (a DEM tile has a dozen of those)
-                const bool has = k0 < K;
-                const int kf = has ? k0 : 0;
-                double u_k = has ? w[(int64_t)WS_U0 * ns] : 0.0, u_last = has ? w[(int64_t)WS_U1 * ns] : 0.0;
-                double du = u_last - u_k;
-                if (K > 0) {
-                    const int kzf = m.kz[kf];
-                    PendingSample<T2> s;
-                    issue_top(fma(0.0 * m.step[kf], du, u_k), window2_base(c.nz, kzf - ((lo_first <= m.ax.ez[kzf].x) ? 1 : 0)), clamp_lo, false, s);
-                    if (has) finish(s, m.hs[kf] * fabs(du));
-                }
-#pragma unroll 1
-                for (int k = kmin; k < K; ++k) {
-                    const int np = __builtin_amdgcn_readfirstlane(m.np[k]);
-                    const int kz = __builtin_amdgcn_readfirstlane(m.kz[k]);
-                    const double step = m.step[k], hs = m.hs[k];
-                    const bool more = k + 1 < K;
-                    if (k >= k0) {
-                        const int zbase = window2_base(c.nz, kz);
-                        const double w_mid = (2.0 * hs) * fabs(du);
-#pragma unroll 1
-                        for (int j = 1; j < np - 1; ++j) {
-                            PendingSample<T2> s;
-                            issue_mid(fma((double)j * step, du, u_k), kz, s);
-                            finish(s, w_mid);
-                        }
-                        PendingSample<T2> top;
-                        issue_top(u_k + du, zbase, false, clamp_hi && !more, top);
-                        double du1 = 0.0;
-                        double w_top = hs * fabs(du);
-                        if (more) {
-                            const double t2 = poly7(xc, m.xv[k + 1]);
-                            du1 = t2 - u_last; u_last = t2;
-                            w_top = fma(m.hs[k + 1], fabs(du1), w_top);
-                        }
-                        finish(top, w_top);
-                        u_k += du; du = du1;
-                    }
-                }
-            } else {
-            // Everything slice-uniform about a level comes from its packed LDS record through ONE address register (la + fixed offsets).
-            typedef __attribute__((address_space(3))) const LevelRec LdsRec;
-            int la = (int)(size_t)m.lev;                                             // LDS byte address of record 0 (a 32-bit LDS pointer)
-            asm volatile("" : "+v"(la));                                             // (a VGPR once, not a v_mov per read)
-            const LdsRec* rec = (const LdsRec*)(size_t)(unsigned)la;
-            int npkz = __builtin_amdgcn_readfirstlane(rec->npkz);
-            int np = npkz & 0x1ffff, kz = npkz >> 17;                                // np >= 2 (fill above)
-            double hs = rec->hs;
-            double u_k = w[(int64_t)WS_U0 * ns];
-            double u_last = w[(int64_t)WS_U1 * ns];
-            double du = u_last - u_k;
-            // the ray's very first sample is the BOTTOM of its segment: when that is a model node (origin at or below it), the
-            // two-entry z window must start one interval lower
-            if (K > 0) {
-                PendingSample<T2> s;
-                issue_top(fma(0.0 * rec->step, du, u_k), window2_base(c.nz, kz - ((m.lo[0] <= m.ax.ez[kz].x) ? 1 : 0)), clamp_lo, false, s);
-                finish(s, hs * fabs(du));
-            }
-#pragma unroll 1
-            for (int k = 0; k < K; ++k) {
-                const int zbase = window2_base(c.nz, kz);                            // first table entry of the two-entry z window
-                const bool more = k + 1 < K;
-                // trapezoid weights per unit of u (delay.py:314-315): interior samples, and the top one with both its segments.  The weight is the
-                // segment's LENGTH (a norm, losreader.py:821): |du| - an origin above zref in zref's model interval walks its one segment downwards
-                const double w_mid = (2.0 * hs) * fabs(du);
-                if (np > 2) {
-                    const double step = rec->step, gk = rec->gk, rk = rec->rk;
-#pragma unroll 1
-                    for (int j = 1; j < np - 1; ++j) {                               // low + frac * (high - low), delay.py:292
-                        PendingSample<T2> s;
-                        const double us = fma((double)j * step, du, u_k);
-                        const double ph = poly5(q.h, us), plat = poly5(q.lat, us), plon = poly5(q.lon, us);
-                        int iz = kz;                                                 // strictly inside model interval kz: one table entry, no select
-                        s.tz = (ph - gk) * rk;
-                        if (!(s.tz >= 0.0) || !(s.tz <= 1.0)) cell_exact(m.ax.ez, c.nz, ph, iz, s.tz);   // rare
-                        gather_corners<T2, true, NC>(c, m.ax, plat, plon, iz, s);
-                        finish(s, w_mid);
-                    }
-                }
-                // top sample: its gathers are issued first, the next level's crossing (7 FMAs that need no memory) is computed
-                // while they are in flight, then the sample is finished with the weight of both its segments
-                PendingSample<T2> top;
-                {
-                    const double us = u_k + du;                                      // fraction exactly 1.0, as np.linspace returns it
-                    double ph = poly5(q.h, us);
-                    const double plat = poly5(q.lat, us), plon = poly5(q.lon, us);   // delay.py:295 through the ray polynomials
-                    if (clamp_hi && !more) { asm volatile("" ::: "memory"); ph = fmin(ph, c.z_hi); }      // delay.py:310-311 (slice-uniform branch)
-                    // z cell: the top sits on node g[zbase+1] within the residual of the three-iteration crossing - ABOVE it for every ray
-                    // whose zenith angle falls with height (profiles/r06_nodetop_ab.txt).  When no live lane of the wave is below the node
-                    // (one compare + a scalar test) the cell index is the scalar zbase+1 and the weight one multiplication; otherwise the
-                    // per-lane two-entry window.  Same values either way.
-                    const double d = ph - rec->zmid;
-                    int iz; bool ok;
-                    if (__builtin_expect((__builtin_amdgcn_ballot_w64(!(d >= 0.0)) & live) == 0ULL, 1)) {
-                        iz = zbase + 1;
-                        top.tz = d * rec->r1;
-                        ok = top.tz <= 1.0;                                                                // (idle lanes: NaN)
-                    } else {
-                        double ds = d;
-                        asm volatile("" : "+v"(ds));                                                       // (nothing of this block is hoisted into the fast path)
-                        const bool up = ds >= 0.0;
-                        iz = zbase + (int)up;
-                        top.tz = fma(ds, up ? rec->r1 : rec->r0, up ? 0.0 : 1.0);
-                        ok = (top.tz >= 0.0) & (top.tz <= 1.0);
-                    }
-                    if (!(ok & (c.nz >= 4))) cell_exact(m.ax.ez, c.nz, ph, iz, top.tz);                  // rare
-                    gather_corners<T2, true, NC>(c, m.ax, plat, plon, iz, top);                          // delay.py:298,319
-                }
-                // (the record after the last level: same abscissa, weight 0 - see the fill above)
-                const double t2 = poly7(xc, rec[1].xv);
-                const double du1 = t2 - u_last, hs1 = rec[1].hs;
-                u_last = t2;
-                const double w_top = fma(hs1, fabs(du1), hs * fabs(du));
-                npkz = __builtin_amdgcn_readfirstlane(rec[1].npkz);
-                finish(top, w_top);
-                u_k += du; du = du1; hs = hs1;
-                np = npkz & 0x1ffff; kz = npkz >> 17;
-                ++rec;
-            }
-            }   // (slice loop)
+                constexpr bool NC = decltype(nochk)::value;
+                if constexpr (PR) march_ray_height_levels<T2, 1, NC>(c, one, m, q, xc, u0r, u1r, K, k0, lo_first, clamp_lo, clamp_hi, &acc_w, &acc_h);
+                else march_slice_levels<T2, 1, NC>(c, one, m, q, xc, u0r, u1r, K, clamp_lo, clamp_hi, live, &acc_w, &acc_h);
             };
             // the wave-wide no-check proof (lane_nocheck): bounds of the cell search from the polynomial coefficients
             bool lane_safe = false;
-            if (REGULAR) lane_safe = lane_nocheck(w[(int64_t)WS_U0 * ns], w[(int64_t)WS_U1 * ns], active, mine, q, xc, c.ny, c.nx);
+            if (REGULAR) lane_safe = lane_nocheck(u0r, u1r, active, mine, q, xc, c.ny, c.nx);
             // ---- f64 cubes: the level's footprint through LDS --------------------------------------------------------------------
             // An f64 cube doubles the bytes of every gather (4 x 32 B per lane and sample): the instantiation is bound by the vector L1's
             // 64 B/clk return path, not by instruction issue (6.8 against 5.0 ms per 16 M rays, round 3).  But the 64 rays of a wave
@@ -1486,7 +1541,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
                         typedef S1 S2 __attribute__((ext_vector_type(2)));
                         typedef __attribute__((address_space(3))) S2 LdsS2;
                         const LdsS2* p = (const LdsS2*)st + (active ? (rz * 16u + ry * 4u + rx) : 0u);
-                        auto get = [&](int i_, int o_) { const S2 t_ = p[o_]; sm.v[i_].x = t_.x; sm.v[i_].y = t_.y; };
+                        auto get = [&](int i_, int o_) { const S2 t_ = p[o_]; sm.v[0][i_].x = t_.x; sm.v[0][i_].y = t_.y; };
                         get(0, 0); get(1, 16); get(2, 1); get(3, 17); get(4, 4); get(5, 20); get(6, 5); get(7, 21);
                         asm volatile("" ::: "memory");
                     } else {
@@ -1495,8 +1550,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
                         const T2* p01 = reinterpret_cast<const T2*>(vb + rowx + off);
                         const T2* p10 = reinterpret_cast<const T2*>(vb + rowy + off);
                         const T2* p11 = reinterpret_cast<const T2*>(vb + rowy + rowx + off);
-                        sm.v[0] = p00[0]; sm.v[1] = p00[1]; sm.v[2] = p01[0]; sm.v[3] = p01[1];
-                        sm.v[4] = p10[0]; sm.v[5] = p10[1]; sm.v[6] = p11[0]; sm.v[7] = p11[1];
+                        T2* const v = sm.v[0];
+                        v[0] = p00[0]; v[1] = p00[1]; v[2] = p01[0]; v[3] = p01[1];
+                        v[4] = p10[0]; v[5] = p10[1]; v[6] = p11[0]; v[7] = p11[1];
                     }
                 };
                 auto finish = [&](const PendingSample<T2>& sm, double wv) {

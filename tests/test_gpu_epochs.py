@@ -277,3 +277,86 @@ def test_small_slice_budget_chunks_the_series(monkeypatch, caplog):
     monkeypatch.setenv('RAIDER_HIP_SLICE_BUDGET_BYTES', str(21 * 17 * 200))      # two slices per call
     with caplog.at_level(logging.INFO):
         _series_vs_loop(files, lambda: GridAOI(xp, yp), Raytracing(inc=38.0, heading=-167.9), [0.0, 300.0, 900.0, 1800.0, 3000.0], caplog)
+
+
+# The one-cube marcher and the stacked one run the same two level loops (raider_kernels.h: march_slice_levels, march_ray_height_levels)
+# in EVERY horizontal-grid variant, not only on exactly uniform axes.  The axes choose the instantiation (raider_hip.hip:
+# axis_uniformity -> march_grid):
+#   regular   np.linspace axes: uniform to round-off (worst node < 1e-11 cells off) -> GRID = 1, REGULAR, sliced and per-ray heights
+#   tables    the same axes rounded through float32: ~1e-6 cells off, so not exact but nearly uniform on both axes -> GRID = 2, TABLES,
+#             for the slices; per-ray heights are not built for TABLES and fall back to GRID = 0, run-time flags (uni = 1)
+#   flags     one node of the y axis moved by a quarter of a spacing: y is not exact any more, x still is -> neither REGULAR (both exact)
+#             nor TABLES (neither exact), whichever side of the 0.25-cell bound of "nearly uniform" round-off puts y: GRID = 0, run-time
+#             flags (exact_x = 1, exact_y = 0), sliced and per-ray heights
+_FOLD_NY, _FOLD_NX, _FOLD_NZ, _FOLD_D = 12, 14, 9, 7          # 7 epochs: the groups 4 + 2 + 1
+
+_STAGE_OFF_CHILD = """
+import sys
+sys.path.insert(0, sys.argv[1])
+import numpy as np
+import raider_amd as R
+d = np.load(sys.argv[2])
+cube = R.Cube(d['ys'], d['xs'], d['zs'], d['wet'], d['hydro'], order='zyx')
+rays = R.Rays.grid(d['xp'], d['yp'], inc=d['inc'], hd=-167.9)
+w, h, K, npt, fl = cube.raytrace_slices(rays, d['hts'], float(d['zref']))
+np.savez(sys.argv[3], w=w, h=h, K=K, npt=npt, fl=fl)
+"""
+
+
+def _fold_axes(c, kind):
+    ys, xs = c['ys'].copy(), c['xs'].copy()
+    if kind == 'tables':
+        ys, xs = ys.astype(np.float32).astype(np.float64), xs.astype(np.float32).astype(np.float64)
+    elif kind == 'flags':
+        ys[5] += 0.25 * (ys[1] - ys[0])
+    return ys, xs
+
+
+@pytest.mark.parametrize('kind', ['regular', 'tables', 'flags'])
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
+def test_stacked_equals_single_in_every_grid_variant(dtype, kind, tmp_path):
+    import os
+    import subprocess
+    import sys
+    import raider_amd as R
+    cs, sc = _epochs(_FOLD_D, _FOLD_NY, _FOLD_NX, _FOLD_NZ)
+    ys, xs = _fold_axes(cs[0], kind)
+    fields = [((c['wet'] * s).astype(dtype), (c['hydro'] * s).astype(dtype)) for c, s in zip(cs, sc)]
+    cubes = [R.Cube(ys, xs, c['zs'], w, h, order='zyx') for c, (w, h) in zip(cs, fields)]
+    zref = float(cs[0]['zs'].max() - 1)
+    # 21 x 37 pixels over the cube's interior: partial 16 x 16 tiles in both directions
+    ny, nx = 21, 37
+    xp = np.linspace(-119.5, -115.5, nx); yp = np.linspace(34.5, 31.5, ny)
+    inc = np.broadcast_to(30.0 + 16.0 * np.arange(nx) / nx, (ny, nx)).copy()
+    # (a) height slices
+    hts = np.array([0.0, 300.0])
+    rays = R.Rays.grid(xp, yp, inc=inc, hd=-167.9)
+    w, h, K, npt, fl = R.raytrace_slices_epochs(cubes, rays, hts, zref)
+    assert w.shape == (_FOLD_D, 2, ny, nx) and np.isfinite(w).all() and np.isfinite(h).all()
+    single = [cb.raytrace_slices(rays, hts, zref) for cb in cubes]
+    for e, (sw, sh, sK, snp, sfl) in enumerate(single):
+        assert np.array_equal(w[e], sw, equal_nan=True) and np.array_equal(h[e], sh, equal_nan=True), e
+        assert np.array_equal(K, sK) and np.array_equal(npt, snp) and np.array_equal(fl[e], sfl), e
+    assert not np.array_equal(w[0], w[1])
+    # (b) per-ray heights: a smooth ramp between 0 and 1500 m (ht = None: the level table of the lowest ray, Rays.table_height)
+    ramp = 1500.0 * (0.5 * np.arange(ny)[:, None] / (ny - 1) + 0.5 * np.arange(nx)[None, :] / (nx - 1))
+    rays_h = R.Rays.grid(xp, yp, inc=inc, hd=-167.9, hts=ramp)
+    wp, hp, npp, flp = R.raytrace_epochs(cubes, rays_h, None, zref)
+    assert wp.shape == (_FOLD_D, ny, nx) and np.isfinite(wp).all() and np.isfinite(hp).all()
+    for e, cb in enumerate(cubes):
+        sw, sh, snp, sfl = cb.raytrace(rays_h, None, zref)
+        assert np.array_equal(wp[e], sw, equal_nan=True) and np.array_equal(hp[e], sh, equal_nan=True), e
+        assert np.array_equal(npp, snp) and flp == sfl, e
+    # (c) f64 cubes on exact axes stage a level's footprint in LDS (march_kernel's STAGED path, which stayed apart from the shared loops):
+    # the same call with the staging switched off runs the shared slice loop - the same bytes.  The switch is read once per process.
+    if dtype is np.float64 and kind == 'regular':
+        repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        src, dst = str(tmp_path / 'scene.npz'), str(tmp_path / 'out.npz')
+        np.savez(src, ys=ys, xs=xs, zs=cs[0]['zs'], wet=fields[0][0], hydro=fields[0][1], xp=xp, yp=yp, inc=inc, hts=hts, zref=zref)
+        env = dict(os.environ, RAIDER_HIP_F64_STAGE='0')
+        done = subprocess.run([sys.executable, '-c', _STAGE_OFF_CHILD, repo, src, dst], env=env, timeout=120, capture_output=True, text=True)
+        assert done.returncode == 0, done.stderr[-2000:]
+        got = np.load(dst)
+        sw, sh, sK, snp, sfl = single[0]
+        assert got['w'].tobytes() == sw.tobytes() and got['h'].tobytes() == sh.tobytes()
+        assert np.array_equal(got['K'], sK) and np.array_equal(got['npt'], snp) and np.array_equal(got['fl'], sfl)
