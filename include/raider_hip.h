@@ -564,6 +564,28 @@ int rdr_raster_sample(rdr_ctx* ctx, const void* raster, int dtype, int64_t heigh
  * exact and no floating-point atomics are used: the same bytes on every run.  a, b and out6 live at `loc`. */
 int rdr_raster_bounds(rdr_ctx* ctx, const void* a, const void* b, int dtype, int64_t n, int has_nodata, double nodata, double* out6, int loc);
 
+/* ---- GeoTIFF segments (raider_amd/tifflite.py): tiles and strips decoded and put together on the device ---------------------------
+ * rdr_tiff_lzw_decode: `nseg` independent TIFF-flavoured LZW streams (MSB-first codes of 9 - 12 bits, Clear = 256, EOI = 257,
+ * libtiff's early change of the code width) out of one byte buffer `src` of `src_bytes`: stream i is src[seg_offset[i] ..
+ * + seg_bytes[i]) and is written to out + i * out_stride, at most seg_out_bytes[i] <= out_stride bytes of it; bytes of a slot the
+ * stream does not reach keep their value.  status[i]: 0 = the stream ended with EOI, or ended exactly as its slot was full;
+ * 1 = the input ended before EOI with the slot not full, or the stream holds more than the slot takes; 2 = a code beyond the
+ * table.  A bad stream sets its status and stops; nothing is read outside its segment or written outside its slot.  src, out and
+ * status live at `loc`; the three int64 tables are HOST arrays.  One wave per segment, the string table in LDS; strings are
+ * expanded from the table and the output is never read back.  RDR_ERR_INVALID: NULL, sizes <= 0, a segment outside src, a slot
+ * beyond out_stride, out_stride >= 2 GiB. */
+int rdr_tiff_lzw_decode(rdr_ctx* ctx, const void* src, int64_t src_bytes, const int64_t* seg_offset, const int64_t* seg_bytes, int64_t nseg,
+                        const int64_t* seg_out_bytes, void* out, int64_t out_stride, int32_t* status, int loc);
+/* rdr_tiff_assemble: decoded segments (segment k at segs + k * seg_stride, seg_stride a multiple of 8; file order: left to right, top
+ * to bottom, plane after plane for planar = 2) -> the raster out[height][width] of band `band` (0-based), or out[bands][height][width]
+ * for band = -1, in native byte order.  Segments are tile_h x tile_w pixels (strips: tile_w = width, tile_h = RowsPerStrip, the
+ * last strip may be short); padding right of `width` and below `height` is clipped.  swap != 0: samples are byte-swapped first;
+ * predictor 2: each segment row is then summed along x per band, modulo 2^(8 * sample_bytes) (NumPy's cumsum in the unsigned type).
+ * sample_bytes 1 / 2 / 4 / 8: samples travel as bits, so every TIFF sample type of that size is served.  No predictor, no swap and
+ * one strip (per plane) covering the raster is a plain copy.  segs and out live at `loc`. */
+int rdr_tiff_assemble(rdr_ctx* ctx, const void* segs, int64_t seg_stride, int64_t height, int64_t width, int64_t tile_h, int64_t tile_w,
+                      int predictor, int swap, int sample_bytes, int planar, int bands, int band, void* out, int loc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,9 @@ SYMBOLS = [
     ('rdr_make_points', C.c_int, [_VP, C.c_double, _VP, _VP, C.c_int64, C.c_double, _VP, C.c_int]),
     ('rdr_raster_sample', C.c_int, [_VP, _VP, C.c_int, C.c_int64, C.c_int64, _VP, _VP, _VP, C.c_int64, C.c_int, C.c_int, C.c_double, _VP, C.c_int]),
     ('rdr_raster_bounds', C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int64, C.c_int, C.c_double, _VP, C.c_int]),
+    ('rdr_tiff_lzw_decode', C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_int]),
+    ('rdr_tiff_assemble', C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    _VP, C.c_int]),
 ]
 
 

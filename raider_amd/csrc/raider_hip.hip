@@ -336,6 +336,7 @@ static hipError_t launch_lds(void (*kern)(KArgs...), dim3 g, dim3 b, size_t sm, 
 #include "proj_kernels.h"
 #include "epoch_kernels.h"
 #include "raster_kernels.h"
+#include "tiff_kernels.h"
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -3486,6 +3487,89 @@ int rdr_raster_bounds(rdr_ctx* c, const void* a, const void* b, int dtype, int64
     }
     HIPCHECK(c, hipGetLastError());
     rc = finish_out(c, out6, dout, 6 * 8, loc); if (rc) return rc;
+    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return RDR_OK;
+}
+
+
+// ---- GeoTIFF segments (tiff_kernels.h): LZW decoding and raster assembly -----------------------------------------------------------
+int rdr_tiff_lzw_decode(rdr_ctx* c, const void* src, int64_t src_bytes, const int64_t* seg_offset, const int64_t* seg_bytes, int64_t nseg,
+                        const int64_t* seg_out_bytes, void* out, int64_t out_stride, int32_t* status, int loc) {
+    if (!c || !src || !seg_offset || !seg_bytes || !seg_out_bytes || !out || !status) return fail(c, RDR_ERR_INVALID, "rdr_tiff_lzw_decode: NULL argument");
+    if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, "rdr_tiff_lzw_decode: loc must be RDR_HOST or RDR_DEVICE");
+    if (src_bytes <= 0 || nseg <= 0 || nseg > (1 << 24)) return fail(c, RDR_ERR_INVALID, "rdr_tiff_lzw_decode: need a non-empty buffer and 1 .. 2^24 segments");
+    if (out_stride <= 0 || out_stride > ((int64_t)1 << 31) - 256 || nseg * out_stride > ((int64_t)1 << 40))
+        return fail(c, RDR_ERR_INVALID, "rdr_tiff_lzw_decode: out_stride must be positive and below 2 GiB (at most 2^40 bytes in all)");
+    for (int64_t i = 0; i < nseg; ++i) {
+        if (seg_offset[i] < 0 || seg_bytes[i] < 0 || seg_offset[i] > src_bytes || seg_bytes[i] > src_bytes - seg_offset[i])
+            return fail(c, RDR_ERR_INVALID, "rdr_tiff_lzw_decode: segment " + std::to_string(i) + " does not lie inside the source buffer");
+        if (seg_bytes[i] >= ((int64_t)1 << 31) - 256) return fail(c, RDR_ERR_INVALID, "rdr_tiff_lzw_decode: segment " + std::to_string(i) + " is 2 GiB or longer");
+        if (seg_out_bytes[i] < 0 || seg_out_bytes[i] > out_stride)
+            return fail(c, RDR_ERR_INVALID, "rdr_tiff_lzw_decode: segment " + std::to_string(i) + " would write beyond its slot of out_stride bytes");
+    }
+    HIPCHECK(c, hipSetDevice(c->device));
+    const void* dsrc; void *dtab, *dout, *dstat;
+    int rc = stage_in(c, SLOT_IN0, src, (size_t)src_bytes, loc, &dsrc); if (rc) return rc;
+    rc = ensure(c, SLOT_IN1, (size_t)nseg * 24, &dtab); if (rc) return rc;
+    int64_t* tab = (int64_t*)dtab;                            // the three tables are host arrays whatever `loc` says: offsets | bytes | out bytes
+    rc = upload(c, tab, seg_offset, (size_t)nseg * 8); if (rc) return rc;
+    rc = upload(c, tab + nseg, seg_bytes, (size_t)nseg * 8); if (rc) return rc;
+    rc = upload(c, tab + 2 * nseg, seg_out_bytes, (size_t)nseg * 8); if (rc) return rc;
+    rc = stage_out(c, SLOT_OUT0, out, (size_t)(nseg * out_stride), loc, &dout); if (rc) return rc;
+    rc = stage_out(c, SLOT_OUT1, status, (size_t)nseg * 4, loc, &dstat); if (rc) return rc;
+    // bytes of a slot the stream does not reach keep their value: a host `out` goes up first
+    if (loc == RDR_HOST) { rc = upload(c, dout, out, (size_t)(nseg * out_stride)); if (rc) return rc; }
+    // one wave per segment; a compute unit holds five of these 29 KB workgroups, the grid strides over the rest
+    const int grid = (int)std::min<int64_t>(nseg, (int64_t)c->num_cus * 5);
+    hipLaunchKernelGGL(tiff_lzw_kernel, dim3(grid), dim3(64), 0, c->stream, (const uint8_t*)dsrc, src_bytes, (const int64_t*)tab, (const int64_t*)(tab + nseg),
+                       (const int64_t*)(tab + 2 * nseg), (int)nseg, (uint8_t*)dout, out_stride, (int32_t*)dstat);
+    HIPCHECK(c, hipGetLastError());
+    rc = finish_out(c, out, dout, (size_t)(nseg * out_stride), loc); if (rc) return rc;
+    rc = finish_out(c, status, dstat, (size_t)nseg * 4, loc); if (rc) return rc;
+    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return RDR_OK;
+}
+
+int rdr_tiff_assemble(rdr_ctx* c, const void* segs, int64_t seg_stride, int64_t height, int64_t width, int64_t tile_h, int64_t tile_w, int predictor,
+                      int swap, int sample_bytes, int planar, int bands, int band, void* out, int loc) {
+    if (!c || !segs || !out) return fail(c, RDR_ERR_INVALID, "rdr_tiff_assemble: NULL argument");
+    if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, "rdr_tiff_assemble: loc must be RDR_HOST or RDR_DEVICE");
+    if (sample_bytes != 1 && sample_bytes != 2 && sample_bytes != 4 && sample_bytes != 8) return fail(c, RDR_ERR_INVALID, "rdr_tiff_assemble: samples of 1, 2, 4 or 8 bytes");
+    if (height <= 0 || width <= 0 || tile_h <= 0 || tile_w <= 0 || height > ((int64_t)1 << 31) || width > ((int64_t)1 << 31) || tile_h > ((int64_t)1 << 31) ||
+        tile_w > ((int64_t)1 << 31))
+        return fail(c, RDR_ERR_INVALID, "rdr_tiff_assemble: raster and segment sizes must be positive (below 2^31)");
+    if (predictor != 1 && predictor != 2) return fail(c, RDR_ERR_INVALID, "rdr_tiff_assemble: predictor must be 1 (none) or 2 (horizontal differencing)");
+    if (planar != 1 && planar != 2) return fail(c, RDR_ERR_INVALID, "rdr_tiff_assemble: planar must be 1 (chunky) or 2 (planar)");
+    if (bands <= 0 || bands > 65535 || band < -1 || band >= bands) return fail(c, RDR_ERR_INVALID, "rdr_tiff_assemble: 1 .. 65535 bands; band is -1 (all) or 0 .. bands - 1");
+    const int64_t tiles_x = (width + tile_w - 1) / tile_w, tiles_y = (height + tile_h - 1) / tile_h;
+    const int64_t spp = planar == 2 ? 1 : bands, nplanes = planar == 2 ? bands : 1;
+    // (tile_h * sample_bytes < 2^35 and tile_w * spp < 2^47: neither product overflows; their product is formed only once it is known to fit)
+    if (tile_w * spp > ((int64_t)1 << 40) / (tile_h * sample_bytes) || seg_stride < tile_h * tile_w * spp * sample_bytes || seg_stride % 8 != 0)
+        return fail(c, RDR_ERR_INVALID, "rdr_tiff_assemble: seg_stride must hold one decoded segment and be a multiple of 8");
+    const int64_t nsegs = tiles_x * tiles_y * nplanes, nout = band < 0 ? bands : 1;
+    if (nsegs > ((int64_t)1 << 42) / seg_stride || nout * height * width > ((int64_t)1 << 40)) return fail(c, RDR_ERR_INVALID, "rdr_tiff_assemble: the raster is beyond 2^40 samples");
+    HIPCHECK(c, hipSetDevice(c->device));
+    const void* dsegs; void* dout;
+    const size_t out_bytes = (size_t)(nout * height * width) * sample_bytes;
+    int rc = stage_in(c, SLOT_IN0, segs, (size_t)(nsegs * seg_stride), loc, &dsegs); if (rc) return rc;
+    rc = stage_out(c, SLOT_OUT0, out, out_bytes, loc, &dout); if (rc) return rc;
+    if ((reinterpret_cast<uintptr_t>(dsegs) | reinterpret_cast<uintptr_t>(dout)) % sample_bytes != 0) return fail(c, RDR_ERR_INVALID, "rdr_tiff_assemble: buffers must be aligned to the sample size");
+    if (predictor == 1 && !swap && tiles_x == 1 && tiles_y == 1 && tile_w == width && (bands == 1 || planar == 2)) {
+        // one strip (per plane) that is the raster already: a copy per output band
+        for (int64_t b = 0; b < nout; ++b)
+            HIPCHECK(c, hipMemcpyAsync((char*)dout + b * (out_bytes / nout), (const char*)dsegs + (band < 0 ? b : band) * seg_stride, out_bytes / nout,
+                                       hipMemcpyDeviceToDevice, c->stream));
+    } else {
+        const TiffLayout L{height, width, tile_h, tile_w, tiles_x, tiles_y, seg_stride, bands, planar, band, predictor, swap != 0};
+        const int64_t nrows = (planar == 2 && band < 0 ? bands : 1) * tiles_x * tiles_y * tile_h;
+        const dim3 G(grid_for(nrows, 4, c->num_cus * 16)), B(256);
+        if (sample_bytes == 1) hipLaunchKernelGGL(tiff_assemble_kernel<uint8_t>, G, B, 0, c->stream, (const uint8_t*)dsegs, L, (uint8_t*)dout);
+        else if (sample_bytes == 2) hipLaunchKernelGGL(tiff_assemble_kernel<uint16_t>, G, B, 0, c->stream, (const uint8_t*)dsegs, L, (uint16_t*)dout);
+        else if (sample_bytes == 4) hipLaunchKernelGGL(tiff_assemble_kernel<uint32_t>, G, B, 0, c->stream, (const uint8_t*)dsegs, L, (uint32_t*)dout);
+        else hipLaunchKernelGGL(tiff_assemble_kernel<uint64_t>, G, B, 0, c->stream, (const uint8_t*)dsegs, L, (uint64_t*)dout);
+        HIPCHECK(c, hipGetLastError());
+    }
+    rc = finish_out(c, out, dout, out_bytes, loc); if (rc) return rc;
     if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
     return RDR_OK;
 }

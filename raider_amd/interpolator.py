@@ -33,6 +33,11 @@ def _is_dev(a):
     return hasattr(a, 'data_ptr')
 
 
+def _points_device(*pts):
+    """The GPU the query points live on, or None for host points."""
+    return next((t.device for t in pts if _is_dev(t) and t.is_cuda), None)
+
+
 def _raster_native(a):
     """The raster as the kernels read it: C-contiguous int16 / float32 / float64 in native byte order (anything else as float64)."""
     if _is_dev(a):
@@ -46,17 +51,28 @@ def _raster_native(a):
     return np.ascontiguousarray(a, dtype=np.dtype(name)), _RASTER_DTYPES[name]
 
 
-def _dem_arg(dem):
-    """(array, geotransform) of `dem`: a path (read through rawraster: band 1; the file must say where it lies, in lon / lat) or an
-    (array, geotransform) pair."""
+def _tiff_on_device(dem, device):
+    """(tensor, profile) of band 1 of a GeoTIFF decoded on `device`, or None when the file is not one / rasterio is there to read it."""
+    import importlib.util
+    from pathlib import Path
+    from .tifflite import is_tiff, read
+    if importlib.util.find_spec('rasterio') is not None or Path(f'{dem}.vrt').exists() or not is_tiff(dem):
+        return None
+    return read(dem, band=1, device=device)
+
+
+def _dem_arg(dem, device=None):
+    """(array, geotransform) of `dem`: a path (read through rawraster / tifflite: band 1; the file must say where it lies, in lon / lat)
+    or an (array, geotransform) pair.  device: where the query points live - a GeoTIFF is then decoded there and never exists on the host."""
     if isinstance(dem, (tuple, list)) and len(dem) == 2 and not isinstance(dem[0], (str, bytes)):
         return dem[0], tuple(float(v) for v in dem[1])
     from .rawraster import rio_open
     from .delay import _is_4326
-    data, prof = rio_open(dem, band=1)
+    got = _tiff_on_device(dem, device) if device is not None else None
+    data, prof = got if got is not None else rio_open(dem, band=1)
     gt = prof.get('transform')
     if gt is None:
-        raise ValueError(f'{dem}: the raster carries no geotransform (an ENVI `map info` or a VRT <GeoTransform>), so it cannot serve as a DEM')
+        raise ValueError(f'{dem}: the raster carries no geotransform (a GeoTIFF tie point, an ENVI `map info` or a VRT <GeoTransform>), so it cannot serve as a DEM')
     gt = tuple(gt.to_gdal()) if hasattr(gt, 'to_gdal') else tuple(float(v) for v in gt)
     crs = prof.get('crs')
     if crs is not None and not _is_4326(crs):
@@ -141,7 +157,7 @@ def raster_bounds(a, b=None, nodata=None):
 def interpolate_elevation(dem, x, y):
     """interpolator.py:154-184: the DEM pixel each (x = lon, y = lat) falls in, any shape, NaN outside the raster.  dem: a path or an
     (array, geotransform) pair.  No-data heights come through unchanged, as in the reference."""
-    raster, gt = _dem_arg(dem)
+    raster, gt = _dem_arg(dem, _points_device(x, y))
     return raster_sample(raster, gt, x, y, 'nearest')
 
 
@@ -154,5 +170,5 @@ def interpolateDEM(dem, outLL, method='nearest'):
     lats, lons = outLL
     if len(lats.shape) == 2:
         return interpolate_elevation(dem, lons, lats)
-    raster, gt = _dem_arg(dem)
+    raster, gt = _dem_arg(dem, _points_device(lons, lats))
     return raster_sample(raster, gt, lons, lats, 'linear')

@@ -9,8 +9,9 @@ ISCE's products is a headerless binary array described by a side-car:
   * `<file>.hdr` / `<stem>.hdr`  ENVI header: samples, lines, bands, data type, interleave (bsq / bil / bip), byte order,
                   header offset.
 
-`rio_open` prefers `<file>.vrt` when it exists; so does this reader.  GeoTIFF, NetCDF sub-datasets and everything else GDAL
-reads are NOT handled here (rasterio is used for them when it is installed).  Returns what rasterio returns: `read()` gives
+`rio_open` prefers `<file>.vrt` when it exists; so does this reader.  GeoTIFFs go to raider_amd.tifflite (open_raster looks at the
+first four bytes); NetCDF sub-datasets and everything else GDAL reads are NOT handled here (rasterio is used for them when it is
+installed).  Returns what rasterio returns: `read()` gives
 (bands, rows, cols) in the file's element type; `profile` carries width / height / count / dtype / nodata and, where the side-car
 names them, `transform` (GDAL's six numbers, from the VRT's <GeoTransform> or the ENVI header's `map info`) and `crs` (an EPSG code or a
 PROJ-style dict, from the VRT's <SRS> or the `map info` datum / UTM zone); a raster without either keeps None."""
@@ -206,7 +207,7 @@ class RawRaster:
         else:
             hdr = _find_envi_header(path)
             if hdr is None or path.suffix.lower() == '.hdr':
-                raise NotARawRaster(f'{path}: no .vrt or ENVI .hdr beside it (GeoTIFF / NetCDF rasters need rasterio)')
+                raise NotARawRaster(f'{path}: no .vrt or ENVI .hdr beside it, and not a TIFF (NetCDF rasters need rasterio)')
             self._data, self.nodatavals = _read_envi(path, hdr)
             gt, crs = _envi_georef(hdr)
         self.nodatavals = tuple(self.nodatavals)
@@ -225,10 +226,14 @@ class RawRaster:
 
 
 def open_raster(path):
-    """rasterio.open when rasterio is installed (the reference's reader), else the built-in raw-raster reader."""
+    """rasterio.open when rasterio is installed (the reference's reader); else a file that starts with a TIFF / BigTIFF header goes to
+    the built-in GeoTIFF reader (tifflite) and everything else to the built-in raw-raster reader."""
     try:
         import rasterio
     except ImportError:
+        from .tifflite import TiffRaster, is_tiff
+        if is_tiff(path) and not Path(str(path) + '.vrt').exists():      # (a `<file>.vrt` beside it describes the file: RawRaster's rule, and _dem_arg's)
+            return TiffRaster(path)
         return RawRaster(path)
     return rasterio.open(path)
 

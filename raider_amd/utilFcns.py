@@ -131,19 +131,25 @@ def transverse_mercator(a_in, b_in, params, inverse=False):
 
 
 def rio_open(path, userNDV=None, band=None):
-    """utilFcns.py:164-202 (rasterio when installed, else flat-binary rasters with a .vrt / ENVI .hdr side-car)."""
+    """utilFcns.py:164-202 (rasterio when installed, else GeoTIFFs and flat-binary rasters with a .vrt / ENVI .hdr side-car)."""
     from .rawraster import rio_open as _rio_open
     return _rio_open(path, userNDV=userNDV, band=band)
 
 
+def _raster_dtype(array):
+    """utilFcns.py:257-304: what a delay raster is written as - float -> float32, complex -> complex64, anything else -> uint8."""
+    return np.complex64 if 'complex' in str(array.dtype) else (np.float32 if 'float' in str(array.dtype) else np.uint8)
+
+
 def writeArrayToRaster(array, path, noDataValue=0.0, fmt='ENVI', proj=None, gt=None):
     """utilFcns.py:257-304: a 2-D array as a GDAL-readable raster (float -> float32, complex -> complex64, anything else -> uint8).
-    rasterio writes it when installed; without it the ENVI format is written natively (flat binary + .hdr), other formats raise."""
+    rasterio writes it when installed; without it the ENVI format is written natively (flat binary + .hdr), other formats raise
+    (writeDelays writes GTiff without rasterio through raider_amd.tifflite; this function's contract is left as it was)."""
     from pathlib import Path
     array = np.asarray(array)
     if array.ndim != 2:
         raise RuntimeError(f'writeArrayToRaster: cannot write an array of shape {np.shape(array)} to a raster image')
-    dtype = np.complex64 if 'complex' in str(array.dtype) else (np.float32 if 'float' in str(array.dtype) else np.uint8)
+    dtype = _raster_dtype(array)
     path = Path(path)
     if fmt == 'nc':
         fmt = 'GTiff'; path = path.with_suffix('.tif')
@@ -168,6 +174,20 @@ def writeArrayToRaster(array, path, noDataValue=0.0, fmt='ENVI', proj=None, gt=N
     write_envi(array.astype(dtype), path, nodata=noDataValue, geotransform=gt, proj=proj)
 
 
+def _write_delay_raster(array, path, ndv, fmt, proj, gt):
+    """One delay raster of writeDelays: writeArrayToRaster, except that GTiff - the reference's default raster_format - is written by
+    raider_amd.tifflite (deflate strips; the element type by writeArrayToRaster's rule, complex refused by name) when rasterio is not installed."""
+    import importlib.util
+    if str(fmt).upper() == 'GTIFF' and importlib.util.find_spec('rasterio') is None:
+        from .tifflite import write as write_tiff
+        array = np.asarray(array)
+        if array.ndim != 2:
+            raise RuntimeError(f'writeArrayToRaster: cannot write an array of shape {np.shape(array)} to a raster image')
+        write_tiff(path, array.astype(_raster_dtype(array)), transform=gt, crs=proj, nodata=ndv, compress='deflate')     # (complex64: refused by name there)
+        return
+    writeArrayToRaster(array, path, noDataValue=ndv, fmt=fmt, proj=proj, gt=gt)
+
+
 def writeDelays(aoi, wetDelay, hydroDelay, wet_path, hydro_path=None, outformat=None, ndv=0.0):
     """utilFcns.py:431-464: station AOIs -> the station CSV with wetDelay / hydroDelay / totalDelay columns; raster AOIs -> two rasters."""
     from pathlib import Path
@@ -186,8 +206,8 @@ def writeDelays(aoi, wetDelay, hydroDelay, wet_path, hydro_path=None, outformat=
         raise ValueError('Hydro delay file path must be specified if the AOI is not a station file')
     proj = aoi.projection() if hasattr(aoi, 'projection') else None
     gt = aoi.geotransform() if hasattr(aoi, 'geotransform') else None
-    writeArrayToRaster(wetDelay, Path(wet_path), noDataValue=ndv, fmt=outformat or 'ENVI', proj=proj, gt=gt)
-    writeArrayToRaster(hydroDelay, Path(hydro_path), noDataValue=ndv, fmt=outformat or 'ENVI', proj=proj, gt=gt)
+    _write_delay_raster(wetDelay, Path(wet_path), ndv, outformat or 'ENVI', proj, gt)
+    _write_delay_raster(hydroDelay, Path(hydro_path), ndv, outformat or 'ENVI', proj, gt)
 
 
 # ---- what llreader.py takes from utilFcns: bounding boxes and raster metadata (utilFcns.py:140-161, 213-254, 586-630) -----------
