@@ -1,4 +1,7 @@
 // Cube packing / blending, look vectors, zenith gathers, partition exchange, azimuth-time weights.
+// The point gathers (interp_points_*_kernel, and interp_points_epochs_kernel of epoch_kernels.h) share ONE body, gather_points below; a
+// route is its corner source (PlainCorners, PairCorners, BlendCorners, QuadCorners).  The cell search, the weights and the corner sum it
+// calls are in raider_kernels.h, next to find_cell.
 // Part of libraider_hip.so (single translation unit: included by raider_hip.hip).  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -230,10 +233,74 @@ struct PointQuery {
         if (x) { py = y[i]; px = x[i]; pz = z[i]; }
         else { py = y[3 * i]; px = y[3 * i + 1]; pz = y[3 * i + 2]; }
     }
-    __device__ __forceinline__ void store(int64_t i, double w, double h, double* __restrict__ wet, double* __restrict__ hyd) const {
-        if (pmode) { const double up = project_divisor(pmode, proj, inc0, i); w = w / up; h = h / up; }
-        if (wet) wet[i] = w;
-        if (hyd) hyd[i] = h;
+    // Point i of E epochs, epoch-major: wet[e * estride + i], hyd[e * estride + i].  pstride 0: one divisor proj[i] for every epoch, made
+    // once; else proj[e * pstride + i] (Conventional with an orbit file: setTime per date, so the divisor may differ by date).
+    template <int E>
+    __device__ __forceinline__ void store(int64_t i, const double (&sw)[E], const double (&sh)[E], int64_t pstride, int64_t estride,
+                                          double* __restrict__ wet, double* __restrict__ hyd) const {
+        const bool shared = pstride == 0;
+        double up0 = 1.0;
+        if (pmode && shared) up0 = project_divisor(pmode, proj, inc0, i);
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            double w = sw[e], h = sh[e];
+            if (pmode) {
+                const double up = shared ? up0 : project_divisor(pmode, proj + e * pstride, inc0, i);
+                w = w / up; h = h / up;
+            }
+            if (wet) wet[e * estride + i] = w;
+            if (hyd) hyd[e * estride + i] = h;
+        }
+    }
+};
+
+// ---- the point gather: ONE body for every route -----------------------------------------------------------------------------
+// scipy RGI __call__ at query points, one point per lane.  Per point the bounds test, the cell search and the weights run once
+// (locate, corner_weights: raider_kernels.h); then per epoch e the corner source src[e] fills the eight (wet, hydro) corners of the
+// located cell, in lexicographic (y, x, z) order, and corner_sum adds them up; PointQuery::store divides and writes.  A route is
+// its corner source and nothing else, so the routes agree bit for bit - with each other and, per epoch, with the one-cube call.
+template <int E, typename T2, typename Src>
+__device__ __forceinline__ void gather_points(const CubeView<T2>& c, const Src (&src)[E], const PointQuery& Q, int64_t pstride, int64_t n, int64_t estride,
+                                              double* __restrict__ wet, double* __restrict__ hyd, int axes_in_lds) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const GatherAxes s = gather_axes(c, smem_raw, axes_in_lds);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        double y, x, z;
+        Q.point(i, y, x, z);
+        double sw[E], sh[E];
+        // (initialised: with L undefined on the outside path the compiler vectorises the corner sum of the f32 kernels in (wet, hydro) pairs
+        // and the date-series kernels grow to as many as 154 VGPRs, NOTES.md)
+        GatherCell L = {};
+        if (locate(c, s, y, x, z, L)) {
+            double k[8];
+            corner_weights(L.ty, L.tx, L.tz, k);
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                double w[8], h[8];
+                src[e].corners(c, L.iy, L.ix, L.iz, w, h);
+                corner_sum(w, h, k, sw[e], sh[e]);
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < E; ++e) { sw[e] = qnan(); sh[e] = qnan(); }
+        }
+        Q.store(i, sw, sh, pstride, estride, wet, hyd);
+    }
+}
+
+// the (y, x, z) cube itself: the two z neighbours of a column are one contiguous read
+template <typename T2>
+struct PlainCorners {
+    const T2* v;
+    __device__ __forceinline__ void corners(const CubeView<T2>& c, int iy, int ix, int iz, double (&w)[8], double (&h)[8]) const {
+        const int64_t o00 = ((int64_t)iy * c.nx + ix) * c.nz + iz;     // (y0,x0)
+        const int64_t o01 = o00 + c.nz;                                // (y0,x1)
+        const int64_t o10 = o00 + (int64_t)c.nx * c.nz;                // (y1,x0)
+        const int64_t o11 = o10 + c.nz;                                // (y1,x1)
+        ld2(v + o00, w[0], h[0]); ld2(v + o00 + 1, w[1], h[1]);
+        ld2(v + o01, w[2], h[2]); ld2(v + o01 + 1, w[3], h[3]);
+        ld2(v + o10, w[4], h[4]); ld2(v + o10 + 1, w[5], h[5]);
+        ld2(v + o11, w[6], h[6]); ld2(v + o11 + 1, w[7], h[7]);
     }
 };
 
@@ -241,23 +308,8 @@ struct PointQuery {
 template <typename T2>
 __global__ __launch_bounds__(256) void interp_points_kernel(CubeView<T2> c, PointQuery Q, int64_t n,
                                                             double* __restrict__ wet, double* __restrict__ hyd, int axes_in_lds) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const double* s_y = c.axes;                       // very long axes stay in global memory (L1 / L2 hits)
-    if (axes_in_lds) {
-        double* t = reinterpret_cast<double*>(smem_raw);
-        for (int i = threadIdx.x; i < c.ny + c.nx + c.nz; i += blockDim.x) t[i] = c.axes[i];
-        __syncthreads();
-        s_y = t;
-    }
-    const double* s_x = s_y + c.ny;
-    const double* s_z = s_x + c.nx;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        double y, x, z;
-        Q.point(i, y, x, z);
-        double w, h;
-        trilinear(c, s_y, s_x, s_z, y, x, z, w, h);
-        Q.store(i, w, h, wet, hyd);
-    }
+    const PlainCorners<T2> src[1] = {{c.v}};
+    gather_points<1>(c, src, Q, 0, n, 0, wet, hyd, axes_in_lds);
 }
 
 // ---- the two-epoch blend made FOR the point gather (round 6) -----------------------------------------------------------------------------
@@ -301,125 +353,76 @@ __global__ __launch_bounds__(256) void blend_pair_kernel(const T2* __restrict__ 
     }
 }
 
-// scipy RGI (trilinear<> of raider_kernels.h, the same weights, corner order and sum) on a PAIRED cube
+// corners from a PAIRED cube (blend_pair_kernel's layout)
+template <typename T2>
+struct PairCorners {
+    const T2* P;
+    __device__ __forceinline__ void corners(const CubeView<T2>& c, int iy, int ix, int iz, double (&w)[8], double (&h)[8]) const {
+        // Whole 16-byte (f32) pair entries, addressed without a data-dependent pointer (left to per-corner selects of ADDRESSES the compiler
+        // issues sixteen 4-byte loads): entries e, e+1 = levels iz, iz+1 of pair px - both x columns of an even cell; an odd cell takes
+        // their odd halves and the even halves of the next pair's entries (two more loads, for those lanes only).
+        typedef decltype(T2().x) T;
+        typedef T V4 __attribute__((ext_vector_type(4)));
+        const V4* P4 = reinterpret_cast<const V4*>(P);
+        const int npx = (c.nx + 1) >> 1;
+        const int px = ix >> 1;
+        const bool even = (ix & 1) == 0;
+        T2 v[8];                                   // corners in (y, x, z) lexicographic order
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int64_t e = ((int64_t)(iy + r) * npx + px) * c.nz + iz;
+            const V4 E0 = P4[e], E1 = P4[e + 1];
+            V4 F0 = E0, F1 = E1;
+            if (!even) { F0 = P4[e + c.nz]; F1 = P4[e + c.nz + 1]; }
+            v[4 * r + 0].x = even ? E0[0] : E0[2]; v[4 * r + 0].y = even ? E0[1] : E0[3];       // (x0, z0)
+            v[4 * r + 1].x = even ? E1[0] : E1[2]; v[4 * r + 1].y = even ? E1[1] : E1[3];       // (x0, z1)
+            v[4 * r + 2].x = even ? E0[2] : F0[0]; v[4 * r + 2].y = even ? E0[3] : F0[1];       // (x1, z0)
+            v[4 * r + 3].x = even ? E1[2] : F1[0]; v[4 * r + 3].y = even ? E1[3] : F1[1];       // (x1, z1)
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { w[j] = (double)v[j].x; h[j] = (double)v[j].y; }
+    }
+};
+
 template <typename T2>
 __global__ __launch_bounds__(256) void interp_points_pair_kernel(CubeView<T2> c, const T2* __restrict__ P, PointQuery Q, int64_t n,
                                                                  double* __restrict__ wet, double* __restrict__ hyd, int axes_in_lds) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const double* s_y = c.axes;
-    if (axes_in_lds) {
-        double* t = reinterpret_cast<double*>(smem_raw);
-        for (int i = threadIdx.x; i < c.ny + c.nx + c.nz; i += blockDim.x) t[i] = c.axes[i];
-        __syncthreads();
-        s_y = t;
-    }
-    const double* s_x = s_y + c.ny;
-    const double* s_z = s_x + c.nx;
-    const int npx = (c.nx + 1) >> 1;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        double y, x, z;
-        Q.point(i, y, x, z);
-        double sw = qnan(), sh = qnan();
-        const bool inside = (y >= c.y_lo) && (y <= c.y_hi) && (x >= c.x_lo) && (x <= c.x_hi) && (z >= c.z_lo) && (z <= c.z_hi);
-        if (inside) {
-            const int iy = find_cell(s_y, c.ny, y, c.y_lo, c.inv_dy, c.uni_y);
-            const int ix = find_cell(s_x, c.nx, x, c.x_lo, c.inv_dx, c.uni_x);
-            const int iz = find_cell(s_z, c.nz, z, c.z_lo, c.inv_dz, c.uni_z);
-            const double ty = (y - s_y[iy]) / (s_y[iy + 1] - s_y[iy]);
-            const double tx = (x - s_x[ix]) / (s_x[ix + 1] - s_x[ix]);
-            const double tz = (z - s_z[iz]) / (s_z[iz + 1] - s_z[iz]);
-            // Whole 16-byte (f32) pair entries, addressed without a data-dependent pointer (left to per-corner selects of ADDRESSES the compiler
-            // issues sixteen 4-byte loads): entries e, e+1 = levels iz, iz+1 of pair px - both x columns of an even cell; an odd cell takes
-            // their odd halves and the even halves of the next pair's entries (two more loads, for those lanes only).
-            typedef decltype(T2().x) T;
-            typedef T V4 __attribute__((ext_vector_type(4)));
-            const V4* P4 = reinterpret_cast<const V4*>(P);
-            const int px = ix >> 1;
-            const bool even = (ix & 1) == 0;
-            T2 v[8];                                   // corners in (y, x, z) lexicographic order
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                const int64_t e = ((int64_t)(iy + r) * npx + px) * c.nz + iz;
-                const V4 E0 = P4[e], E1 = P4[e + 1];
-                V4 F0 = E0, F1 = E1;
-                if (!even) { F0 = P4[e + c.nz]; F1 = P4[e + c.nz + 1]; }
-                v[4 * r + 0].x = even ? E0[0] : E0[2]; v[4 * r + 0].y = even ? E0[1] : E0[3];       // (x0, z0)
-                v[4 * r + 1].x = even ? E1[0] : E1[2]; v[4 * r + 1].y = even ? E1[1] : E1[3];       // (x0, z1)
-                v[4 * r + 2].x = even ? E0[2] : F0[0]; v[4 * r + 2].y = even ? E0[3] : F0[1];       // (x1, z0)
-                v[4 * r + 3].x = even ? E1[2] : F1[0]; v[4 * r + 3].y = even ? E1[3] : F1[1];       // (x1, z1)
-            }
-            const double wy0 = 1.0 - ty, wx0 = 1.0 - tx, wz0 = 1.0 - tz;
-            const double a00 = wy0 * wx0, a01 = wy0 * tx, a10 = ty * wx0, a11 = ty * tx;
-            const double k[8] = {a00 * wz0, a00 * tz, a01 * wz0, a01 * tz, a10 * wz0, a10 * tz, a11 * wz0, a11 * tz};
-            sw = 0.0; sh = 0.0;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { sw += (double)v[j].x * k[j]; sh += (double)v[j].y * k[j]; }
-        }
-        Q.store(i, sw, sh, wet, hyd);
-    }
+    const PairCorners<T2> src[1] = {{P}};
+    gather_points<1>(c, src, Q, 0, n, 0, wet, hyd, axes_in_lds);
 }
 
 // The two-epoch temporal interpolation (cli/raider.py:817-819) applied ON THE FLY at the eight corners of every query point instead of
 // to the whole cube first: corner = w1 * a + w2 * b in the cube's own dtype, the two products rounded separately - exactly blend_kernel's
-// arithmetic - then the gather of trilinear<>: the same bits as blend-then-gather.  Reads eight lines per point instead of four but
+// arithmetic - then the gather every route shares: the same bits as blend-then-gather.  Reads eight lines per point instead of four but
 // never touches the 24 B per cell of a blend: it wins when a rank queries fewer points than ~5 % of the cube's cells - the station block of
 // one rank of an 8-GPU job (BASELINE configs[4]: 625 k of 5 M stations on a 50 M-cell cube), where the replicated blend is what stops
 // the job from scaling.
 template <typename T2>
+struct BlendCorners {
+    typedef decltype(T2().x) T;
+    const T2 *va, *vb;
+    T w1, w2;
+    __device__ __forceinline__ void corners(const CubeView<T2>& c, int iy, int ix, int iz, double (&w)[8], double (&h)[8]) const {
+        const int64_t o00 = ((int64_t)iy * c.nx + ix) * c.nz + iz;
+        const int64_t off[4] = {o00, o00 + c.nz, o00 + (int64_t)c.nx * c.nz, o00 + (int64_t)c.nx * c.nz + c.nz};
+        T2 a[8], b[8];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { a[2 * k] = va[off[k]]; a[2 * k + 1] = va[off[k] + 1]; b[2 * k] = vb[off[k]]; b[2 * k + 1] = vb[off[k] + 1]; }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+#pragma clang fp contract(off)
+            const T pw = w1 * a[k].x, qw = w2 * b[k].x, ph = w1 * a[k].y, qh = w2 * b[k].y;
+            w[k] = (double)(T)(pw + qw); h[k] = (double)(T)(ph + qh);
+        }
+    }
+};
+
+template <typename T2>
 __global__ __launch_bounds__(256) void interp_points_blend_kernel(CubeView<T2> c, const T2* __restrict__ vb, double w1d, double w2d, PointQuery Q, int64_t n,
                                                                   double* __restrict__ wet, double* __restrict__ hyd, int axes_in_lds) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     typedef decltype(T2().x) T;
-    const T w1 = (T)w1d, w2 = (T)w2d;
-    const double* s_y = c.axes;
-    if (axes_in_lds) {
-        double* t = reinterpret_cast<double*>(smem_raw);
-        for (int i = threadIdx.x; i < c.ny + c.nx + c.nz; i += blockDim.x) t[i] = c.axes[i];
-        __syncthreads();
-        s_y = t;
-    }
-    const double* s_x = s_y + c.ny;
-    const double* s_z = s_x + c.nx;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        double y, x, z;
-        Q.point(i, y, x, z);
-        double sw = qnan(), sh = qnan();
-        const bool inside = (y >= c.y_lo) && (y <= c.y_hi) && (x >= c.x_lo) && (x <= c.x_hi) && (z >= c.z_lo) && (z <= c.z_hi);
-        if (inside) {
-            const int iy = find_cell(s_y, c.ny, y, c.y_lo, c.inv_dy, c.uni_y);
-            const int ix = find_cell(s_x, c.nx, x, c.x_lo, c.inv_dx, c.uni_x);
-            const int iz = find_cell(s_z, c.nz, z, c.z_lo, c.inv_dz, c.uni_z);
-            const double ty = (y - s_y[iy]) / (s_y[iy + 1] - s_y[iy]);
-            const double tx = (x - s_x[ix]) / (s_x[ix + 1] - s_x[ix]);
-            const double tz = (z - s_z[iz]) / (s_z[iz + 1] - s_z[iz]);
-            const int64_t o00 = ((int64_t)iy * c.nx + ix) * c.nz + iz;
-            const int64_t off[4] = {o00, o00 + c.nz, o00 + (int64_t)c.nx * c.nz, o00 + (int64_t)c.nx * c.nz + c.nz};
-            T2 a[8], b[8];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { a[2 * k] = c.v[off[k]]; a[2 * k + 1] = c.v[off[k] + 1]; b[2 * k] = vb[off[k]]; b[2 * k + 1] = vb[off[k] + 1]; }
-            double w[8], h[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-#pragma clang fp contract(off)
-                const T pw = w1 * a[k].x, qw = w2 * b[k].x, ph = w1 * a[k].y, qh = w2 * b[k].y;
-                w[k] = (double)(T)(pw + qw); h[k] = (double)(T)(ph + qh);
-            }
-            const double wy0 = 1.0 - ty, wx0 = 1.0 - tx, wz0 = 1.0 - tz;
-            const double a00 = wy0 * wx0, a01 = wy0 * tx, a10 = ty * wx0, a11 = ty * tx;
-            const double k0 = a00 * wz0, k1 = a00 * tz, k2 = a01 * wz0, k3 = a01 * tz;
-            const double k4 = a10 * wz0, k5 = a10 * tz, k6 = a11 * wz0, k7 = a11 * tz;
-            sw = 0.0; sh = 0.0;
-            sw += w[0] * k0; sh += h[0] * k0;
-            sw += w[1] * k1; sh += h[1] * k1;
-            sw += w[2] * k2; sh += h[2] * k2;
-            sw += w[3] * k3; sh += h[3] * k3;
-            sw += w[4] * k4; sh += h[4] * k4;
-            sw += w[5] * k5; sh += h[5] * k5;
-            sw += w[6] * k6; sh += h[6] * k6;
-            sw += w[7] * k7; sh += h[7] * k7;
-        }
-        Q.store(i, sw, sh, wet, hyd);
-    }
+    const BlendCorners<T2> src[1] = {{c.v, vb, (T)w1d, (T)w2d}};
+    gather_points<1>(c, src, Q, 0, n, 0, wet, hyd, axes_in_lds);
 }
 
 // ---- station queries on a cube that fits no cache: the corner-quad copy ----------------------------------------------------
@@ -496,75 +499,44 @@ __global__ __launch_bounds__(256) void quad_build_kernel(const T2* __restrict__ 
     }
 }
 
-// the same interpolant as interp_points_kernel / trilinear<> (cell search, weights, summation order: bit-identical results), corners
-// from the quad copy: 64 contiguous bytes of one block for an f32 cube, the whole 128 B block for an f64 one
+// corners from the quad copy: 64 contiguous bytes of one block for an f32 cube, the whole 128 B block for an f64 one
+template <typename T2>
+struct QuadCorners {
+    const uint4* q; int nblk;
+    __device__ __forceinline__ void corners(const CubeView<T2>& c, int iy, int ix, int iz, double (&w)[8], double (&h)[8]) const {
+        const int j = iz / Quad<T2>::CPB, l0 = iz - j * Quad<T2>::CPB;
+        const uint4* blk = q + (((int64_t)iy * (c.nx - 1) + ix) * nblk + j) * 8;
+        if constexpr (sizeof(T2) == 8) {
+            const uint4 A = blk[2 * l0], B = blk[2 * l0 + 1], C = blk[2 * l0 + 2], D = blk[2 * l0 + 3];
+            w[0] = (double)__uint_as_float(A.x); h[0] = (double)__uint_as_float(A.y); w[2] = (double)__uint_as_float(A.z); h[2] = (double)__uint_as_float(A.w);
+            w[4] = (double)__uint_as_float(B.x); h[4] = (double)__uint_as_float(B.y); w[6] = (double)__uint_as_float(B.z); h[6] = (double)__uint_as_float(B.w);
+            w[1] = (double)__uint_as_float(C.x); h[1] = (double)__uint_as_float(C.y); w[3] = (double)__uint_as_float(C.z); h[3] = (double)__uint_as_float(C.w);
+            w[5] = (double)__uint_as_float(D.x); h[5] = (double)__uint_as_float(D.y); w[7] = (double)__uint_as_float(D.z); h[7] = (double)__uint_as_float(D.w);
+        } else {
+#pragma unroll
+            for (int cc = 0; cc < 4; ++cc)
+#pragma unroll
+                for (int l = 0; l < 2; ++l) {
+                    const uint4 P = blk[l * 4 + cc];
+                    w[2 * cc + l] = __longlong_as_double((long long)(((unsigned long long)P.y << 32) | P.x));
+                    h[2 * cc + l] = __longlong_as_double((long long)(((unsigned long long)P.w << 32) | P.z));
+                }
+        }
+    }
+};
+
 template <typename T2>
 __global__ __launch_bounds__(256) void interp_points_quad_kernel(CubeView<T2> c, const uint4* __restrict__ q, int nblk, PointQuery Q,
                                                                  int64_t n, double* __restrict__ wet, double* __restrict__ hyd, int axes_in_lds) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const double* s_y = c.axes;
-    if (axes_in_lds) {
-        double* t = reinterpret_cast<double*>(smem_raw);
-        for (int i = threadIdx.x; i < c.ny + c.nx + c.nz; i += blockDim.x) t[i] = c.axes[i];
-        __syncthreads();
-        s_y = t;
-    }
-    const double* s_x = s_y + c.ny;
-    const double* s_z = s_x + c.nx;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        double y, x, z;
-        Q.point(i, y, x, z);
-        double sw = qnan(), sh = qnan();
-        const bool inside = (y >= c.y_lo) && (y <= c.y_hi) && (x >= c.x_lo) && (x <= c.x_hi) && (z >= c.z_lo) && (z <= c.z_hi);
-        if (inside) {
-            const int iy = find_cell(s_y, c.ny, y, c.y_lo, c.inv_dy, c.uni_y);
-            const int ix = find_cell(s_x, c.nx, x, c.x_lo, c.inv_dx, c.uni_x);
-            const int iz = find_cell(s_z, c.nz, z, c.z_lo, c.inv_dz, c.uni_z);
-            const double ty = (y - s_y[iy]) / (s_y[iy + 1] - s_y[iy]);
-            const double tx = (x - s_x[ix]) / (s_x[ix + 1] - s_x[ix]);
-            const double tz = (z - s_z[iz]) / (s_z[iz + 1] - s_z[iz]);
-            const int j = iz / Quad<T2>::CPB, l0 = iz - j * Quad<T2>::CPB;
-            const uint4* blk = q + (((int64_t)iy * (c.nx - 1) + ix) * nblk + j) * 8;
-            double w[8], h[8];
-            if constexpr (sizeof(T2) == 8) {
-                const uint4 A = blk[2 * l0], B = blk[2 * l0 + 1], C = blk[2 * l0 + 2], D = blk[2 * l0 + 3];
-                w[0] = (double)__uint_as_float(A.x); h[0] = (double)__uint_as_float(A.y); w[2] = (double)__uint_as_float(A.z); h[2] = (double)__uint_as_float(A.w);
-                w[4] = (double)__uint_as_float(B.x); h[4] = (double)__uint_as_float(B.y); w[6] = (double)__uint_as_float(B.z); h[6] = (double)__uint_as_float(B.w);
-                w[1] = (double)__uint_as_float(C.x); h[1] = (double)__uint_as_float(C.y); w[3] = (double)__uint_as_float(C.z); h[3] = (double)__uint_as_float(C.w);
-                w[5] = (double)__uint_as_float(D.x); h[5] = (double)__uint_as_float(D.y); w[7] = (double)__uint_as_float(D.z); h[7] = (double)__uint_as_float(D.w);
-            } else {
-#pragma unroll
-                for (int cc = 0; cc < 4; ++cc)
-#pragma unroll
-                    for (int l = 0; l < 2; ++l) {
-                        const uint4 P = blk[l * 4 + cc];
-                        w[2 * cc + l] = __longlong_as_double((long long)(((unsigned long long)P.y << 32) | P.x));
-                        h[2 * cc + l] = __longlong_as_double((long long)(((unsigned long long)P.w << 32) | P.z));
-                    }
-            }
-            const double wy0 = 1.0 - ty, wx0 = 1.0 - tx, wz0 = 1.0 - tz;
-            const double a00 = wy0 * wx0, a01 = wy0 * tx, a10 = ty * wx0, a11 = ty * tx;
-            const double k0 = a00 * wz0, k1 = a00 * tz, k2 = a01 * wz0, k3 = a01 * tz;
-            const double k4 = a10 * wz0, k5 = a10 * tz, k6 = a11 * wz0, k7 = a11 * tz;
-            sw = 0.0; sh = 0.0;
-            sw += w[0] * k0; sh += h[0] * k0;
-            sw += w[1] * k1; sh += h[1] * k1;
-            sw += w[2] * k2; sh += h[2] * k2;
-            sw += w[3] * k3; sh += h[3] * k3;
-            sw += w[4] * k4; sh += h[4] * k4;
-            sw += w[5] * k5; sh += h[5] * k5;
-            sw += w[6] * k6; sh += h[6] * k6;
-            sw += w[7] * k7; sh += h[7] * k7;
-        }
-        Q.store(i, sw, sh, wet, hyd);
-    }
+    const QuadCorners<T2> src[1] = {{q, nblk}};
+    gather_points<1>(c, src, Q, 0, n, 0, wet, hyd, axes_in_lds);
 }
 
 constexpr int BUILD_STAGE_BYTES = 32 << 10;   // LDS staging area of build_cube_kernel: (2 levels x heights per round) x footprint columns x 16 B (8 B for f32 cubes)
 constexpr int BUILD_NCOL_MAX = 256;           // a tile footprint of more cube columns than this takes the direct loads
 
 // _build_cube (delay.py:196-216): points generated on the fly from (xpts, ypts, zpts); the arithmetic per point is that of
-// trilinear<> (scipy's weight order, _rgi.py:490-498), so the values are the same bit for bit.  Output (nz, ny, nx).  Two kernels:
+// the point gather (scipy's weight order, _rgi.py:490-498), so the values are the same bit for bit.  Output (nz, ny, nx).  Two kernels:
 //
 // build_cube_setup_kernel - everything that depends on ONE coordinate only, once: per output node (iy, ix) the model-CRS projection
 //   (LCC / polar stereographic cubes), its x / y cell and the two weights; per output height its z cell and weight.  24 B per node

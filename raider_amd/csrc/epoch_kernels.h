@@ -14,8 +14,9 @@
 // The f64 LDS staging of march_kernel (STAGED) is not carried over: with E gathers per sample in flight the direct loads are what the
 // stacked loop needs.
 //
-//   interp_points_epochs_kernel  the point gather of interp_points_kernel (cube_kernels.h) with E cubes: a date series at query points
-//                         (rdr_interp3_project_epochs, rdr_point_delays_epochs), at the end of this file.
+//   interp_points_epochs_kernel  the point gather of interp_points_kernel with E cubes: a date series at query points
+//                         (rdr_interp3_project_epochs, rdr_point_delays_epochs), at the end of this file.  Its body is gather_points
+//                         (cube_kernels.h), the one every point gather shares.
 //
 // Layout: pointer per epoch.  The E cubes share shape, axes and projection (checked on the host), so one element offset serves
 // every epoch and the corner-pair reads of an epoch are exactly the single-epoch kernel's (16 B / 32 B contiguous per corner pair).
@@ -108,86 +109,20 @@ void march_epochs_kernel(CubeView<T2> c_in, EpochCubes<T2, E> ev, RayParams P, i
 }
 
 // ---- a date series at query points (rdr_interp3_project_epochs, rdr_point_delays_epochs) ------------------------------------
-// interp_points_epochs_kernel: interp_points_kernel (cube_kernels.h) with E cubes of one grid.  One query point per lane; per point the
-// bounds test, the three cell searches, the three divisions, the eight weights and the element offset run ONCE; then per epoch the eight
-// corner loads from that epoch's own base pointer and trilinear<>'s sum (raider_kernels.h), in its corner order and operation order: the
-// same source expressions, so the compiler contracts them into the same fma chain - epoch e's values are bit for bit what
-// interp_points_kernel gives on cube e.  The plain (y, x, z) layout only: no corner quads, no paired columns.
+// interp_points_epochs_kernel: interp_points_kernel (cube_kernels.h) with E cubes of one grid - the same body, gather_points, with E plain
+// corner sources, one per epoch's base pointer.  One query point per lane; per point the bounds test, the three cell searches, the three
+// divisions and the eight weights run ONCE; then per epoch the eight corner loads and the corner sum: epoch e's values are bit for bit
+// what interp_points_kernel gives on cube e, because it is the same code.  The plain (y, x, z) layout only: no corner quads, no paired
+// columns.
 // Outputs are epoch-major: wet[e * estride + i], hyd[e * estride + i] (estride >= n: a chunk of a pipelined call keeps the full stride).
-// The projection is PointQuery::store's: pmode 0..3; pstride 0: one divisor proj[i] for every epoch, else proj[e * pstride + i]
-// (Conventional with an orbit file: setTime per date, so the divisor may differ by date).
+// The projection is PointQuery::store's: pmode 0..3; pstride 0: one divisor proj[i] for every epoch, else proj[e * pstride + i].
 template <typename T2, int E>
 __global__ __launch_bounds__(256) void interp_points_epochs_kernel(CubeView<T2> c, EpochCubes<T2, E> ev, PointQuery Q, int64_t pstride, int64_t n, int64_t estride,
                                                                    double* __restrict__ wet, double* __restrict__ hyd, int axes_in_lds) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const double* s_y = c.axes;                       // very long axes stay in global memory (L1 / L2 hits)
-    if (axes_in_lds) {
-        double* t = reinterpret_cast<double*>(smem_raw);
-        for (int i = threadIdx.x; i < c.ny + c.nx + c.nz; i += blockDim.x) t[i] = c.axes[i];
-        __syncthreads();
-        s_y = t;
-    }
-    const double* s_x = s_y + c.ny;
-    const double* s_z = s_x + c.nx;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        double y, x, z;
-        Q.point(i, y, x, z);
-        double sw[E], sh[E];
-        // out of bounds -> fill_value nan; nan coordinate -> nan (trilinear<>)
-        const bool inside = (y >= c.y_lo) && (y <= c.y_hi) && (x >= c.x_lo) && (x <= c.x_hi) && (z >= c.z_lo) && (z <= c.z_hi);
-        if (!inside) {
+    PlainCorners<T2> src[E];
 #pragma unroll
-            for (int e = 0; e < E; ++e) { sw[e] = qnan(); sh[e] = qnan(); }
-        } else {
-            const int iy = find_cell(s_y, c.ny, y, c.y_lo, c.inv_dy, c.uni_y);
-            const int ix = find_cell(s_x, c.nx, x, c.x_lo, c.inv_dx, c.uni_x);
-            const int iz = find_cell(s_z, c.nz, z, c.z_lo, c.inv_dz, c.uni_z);
-            const double ty = (y - s_y[iy]) / (s_y[iy + 1] - s_y[iy]);
-            const double tx = (x - s_x[ix]) / (s_x[ix + 1] - s_x[ix]);
-            const double tz = (z - s_z[iz]) / (s_z[iz + 1] - s_z[iz]);
-            const int64_t o00 = ((int64_t)iy * c.nx + ix) * c.nz + iz;     // (y0,x0)
-            const int64_t o01 = o00 + c.nz;                                // (y0,x1)
-            const int64_t o10 = o00 + (int64_t)c.nx * c.nz;                // (y1,x0)
-            const int64_t o11 = o10 + c.nz;                                // (y1,x1)
-            const double wy0 = 1.0 - ty, wx0 = 1.0 - tx, wz0 = 1.0 - tz;
-            const double a00 = wy0 * wx0, a01 = wy0 * tx, a10 = ty * wx0, a11 = ty * tx;
-            const double k0 = a00 * wz0, k1 = a00 * tz, k2 = a01 * wz0, k3 = a01 * tz;
-            const double k4 = a10 * wz0, k5 = a10 * tz, k6 = a11 * wz0, k7 = a11 * tz;
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const T2* p = ev.v[e];
-                double w[8], h[8];
-                ld2(p + o00, w[0], h[0]); ld2(p + o00 + 1, w[1], h[1]);
-                ld2(p + o01, w[2], h[2]); ld2(p + o01 + 1, w[3], h[3]);
-                ld2(p + o10, w[4], h[4]); ld2(p + o10 + 1, w[5], h[5]);
-                ld2(p + o11, w[6], h[6]); ld2(p + o11 + 1, w[7], h[7]);
-                double aw = 0.0, ah = 0.0;
-                aw += w[0] * k0; ah += h[0] * k0;
-                aw += w[1] * k1; ah += h[1] * k1;
-                aw += w[2] * k2; ah += h[2] * k2;
-                aw += w[3] * k3; ah += h[3] * k3;
-                aw += w[4] * k4; ah += h[4] * k4;
-                aw += w[5] * k5; ah += h[5] * k5;
-                aw += w[6] * k6; ah += h[6] * k6;
-                aw += w[7] * k7; ah += h[7] * k7;
-                sw[e] = aw; sh[e] = ah;
-            }
-        }
-        // PointQuery::store's arithmetic (delay / divisor), the shared divisor made once
-        const bool shared = pstride == 0;
-        double up0 = 1.0;
-        if (Q.pmode && shared) up0 = project_divisor(Q.pmode, Q.proj, Q.inc0, i);
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            double w = sw[e], h = sh[e];
-            if (Q.pmode) {
-                const double up = shared ? up0 : project_divisor(Q.pmode, Q.proj + e * pstride, Q.inc0, i);
-                w = w / up; h = h / up;
-            }
-            if (wet) wet[e * estride + i] = w;
-            if (hyd) hyd[e * estride + i] = h;
-        }
-    }
+    for (int e = 0; e < E; ++e) src[e].v = ev.v[e];
+    gather_points<E>(c, src, Q, pstride, n, estride, wet, hyd, axes_in_lds);
 }
 
 }  // namespace rdr

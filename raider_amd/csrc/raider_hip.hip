@@ -1,5 +1,7 @@
 // libraider_hip.so - C ABI (include/raider_hip.h) + the remaining kernels.  gfx950 only.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC raider_hip.hip -o libraider_hip.so
+// The point path (launch_interp, launch_interp_epochs, the paired blend of interp3_impl) picks its kernels' element type with by_dtype and
+// checks two cubes' grids with same_grid_dtype, both above rdr_cube_blend; the gathers' one device body is gather_points (cube_kernels.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1068,10 +1070,21 @@ int rdr_grid_geodetic(rdr_ctx* c, int grid_kind, const double* params, int npara
     return RDR_OK;
 }
 
+// the same shape, dtype and axis vectors: what the two-epoch blends and the blended point gathers ask of their cubes
+static bool same_grid_dtype(const rdr_cube* a, const rdr_cube* b) {
+    return a->ny == b->ny && a->nx == b->nx && a->nz == b->nz && a->dtype == b->dtype && a->ys == b->ys && a->xs == b->xs && a->zs == b->zs;
+}
+
+// f(float2()) or f(double2()) by the cube's dtype: a generic lambda takes the element type of its kernel from the tag (the point path)
+template <typename F>
+static void by_dtype(const rdr_cube* q, F&& f) {
+    if (q->dtype == RDR_F32) f(float2()); else f(double2());
+}
+
 int rdr_cube_blend(rdr_ctx* c, const rdr_cube* a, double w1, const rdr_cube* b, double w2, rdr_cube** out) {
     if (!c || !a || !b || !out) return fail(c, RDR_ERR_INVALID, "rdr_cube_blend: NULL argument");
     note_use(c, a); note_use(c, b);
-    if (a->ny != b->ny || a->nx != b->nx || a->nz != b->nz || a->dtype != b->dtype || a->ys != b->ys || a->xs != b->xs || a->zs != b->zs)
+    if (!same_grid_dtype(a, b))
         return fail(c, RDR_ERR_INVALID, "rdr_cube_blend: cubes are not on the same grid / dtype");
     HIPCHECK(c, hipSetDevice(c->device));
     rdr_cube* q = new rdr_cube();
@@ -1144,7 +1157,7 @@ int rdr_cube_blend_weighted(rdr_ctx* c, const rdr_cube* const* cubes, int32_t nd
         const rdr_cube* b = cubes[i];
         if (!b) return fail(c, RDR_ERR_INVALID, "rdr_cube_blend_weighted: NULL cube");
         note_use(c, b);
-        if (a->ny != b->ny || a->nx != b->nx || a->nz != b->nz || a->dtype != b->dtype || a->ys != b->ys || a->xs != b->xs || a->zs != b->zs)
+        if (!same_grid_dtype(a, b))
             return fail(c, RDR_ERR_INVALID, "rdr_cube_blend_weighted: cubes are not on the same grid / dtype");
         S.v[i] = b->d_vals;
     }
@@ -1314,33 +1327,20 @@ struct BlendSpec { const void* vb = nullptr; double w1 = 1.0, w2 = 0.0; const vo
 static void launch_interp(rdr_ctx* c, const rdr_cube* q, const PointQuery& Qk, int64_t cnt, double* dwk, double* dhk, bool quad, const BlendSpec& B = BlendSpec()) {
     const int g = grid_for(cnt, 256, c->num_cus * 8);
     KTimer t(c, 2);
-    if (B.pair) {
-        if (q->dtype == RDR_F32)
-            hipLaunchKernelGGL((interp_points_pair_kernel<float2>), dim3(g), dim3(256), axes_smem(q), c->stream, make_view<float2>(q), (const float2*)B.pair, Qk, cnt, dwk, dhk,
-                               (int)axes_fit_lds(q));
+    by_dtype(q, [&](auto tag) {
+        typedef decltype(tag) T2;
+        const CubeView<T2> v = make_view<T2>(q);
+        const int lds = (int)axes_fit_lds(q);
+        if (B.pair)
+            hipLaunchKernelGGL((interp_points_pair_kernel<T2>), dim3(g), dim3(256), axes_smem(q), c->stream, v, (const T2*)B.pair, Qk, cnt, dwk, dhk, lds);
+        else if (B.vb)
+            hipLaunchKernelGGL((interp_points_blend_kernel<T2>), dim3(g), dim3(256), axes_smem(q), c->stream, v, (const T2*)B.vb, B.w1, B.w2, Qk, cnt, dwk, dhk, lds);
+        else if (quad)
+            hipLaunchKernelGGL((interp_points_quad_kernel<T2>), dim3(g), dim3(256), axes_smem(q), c->stream, v, (const uint4*)root(q)->d_quad, root(q)->quad_nblk,
+                               Qk, cnt, dwk, dhk, lds);
         else
-            hipLaunchKernelGGL((interp_points_pair_kernel<double2>), dim3(g), dim3(256), axes_smem(q), c->stream, make_view<double2>(q), (const double2*)B.pair, Qk, cnt, dwk, dhk,
-                               (int)axes_fit_lds(q));
-    } else if (B.vb) {
-        if (q->dtype == RDR_F32)
-            hipLaunchKernelGGL((interp_points_blend_kernel<float2>), dim3(g), dim3(256), axes_smem(q), c->stream, make_view<float2>(q), (const float2*)B.vb, B.w1, B.w2,
-                               Qk, cnt, dwk, dhk, (int)axes_fit_lds(q));
-        else
-            hipLaunchKernelGGL((interp_points_blend_kernel<double2>), dim3(g), dim3(256), axes_smem(q), c->stream, make_view<double2>(q), (const double2*)B.vb, B.w1, B.w2,
-                               Qk, cnt, dwk, dhk, (int)axes_fit_lds(q));
-    } else if (quad) {
-        if (q->dtype == RDR_F32)
-            hipLaunchKernelGGL((interp_points_quad_kernel<float2>), dim3(g), dim3(256), axes_smem(q), c->stream, make_view<float2>(q),
-                               (const uint4*)root(q)->d_quad, root(q)->quad_nblk, Qk, cnt, dwk, dhk, (int)axes_fit_lds(q));
-        else
-            hipLaunchKernelGGL((interp_points_quad_kernel<double2>), dim3(g), dim3(256), axes_smem(q), c->stream, make_view<double2>(q),
-                               (const uint4*)root(q)->d_quad, root(q)->quad_nblk, Qk, cnt, dwk, dhk, (int)axes_fit_lds(q));
-    } else if (q->dtype == RDR_F32)
-        hipLaunchKernelGGL((interp_points_kernel<float2>), dim3(g), dim3(256), axes_smem(q), c->stream, make_view<float2>(q), Qk, cnt, dwk, dhk,
-                           (int)axes_fit_lds(q));
-    else
-        hipLaunchKernelGGL((interp_points_kernel<double2>), dim3(g), dim3(256), axes_smem(q), c->stream, make_view<double2>(q), Qk, cnt, dwk, dhk,
-                           (int)axes_fit_lds(q));
+            hipLaunchKernelGGL((interp_points_kernel<T2>), dim3(g), dim3(256), axes_smem(q), c->stream, v, Qk, cnt, dwk, dhk, lds);
+    });
 }
 
 // An error return must not leave asynchronous copies into (or out of) the caller's buffers in flight: whoever enqueued on the three
@@ -1465,15 +1465,16 @@ static int interp3_impl(rdr_ctx* c, const char* who, const rdr_cube* q, const do
         const int g = grid_for(q->ny * npx * (q->nz / zv), 256, 1 << 22);
         {
             KTimer t(c, 3);
-            if (q->dtype == RDR_F32 && zv == 2)
-                hipLaunchKernelGGL((blend_pair_kernel<float2, 2>), dim3(g), dim3(256), 0, c->stream, (const float2*)q->d_vals, (float)B.w1, (const float2*)B.vb, (float)B.w2,
-                                   (float2*)dp, (int)q->ny, (int)q->nx, (int)q->nz);
-            else if (q->dtype == RDR_F32)
-                hipLaunchKernelGGL((blend_pair_kernel<float2, 1>), dim3(g), dim3(256), 0, c->stream, (const float2*)q->d_vals, (float)B.w1, (const float2*)B.vb, (float)B.w2,
-                                   (float2*)dp, (int)q->ny, (int)q->nx, (int)q->nz);
-            else
-                hipLaunchKernelGGL((blend_pair_kernel<double2, 1>), dim3(g), dim3(256), 0, c->stream, (const double2*)q->d_vals, B.w1, (const double2*)B.vb, B.w2,
-                                   (double2*)dp, (int)q->ny, (int)q->nx, (int)q->nz);
+            by_dtype(q, [&](auto tag) {
+                typedef decltype(tag) T2;
+                typedef decltype(tag.x) T;
+                auto launch = [&](auto kernel) {
+                    hipLaunchKernelGGL(kernel, dim3(g), dim3(256), 0, c->stream, (const T2*)q->d_vals, (T)B.w1, (const T2*)B.vb, (T)B.w2, (T2*)dp, (int)q->ny, (int)q->nx,
+                                       (int)q->nz);
+                };
+                if constexpr (sizeof(T) == 4) { if (zv == 2) return launch(blend_pair_kernel<float2, 2>); }
+                launch(blend_pair_kernel<T2, 1>);
+            });
         }
         HIPCHECK(c, hipGetLastError());
         B.pair = dp;
@@ -1513,7 +1514,7 @@ int rdr_interp3_blend(rdr_ctx* c, const rdr_cube* a, double w1, const rdr_cube* 
                       double* wet, double* hydro, int loc) {
     if (!c || !a || !b) return fail(c, RDR_ERR_INVALID, "rdr_interp3_blend: NULL argument");
     note_use(c, b);
-    if (a->ny != b->ny || a->nx != b->nx || a->nz != b->nz || a->dtype != b->dtype || a->ys != b->ys || a->xs != b->xs || a->zs != b->zs)
+    if (!same_grid_dtype(a, b))
         return fail(c, RDR_ERR_INVALID, "rdr_interp3_blend: the two epochs are not on the same grid / dtype");
     BlendSpec B; B.vb = b->d_vals; B.w1 = w1; B.w2 = w2;
     return interp3_impl(c, "rdr_interp3_blend", a, y, x, z, n, 0, nullptr, 0.0, wet, hydro, loc, B);
@@ -1523,7 +1524,7 @@ int rdr_interp3_blend_cube(rdr_ctx* c, const rdr_cube* a, double w1, const rdr_c
                            double* wet, double* hydro, int loc) {
     if (!c || !a || !b) return fail(c, RDR_ERR_INVALID, "rdr_interp3_blend_cube: NULL argument");
     note_use(c, b);
-    if (a->ny != b->ny || a->nx != b->nx || a->nz != b->nz || a->dtype != b->dtype || a->ys != b->ys || a->xs != b->xs || a->zs != b->zs)
+    if (!same_grid_dtype(a, b))
         return fail(c, RDR_ERR_INVALID, "rdr_interp3_blend_cube: the two epochs are not on the same grid / dtype");
     if (a->ny > INT32_MAX || a->nx > INT32_MAX || a->nz > INT32_MAX) return fail(c, RDR_ERR_INVALID, "rdr_interp3_blend_cube: axis longer than 2^31");
     BlendSpec B; B.vb = b->d_vals; B.w1 = w1; B.w2 = w2; B.want_pair = true;
@@ -2568,15 +2569,12 @@ static void launch_interp_epochs(rdr_ctx* c, const rdr_cube* q, const void* cons
         double* we = dw ? dw + (int64_t)e * estride : nullptr;
         double* he = dh ? dh + (int64_t)e * estride : nullptr;
         KTimer t(c, 2);
-        if (q->dtype == RDR_F32) {
-            if (ge == 4) launch_points_stacked<float2, 4>(c, q, vals + e, Qe, pstride, cnt, estride, we, he);
-            else if (ge == 2) launch_points_stacked<float2, 2>(c, q, vals + e, Qe, pstride, cnt, estride, we, he);
-            else launch_points_stacked<float2, 1>(c, q, vals + e, Qe, pstride, cnt, estride, we, he);
-        } else {
-            if (ge == 4) launch_points_stacked<double2, 4>(c, q, vals + e, Qe, pstride, cnt, estride, we, he);
-            else if (ge == 2) launch_points_stacked<double2, 2>(c, q, vals + e, Qe, pstride, cnt, estride, we, he);
-            else launch_points_stacked<double2, 1>(c, q, vals + e, Qe, pstride, cnt, estride, we, he);
-        }
+        by_dtype(q, [&](auto tag) {
+            typedef decltype(tag) T2;
+            if (ge == 4) launch_points_stacked<T2, 4>(c, q, vals + e, Qe, pstride, cnt, estride, we, he);
+            else if (ge == 2) launch_points_stacked<T2, 2>(c, q, vals + e, Qe, pstride, cnt, estride, we, he);
+            else launch_points_stacked<T2, 1>(c, q, vals + e, Qe, pstride, cnt, estride, we, he);
+        });
         e += ge;
     }
 }

@@ -1,7 +1,7 @@
 // Device-side building blocks of libraider_hip (gfx950 / CDNA4 only).
 //
-//   CubeView + trilinear()     scipy RegularGridInterpolator(linear, fill=nan) on the interleaved (wet,hydro) cube
-//                              [delayFcns.py:55-56, scipy _rgi.py:405-499]               (zenith / station kernels)
+//   CubeView + locate /        scipy RegularGridInterpolator(linear, fill=nan) on the interleaved (wet,hydro) cube
+//   corner_weights / _sum      [delayFcns.py:55-56, scipy _rgi.py:405-499]: the pieces every point gather shares (cube_kernels.h)
 //   sample_issue / _finish     the same interpolation for the ray kernels, split so that several samples' gathers fly together
 //   toa_newton / _t            getTopOfAtmosphere [losreader.py:706-733] (materialising API kernels / generic ray kernels)
 //   crossings_kernel           pass 1: build_ray [losreader.py:772-835] -> per-level batch maximum of the ray length
@@ -75,42 +75,62 @@ __device__ __forceinline__ int find_cell(const double* g, int n, double x, doubl
 __device__ __forceinline__ void ld2(const float2* p, double& a, double& b) { const float2 t = *p; a = (double)t.x; b = (double)t.y; }
 __device__ __forceinline__ void ld2(const double2* p, double& a, double& b) { const double2 t = *p; a = t.x; b = t.y; }
 
-// scipy linear RGI on both fields (zenith / station kernels).  sy/sx/sz: the axes (LDS or global).
+// ---- the point gather's shared pieces (zenith / station kernels) ---------------------------------------------------------------------
+// scipy linear RGI on both fields, written once: every point-gather kernel (gather_points of cube_kernels.h: the plain, paired, blended,
+// quad and date-series routes) is gather_axes + locate + corner_weights + corner_sum around its own corner loads, so the routes give the
+// same bits because they run the same code.
+
+// The three axes: copied into LDS when they fit (axes_in_lds), else read from global memory (L1 / L2 hits).
+struct GatherAxes { const double *y, *x, *z; };
+
 template <typename T2>
-__device__ __forceinline__ void trilinear(const CubeView<T2>& c, const double* sy, const double* sx, const double* sz,
-                                          double y, double x, double z, double& wet, double& hyd) {
-    // out of bounds (x < g[0] or x > g[-1]) -> fill_value nan; nan coordinate -> nan   (_rgi.py:437-442,585-592)
+__device__ __forceinline__ GatherAxes gather_axes(const CubeView<T2>& c, unsigned char* smem_raw, int axes_in_lds) {
+    const double* s_y = c.axes;
+    if (axes_in_lds) {
+        double* t = reinterpret_cast<double*>(smem_raw);
+        for (int i = threadIdx.x; i < c.ny + c.nx + c.nz; i += blockDim.x) t[i] = c.axes[i];
+        __syncthreads();
+        s_y = t;
+    }
+    return {s_y, s_y + c.ny, s_y + c.ny + c.nx};
+}
+
+// A located point: its cell (the lower corner's node indices) and the fractions along the three axes.
+struct GatherCell { int iy, ix, iz; double ty, tx, tz; };
+
+// false: out of bounds (x < g[0] or x > g[-1]) -> fill_value nan; nan coordinate -> nan   (_rgi.py:437-442,585-592)
+template <typename T2>
+__device__ __forceinline__ bool locate(const CubeView<T2>& c, const GatherAxes& s, double y, double x, double z, GatherCell& L) {
     const bool inside = (y >= c.y_lo) && (y <= c.y_hi) && (x >= c.x_lo) && (x <= c.x_hi) && (z >= c.z_lo) && (z <= c.z_hi);
-    if (!inside) { wet = qnan(); hyd = qnan(); return; }
-    const int iy = find_cell(sy, c.ny, y, c.y_lo, c.inv_dy, c.uni_y);
-    const int ix = find_cell(sx, c.nx, x, c.x_lo, c.inv_dx, c.uni_x);
-    const int iz = find_cell(sz, c.nz, z, c.z_lo, c.inv_dz, c.uni_z);
-    const double ty = (y - sy[iy]) / (sy[iy + 1] - sy[iy]);
-    const double tx = (x - sx[ix]) / (sx[ix + 1] - sx[ix]);
-    const double tz = (z - sz[iz]) / (sz[iz + 1] - sz[iz]);
-    const T2* p00 = c.v + ((int64_t)iy * c.nx + ix) * c.nz + iz;   // (y0,x0)
-    const T2* p01 = p00 + c.nz;                                    // (y0,x1)
-    const T2* p10 = p00 + (int64_t)c.nx * c.nz;                    // (y1,x0)
-    const T2* p11 = p10 + c.nz;                                    // (y1,x1)
-    double w[8], h[8];
-    ld2(p00, w[0], h[0]); ld2(p00 + 1, w[1], h[1]);
-    ld2(p01, w[2], h[2]); ld2(p01 + 1, w[3], h[3]);
-    ld2(p10, w[4], h[4]); ld2(p10 + 1, w[5], h[5]);
-    ld2(p11, w[6], h[6]); ld2(p11 + 1, w[7], h[7]);
+    if (!inside) return false;
+    L.iy = find_cell(s.y, c.ny, y, c.y_lo, c.inv_dy, c.uni_y);
+    L.ix = find_cell(s.x, c.nx, x, c.x_lo, c.inv_dx, c.uni_x);
+    L.iz = find_cell(s.z, c.nz, z, c.z_lo, c.inv_dz, c.uni_z);
+    L.ty = (y - s.y[L.iy]) / (s.y[L.iy + 1] - s.y[L.iy]);
+    L.tx = (x - s.x[L.ix]) / (s.x[L.ix + 1] - s.x[L.ix]);
+    L.tz = (z - s.z[L.iz]) / (s.z[L.iz + 1] - s.z[L.iz]);
+    return true;
+}
+
+// weight = ((1*wy)*wx)*wz, corners in lexicographic (y,x,z) order   (_rgi.py:490-498)
+__device__ __forceinline__ void corner_weights(double ty, double tx, double tz, double (&k)[8]) {
     const double wy0 = 1.0 - ty, wx0 = 1.0 - tx, wz0 = 1.0 - tz;
-    // weight = ((1*wy)*wx)*wz, corners in lexicographic (y,x,z) order, value = 0 + sum   (_rgi.py:490-498)
     const double a00 = wy0 * wx0, a01 = wy0 * tx, a10 = ty * wx0, a11 = ty * tx;
-    const double k0 = a00 * wz0, k1 = a00 * tz, k2 = a01 * wz0, k3 = a01 * tz;
-    const double k4 = a10 * wz0, k5 = a10 * tz, k6 = a11 * wz0, k7 = a11 * tz;
+    k[0] = a00 * wz0; k[1] = a00 * tz; k[2] = a01 * wz0; k[3] = a01 * tz;
+    k[4] = a10 * wz0; k[5] = a10 * tz; k[6] = a11 * wz0; k[7] = a11 * tz;
+}
+
+// value = 0 + sum over the corners in that order (_rgi.py:490-498): per field one v_fma_f64 on 0 and seven v_fmac_f64
+__device__ __forceinline__ void corner_sum(const double (&w)[8], const double (&h)[8], const double (&k)[8], double& wet, double& hyd) {
     double sw = 0.0, sh = 0.0;
-    sw += w[0] * k0; sh += h[0] * k0;
-    sw += w[1] * k1; sh += h[1] * k1;
-    sw += w[2] * k2; sh += h[2] * k2;
-    sw += w[3] * k3; sh += h[3] * k3;
-    sw += w[4] * k4; sh += h[4] * k4;
-    sw += w[5] * k5; sh += h[5] * k5;
-    sw += w[6] * k6; sh += h[6] * k6;
-    sw += w[7] * k7; sh += h[7] * k7;
+    sw += w[0] * k[0]; sh += h[0] * k[0];
+    sw += w[1] * k[1]; sh += h[1] * k[1];
+    sw += w[2] * k[2]; sh += h[2] * k[2];
+    sw += w[3] * k[3]; sh += h[3] * k[3];
+    sw += w[4] * k[4]; sh += h[4] * k[4];
+    sw += w[5] * k[5]; sh += h[5] * k[5];
+    sw += w[6] * k[6]; sh += h[6] * k[6];
+    sw += w[7] * k[7]; sh += h[7] * k[7];
     wet = sw; hyd = sh;
 }
 
@@ -118,7 +138,7 @@ __device__ __forceinline__ void trilinear(const CubeView<T2>& c, const double* s
 struct AxisTabs { const double2* ey; const double2* ex; const double2* ez; };
 
 // ---- ray-kernel sampler ----------------------------------------------------------------------------------------
-// Same scipy semantics as trilinear<> (interval g[i] <= v < g[i+1], last cell closed; outside / NaN -> NaN).
+// Same scipy semantics as locate (interval g[i] <= v < g[i+1], last cell closed; outside / NaN -> NaN).
 // The axis table is stored in LDS as (g[i], 1/(g[i+1]-g[i])) pairs.  x / y: arithmetic cell on exactly-uniform axes,
 // guess-and-verify on nearly uniform ones; z: the segment's model interval is known, a 2- (light kernel) or 3-entry
 // (generic kernel) window around it is fetched and the right entry selected in registers.  A lane whose guess fails

@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void raster_sample_kernel(const T* __restrict_
                 const double v01 = raster_value(raster, r0 * g.width + c1, has_nodata, nodata);
                 const double v10 = raster_value(raster, r1 * g.width + c0, has_nodata, nodata);
                 const double v11 = raster_value(raster, r1 * g.width + c1, has_nodata, nodata);
-                // the lerp order of trilinear<> (raider_kernels.h) on two axes: weight = (1 * wy) * wx, corners in (y, x) order, 0 + sum
+                // the weight order of corner_weights / corner_sum (raider_kernels.h) on two axes: weight = (1 * wy) * wx, corners in (y, x) order, 0 + sum
                 const double wy0 = 1.0 - ty, wx0 = 1.0 - tx;
                 double s = 0.0;
                 s += v00 * (wy0 * wx0);

@@ -1,5 +1,5 @@
 """GPU: every schedule of the zenith-cube gather (build_cube_kernel, cube_kernels.h, driven by build_cube_impl, raider_hip.hip) against
-a long-double trilinear interpolant written here, and bit for bit against Cube.interp (interp_points_kernel / trilinear<>).
+a long-double trilinear interpolant written here, and bit for bit against Cube.interp (interp_points_kernel).
 
 Which path a tile takes - its footprint staged in LDS in one round or in several rounds of U heights, or direct loads UD heights at
 a time with a clamped tail; the CLEAN or the guarded instantiation; a second and third trip of the grid-stride loop over tiles; one or
