@@ -585,6 +585,29 @@ int rdr_tiff_lzw_decode(rdr_ctx* ctx, const void* src, int64_t src_bytes, const 
  * one strip (per plane) covering the raster is a plain copy.  segs and out live at `loc`. */
 int rdr_tiff_assemble(rdr_ctx* ctx, const void* segs, int64_t seg_stride, int64_t height, int64_t width, int64_t tile_h, int64_t tile_w,
                       int predictor, int swap, int sample_bytes, int planar, int bands, int band, void* out, int loc);
+/* rdr_tiff_predict: what rdr_tiff_assemble's predictor 2 undoes - out[y][x] = in[y][x] - in[y][x-1] along every row of `width` samples,
+ * modulo 2^(8 * sample_bytes); the first sample of a row is kept.  in and out are different buffers at `loc`. */
+int rdr_tiff_predict(rdr_ctx* ctx, const void* in, int sample_bytes, int64_t height, int64_t width, void* out, int loc);
+
+/* ---- zlib streams written on the device (raider_amd/deflate.py; csrc/deflate_kernels.h) --------------------------------------------
+ * rdr_deflate_bound(n): the largest stream rdr_deflate_encode makes of n bytes: n + 5 * ceil(n / 32768) + 6 <= n + n / 2048 + 32.
+ * rdr_deflate_encode: `nseg` independent byte ranges src[seg_offset[i] .. + seg_bytes[i]) (any byte offset) -> one complete zlib
+ * stream each (RFC 1950 / 1951: 78 01, deflate blocks, the big-endian Adler-32 of the range), packed back to back into `out` in
+ * segment order; out_offset[i] = where stream i starts, out_offset[nseg] = the total (HOST array of nseg + 1).  The call
+ * synchronises.  Every 32 KiB sub-block of a range is encoded by one wave, independently of all others (no match reaches across a
+ * sub-block start), as one fixed-Huffman block closed by an empty stored block, or as a stored block when that is not smaller;
+ * dynamic Huffman tables are not written.  The same input gives the same bytes on every run.  src and out live at `loc`, the
+ * tables are HOST arrays.  RDR_ERR_INVALID (and nothing written): NULL, a segment outside src, seg_bytes[i] <= 0, out_capacity
+ * below the sum of rdr_deflate_bound(seg_bytes[i]).  Nothing is written at or beyond out + out_offset[nseg]. */
+int64_t rdr_deflate_bound(int64_t n);
+int rdr_deflate_encode(rdr_ctx* ctx, const void* src, int64_t src_bytes, const int64_t* seg_offset, const int64_t* seg_bytes, int64_t nseg,
+                       void* out, int64_t out_capacity, int64_t* out_offset, int loc);
+/* rdr_h5_chunks: a C-ordered array of `ndim` <= 4 axes (shape, HOST) of elem_bytes 1 / 2 / 4 / 8 cut into chunks (chunk, HOST) in
+ * row-major chunk order.  Every chunk is full size: elements beyond the array's edge are `fill` (HOST, elem_bytes bytes).  shuffle:
+ * each chunk is byte-transposed as HDF5's shuffle filter does, out[j * n + i] = in[i * elem_bytes + j] over the chunk's n elements.
+ * out holds prod(ceil(shape / chunk)) * prod(chunk) elements; array and out live at `loc`. */
+int rdr_h5_chunks(rdr_ctx* ctx, const void* array, int elem_bytes, int ndim, const int64_t* shape, const int64_t* chunk, const void* fill,
+                  int shuffle, void* out, int loc);
 
 #ifdef __cplusplus
 }

@@ -151,6 +151,10 @@ SYMBOLS = [
     ('rdr_tiff_lzw_decode', C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_int]),
     ('rdr_tiff_assemble', C.c_int, [_VP, _VP, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     _VP, C.c_int]),
+    ('rdr_tiff_predict', C.c_int, [_VP, _VP, C.c_int, C.c_int64, C.c_int64, _VP, C.c_int]),
+    ('rdr_deflate_bound', C.c_int64, [C.c_int64]),
+    ('rdr_deflate_encode', C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int]),
+    ('rdr_h5_chunks', C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, _VP, C.c_int]),
 ]
 
 

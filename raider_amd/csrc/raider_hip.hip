@@ -35,6 +35,7 @@ constexpr int MAX_SLICES = 512;   // height slices per rdr_raytrace_slices call
 
 enum { SLOT_IN0 = 0, SLOT_IN1, SLOT_IN2, SLOT_IN3, SLOT_IN4, SLOT_IN5, SLOT_IN6, SLOT_OUT0, SLOT_OUT1, SLOT_OUT2, SLOT_AUX,
        SLOT_PT0, SLOT_PT1, SLOT_PT2, SLOT_PT3, SLOT_PT4, SLOT_PT5, SLOT_TMPCUBE, SLOT_TMPAXES,      // rdr_point_delays: points, delays, the intermediate cube
+       SLOT_DEFL,                                                                                    // rdr_deflate_encode: the sub-blocks' slots
        NSLOT };
 
 struct rdr_ctx {
@@ -339,6 +340,7 @@ static hipError_t launch_lds(void (*kern)(KArgs...), dim3 g, dim3 b, size_t sm, 
 #include "epoch_kernels.h"
 #include "raster_kernels.h"
 #include "tiff_kernels.h"
+#include "deflate_kernels.h"
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -3568,6 +3570,138 @@ int rdr_tiff_assemble(rdr_ctx* c, const void* segs, int64_t seg_stride, int64_t 
         HIPCHECK(c, hipGetLastError());
     }
     rc = finish_out(c, out, dout, out_bytes, loc); if (rc) return rc;
+    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return RDR_OK;
+}
+
+
+// ---- zlib streams and HDF5 chunks (deflate_kernels.h) ------------------------------------------------------------------------------
+int64_t rdr_deflate_bound(int64_t n) {
+    if (n < 0) n = 0;
+    return n + 5 * ((n + DEFL_SUB - 1) / DEFL_SUB) + 6;        // a stored block per sub-block, 78 01 and the Adler-32
+}
+
+int rdr_deflate_encode(rdr_ctx* c, const void* src, int64_t src_bytes, const int64_t* seg_offset, const int64_t* seg_bytes, int64_t nseg, void* out,
+                       int64_t out_capacity, int64_t* out_offset, int loc) {
+    if (!c || !src || !seg_offset || !seg_bytes || !out || !out_offset) return fail(c, RDR_ERR_INVALID, "rdr_deflate_encode: NULL argument");
+    if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, "rdr_deflate_encode: loc must be RDR_HOST or RDR_DEVICE");
+    if (src_bytes <= 0 || src_bytes > ((int64_t)1 << 40) || nseg <= 0 || nseg > (1 << 24))
+        return fail(c, RDR_ERR_INVALID, "rdr_deflate_encode: need a non-empty buffer (at most 2^40 bytes) and 1 .. 2^24 segments");
+    int64_t need = 0, nsub = 0;
+    for (int64_t i = 0; i < nseg; ++i) {
+        if (seg_bytes[i] <= 0) return fail(c, RDR_ERR_INVALID, "rdr_deflate_encode: segment " + std::to_string(i) + " is empty");
+        if (seg_offset[i] < 0 || seg_offset[i] > src_bytes || seg_bytes[i] > src_bytes - seg_offset[i])
+            return fail(c, RDR_ERR_INVALID, "rdr_deflate_encode: segment " + std::to_string(i) + " does not lie inside the source buffer");
+        need += rdr_deflate_bound(seg_bytes[i]);
+        nsub += (seg_bytes[i] + DEFL_SUB - 1) / DEFL_SUB;
+        if (need > ((int64_t)1 << 41)) return fail(c, RDR_ERR_INVALID, "rdr_deflate_encode: the segments hold more than 2^40 bytes");
+    }
+    if (out_capacity < need)
+        return fail(c, RDR_ERR_INVALID, "rdr_deflate_encode: out_capacity " + std::to_string(out_capacity) + " is below the sum of the bounds, " + std::to_string(need));
+    HIPCHECK(c, hipSetDevice(c->device));
+    std::vector<DeflSub> subs((size_t)nsub);
+    {
+        int64_t k = 0;
+        for (int64_t i = 0; i < nseg; ++i)
+            for (int64_t o = 0; o < seg_bytes[i]; o += DEFL_SUB, ++k) {
+                const int64_t m = std::min<int64_t>(DEFL_SUB, seg_bytes[i] - o);
+                subs[(size_t)k] = DeflSub{seg_offset[i] + o, 0, (int32_t)m, (o == 0 ? 1 : 0) | (o + m == seg_bytes[i] ? 2 : 0), 0u, 0};
+            }
+    }
+    const void* dsrc; void *dsubs, *dslots, *dres, *dout;
+    int rc = stage_in(c, SLOT_IN0, src, (size_t)src_bytes, loc, &dsrc); if (rc) return rc;
+    rc = ensure(c, SLOT_IN1, (size_t)nsub * sizeof(DeflSub), &dsubs); if (rc) return rc;
+    rc = ensure(c, SLOT_DEFL, (size_t)nsub * DEFL_SLOT, &dslots); if (rc) return rc;
+    rc = ensure(c, SLOT_OUT1, (size_t)nsub * sizeof(DeflResult), &dres); if (rc) return rc;
+    rc = upload(c, dsubs, subs.data(), (size_t)nsub * sizeof(DeflSub)); if (rc) return rc;
+    // one wave per sub-block; a compute unit holds three of these 53 KB workgroups, the grid strides over the rest
+    hipLaunchKernelGGL(deflate_encode_kernel, dim3((unsigned)std::min<int64_t>(nsub, (int64_t)c->num_cus * 3)), dim3(64), 0, c->stream, (const uint8_t*)dsrc,
+                       (const DeflSub*)dsubs, nsub, (uint8_t*)dslots, (DeflResult*)dres);
+    HIPCHECK(c, hipGetLastError());
+    std::vector<DeflResult> res((size_t)nsub);
+    HIPCHECK(c, hipMemcpyAsync(res.data(), dres, (size_t)nsub * sizeof(DeflResult), hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    // sizes -> offsets; the sub-blocks' Adler sums -> the streams' (A' = A + s1, B' = B + n A + s2: adler32_combine's rule)
+    int64_t pos = 0, seg = 0;
+    uint32_t A = 1u, B = 0u;
+    for (int64_t k = 0; k < nsub; ++k) {
+        DeflSub& d = subs[(size_t)k];
+        const DeflResult& r = res[(size_t)k];
+        if (r.fixed_bytes < 0 || r.fixed_bytes >= d.n + 5 || r.s1 >= 65521u || r.s2 >= 65521u) return fail(c, RDR_ERR_HIP, "rdr_deflate_encode: the encoder returned an impossible size");
+        if (d.flags & 1) { out_offset[seg] = pos; A = 1u; B = 0u; }
+        d.dst_off = pos;
+        d.fixed_bytes = r.fixed_bytes;
+        B = (uint32_t)((B + (uint64_t)d.n % 65521u * A + r.s2) % 65521u);
+        A = (A + r.s1) % 65521u;
+        pos += ((d.flags & 1) ? 2 : 0) + (r.fixed_bytes > 0 ? r.fixed_bytes : d.n + 5) + ((d.flags & 2) ? 4 : 0);
+        if (d.flags & 2) { d.adler = (B << 16) | A; ++seg; }
+    }
+    out_offset[nseg] = pos;
+    if (pos > out_capacity) return fail(c, RDR_ERR_HIP, "rdr_deflate_encode: the streams exceed their bound");       // (cannot happen: every sub-block is at most n + 5)
+    rc = upload(c, dsubs, subs.data(), (size_t)nsub * sizeof(DeflSub)); if (rc) return rc;
+    rc = stage_out(c, SLOT_OUT0, out, (size_t)pos, loc, &dout); if (rc) return rc;
+    hipLaunchKernelGGL(deflate_pack_kernel, dim3((unsigned)std::min<int64_t>(nsub, (int64_t)c->num_cus * 8)), dim3(256), 0, c->stream, (const uint8_t*)dsrc,
+                       (const DeflSub*)dsubs, nsub, (const uint8_t*)dslots, (uint8_t*)dout, pos);
+    HIPCHECK(c, hipGetLastError());
+    rc = finish_out(c, out, dout, (size_t)pos, loc); if (rc) return rc;
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return RDR_OK;
+}
+
+int rdr_tiff_predict(rdr_ctx* c, const void* in, int sample_bytes, int64_t height, int64_t width, void* out, int loc) {
+    if (!c || !in || !out) return fail(c, RDR_ERR_INVALID, "rdr_tiff_predict: NULL argument");
+    if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, "rdr_tiff_predict: loc must be RDR_HOST or RDR_DEVICE");
+    if (sample_bytes != 1 && sample_bytes != 2 && sample_bytes != 4 && sample_bytes != 8) return fail(c, RDR_ERR_INVALID, "rdr_tiff_predict: samples of 1, 2, 4 or 8 bytes");
+    if (height <= 0 || width <= 0 || height > ((int64_t)1 << 31) || width > ((int64_t)1 << 31) || height * width > ((int64_t)1 << 36))
+        return fail(c, RDR_ERR_INVALID, "rdr_tiff_predict: raster sizes must be positive, at most 2^36 samples");
+    if (in == out) return fail(c, RDR_ERR_INVALID, "rdr_tiff_predict: in and out must be different buffers");
+    HIPCHECK(c, hipSetDevice(c->device));
+    const int64_t n = height * width;
+    const void* din; void* dout;
+    int rc = stage_in(c, SLOT_IN0, in, (size_t)n * sample_bytes, loc, &din); if (rc) return rc;
+    rc = stage_out(c, SLOT_OUT0, out, (size_t)n * sample_bytes, loc, &dout); if (rc) return rc;
+    if ((reinterpret_cast<uintptr_t>(din) | reinterpret_cast<uintptr_t>(dout)) % sample_bytes != 0) return fail(c, RDR_ERR_INVALID, "rdr_tiff_predict: buffers must be aligned to the sample size");
+    const dim3 G(grid_for(n, 256, c->num_cus * 16)), Bk(256);
+    if (sample_bytes == 1) hipLaunchKernelGGL(tiff_predict_kernel<uint8_t>, G, Bk, 0, c->stream, (const uint8_t*)din, n, width, (uint8_t*)dout);
+    else if (sample_bytes == 2) hipLaunchKernelGGL(tiff_predict_kernel<uint16_t>, G, Bk, 0, c->stream, (const uint16_t*)din, n, width, (uint16_t*)dout);
+    else if (sample_bytes == 4) hipLaunchKernelGGL(tiff_predict_kernel<uint32_t>, G, Bk, 0, c->stream, (const uint32_t*)din, n, width, (uint32_t*)dout);
+    else hipLaunchKernelGGL(tiff_predict_kernel<uint64_t>, G, Bk, 0, c->stream, (const uint64_t*)din, n, width, (uint64_t*)dout);
+    HIPCHECK(c, hipGetLastError());
+    rc = finish_out(c, out, dout, (size_t)n * sample_bytes, loc); if (rc) return rc;
+    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return RDR_OK;
+}
+
+int rdr_h5_chunks(rdr_ctx* c, const void* array, int elem_bytes, int ndim, const int64_t* shape, const int64_t* chunk, const void* fill, int shuffle,
+                  void* out, int loc) {
+    if (!c || !array || !shape || !chunk || !fill || !out) return fail(c, RDR_ERR_INVALID, "rdr_h5_chunks: NULL argument");
+    if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, "rdr_h5_chunks: loc must be RDR_HOST or RDR_DEVICE");
+    if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) return fail(c, RDR_ERR_INVALID, "rdr_h5_chunks: elements of 1, 2, 4 or 8 bytes");
+    if (ndim < 1 || ndim > 4) return fail(c, RDR_ERR_INVALID, "rdr_h5_chunks: 1 .. 4 dimensions");
+    H5ChunkLayout L{};
+    int64_t in_elems = 1, nchunks = 1;
+    L.chunk_elems = 1;
+    for (int d = 0; d < 4; ++d) { L.shape[d] = L.chunk[d] = L.nchunk[d] = 1; }
+    for (int d = 0; d < ndim; ++d) {
+        const int64_t s = shape[d], k = chunk[d];
+        if (s <= 0 || k <= 0 || s > ((int64_t)1 << 31) || k > ((int64_t)1 << 31)) return fail(c, RDR_ERR_INVALID, "rdr_h5_chunks: shape and chunk sizes must be positive (below 2^31)");
+        const int e = 4 - ndim + d;
+        L.shape[e] = s; L.chunk[e] = k; L.nchunk[e] = (s + k - 1) / k;
+        if (in_elems > ((int64_t)1 << 36) / s || L.chunk_elems > ((int64_t)1 << 36) / k) return fail(c, RDR_ERR_INVALID, "rdr_h5_chunks: more than 2^36 elements");
+        in_elems *= s; L.chunk_elems *= k;
+        nchunks *= L.nchunk[e];
+        if (nchunks > ((int64_t)1 << 36) / L.chunk_elems) return fail(c, RDR_ERR_INVALID, "rdr_h5_chunks: more than 2^36 elements");
+    }
+    L.total_elems = nchunks * L.chunk_elems;
+    L.es = elem_bytes; L.shuffle = shuffle != 0;
+    std::memcpy(L.fill, fill, (size_t)elem_bytes);
+    HIPCHECK(c, hipSetDevice(c->device));
+    const void* din; void* dout;
+    int rc = stage_in(c, SLOT_IN0, array, (size_t)in_elems * elem_bytes, loc, &din); if (rc) return rc;
+    rc = stage_out(c, SLOT_OUT0, out, (size_t)L.total_elems * elem_bytes, loc, &dout); if (rc) return rc;
+    hipLaunchKernelGGL(h5_chunks_kernel, dim3(grid_for(L.total_elems, 256, c->num_cus * 16)), dim3(256), 0, c->stream, (const uint8_t*)din, L, (uint8_t*)dout);
+    HIPCHECK(c, hipGetLastError());
+    rc = finish_out(c, out, dout, (size_t)L.total_elems * elem_bytes, loc); if (rc) return rc;
     if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
     return RDR_OK;
 }

@@ -1,0 +1,125 @@
+"""zlib streams written on the GPU (rdr_deflate_encode) and the chunk cutter of the NetCDF-4 writer (rdr_h5_chunks).
+
+The encoder turns independent byte ranges of one buffer into complete zlib streams, one wave per 32 KiB sub-block, with fixed-Huffman
+and stored blocks only.  NumPy arrays go up and come back in one transfer each; device tensors stay where they are.
+There is no CPU fallback: the writers that want host zlib call zlib."""
+import numpy as np
+
+from . import _lib as L
+
+
+def bound(n):
+    """The largest stream the encoder makes of `n` bytes (<= n + n // 2048 + 32)."""
+    return int(L.load().rdr_deflate_bound(int(n)))
+
+
+def _is_tensor(a):
+    return type(a).__module__.split('.')[0] == 'torch'
+
+
+def require_gpu(what):
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError(f'{what} runs on the GPU; no GPU is visible and there is no CPU fallback')
+
+
+def deflate_segments(buf, offsets, sizes):
+    """(packed, out_offsets): the byte ranges buf[offsets[i] : offsets[i] + sizes[i]] as zlib streams packed back to back; stream i is
+    packed[out_offsets[i] : out_offsets[i + 1]].  buf: a C-contiguous NumPy array or device tensor of any element type (taken as bytes);
+    packed is a uint8 array / tensor of the same kind, out_offsets an int64 NumPy array of len(sizes) + 1."""
+    so = np.ascontiguousarray(offsets, dtype=np.int64).ravel()
+    sb = np.ascontiguousarray(sizes, dtype=np.int64).ravel()
+    if so.size != sb.size:
+        raise ValueError('offsets and sizes differ in length')
+    if so.size == 0:
+        raise ValueError('deflate_segments: no segments')
+    if np.any(sb <= 0):
+        raise ValueError('deflate_segments: every segment needs at least one byte')
+    cap = sum(bound(int(v)) * int(c) for v, c in zip(*np.unique(sb, return_counts=True)))
+    oo = np.zeros(so.size + 1, dtype=np.int64)
+    if _is_tensor(buf):
+        import torch
+        if not buf.is_cuda or not buf.is_contiguous():
+            raise TypeError('deflate_segments: a tensor must be contiguous and live on the GPU')
+        src = buf.reshape(-1).view(torch.uint8)
+        out = torch.empty(cap, dtype=torch.uint8, device=buf.device)
+        ctx = L.Context.default()
+        ctx.adopt_torch_stream(src)
+        L.check(ctx.lib.rdr_deflate_encode(ctx.handle, L.ptr(src), src.numel(), L.ptr(so), L.ptr(sb), so.size, L.ptr(out), cap, L.ptr(oo), L.RDR_DEVICE), ctx.handle)
+        return out[:int(oo[-1])], oo
+    require_gpu('deflate_segments (rdr_deflate_encode)')
+    src = np.ascontiguousarray(buf).reshape(-1).view(np.uint8)
+    out = np.empty(cap, dtype=np.uint8)
+    ctx = L.Context.default()
+    L.check(ctx.lib.rdr_deflate_encode(ctx.handle, L.ptr(src), src.size, L.ptr(so), L.ptr(sb), so.size, L.ptr(out), cap, L.ptr(oo), L.RDR_HOST), ctx.handle)
+    return out[:int(oo[-1])], oo
+
+
+def chunk_grid(shape, chunk):
+    """Chunks along every axis: ceil(shape / chunk)."""
+    return tuple(-(-int(s) // int(c)) for s, c in zip(shape, chunk))
+
+
+def h5_chunks(array, chunk, fill, shuffle=True):
+    """`array` (NumPy or device tensor, at most 4-D) cut into full-size chunks in row-major chunk order, edge chunks padded with `fill`,
+    each chunk byte-shuffled as HDF5's shuffle filter does when `shuffle`.  Returns a uint8 array / tensor of
+    n_chunks * prod(chunk) * itemsize bytes: chunk k is bytes [k * chunk_bytes, (k + 1) * chunk_bytes)."""
+    tensor = _is_tensor(array)
+    if tensor:
+        import torch
+        if not array.is_cuda:
+            raise TypeError('h5_chunks: a tensor must live on the GPU')
+        a = array.contiguous()
+        dt = np.dtype(str(a.dtype).replace('torch.', ''))
+        shape = tuple(a.shape)
+    else:
+        require_gpu('h5_chunks (rdr_h5_chunks)')
+        a = np.ascontiguousarray(array)
+        dt, shape = a.dtype, a.shape
+    chunk = tuple(int(c) for c in chunk)
+    if len(chunk) != len(shape) or not 1 <= len(shape) <= 4:
+        raise ValueError(f'h5_chunks: chunk {chunk} does not fit an array of shape {shape} (1 to 4 axes)')
+    if any(c <= 0 for c in chunk) or any(s <= 0 for s in shape):
+        raise ValueError('h5_chunks: shape and chunk sizes must be positive')
+    nbytes = int(np.prod(chunk_grid(shape, chunk), dtype=np.int64) * np.prod(chunk, dtype=np.int64)) * dt.itemsize
+    fv = np.array([fill], dtype=dt)
+    sh, ck = np.array(shape, dtype=np.int64), np.array(chunk, dtype=np.int64)
+    ctx = L.Context.default()
+    if tensor:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
+        ctx.adopt_torch_stream(a)
+        loc = L.RDR_DEVICE
+    else:
+        out = np.empty(nbytes, dtype=np.uint8)
+        loc = L.RDR_HOST
+    L.check(ctx.lib.rdr_h5_chunks(ctx.handle, L.ptr(a), dt.itemsize, len(shape), L.ptr(sh), L.ptr(ck), L.ptr(fv), int(bool(shuffle)), L.ptr(out), loc), ctx.handle)
+    return out
+
+
+def h5_chunks_host(array, chunk, fill, shuffle=True):
+    """NumPy restatement of rdr_h5_chunks (what the tests compare it with, and what a caller without a GPU feeds to zlib)."""
+    a = np.ascontiguousarray(array)
+    chunk = tuple(int(c) for c in chunk)
+    grid = chunk_grid(a.shape, chunk)
+    padded = np.full(tuple(g * c for g, c in zip(grid, chunk)), fill, dtype=a.dtype)
+    padded[tuple(slice(0, s) for s in a.shape)] = a
+    out = []
+    for idx in np.ndindex(*grid):
+        blk = np.ascontiguousarray(padded[tuple(slice(i * c, (i + 1) * c) for i, c in zip(idx, chunk))])
+        b = blk.reshape(-1).view(np.uint8)
+        if shuffle:
+            b = b.reshape(-1, a.dtype.itemsize).T
+        out.append(np.ascontiguousarray(b).reshape(-1))
+    return np.concatenate(out)
+
+
+def compress_chunks(array, chunk, fill, shuffle=True):
+    """(packed bytes as a NumPy uint8 array, offsets): `array` cut into chunks, shuffled and deflated on the device - what
+    h5write takes as a chunked variable's data.  One download, of the packed streams."""
+    raw = h5_chunks(array, chunk, fill, shuffle)
+    n = int(np.prod(chunk_grid(tuple(array.shape), chunk), dtype=np.int64))
+    cb = (raw.numel() if _is_tensor(raw) else raw.size) // n
+    packed, oo = deflate_segments(raw, np.arange(n, dtype=np.int64) * cb, np.full(n, cb, dtype=np.int64))
+    if _is_tensor(packed):
+        packed = packed.cpu().numpy()
+    return packed, oo

@@ -226,6 +226,25 @@ class PointsAOI:
         self.ypts = np.arange(N, S - sp, -sp)
 
 
+def gunw_chunks(shape):
+    """aria/calcGUNW.py:65-72: the chunks of a (nz, ny, nx) layer - all heights, a third of each horizontal axis."""
+    nz, ny, nx = (int(s) for s in shape)
+    return (nz, max(1, ny // 3), max(1, nx // 3))
+
+
+def _compressed(data, chunks, fill):
+    """A cube (NumPy or device tensor) as h5write.ChunkedData: cut into chunks, shuffled and deflated on the device."""
+    from . import deflate
+    from .h5write import ChunkedData
+    shape = tuple(int(s) for s in data.shape)
+    if len(shape) != 3:
+        raise ValueError(f'a compressed cube has three axes, not shape {shape}')
+    chunks = gunw_chunks(shape) if chunks is None else tuple(int(c) for c in chunks)
+    dtype = np.dtype(str(data.dtype).replace('torch.', ''))
+    packed, offsets = deflate.compress_chunks(data, chunks, fill, shuffle=True)
+    return ChunkedData(shape, dtype, chunks, packed, offsets, filters=('shuffle', 'deflate'), level=1)
+
+
 class DelayCube:
     """What writeResultsToXarray returns when xarray is not installed: the same variables/coords,
     readable by getInterpolators (`.variables[name][:]`)."""
@@ -243,12 +262,17 @@ class DelayCube:
         except KeyError:
             raise AttributeError(k)
 
-    def to_netcdf(self, path, format='NETCDF4'):
+    def to_netcdf(self, path, format='NETCDF4', compress=False, chunks=None):
         """The delay-cube file of delay.py:329-401 / cli/raider.py:373-398 (`ds.to_netcdf`): dims z, y, x; variables wet, hydro (f64,
         units m, grid_mapping crs), coordinate variables, the integer `crs` grid-mapping variable and the global attributes.
         format='NETCDF4' (what the reference writes): HDF5 through raider_amd.h5write; 'NETCDF3_64BIT': classic format through
-        scipy.  (When xarray is installed writeResultsToXarray returns a real Dataset instead of this class.)"""
+        scipy.  (When xarray is installed writeResultsToXarray returns a real Dataset instead of this class.)
+        compress=True (NETCDF4 only, needs the GPU): wet and hydro are written chunked + shuffle + deflate, cut, shuffled and deflated
+        on the device (raider_amd.deflate); `chunks` defaults to the reference's GUNW rule (nz, max(1, ny // 3), max(1, nx // 3))
+        (aria/calcGUNW.py:65-72), at most 16 chunks.  Coordinates and crs stay contiguous.  compress=False writes what it always wrote."""
         v = self.variables
+        if compress and not format.upper().startswith('NETCDF4'):
+            raise ValueError('compress=True needs format NETCDF4 (the classic format has no filters)')
         degrees = self.attrs.get('_degrees', True)
         desc = str(self.attrs.get('description', '')).replace('RAiDER geo cube - ', '')
         gattrs = {k: str(val) for k, val in self.attrs.items() if not k.startswith('_')}   # (_degrees / _crs_cf steer the writer)
@@ -261,8 +285,12 @@ class DelayCube:
             from .h5write import write_netcdf4
             variables = {d: ((d,), np.asarray(v[d], dtype=np.float64), coord_attrs[d]) for d in ('z', 'y', 'x')}
             for name, long in (('wet', 'wet'), ('hydro', 'hydrostatic')):
-                variables[name] = (('z', 'y', 'x'), np.asarray(v[name], dtype=np.float64),
-                                   dict(units='m', description=f'{long} {desc} delay', grid_mapping='crs'))
+                data = v[name].double() if hasattr(v[name], 'data_ptr') else np.asarray(v[name], dtype=np.float64)
+                if compress:
+                    data = _compressed(data, chunks, np.nan)
+                elif hasattr(data, 'data_ptr'):
+                    data = data.cpu().numpy()
+                variables[name] = (('z', 'y', 'x'), data, dict(units='m', description=f'{long} {desc} delay', grid_mapping='crs'))
             variables['crs'] = ((), np.array(-2147483647, dtype=np.int64), dict(self.attrs.get('_crs_cf') or {}))
             write_netcdf4(path, {d: int(np.size(v[d])) for d in ('z', 'y', 'x')}, variables, gattrs)
             return str(path)

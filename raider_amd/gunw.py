@@ -3,8 +3,10 @@
 `compute_delays_slc` mirrors the reference function of the same name for the part that is arithmetic: the delays of the
 reference and the secondary date are multiplied by `phase2range = -4 pi / wavelength` (calcGUNW.py:54-59) - on the GPU
 through `rdr_delays_to_phase` - renamed to the GUNW layer names, given the GUNW attributes and float32 coordinates
-(calcGUNW.py:75-108).  Writing the result INTO a GUNW product (`update_gunw_slc`, HDF5 through h5py/netCDF4) is outside
-the hot path and not provided.
+(calcGUNW.py:75-108).  `write_delays_slc` writes that object as a standalone NetCDF-4 file with the on-disk encoding the
+reference prescribes for it (calcGUNW.py:65-72: float32, _FillValue 0.0, chunks (nz, ny // 3, nx // 3)), shuffled and deflated
+on the device.  Writing the result INTO a GUNW product (`update_gunw_slc`, HDF5 through h5py/netCDF4) is outside the hot path
+and not provided.
 """
 import datetime as dt
 from pathlib import Path
@@ -110,3 +112,25 @@ def compute_delays_slc(cube_paths, wavelength, ctx=None):
     ds = DelayCube(out, {'model': model, 'method': 'ray tracing'})
     ds.layer_attrs = layer_attrs
     return ds
+
+
+def write_delays_slc(ds_slc, path):
+    """The object compute_delays_slc returns as a standalone NetCDF-4 file: the four layers as float32 with _FillValue 0.0 and chunks
+    (nz, max(1, ny // 3), max(1, nx // 3)) (calcGUNW.py:65-72), cut, shuffled and deflated on the device; float32 coordinate
+    variables heightsMeta / latitudeMeta / longitudeMeta; the per-layer attributes compute_delays_slc collected."""
+    from .delay import _compressed, gunw_chunks
+    from .h5write import write_netcdf4
+    v = ds_slc.variables
+    dims = {d: int(np.size(v[d])) for d in DIM_NAMES}
+    variables = {d: ((d,), np.asarray(v[d], dtype=np.float32), {}) for d in DIM_NAMES}
+    layer_attrs = getattr(ds_slc, 'layer_attrs', {})
+    for key in ('reference', 'secondary'):
+        for name in TROPO_NAMES:
+            layer = f'{key}_{name}'
+            data = v[layer].float() if hasattr(v[layer], 'data_ptr') else np.asarray(v[layer], dtype=np.float32)
+            attrs = {k: (val if isinstance(val, (str, int, float, np.number)) else str(val)) for k, val in layer_attrs.get(layer, {}).items() if val is not None}
+            attrs['_FillValue'] = np.float32(0.0)
+            variables[layer] = (tuple(DIM_NAMES), _compressed(data, gunw_chunks(data.shape), 0.0), attrs)
+    gattrs = {k: str(val) for k, val in getattr(ds_slc, 'attrs', {}).items() if val is not None and not k.startswith('_')}
+    write_netcdf4(path, dims, variables, gattrs)
+    return str(path)

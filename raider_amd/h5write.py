@@ -9,7 +9,9 @@ netCDF-C / h5netcdf / xarray rely on:
   * superblock version 0; version-1 object headers; the root group as a symbol table (one version-1 B-tree node, one symbol
     table node, a local heap with the link names) - readable by every libhdf5 since 1.0;
   * datasets: contiguous storage, little-endian IEEE floats / two's-complement integers, a fill-value message; scalar or
-    N-dimensional simple dataspaces;
+    N-dimensional simple dataspaces; or chunked storage behind a shuffle + deflate filter pipeline (ChunkedData: version-3 layout
+    class 2, filter pipeline message version 1, ONE version-1 B-tree leaf - at most 64 chunks - and the chunks behind it), from
+    chunk bytes the caller compressed;
   * attributes (version-1 attribute messages): fixed-length NUL-terminated ASCII strings, numeric scalars / vectors;
   * NetCDF-4 dimensions as HDF5 DIMENSION SCALES: every dimension has a coordinate variable carrying CLASS =
     "DIMENSION_SCALE", NAME, _Netcdf4Dimid and the REFERENCE_LIST back pointers (compound {object reference, uint32}); every
@@ -139,33 +141,113 @@ def _object_header(messages):
     return struct.pack('<BxHII4x', 1, len(messages), 1, len(body)) + body
 
 
+class ChunkedData:
+    """The data of a chunked, filtered variable, compressed by the CALLER: this writer lays the file out and never compresses.
+    shape / dtype: the variable's; chunks: the chunk shape (every chunk is stored full size, edge chunks padded with the fill
+    value); filters: ('shuffle', 'deflate'), ('deflate',) or () in HDF5's pipeline order; packed: the chunks' stored bytes back to
+    back in row-major chunk order (a uint8 array or bytes), chunk k being packed[offsets[k]:offsets[k + 1]].  raider_amd.deflate
+    .compress_chunks makes (packed, offsets) on the device; NumPy shuffle + zlib.compress make the same on the host."""
+
+    def __init__(self, shape, dtype, chunks, packed, offsets, filters=('shuffle', 'deflate'), level=1):
+        self.shape = tuple(int(s) for s in shape)
+        self.dtype = np.dtype(dtype)
+        self.chunks = tuple(int(c) for c in chunks)
+        self.filters = tuple(filters)
+        self.level = int(level)
+        self.packed = np.frombuffer(packed, dtype=np.uint8) if isinstance(packed, (bytes, bytearray, memoryview)) else np.ascontiguousarray(packed, dtype=np.uint8).ravel()
+        self.offsets = np.asarray(offsets, dtype=np.int64).ravel()
+        if len(self.chunks) != len(self.shape) or not self.shape:
+            raise ValueError(f'chunks {self.chunks} do not fit a variable of shape {self.shape}')
+        if any(c <= 0 or c > s for c, s in zip(self.chunks, self.shape)):
+            raise ValueError(f'chunk sizes must lie in 1 .. the dimension size: chunks {self.chunks}, shape {self.shape}')
+        if any(f not in ('shuffle', 'deflate') for f in self.filters):
+            raise ValueError(f"filters are 'shuffle' and 'deflate', not {self.filters}")
+        self.grid = tuple(-(-s // c) for s, c in zip(self.shape, self.chunks))
+        self.nchunks = int(np.prod(self.grid))
+        if self.offsets.size != self.nchunks + 1 or self.offsets[0] != 0 or np.any(np.diff(self.offsets) <= 0) or self.offsets[-1] != self.packed.size:
+            raise ValueError(f'{self.nchunks} chunks need {self.nchunks + 1} increasing offsets from 0 to len(packed) = {self.packed.size}')
+        if np.any(np.diff(self.offsets) >= 1 << 32):
+            raise ValueError('a stored chunk must be smaller than 4 GiB')
+
+
+_CHUNK_K = 32         # superblock version 0 implies it: one leaf of the chunk B-tree holds 2 * K chunks
+_FILTER_IDS = {'deflate': 1, 'shuffle': 2}
+
+
 class _Dataset:
     def __init__(self, name, data, attrs, fill=None):
         self.name = name
-        self.data = _le_array(data)
+        self.chunked = data if isinstance(data, ChunkedData) else None
+        if self.chunked is not None:
+            if self.chunked.nchunks > 2 * _CHUNK_K:
+                raise ValueError(f'variable {name!r} needs {self.chunked.nchunks} chunks; one B-tree leaf holds {2 * _CHUNK_K} '
+                                 '(multi-level chunk trees are not written: choose larger chunks)')
+            _dt_numeric(self.chunked.dtype)
+            self.data = None
+            self.shape, self.dtype = self.chunked.shape, self.chunked.dtype
+        else:
+            self.data = _le_array(data)
+            self.shape, self.dtype = self.data.shape, self.data.dtype
         self.attrs = [_Attr(k, v) for k, v in attrs]
         self.fill = fill
         self.header_addr = None
         self.data_addr = None
 
+    def storage_bytes(self):
+        """Bytes behind data_addr: the array, or the chunk B-tree's leaf followed by the stored chunks."""
+        if self.chunked is None:
+            return self.data.nbytes
+        return self._node_bytes() + int(self.chunked.packed.size)
+
+    def _node_bytes(self):
+        key = 8 + 8 * (len(self.shape) + 1)
+        return 24 + 2 * _CHUNK_K * 8 + (2 * _CHUNK_K + 1) * key
+
+    def storage(self):
+        if self.chunked is None:
+            return self.data.tobytes()
+        c = self.chunked
+        first = self.data_addr + self._node_bytes()
+        node = b'TREE' + struct.pack('<BBHQQ', 1, 0, c.nchunks, UNDEF, UNDEF)
+        for k, idx in enumerate(np.ndindex(*c.grid)):
+            offs = [i * ch for i, ch in zip(idx, c.chunks)] + [0]
+            node += struct.pack('<II', int(c.offsets[k + 1] - c.offsets[k]), 0) + struct.pack(f'<{len(offs)}Q', *offs)
+            node += struct.pack('<Q', first + int(c.offsets[k]))
+        beyond = [c.grid[0] * c.chunks[0]] + [0] * len(c.shape)              # the last key: greater than every chunk's offsets
+        node += struct.pack('<II', 0, 0) + struct.pack(f'<{len(beyond)}Q', *beyond)
+        node += bytes(self._node_bytes() - len(node))
+        return node + c.packed.tobytes()
+
     def header(self, addr_of, gcol_addr):
-        d = self.data
-        msgs = [_message(0x01, _dataspace(d.shape)), _message(0x03, _dt_numeric(d.dtype), flags=1)]
+        c = self.chunked
+        msgs = [_message(0x01, _dataspace(self.shape)), _message(0x03, _dt_numeric(self.dtype), flags=1)]
+        alloc = 2 if c is None else 3                                        # late for contiguous, incremental for chunked storage: libhdf5's defaults
         if self.fill is not None:
-            fv = np.asarray(self.fill, dtype=d.dtype).tobytes()
-            msgs.append(_message(0x05, struct.pack('<BBBBI', 2, 2, 2, 1, len(fv)) + fv))          # v2: alloc late, write if set, defined
+            fv = np.asarray(self.fill, dtype=self.dtype).tobytes()
+            msgs.append(_message(0x05, struct.pack('<BBBBI', 2, alloc, 2, 1, len(fv)) + fv))       # v2: write if set, defined
         else:
-            msgs.append(_message(0x05, struct.pack('<BBBB', 2, 2, 2, 0)))
-        addr = (self.data_addr or 0) if d.size else UNDEF
-        msgs.append(_message(0x08, struct.pack('<BBQQ', 3, 1, addr, d.nbytes)))                  # v3 layout, contiguous
+            msgs.append(_message(0x05, struct.pack('<BBBB', 2, alloc, 2, 0)))
+        if c is None:
+            addr = (self.data_addr or 0) if self.data.size else UNDEF
+            msgs.append(_message(0x08, struct.pack('<BBQQ', 3, 1, addr, self.data.nbytes)))          # v3 layout, contiguous
+        else:
+            if c.filters:
+                body = struct.pack('<BB6x', 1, len(c.filters))
+                for f in c.filters:
+                    client = [self.dtype.itemsize] if f == 'shuffle' else [c.level]
+                    body += struct.pack('<HHHH', _FILTER_IDS[f], 8, 1, len(client)) + _pad8(f.encode() + b'\0')   # optional filter, named as libhdf5 names it
+                    body += struct.pack(f'<{len(client)}I', *client) + (b'\0' * 4 if len(client) % 2 else b'')
+                msgs.append(_message(0x0B, body))
+            dims = list(c.chunks) + [self.dtype.itemsize]
+            msgs.append(_message(0x08, struct.pack('<BBBQ', 3, 2, len(dims), self.data_addr or 0) + struct.pack(f'<{len(dims)}I', *dims)))
         for a in self.attrs:
             msgs.append(_message(0x0C, a.message(addr_of, gcol_addr)))
         return _object_header(msgs)
 
 
 def write_hdf5(path, datasets, root_attrs=()):
-    """datasets: list of (name, array, [(attr name, value), ...], fill value or None).  Attribute values: str, numbers / NumPy
-    arrays, DimensionList, ReferenceList."""
+    """datasets: list of (name, array or ChunkedData, [(attr name, value), ...], fill value or None).  Attribute values: str, numbers /
+    NumPy arrays, DimensionList, ReferenceList."""
     dsets = [_Dataset(n, a, at, fv) for n, a, at, fv in datasets]
     names = [d.name for d in dsets]
     if len(set(names)) != len(names):
@@ -215,7 +297,7 @@ def write_hdf5(path, datasets, root_attrs=()):
     for d in dsets:
         d.header_addr = pos; pos += dry(d.header); pos += -pos % 8
     for d in dsets:
-        d.data_addr = pos; pos += d.data.nbytes; pos += -pos % 8
+        d.data_addr = pos; pos += d.storage_bytes(); pos += -pos % 8
     eof = pos
     addr_of = lambda nm: by_name[nm].header_addr
 
@@ -258,8 +340,8 @@ def write_hdf5(path, datasets, root_attrs=()):
         put(gcol_addr, g)
     for d in dsets:
         put(d.header_addr, d.header(addr_of, gcol_addr))
-        if d.data.nbytes:
-            put(d.data_addr, d.data.tobytes())
+        if d.storage_bytes():
+            put(d.data_addr, d.storage())
     with open(path, 'wb') as fh:
         fh.write(out)
     return str(path)
@@ -269,7 +351,8 @@ def write_netcdf4(path, dims, variables, global_attrs=None, fill_floats=True):
     """A NetCDF-4 (HDF5) file with the classic data model the reference's cubes use.
 
     dims: ordered {name: size}; every dimension needs a coordinate variable of the same name in `variables`.
-    variables: ordered {name: (dim names tuple, array, {attribute: value})}; a scalar variable has dims ().
+    variables: ordered {name: (dim names tuple, array, {attribute: value})}; a scalar variable has dims ().  A ChunkedData in the
+    array's place makes the variable chunked and filtered, from chunk bytes the caller has compressed.
     Floating-point variables get the _FillValue = NaN attribute and fill value xarray writes for them."""
     dims = dict(dims)
     for dname, size in dims.items():
@@ -280,16 +363,16 @@ def write_netcdf4(path, dims, variables, global_attrs=None, fill_floats=True):
     dimid = {d: i for i, d in enumerate(dims)}
     users = {d: [] for d in dims}                      # REFERENCE_LIST back pointers
     for name, (vd, arr, _) in variables.items():
-        arr = np.asarray(arr)
-        if tuple(np.shape(arr)) != tuple(int(dims[d]) for d in vd):
-            raise ValueError(f'variable {name!r} has shape {np.shape(arr)}, its dimensions say {tuple(int(dims[d]) for d in vd)}')
+        arr = arr if isinstance(arr, ChunkedData) else np.asarray(arr)
+        if tuple(arr.shape) != tuple(int(dims[d]) for d in vd):
+            raise ValueError(f'variable {name!r} has shape {tuple(arr.shape)}, its dimensions say {tuple(int(dims[d]) for d in vd)}')
         if name in dims:
             continue
         for ax, d in enumerate(vd):
             users[d].append((name, ax))
     dsets = []
     for name, (vd, arr, attrs) in variables.items():
-        arr = np.asarray(arr)
+        arr = arr if isinstance(arr, ChunkedData) else np.asarray(arr)
         at = []
         fill = None
         if name in dims:

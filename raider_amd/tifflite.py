@@ -8,7 +8,8 @@ samples of uint8/16/32, int8/16/32, float32/64 in any band count; compression 1 
 Where the bytes are decoded: deflate (zlib) and PackBits on the host; LZW on the GPU (rdr_tiff_lzw_decode: the compressed segments go
 up as they are, one wave decodes each) - there is no host LZW decoder here, a pure-Python one needs minutes for a real DEM.  With
 `device=` the decoded segments are put together there too (rdr_tiff_assemble: padding clipped, bytes swapped, predictor undone) and
-the raster never exists on the host; without it, and without LZW, everything is NumPy and no GPU is needed.
+the raster never exists on the host; without it, and without LZW, everything is NumPy and no GPU is needed.  The writer deflates its
+strips with zlib on the host or, with `encoder='device'`, on the GPU in one call (rdr_tiff_predict, rdr_deflate_encode).
 
 Georeferencing as GDAL reads it: ModelPixelScale + ModelTiepoint or ModelTransformation -> the six-number geotransform (a raster-space
 PixelIsPoint moves it by half a pixel), the GeoKey directory -> an EPSG code (ProjectedCSTypeGeoKey, else GeographicTypeGeoKey, else
@@ -467,7 +468,7 @@ class TiffRaster:
 
 # ---- writer ------------------------------------------------------------------------------------------------------------------------
 _BIGTIFF_ABOVE = 0xFFFF0000                               # strip bytes + tables beyond this many bytes: classic 32-bit offsets no longer reach
-_WRITE_TYPES = {'uint8': (8, 1), 'int16': (16, 2), 'float32': (32, 3), 'float64': (64, 3)}
+_WRITE_TYPES = {'uint8': (8, 1), 'uint16': (16, 1), 'int16': (16, 2), 'float32': (32, 3), 'float64': (64, 3)}
 
 
 def _epsg_of(proj):
@@ -497,30 +498,80 @@ def _is_geographic(epsg):
     return 4000 <= epsg <= 4999
 
 
-def write(path, array, transform=None, crs=None, nodata=None, compress=None, rows_per_strip=None):
+def _device_strips(array, h, w, itemsize, rps, predictor):
+    """The strips of `array` (NumPy or device tensor) as zlib streams from the device encoder: the predictor as a kernel of its own
+    (rdr_tiff_predict), every strip in ONE rdr_deflate_encode call, one download of the packed streams."""
+    import torch
+    from . import _lib as L
+    from . import deflate as D
+    if not torch.cuda.is_available():
+        raise RuntimeError("tifflite.write(encoder='device') deflates the strips on the GPU (rdr_deflate_encode); no GPU is visible - use encoder='host'")
+    t = array if D._is_tensor(array) else torch.from_numpy(np.ascontiguousarray(array)).cuda()
+    if not t.is_cuda:
+        t = t.cuda()
+    t = t.contiguous().reshape(-1).view(torch.uint8)
+    if predictor == 2:
+        ctx = L.Context.default()
+        ctx.adopt_torch_stream(t)
+        d = torch.empty_like(t)
+        L.check(ctx.lib.rdr_tiff_predict(ctx.handle, L.ptr(t), itemsize, h, w, L.ptr(d), L.RDR_DEVICE), ctx.handle)
+        t = d
+    row_bytes = w * itemsize
+    offs = np.arange(0, h, rps, dtype=np.int64) * row_bytes
+    sizes = np.minimum(rps, h - np.arange(0, h, rps, dtype=np.int64)) * row_bytes
+    packed, oo = D.deflate_segments(t, offs, sizes)
+    packed = packed.cpu().numpy()
+    return [packed[oo[i]:oo[i + 1]] for i in range(offs.size)]
+
+
+def write(path, array, transform=None, crs=None, nodata=None, compress=None, rows_per_strip=None, predictor=None, encoder='host'):
     """One band as a GeoTIFF in strips: classic TIFF, BigTIFF when the pixels pass 4 GiB; little-endian; compress None or 'deflate'
-    (zlib).  array: 2-D int16 / float32 / float64 (and uint8, what the delay writers make of integer arrays).  transform: GDAL's six numbers (north-up); crs: an EPSG code (see _epsg_of);
-    nodata: written as GDAL_NODATA."""
-    a = np.asarray(array)
-    if a.ndim != 2:
-        raise RuntimeError(f'tifflite.write: cannot write an array of shape {a.shape} to a raster image')
-    if a.dtype.name not in _WRITE_TYPES:
-        raise TypeError(f'tifflite.write: uint8, int16, float32 and float64 are written, not {a.dtype}')
+    (zlib).  array: 2-D uint16 / int16 / float32 / float64 (and uint8, what the delay writers make of integer arrays).  transform: GDAL's six numbers (north-up); crs: an EPSG code (see _epsg_of);
+    nodata: written as GDAL_NODATA.  predictor: None, or 2 (with 'deflate': every row differenced along x in the unsigned integer type
+    of the sample width, tag 317 - what the readers undo).  encoder: 'host' (zlib level 6), or 'device' (with 'deflate': the strips
+    are deflated on the GPU in one call; array may then be a device tensor, and no GPU is an error by name)."""
     if compress not in (None, 'none', 'deflate', 'DEFLATE'):
         raise ValueError(f"compress must be None or 'deflate', not {compress!r}")
     deflate = compress in ('deflate', 'DEFLATE')
-    bits, sfmt = _WRITE_TYPES[a.dtype.name]
-    a = np.ascontiguousarray(a.astype(a.dtype.newbyteorder('<'), copy=False))
-    h, w = a.shape
+    if predictor not in (None, 1, 2):
+        raise ValueError(f'predictor must be None or 2, not {predictor!r}')
+    predictor = 2 if predictor == 2 else None
+    if encoder not in ('host', 'device'):
+        raise ValueError(f"encoder must be 'host' or 'device', not {encoder!r}")
+    if (predictor or encoder == 'device') and not deflate:
+        raise ValueError("predictor=2 and encoder='device' belong to compress='deflate'")
+    tensor = type(array).__module__.split('.')[0] == 'torch'
+    if tensor and encoder != 'device':
+        array = array.cpu().numpy()
+        tensor = False
+    a = None if tensor else np.asarray(array)
+    shape = tuple(array.shape) if tensor else a.shape
+    dtype = np.dtype(str(array.dtype).replace('torch.', '')) if tensor else a.dtype
+    if len(shape) != 2:
+        raise RuntimeError(f'tifflite.write: cannot write an array of shape {shape} to a raster image')
+    if dtype.name not in _WRITE_TYPES:
+        raise TypeError(f'tifflite.write: uint8, uint16, int16, float32 and float64 are written, not {dtype}')
+    bits, sfmt = _WRITE_TYPES[dtype.name]
+    if a is not None:
+        a = np.ascontiguousarray(a.astype(a.dtype.newbyteorder('<'), copy=False))
+    h, w = shape
     if h == 0 or w == 0:
         raise ValueError('tifflite.write: empty raster')
-    row_bytes = w * a.dtype.itemsize
+    row_bytes = w * dtype.itemsize
     rps = int(rows_per_strip) if rows_per_strip else max(1, (1 << 16) // row_bytes)
     rps = min(max(rps, 1), h)
-    strips = []
-    for y in range(0, h, rps):
-        b = a[y:y + rps].tobytes()
-        strips.append(zlib.compress(b, 6) if deflate else b)
+    if encoder == 'device':
+        strips = _device_strips(array if tensor else a, h, w, dtype.itemsize, rps, predictor)
+    else:
+        strips = []
+        for y in range(0, h, rps):
+            rows = a[y:y + rps]
+            if predictor:
+                u = rows.view(f'<u{dtype.itemsize}')
+                rows = u.copy()
+                rows[:, 1:] -= u[:, :-1]
+            b = rows.tobytes()
+            strips.append(zlib.compress(b, 6) if deflate else b)
     data_bytes = sum(len(s) for s in strips)
     big = data_bytes + 16 * len(strips) + 4096 > _BIGTIFF_ABOVE
     epsg = _epsg_of(crs)
@@ -528,6 +579,8 @@ def write(path, array, transform=None, crs=None, nodata=None, compress=None, row
     off_t = 16 if big else 4
     entries += [(_W, 4, [w]), (_H, 4, [h]), (_BPS, 3, [bits]), (_COMP, 3, [8 if deflate else 1]), (_PHOTO, 3, [1]), (_STRIP_OFF, off_t, None), (_SPP, 3, [1]),
                 (_RPS, 4, [rps]), (_STRIP_CNT, off_t, [len(s) for s in strips]), (_PLANAR, 3, [1]), (_SFMT, 3, [sfmt])]
+    if predictor:
+        entries.append((_PRED, 3, [2]))
     if transform is not None:
         gt = [float(v) for v in (transform.to_gdal() if hasattr(transform, 'to_gdal') else transform)]
         if gt[2] != 0.0 or gt[4] != 0.0:

@@ -174,16 +174,28 @@ def writeArrayToRaster(array, path, noDataValue=0.0, fmt='ENVI', proj=None, gt=N
     write_envi(array.astype(dtype), path, nodata=noDataValue, geotransform=gt, proj=proj)
 
 
+def _gpu_visible():
+    try:
+        import torch
+        return bool(torch.cuda.is_available())
+    except ImportError:
+        return False
+
+
 def _write_delay_raster(array, path, ndv, fmt, proj, gt):
     """One delay raster of writeDelays: writeArrayToRaster, except that GTiff - the reference's default raster_format - is written by
-    raider_amd.tifflite (deflate strips; the element type by writeArrayToRaster's rule, complex refused by name) when rasterio is not installed."""
+    raider_amd.tifflite (deflate strips; the element type by writeArrayToRaster's rule, complex refused by name) when rasterio is not installed.
+    With a GPU visible the strips are differenced (predictor 2) and deflated there in one call; without one, zlib on the host as
+    before.  The decoded pixels and every tag but Predictor and the strip byte counts are the same on both routes."""
     import importlib.util
     if str(fmt).upper() == 'GTIFF' and importlib.util.find_spec('rasterio') is None:
         from .tifflite import write as write_tiff
         array = np.asarray(array)
         if array.ndim != 2:
             raise RuntimeError(f'writeArrayToRaster: cannot write an array of shape {np.shape(array)} to a raster image')
-        write_tiff(path, array.astype(_raster_dtype(array)), transform=gt, crs=proj, nodata=ndv, compress='deflate')     # (complex64: refused by name there)
+        dtype = _raster_dtype(array)
+        on_device = dict(encoder='device', predictor=2) if dtype != np.complex64 and array.size and _gpu_visible() else {}
+        write_tiff(path, array.astype(dtype), transform=gt, crs=proj, nodata=ndv, compress='deflate', **on_device)     # (complex64: refused by name there)
         return
     writeArrayToRaster(array, path, noDataValue=ndv, fmt=fmt, proj=proj, gt=gt)
 
