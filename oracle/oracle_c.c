@@ -294,12 +294,16 @@ void orc_prepass_pp(const double* lat, const double* lon, const double* hts, con
     clamp[0] = all_below; clamp[1] = all_above; *any_level = any;
 }
 
-void orc_march_pp(const double* lat, const double* lon, const double* hts, const double* los, int64_t n, const double* zs_lev, double zref,
-                  const int* nparts, int clamp_lo, int clamp_hi,
-                  const double* ys, int ny, const double* xs, int nx, const double* zs, int nz, const void* wet, const void* hyd, int dtype,
-                  double* out_w, double* out_h) {
+/* proj: as in orc_march_proj - every sample goes through the cube's Lambert cone where the slice march sends it, after the z-clamp and
+ * before the interpolation; the partition (orc_prepass_pp) is made in ECEF and does not see the projection */
+void orc_march_pp_proj(const double* lat, const double* lon, const double* hts, const double* los, int64_t n, const double* zs_lev, double zref,
+                       const int* nparts, int clamp_lo, int clamp_hi,
+                       const double* ys, int ny, const double* xs, int nx, const double* zs, int nz, const void* wet, const void* hyd, int dtype,
+                       const double* proj, double* out_w, double* out_h) {
     (void)zs_lev;
     const int M = nz - 1;
+    lcc_t LC;
+    if (proj) lcc_setup(proj, &LC);
 #pragma omp parallel for schedule(static)
     for (int64_t i = 0; i < n; ++i) {
         double o[3], low[3], high[3] = {0, 0, 0}, cosf = 1.0, aw = 0.0, ah = 0.0;
@@ -323,6 +327,7 @@ void orc_march_pp(const double* lat, const double* lon, const double* hts, const
                 ecef2lla(low[0] + f * dx, low[1] + f * dy, low[2] + f * dz, &plon, &plat, &ph);
                 if (clamp_lo && first && j == 0) ph = zs[0];
                 if (clamp_hi && zz == last_zz && j == np - 1) ph = zs[nz - 1];
+                if (proj) { double px, py; lcc_fwd(&LC, plat, plon, &px, &py); plon = px; plat = py; }
                 double vw, vh;
                 rgi2(ys, ny, xs, nx, zs, nz, wet, hyd, dtype, plat, plon, ph, &vw, &vh);
                 double wt = (j == 0 || j == np - 1) ? 0.5 : 1.0;
@@ -333,4 +338,11 @@ void orc_march_pp(const double* lat, const double* lon, const double* hts, const
         }
         out_w[i] = aw; out_h[i] = ah;
     }
+}
+
+void orc_march_pp(const double* lat, const double* lon, const double* hts, const double* los, int64_t n, const double* zs_lev, double zref,
+                  const int* nparts, int clamp_lo, int clamp_hi,
+                  const double* ys, int ny, const double* xs, int nx, const double* zs, int nz, const void* wet, const void* hyd, int dtype,
+                  double* out_w, double* out_h) {
+    orc_march_pp_proj(lat, lon, hts, los, n, zs_lev, zref, nparts, clamp_lo, clamp_hi, ys, ny, xs, nx, zs, nz, wet, hyd, dtype, NULL, out_w, out_h);
 }

@@ -98,6 +98,16 @@ def nparts_of(maxlen, max_seg=1000.0):
     return np.ceil(np.asarray(maxlen) / max_seg).astype(int) + 1          # delay.py:283
 
 
+def _lcc_params(model_proj):
+    """the eight doubles orc_march_proj / orc_march_pp_proj take for a Lambert-conic cube (None: a lon/lat cube)"""
+    if model_proj is None:
+        return None
+    mp = dict(x_0=0.0, y_0=0.0, a=6371229.0, es=0.0); mp.update(model_proj)
+    if mp.pop('proj', 'lcc') != 'lcc':
+        raise ValueError('the C oracle projects Lambert-conic cubes only (raider_oracle has the others)')
+    return np.array([mp['a'], mp['es'], mp['lat_1'], mp['lat_2'], mp['lat_0'], mp['lon_0'], mp['x_0'], mp['y_0']], dtype=np.float64)
+
+
 def build_cube_ray_slice(cube, xpts, ypts, ht, los, zref, max_seg=1000.0, nparts=None, clamp=None, model_proj=None):
     """One height slice of _build_cube_ray (delay.py:256-323) on meshgrid(xpts, ypts) with look vectors los (ny,nx,3).
     cube: dict(xs, ys, zs, wet, hydro (z,y,x)).  Returns (wet, hydro, nparts).  nparts / clamp: the whole slice's partition and
@@ -120,10 +130,7 @@ def build_cube_ray_slice(cube, xpts, ypts, ht, los, zref, max_seg=1000.0, nparts
             clamp = (own[0], own[1])
     np32 = np.ascontiguousarray(nparts, dtype=np.int32)
     ow, oh = np.empty(n), np.empty(n)
-    proj = None
-    if model_proj is not None:
-        mp = dict(x_0=0.0, y_0=0.0, a=6371229.0, es=0.0); mp.update(model_proj)
-        proj = np.array([mp['a'], mp['es'], mp['lat_1'], mp['lat_2'], mp['lat_0'], mp['lon_0'], mp['x_0'], mp['y_0']], dtype=np.float64)
+    proj = _lcc_params(model_proj)
     L.orc_march_proj(_p(lat), _p(lon), _p(los), C.c_int64(n), C.c_double(ht), _p(lo), _p(hi), C.c_int(K), _p(np32), C.c_int(clamp[0]), C.c_int(clamp[1]),
                      _p(ys), C.c_int(ys.size), _p(xs), C.c_int(xs.size), _p(zs), C.c_int(zs.size), _p(wet), _p(hyd), C.c_int(dtype),
                      _p(proj) if proj is not None else None, _p(ow), _p(oh))
@@ -155,10 +162,10 @@ def per_pixel_nparts(maxlen, max_seg=1000.0):
         return np.where(maxlen > 0, np.ceil(maxlen / max_seg) + 1, 0).astype(np.int32)
 
 
-def build_cube_ray_per_pixel(cube, lat, lon, hts, los, zref, max_seg=1000.0, nparts=None, clamp=None):
+def build_cube_ray_per_pixel(cube, lat, lon, hts, los, zref, max_seg=1000.0, nparts=None, clamp=None, model_proj=None):
     """Rays with their OWN origin heights (no reference semantics; rule in oracle_c.c / DESIGN.md 5c): lat, lon, hts of one shape,
     los (..., 3).  Returns (wet, hydro, nparts[nz-1]) with nparts indexed by model interval (0 where no ray passes).  nparts / clamp:
-    the whole batch's when these rays are only a block of it."""
+    the whole batch's when these rays are only a block of it.  model_proj: as in build_cube_ray_slice, applied where it applies it."""
     L = lib()
     shape, lat, lon, hts, los = _pp_inputs(cube, lat, lon, hts, los)
     n = lat.size
@@ -178,6 +185,8 @@ def build_cube_ray_per_pixel(cube, lat, lon, hts, los, zref, max_seg=1000.0, npa
             clamp = (own[0], own[1])
     np32 = np.ascontiguousarray(nparts, dtype=np.int32)
     ow, oh = np.empty(n), np.empty(n)
-    L.orc_march_pp(_p(lat), _p(lon), _p(hts), _p(los), C.c_int64(n), _p(zs), C.c_double(zref), _p(np32), C.c_int(clamp[0]), C.c_int(clamp[1]),
-                   _p(ys), C.c_int(ys.size), _p(xs), C.c_int(xs.size), _p(zs), C.c_int(zs.size), _p(wet), _p(hyd), C.c_int(dtype), _p(ow), _p(oh))
+    proj = _lcc_params(model_proj)
+    L.orc_march_pp_proj(_p(lat), _p(lon), _p(hts), _p(los), C.c_int64(n), _p(zs), C.c_double(zref), _p(np32), C.c_int(clamp[0]), C.c_int(clamp[1]),
+                        _p(ys), C.c_int(ys.size), _p(xs), C.c_int(xs.size), _p(zs), C.c_int(zs.size), _p(wet), _p(hyd), C.c_int(dtype),
+                        _p(proj) if proj is not None else None, _p(ow), _p(oh))
     return ow.reshape(shape), oh.reshape(shape), np.asarray(np32)

@@ -654,14 +654,16 @@ def ray_levels_idx(model_zs, ht, zref):
     return out
 
 
-def build_cube_ray_per_pixel(lat, lon, hts, LOS, interpolators, MAX_SEGMENT_LENGTH=1000.0, MAX_TROPO_HEIGHT=_ZREF, nParts_override=None):
+def build_cube_ray_per_pixel(lat, lon, hts, LOS, interpolators, MAX_SEGMENT_LENGTH=1000.0, MAX_TROPO_HEIGHT=_ZREF, nParts_override=None,
+                             model_proj=None):
     """Rays with their OWN origin heights (SURVEY 8d "c3b": no reference semantics).  The rule: the reference's
     slice algorithm (delay.py:256-323) ray by ray wherever it is per ray - build_ray with the ray's height, its first contributing
     interval fixing cos_factor - and batch-level wherever the reference reduces over the slice: nParts[zz] = ceil(max over the
     rays interval zz contributes to / MAX_SEGMENT_LENGTH) + 1 (delay.py:283), and the all-pixels z-clamp (delay.py:306-311) asked
     about every ray's own first / last sample.  Built from the pinned slice functions (build_ray, scipy-RGI restatement), one ray
     at a time - small inputs only; oracle_c.build_cube_ray_per_pixel is the fast form.
-    lat, lon, hts: 1-D arrays; LOS (n, 3).  Returns (wet[n], hydro[n], nparts[nz-1] indexed by model interval)."""
+    lat, lon, hts: 1-D arrays; LOS (n, 3).  Returns (wet[n], hydro[n], nparts[nz-1] indexed by model interval).
+    model_proj: the cube's CRS as integrate_slice takes it, applied to every sample where integrate_slice applies it."""
     model_zs = np.asarray(interpolators[0].grid[2], dtype=np.float64)
     lat = np.asarray(lat, dtype=np.float64).ravel(); lon = np.asarray(lon, dtype=np.float64).ravel()
     hts = np.asarray(hts, dtype=np.float64)
@@ -698,6 +700,8 @@ def build_cube_ray_per_pixel(lat, lon, hts, LOS, interpolators, MAX_SEGMENT_LENG
             for findex, ff in enumerate(fracs):
                 pts_xyz = lows[k] + ff * (highs[k] - lows[k])
                 plon, plat, ph = ecef2lla(pts_xyz[..., 0], pts_xyz[..., 1], pts_xyz[..., 2])
+                if model_proj is not None:
+                    plon, plat = project_forward(plat, plon, model_proj)
                 pts = np.stack((plat, plon, ph), axis=-1)
                 if clamp_lo and k == 0 and findex == 0:
                     pts[..., -1] = zmin
