@@ -401,6 +401,16 @@ int rdr_ray_prepass_device(rdr_ctx* ctx, const rdr_cube* cube, const rdr_rays* r
 int rdr_ray_march_device(rdr_ctx* ctx, const rdr_cube* cube, const rdr_rays* rays, double ht, double zref, double max_seg,
                          const double* partition, double* wet, double* hydro);
 
+/* The level table pass 2 reads (tests, diagnostics): per slice hts[s] nz+1 records of 80 bytes - the slice's K levels, a weight-0
+ * sentinel behind the last one, zeros after it - written by the kernel that writes it before every pass 2.  A record is, in order,
+ * the doubles xv, hs, step, zmid, r0, r1, gk, rk (abscissa of the level's top in the crossing polynomial; 0.5e-6/(nParts-1);
+ * 1/(nParts-1); node g[zb+1] under the level's top and 1/(g[zb+1]-g[zb]), 1/(g[zb+2]-g[zb+1]), zb = clamp(kz, 0, nz-3); g[kz] and
+ * 1/(g[kz+1]-g[kz])), then int32 npkz = nParts | kz << 17 and three zero int32.  The partition is given as rdr_ray_march takes it,
+ * nparts[nslices][ld] (maxlen NULL), or as pass 1 leaves it, length maxima maxlen[nslices][ld] with max_seg (nparts NULL);
+ * nz-1 <= ld <= 512.  records: HOST buffer of nslices * (nz+1) * 80 bytes.  Synchronises. */
+int rdr_level_table(rdr_ctx* ctx, const rdr_cube* cube, const double* hts, int32_t nslices, double zref, const int32_t* nparts,
+                    const double* maxlen, int32_t ld, double max_seg, void* records);
+
 /* Pass 2 (delay.py:285-323 + build_ray recomputed in registers): trapezoid integral of both fields along
  * each ray with the GIVEN partition nparts[K] (host array) and clamp decision `flags`.
  * wet/hydro: [n] outputs (overwritten, not accumulated), location = rays->loc. */

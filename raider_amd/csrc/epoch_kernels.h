@@ -64,7 +64,7 @@ void march_epochs_kernel(CubeView<T2> c_in, EpochCubes<T2, E> ev, RayParams P, i
         if (sl != slice) {                                 // the slice's level table and partition (packed records: the slice loop only)
             slice = sl;
             K = fill_levels(c.nz, m, P.hts ? P.hts[sl] : P.ht, P.zref);
-            const SlicePartition part = fill_partition<!PR>(P, m, c.nz, sl, K);
+            const SlicePartition part = fill_partition(P, m, sl, K);
             poison = part.poison; clamp_lo = part.clamp_lo; clamp_hi = part.clamp_hi;
         }
         int tl = threadIdx.x;
@@ -87,10 +87,11 @@ void march_epochs_kernel(CubeView<T2> c_in, EpochCubes<T2, E> ev, RayParams P, i
         const double scale = scale_rec;
         const double u0r = w[(int64_t)WS_U0 * ns], u1r = w[(int64_t)WS_U1 * ns];
         const unsigned long long live = __builtin_amdgcn_ballot_w64(active && mine);
+        const LevelRec* const lev = PR ? nullptr : P.lev + (int64_t)__builtin_amdgcn_readfirstlane(sl) * (c.nz + 1);     // (per tile: march_kernel)
         auto run = [&](auto nochk) {
             constexpr bool NC = decltype(nochk)::value;
             if constexpr (PR) march_ray_height_levels<T2, E, NC>(c, ev, m, q, xc, u0r, u1r, K, k0, lo_first, clamp_lo, clamp_hi, acc_w, acc_h);
-            else march_slice_levels<T2, E, NC>(c, ev, m, q, xc, u0r, u1r, K, clamp_lo, clamp_hi, live, acc_w, acc_h);
+            else march_slice_levels<T2, E, NC>(c, ev, m, q, xc, lev, u0r, u1r, K, clamp_lo, clamp_hi, live, acc_w, acc_h);
         };
         // the wave-wide no-check proof (lane_nocheck): bounds of the cell search from the polynomial coefficients
         bool lane_safe = false;

@@ -68,6 +68,7 @@ struct rdr_ctx {
     DevBuf ws;                                // pass 1 -> pass 2 workspace (field-major ray records, 232 B per ray)
     DevBuf side;                              // level crossings of the generic rays (compact columns of K+1 doubles)
     int64_t side_cap = 0;                     // columns of `side` in the current layout
+    DevBuf lev;                               // level table of pass 2: [nslices][nz + 1] LevelRec (level_table_kernel)
     int* d_sidectr = nullptr;                 // [1] next free column
     int* h_word = nullptr;                    // [16] page-locked host words: flags read back WITHOUT stalling the host before the final sync
     // Small host inputs (axes, level lists, a cube's three axes) go up through a ring of page-locked buffers: the caller's array is consumed by a
@@ -416,6 +417,7 @@ void rdr_destroy(rdr_ctx* c) {
     if (c->d_tilectr) (void)hipFree(c->d_tilectr);
     if (c->ws.p) (void)hipFree(c->ws.p);
     if (c->side.p) (void)hipFree(c->side.p);
+    if (c->lev.p) (void)hipFree(c->lev.p);
     if (c->d_sidectr) (void)hipFree(c->d_sidectr);
     if (c->h_word) (void)hipHostFree(c->h_word);
     if (c->nan_words) (void)hipHostFree(c->nan_words);
@@ -535,6 +537,7 @@ int rdr_trim(rdr_ctx* c, int64_t keep_bytes, int64_t* released) {
     if ((c->ws.p && c->ws.cap > keep) || (c->side.p && c->side.cap > keep)) c->wsig.valid = false;      // (the stored ray records go with them)
     drop(c->ws);
     if (c->side.p && c->side.cap > keep) { drop(c->side); c->side_cap = 0; }
+    drop(c->lev);
     std::lock_guard<std::recursive_mutex> guard(g_view_mutex);
     while (!c->cube_pool.empty() && c->cube_pool_bytes > keep) {          // oldest first
         rdr_ctx::PoolEntry e = c->cube_pool.front();
@@ -2088,6 +2091,36 @@ static int march_grid(const rdr_cube* q, bool per_ray) {
     return (!per_ray && !q->exact[0] && !q->exact[1] && q->uni[0] && q->uni[1]) ? 2 : 0;
 }
 
+// The level table of a pass 2 over slices [s0, s0 + ns) of P's batch (level_table_kernel: one workgroup per slice, all inputs on the
+// device, no host synchronisation) and P.lev -> it.  ONCE per pass 2 - by whoever runs the pass-2 launches of a partition (ray_passes,
+// raytrace_pipelined, the record-reusing marches), not per chunk of tiles - after the slices' partition is complete on the stream and
+// inside the timing scope of pass 2.  Per-ray heights: nothing reads a table (P.lev stays null).
+static int launch_level_table(rdr_ctx* c, const rdr_cube* q, RayParams& P, int64_t s0, int64_t ns) {
+    P.lev = nullptr;
+    if (P.ht_ray || ns <= 0) return RDR_OK;
+    const size_t need = (size_t)P.nslices * (size_t)(q->nz + 1) * sizeof(LevelRec);
+    if (c->lev.cap < need) {
+        if (c->lev.p) { HIPCHECK(c, hipStreamSynchronize(c->stream)); HIPCHECK(c, hipFree(c->lev.p)); c->lev.p = nullptr; c->lev.cap = 0; }
+        { const int rc_ = dev_malloc(c, &c->lev.p, need); if (rc_) return rc_; }
+        c->lev.cap = need;
+    }
+    P.lev = (const LevelRec*)c->lev.p;
+    hipError_t e;
+    {
+        KTimer t(c, 1);
+        e = launch_lds(level_table_kernel<float2>, dim3((unsigned)ns), dim3(BLOCK), ray_smem_bytes(0, 0, q->nz, 1, 1), c->stream, make_view<float2>(q), P, (int)s0,
+                       (LevelRec*)c->lev.p);
+    }
+    if (e != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("level_table_kernel launch: ") + hipGetErrorString(e));
+    return RDR_OK;
+}
+
+// a light slice march without its level table is a driver's mistake, not something to trace around
+static int check_level_table(rdr_ctx* c, const RayParams& P) {
+    if (!P.ht_ray && !P.lev) return fail(c, RDR_ERR_INVALID, "pass 2 was launched without its level table (launch_level_table)");
+    return RDR_OK;
+}
+
 // generic-ray mop-up of pass 2 on the records of P, tile counters d_tilectr + 24 (zero_ctr: not yet zeroed); the kernel returns at once
 // when pass 1 found no generic ray
 static int launch_march_generic(rdr_ctx* c, const rdr_cube* q, RayParams P, dim3 G, dim3 B, size_t sm, bool zero_ctr) {
@@ -2102,6 +2135,7 @@ static int launch_march_generic(rdr_ctx* c, const rdr_cube* q, RayParams P, dim3
 
 static int launch_march(rdr_ctx* c, const rdr_cube* q, RayParams P, int64_t tb, int64_t tc, int64_t nslots_total = 0) {
     P.tile_begin = tb; P.tile_count = tc; P.nslots = nslots_total > 0 ? nslots_total : tc * BLOCK;
+    { const int rc = check_level_table(c, P); if (rc) return rc; }
     static const int stage_f64 = []() { const char* e = std::getenv("RAIDER_HIP_F64_STAGE"); return e ? std::atoi(e) : 1; }();
     P.stage_f64 = stage_f64;
     const int g = ray_grid(c, tc, 8);
@@ -2154,6 +2188,7 @@ static hipError_t launch_stacked(rdr_ctx* c, const rdr_cube* const* qs, int grid
 // P.wet / P.hyd: epoch 0's [nslices][n] block, epoch e's is estride doubles further.
 static int launch_march_epochs(rdr_ctx* c, const rdr_cube* const* qs, int D, RayParams P, int64_t tb, int64_t tc, int64_t estride) {
     const rdr_cube* q = qs[0];
+    { const int rc = check_level_table(c, P); if (rc) return rc; }
     const int emax = epochs_max();
     const bool per_ray = P.ht_ray != nullptr;
     const int grid = march_grid(q, per_ray);
@@ -2232,6 +2267,7 @@ static int ray_passes(rdr_ctx* c, const rdr_cube* q, const RayParams& P, int K, 
             int rc = ws_reserve(c, ns * per, K, Pg); if (rc) return rc;
             rc = launch_crossings(c, q, Pg, s0 * per, ns * per); if (rc) return rc;
             Pg.maxlen_bits = P.maxlen_bits;
+            rc = launch_level_table(c, q, Pg, s0, ns); if (rc) return rc;
             rc = pass2(Pg, s0 * per, ns * per); if (rc) return rc;
             if (after_group) { rc = after_group(s0, ns); if (rc) return rc; }
         }
@@ -2246,6 +2282,7 @@ static int ray_passes(rdr_ctx* c, const rdr_cube* q, const RayParams& P, int K, 
         }
         RayParams Pw = P;
         rc = ws_reserve(c, fit, K, Pw); if (rc) return rc;
+        rc = launch_level_table(c, q, Pw, s, 1); if (rc) return rc;      // (the slice's partition is complete: once for all its chunks)
         for (int64_t tb = 0; tb < per; tb += fit) {
             const int64_t tc = std::min<int64_t>(fit, per - tb);
             RayParams Pc = Pw;
@@ -2292,6 +2329,7 @@ static int raytrace_pipelined(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, 
         RayParams Pk = P; Pk.ws = ws + tb * BLOCK;
         status = launch_crossings(c, q, Pk, tb, tc, nslots_total, k == 0);
     }
+    if (status == RDR_OK) status = launch_level_table(c, q, P, 0, 1);      // (every chunk's pass 1 is enqueued: the partition is complete)
     for (int k = 0; k < nchunk && status == RDR_OK; ++k) {
         int64_t tb, tc, r0, cnt; range(k, tb, tc, r0, cnt);
         RayParams Pk = P; Pk.ws = ws + tb * BLOCK;
@@ -2395,10 +2433,45 @@ int rdr_ray_march_device(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, doubl
     P.wet = wet; P.hyd = hydro;
     hipLaunchKernelGGL(unpack_partition_kernel, dim3(1), dim3(256), 0, c->stream, partition, K, c->d_maxlen, c->d_flags);
     HIPCHECK(c, hipGetLastError());
-    if (reuse) { ws_attach(c, P); rc = launch_march(c, q, P, 0, P.ntiles); }
+    if (reuse) { ws_attach(c, P); rc = launch_level_table(c, q, P, 0, 1); if (!rc) rc = launch_march(c, q, P, 0, P.ntiles); }
     else rc = ray_passes(c, q, P, K, P.ntiles, 1, ws_chunk_tiles(c, K), 1, false);
     c->wsig.valid = false;
     return rc;
+}
+
+// The level table pass 2 would read for slices at hts[] with the given partition, back on the host (tests, diagnostics): the same kernel
+// on the same inputs - nParts rows (the rdr_ray_march form) or length maxima and max_seg (what pass 1 leaves on the device).
+int rdr_level_table(rdr_ctx* c, const rdr_cube* q, const double* hts, int32_t nslices, double zref, const int32_t* nparts, const double* maxlen,
+                    int32_t ld, double max_seg, void* records) {
+    if (!c || !q || !hts || !records || (nparts == nullptr) == (maxlen == nullptr))
+        return fail(c, RDR_ERR_INVALID, "rdr_level_table: NULL argument, or not exactly one of nparts / maxlen");
+    if (nslices < 1 || nslices > MAX_SLICES) return fail(c, RDR_ERR_INVALID, "rdr_level_table: 1..512 slices per call");
+    if (ld < (int32_t)q->nz - 1 || ld > MAX_LEVELS) return fail(c, RDR_ERR_INVALID, "rdr_level_table: rows of nz-1 .. 512 entries");
+    if (maxlen && !(max_seg > 0)) return fail(c, RDR_ERR_INVALID, "rdr_level_table: MAX_SEGMENT_LENGTH must be positive");
+    note_use(c, q);
+    HIPCHECK(c, hipSetDevice(c->device));
+    RayParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.nslices = nslices; P.ht = hts[0]; P.zref = zref; P.max_seg = maxlen ? max_seg : 1000.0;
+    // rows of MAX_LEVELS entries, as the kernels index them: nParts as they are, maxima as their bit patterns
+    std::vector<unsigned long long> rows(maxlen ? (size_t)nslices * MAX_LEVELS : 0, 0ULL);
+    std::vector<int> irows(nparts ? (size_t)nslices * MAX_LEVELS : 0, 0);
+    for (int s = 0; s < nslices; ++s)
+        for (int k = 0; k < ld; ++k) {
+            if (nparts) irows[(size_t)s * MAX_LEVELS + k] = nparts[(size_t)s * ld + k];
+            else std::memcpy(&rows[(size_t)s * MAX_LEVELS + k], &maxlen[(size_t)s * ld + k], 8);
+        }
+    const void *dht, *drows;
+    int rc = stage_in(c, SLOT_AUX, hts, (size_t)nslices * 8, RDR_HOST, &dht); if (rc) return rc;
+    rc = nparts ? stage_in(c, SLOT_IN4, irows.data(), irows.size() * sizeof(int), RDR_HOST, &drows)
+                : stage_in(c, SLOT_IN4, rows.data(), rows.size() * 8, RDR_HOST, &drows);
+    if (rc) return rc;
+    P.hts = (const double*)dht;
+    if (nparts) P.nparts_override = (const int*)drows; else P.maxlen_bits = (unsigned long long*)const_cast<void*>(drows);
+    rc = launch_level_table(c, q, P, 0, nslices); if (rc) return rc;
+    HIPCHECK(c, hipMemcpyAsync(records, P.lev, (size_t)nslices * (size_t)(q->nz + 1) * sizeof(LevelRec), hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return RDR_OK;
 }
 
 int rdr_ray_march(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, double ht, double zref, const int32_t* nparts, int32_t flags,
@@ -2425,7 +2498,7 @@ int rdr_ray_march(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, double ht, d
     rc = stage_out(c, SLOT_OUT0, wet, (size_t)r->n * 8, r->loc, &dw); if (rc) return rc;
     rc = stage_out(c, SLOT_OUT1, hydro, (size_t)r->n * 8, r->loc, &dh); if (rc) return rc;
     P.wet = (double*)dw; P.hyd = (double*)dh;
-    if (reuse) { ws_attach(c, P); rc = launch_march(c, q, P, 0, P.ntiles); }
+    if (reuse) { ws_attach(c, P); rc = launch_level_table(c, q, P, 0, 1); if (!rc) rc = launch_march(c, q, P, 0, P.ntiles); }
     else rc = ray_passes(c, q, P, K, P.ntiles, 1, ws_chunk_tiles(c, K), 1, false);
     c->wsig.valid = false;
     if (rc) return rc;

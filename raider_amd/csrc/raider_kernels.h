@@ -467,6 +467,7 @@ __device__ __forceinline__ void fit_crossing_poly(const double* hpoly, double su
 constexpr int WS_POLY_H = 0, WS_POLY_LAT = 6, WS_POLY_LON = 12, WS_XPOLY = 18, WS_SCALE = 26, WS_U0 = 27, WS_U1 = 28, WS_NFIELDS = 29;
 constexpr int WS_ORIGIN = 0, WS_LOS = 3, WS_LAT0 = 6, WS_LON0 = 7, WS_S0 = 8, WS_C0 = 9, WS_SL0 = 10, WS_CL0 = 11, WS_SIDE = 12;
 
+struct LevelRec;
 struct RayParams {
     // geometry
     int64_t n;
@@ -496,6 +497,8 @@ struct RayParams {
     double* side; int64_t side_cap;    // crossings of the generic rays (compact columns), int* side_ctr = next free column
     int* side_ctr;
     int64_t tile_begin, tile_count;
+    const LevelRec* lev;               // [nslices][nz + 1] level records of the light slice loop, written by level_table_kernel BEFORE pass 2 (the march
+                                       // kernels read them through the scalar cache and never write them); nullptr: per-ray heights, pass 1
     // outputs
     double* wet; double* hyd;
     // tiling of the whole batch
@@ -551,8 +554,10 @@ __device__ __forceinline__ int first_level(const double2* ez, int nz, const doub
 // Shared LDS layout of the two ray kernels.  Axis tables are (g[i], 1/(g[i+1]-g[i])) pairs; an x / y axis that is uniform to
 // round-off (CubeView::exact_*) needs no table at all (cell_xy works from g0 and the spacing), so the usual lat/lon or LCC grid
 // costs 16 B per z level only - a CONUS-sized HRRR grid (1059 x 1799 nodes) would otherwise take 69 KB per workgroup.
-// Pass 2's per-level record (slice loop of the light marcher): everything a level needs that is the same for every ray of the slice,
-// packed so that ONE LDS address register serves all the reads of a level (as separate arrays every read cost a v_mov of its own).
+// Pass 2's per-level record (slice loop of the light marcher): everything a level needs that is the same for every ray of the slice.
+// The records live in a device table (RayParams::lev: per slice nz + 1 of them - the K levels, the weight-0 sentinel behind the last,
+// zeros after it), written by level_table_kernel before pass 2 and read by the march kernels with SCALAR loads one level ahead: the
+// values are SGPR operands of the fp64 instructions, no vector register, no LDS access and no wait stands in front of a level's gathers.
 struct __attribute__((aligned(16))) LevelRec {
     double xv, hs;          // abscissa of the level's top in the crossing polynomial; 0.5e-6/(nParts-1)
     double step, zmid;      // 1/(nParts-1); node g[zb+1] the level's top sits on, zb = window2_base(nz, kz)
@@ -560,14 +565,13 @@ struct __attribute__((aligned(16))) LevelRec {
     double gk, rk;          // g[kz], 1/(g[kz+1]-g[kz]): the model interval of the level's interior samples
     int npkz, pad[3];       // nParts | kz << 17
 };
-static_assert(sizeof(LevelRec) == 80, "LevelRec is read with fixed LDS offsets");
+static_assert(sizeof(LevelRec) == 80, "LevelRec is the host-visible record of rdr_level_table (include/raider_hip.h)");
 
 struct RaySmem {
     AxisTabs ax;            // axis tables (ey / ex are null for exact axes)
     double2* tab2;          // backing store of the tables
     double* lo; double* hi; // level table
     unsigned long long* mxcol; // [nz][MXCOLS] per-level running maxima of the workgroup, one column per lane%MXCOLS (pass 1)
-    LevelRec* lev;          // [nz] pass 2 only: the same bytes as mxcol (80 <= 8 * MXCOLS per level)
     double* step;           // [nz] 1/(nParts-1) (pass 2)
     double* hs;             // [nz] 0.5e-6/(nParts-1): half the trapezoid weight per unit of ray length (pass 2)
     double* trig;           // [64] (sin, cos) of the tile's 16 row latitudes, then of its 16 column longitudes (pass 1, GRID rays);
@@ -577,7 +581,6 @@ struct RaySmem {
     int* kz; int* np; int* K;
 };
 constexpr int MXCOLS = 16;
-static_assert(sizeof(LevelRec) <= 8 * MXCOLS, "LevelRec aliases a level's mxcol columns");
 __host__ __device__ inline int64_t table_nodes(int64_t ny, int64_t nx, int64_t nz, int exact_y, int exact_x) {
     return (exact_y ? 0 : ny) + (exact_x ? 0 : nx) + nz;
 }
@@ -591,7 +594,6 @@ __device__ __forceinline__ RaySmem carve_smem(unsigned char* raw, int ny, int nx
     m.lo = reinterpret_cast<double*>(m.tab2 + nyt + nxt + nz);
     m.hi = m.lo + nz;
     m.mxcol = reinterpret_cast<unsigned long long*>(m.hi + nz);
-    m.lev = reinterpret_cast<LevelRec*>(m.mxcol);
     m.step = reinterpret_cast<double*>(m.mxcol + (size_t)nz * MXCOLS);
     m.hs = m.step + nz;
     m.trig = m.hs + nz;
@@ -1161,42 +1163,39 @@ struct SlicePartition {
     bool clamp_lo, clamp_hi;
 };
 
-// Integration partition of slice sl, after fill_levels (workgroup-uniform; called by every thread).  REC: also the packed records
-// of the light slice loops (the per-ray-height loops and the generic kernel read the separate arrays).
-template <bool REC>
-__device__ __forceinline__ SlicePartition fill_partition(const RayParams& P, const RaySmem& m, int nz, int sl, int K) {
+// nParts of level k of slice sl (delay.py:283) from the given partition or the slice's length maxima; diverged: the lengths ask for
+// fewer than 2 or more than MAX_NPARTS parts (e.g. look vectors far from unit length) - the loops run with 2, the caller flags it.
+__device__ __forceinline__ int level_nparts(const RayParams& P, int sl, int k, bool& diverged) {
+    int np;
+    if (P.nparts_override) np = P.nparts_override[(int64_t)sl * MAX_LEVELS + k];
+    else {
+        const double parts = ceil(__longlong_as_double((long long)P.maxlen_bits[(int64_t)sl * MAX_LEVELS + k]) / P.max_seg) + 1.0;   // delay.py:283
+        np = (parts >= 1.0 && parts <= (double)MAX_NPARTS) ? (int)parts : -1;
+    }
+    diverged = np < 2 || np > MAX_NPARTS;
+    return diverged ? 2 : np;
+}
+__device__ __forceinline__ double level_step(int np) { return 1.0 / ((double)np - 1.0); }       // np.linspace(0,1,np) (delay.py:287)
+__device__ __forceinline__ double level_half_weight(double step) { return 0.5e-6 * step; }       // delay.py:314-315: end points get half of L*1e-6/(np-1)
+
+// Integration partition of slice sl, after fill_levels (workgroup-uniform; called by every thread): the separate LDS arrays the
+// per-ray-height loops and the generic kernel read, and what the partition decides for every ray of the slice.  (The light slice
+// loop reads the same values from the level table: level_table_kernel.)
+__device__ __forceinline__ SlicePartition fill_partition(const RayParams& P, const RaySmem& m, int sl, int K) {
     int tz = threadIdx.x;
     asm volatile("" : "+v"(tz));                   // (opaque: nothing derived from it is hoisted out of the tile loop and spilled)
     if (tz == 0) m.K[1] = 0;
     __syncthreads();
     for (int k = tz; k < K; k += BLOCK) {
-        int np;
-        if (P.nparts_override) np = P.nparts_override[(int64_t)sl * MAX_LEVELS + k];
-        else {
-            const double parts = ceil(__longlong_as_double((long long)P.maxlen_bits[(int64_t)sl * MAX_LEVELS + k]) / P.max_seg) + 1.0;   // delay.py:283
-            np = (parts >= 1.0 && parts <= (double)MAX_NPARTS) ? (int)parts : -1;
-        }
-        if (np < 2 || np > MAX_NPARTS) {      // diverged lengths (e.g. look vectors far from unit length): refuse to loop over them
-            np = 2;
+        bool diverged;
+        const int np = level_nparts(P, sl, k, diverged);
+        if (diverged) {                       // refuse to loop over diverged lengths
             atomicOr(P.flags + sl, 16);       // RDR_FLAG_DIVERGED
             m.K[1] = 1;
         }
         m.np[k] = np;
-        m.step[k] = 1.0 / ((double)np - 1.0);                    // np.linspace(0,1,np) (delay.py:287)
-        m.hs[k] = 0.5e-6 * m.step[k];                            // delay.py:314-315: end points get half of L*1e-6/(np-1)
-        if constexpr (REC) {                                     // the slice loop's packed record of the level
-            const int kzk = m.kz[k], last = nz - 1;
-            const int zb = max(window2_base(nz, kzk), 0);        // (nz = 2: the window is never trusted, only in-range reads matter)
-            LevelRec r;
-            r.xv = m.xv[k]; r.hs = m.hs[k]; r.step = m.step[k];
-            r.zmid = m.ax.ez[min(zb + 1, last)].x; r.r0 = m.ax.ez[zb].y; r.r1 = m.ax.ez[min(zb + 1, last)].y;
-            r.gk = m.ax.ez[kzk].x; r.rk = m.ax.ez[kzk].y;
-            r.npkz = np | (kzk << 17); r.pad[0] = r.pad[1] = r.pad[2] = 0;
-            m.lev[k] = r;
-            // one record past the last level (K <= nz-1): the "next level" of the last one repeats its top abscissa with weight 0,
-            // so the loop computes du1 = X(v) - X(v) = 0 and adds 0 * 0 to the top weight instead of branching on `more`
-            if (k == K - 1) { r.hs = 0.0; r.npkz = 2 | (kzk << 17); m.lev[K] = r; }
-        }
+        m.step[k] = level_step(np);
+        m.hs[k] = level_half_weight(m.step[k]);
     }
     __syncthreads();
     const int flags_in = P.flags[sl];
@@ -1209,6 +1208,51 @@ __device__ __forceinline__ SlicePartition fill_partition(const RayParams& P, con
     s.clamp_lo = !(flags_in & 4);               // ALL first samples below zmin  (delay.py:306-307)
     s.clamp_hi = !(flags_in & 8);               // ALL last samples above zmax   (delay.py:310-311)
     return s;
+}
+
+// The record of level k of a slice (after fill_levels; np: the level's nParts): what the slice loop reads of it.
+__device__ __forceinline__ LevelRec make_level_rec(const RaySmem& m, int nz, int k, int np) {
+    const int kzk = m.kz[k], last = nz - 1;
+    const int zb = max(window2_base(nz, kzk), 0);            // (nz = 2: the window is never trusted, only in-range reads matter)
+    LevelRec r;
+    r.step = level_step(np); r.hs = level_half_weight(r.step); r.xv = m.xv[k];
+    r.zmid = m.ax.ez[min(zb + 1, last)].x; r.r0 = m.ax.ez[zb].y; r.r1 = m.ax.ez[min(zb + 1, last)].y;
+    r.gk = m.ax.ez[kzk].x; r.rk = m.ax.ez[kzk].y;
+    r.npkz = np | (kzk << 17); r.pad[0] = r.pad[1] = r.pad[2] = 0;
+    return r;
+}
+
+// The level table of pass 2 (RayParams::lev): workgroup b writes the nz + 1 records of slice first_slice + b from what fill_partition
+// reads - the slice's height, zref, the z axis and its partition (length maxima or given nParts), all on the device, no host round trip.
+// A kernel of its own, once per pass 2: the march kernels read the table through the scalar cache, which does not see vector stores of the
+// same kernel - the table is complete at a kernel boundary of the stream.  It only reads the partition: flags are fill_partition's.
+// Launched with ray_smem_bytes(0, 0, nz, 1, 1) of LDS (the z table and the level arrays; no horizontal axis).
+template <typename T2>
+__global__ __launch_bounds__(BLOCK) void level_table_kernel(CubeView<T2> c, RayParams P, int first_slice, LevelRec* table) {
+    c.exact_y = 1; c.exact_x = 1;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const RaySmem m = carve_smem(smem_raw, c.ny, c.nx, c.nz, 1, 1);
+    fill_axes(c, m);
+    const int sl = first_slice + (int)blockIdx.x;
+    const int K = fill_levels(c.nz, m, P.hts ? P.hts[sl] : P.ht, P.zref);
+    LevelRec* const out = table + (int64_t)sl * (c.nz + 1);
+    for (int k = threadIdx.x; k <= c.nz; k += BLOCK) {
+        LevelRec r;
+        if (k < K) {
+            bool diverged;
+            r = make_level_rec(m, c.nz, k, level_nparts(P, sl, k, diverged));
+        } else if (k == K && K > 0) {
+            // one record past the last level (K <= nz-1): the "next level" of the last one repeats its top abscissa with weight 0,
+            // so the loop computes du1 = X(v) - X(v) = 0 and adds 0 * 0 to the top weight instead of branching on `more`
+            bool diverged;
+            r = make_level_rec(m, c.nz, K - 1, level_nparts(P, sl, K - 1, diverged));
+            r.hs = 0.0; r.npkz = 2 | (m.kz[K - 1] << 17);
+        } else {
+            r.xv = r.hs = r.step = r.zmid = r.r0 = r.r1 = r.gk = r.rk = 0.0;     // (the unconditional load of record 0 of a slice without levels)
+            r.npkz = 0; r.pad[0] = r.pad[1] = r.pad[2] = 0;
+        }
+        out[k] = r;
+    }
 }
 
 // Thread tl of tile t (within its slice) -> ray i of the batch; active: the ray exists (false: tile padding).
@@ -1305,18 +1349,27 @@ __device__ __forceinline__ void finish_into(const PendingSample<T2, E>& s, doubl
 // The slice loop: every ray of the slice starts at the slice's height.  u0, u1: fields WS_U0, WS_U1 of the ray's record (the crossings
 // of its first level); live: the lanes whose samples count - a lane of tile padding or a generic ray (its record is not a polynomial)
 // computes garbage that is never stored, and must not decide a wave-uniform branch.  Adds into acc_w[E], acc_h[E] (per unit of u).
+// A level record in scalar registers: the fields the slice loop reads, loaded through the constant address space (scalar loads).
+struct LevelRegs { double xv, hs, step, zmid, r0, r1, gk, rk; int npkz; };
+typedef __attribute__((address_space(4))) const LevelRec ConstLevelRec;
+__device__ __forceinline__ LevelRegs load_level(const ConstLevelRec* r) {
+    LevelRegs v;
+    v.xv = r->xv; v.hs = r->hs; v.step = r->step; v.zmid = r->zmid; v.r0 = r->r0; v.r1 = r->r1; v.gk = r->gk; v.rk = r->rk; v.npkz = r->npkz;
+    return v;
+}
+
+// lev: the slice's records in the level table (wave-uniform pointer; K + 1 of them are read).
 template <typename T2, int E, bool NC>
 __device__ __forceinline__ void march_slice_levels(const CubeView<T2>& c, const EpochCubes<T2, E>& ev, const RaySmem& m, const RayPoly& q, const double (&xc)[PX],
-                                                   double u0, double u1, int K, bool clamp_lo, bool clamp_hi, unsigned long long live,
+                                                   const LevelRec* lev, double u0, double u1, int K, bool clamp_lo, bool clamp_hi, unsigned long long live,
                                                    double* acc_w, double* acc_h) {
-    // Everything slice-uniform about a level comes from its packed LDS record through ONE address register (la + fixed offsets).
-    typedef __attribute__((address_space(3))) const LevelRec LdsRec;
-    int la = (int)(size_t)m.lev;                                             // LDS byte address of record 0 (a 32-bit LDS pointer)
-    asm volatile("" : "+v"(la));                                             // (a VGPR once, not a v_mov per read)
-    const LdsRec* rec = (const LdsRec*)(size_t)(unsigned)la;
-    int npkz = __builtin_amdgcn_readfirstlane(rec->npkz);
-    int np = npkz & 0x1ffff, kz = npkz >> 17;                                // np >= 2 (fill_partition)
-    double hs = rec->hs;
+    // Everything slice-uniform about a level sits in scalar registers, loaded ONE LEVEL AHEAD: `cur` is the level being integrated, `nxt`
+    // is requested at its top and first needed behind its top sample's gathers (loaded at the point of use, the scalar-cache latency
+    // would stand where the LDS latency stood).  Record 0 of a slice without levels is zeros (level_table_kernel).
+    const ConstLevelRec* rec = (const ConstLevelRec*)(size_t)lev;
+    LevelRegs cur = load_level(rec);
+    int np = cur.npkz & 0x1ffff, kz = cur.npkz >> 17;                        // np >= 2 (level_nparts)
+    double hs = cur.hs;
     double u_k = u0;
     double u_last = u1;
     double du = u_last - u_k;
@@ -1324,18 +1377,19 @@ __device__ __forceinline__ void march_slice_levels(const CubeView<T2>& c, const 
     // two-entry z window must start one interval lower
     if (K > 0) {
         PendingSample<T2, E> s;
-        issue_top<T2, E, NC>(c, ev, m, q, fma(0.0 * rec->step, du, u_k), window2_base(c.nz, kz - ((m.lo[0] <= m.ax.ez[kz].x) ? 1 : 0)), clamp_lo, false, s);
+        issue_top<T2, E, NC>(c, ev, m, q, fma(0.0 * cur.step, du, u_k), window2_base(c.nz, kz - ((m.lo[0] <= m.ax.ez[kz].x) ? 1 : 0)), clamp_lo, false, s);
         finish_into(s, hs * fabs(du), acc_w, acc_h);
     }
 #pragma unroll 1
     for (int k = 0; k < K; ++k) {
+        const LevelRegs nxt = load_level(rec + k + 1);                       // (the record after the last level: the sentinel)
         const int zbase = window2_base(c.nz, kz);                            // first table entry of the two-entry z window
         const bool more = k + 1 < K;
         // trapezoid weights per unit of u (delay.py:314-315): interior samples, and the top one with both its segments.  The weight is the
         // segment's LENGTH (a norm, losreader.py:821): |du| - an origin above zref in zref's model interval walks its one segment downwards
         const double w_mid = (2.0 * hs) * fabs(du);
         if (np > 2) {
-            const double step = rec->step, gk = rec->gk, rk = rec->rk;
+            const double step = cur.step, gk = cur.gk, rk = cur.rk;
 #pragma unroll 1
             for (int j = 1; j < np - 1; ++j) {                               // low + frac * (high - low), delay.py:292
                 PendingSample<T2, E> s;
@@ -1360,33 +1414,32 @@ __device__ __forceinline__ void march_slice_levels(const CubeView<T2>& c, const 
             // whose zenith angle falls with height (profiles/r06_nodetop_ab.txt).  When no live lane of the wave is below the node
             // (one compare + a scalar test) the cell index is the scalar zbase+1 and the weight one multiplication; otherwise the
             // per-lane two-entry window.  Same values either way.
-            const double d = ph - rec->zmid;
+            const double d = ph - cur.zmid;
             int iz; bool ok;
             if (__builtin_expect((__builtin_amdgcn_ballot_w64(!(d >= 0.0)) & live) == 0ULL, 1)) {
                 iz = zbase + 1;
-                top.tz = d * rec->r1;
+                top.tz = d * cur.r1;
                 ok = top.tz <= 1.0;                                                                // (idle lanes: NaN)
             } else {
                 double ds = d;
                 asm volatile("" : "+v"(ds));                                                       // (nothing of this block is hoisted into the fast path)
                 const bool up = ds >= 0.0;
                 iz = zbase + (int)up;
-                top.tz = fma(ds, up ? rec->r1 : rec->r0, up ? 0.0 : 1.0);
+                top.tz = fma(ds, up ? cur.r1 : cur.r0, up ? 0.0 : 1.0);
                 ok = (top.tz >= 0.0) & (top.tz <= 1.0);
             }
             if (!(ok & (c.nz >= 4))) cell_exact(m.ax.ez, c.nz, ph, iz, top.tz);                  // rare
             gather_corners<T2, E, true, NC>(c, ev, m.ax, plat, plon, iz, top);                   // delay.py:298,319
         }
-        // (the record after the last level: same abscissa, weight 0 - see fill_partition)
-        const double t2 = poly7(xc, rec[1].xv);
-        const double du1 = t2 - u_last, hs1 = rec[1].hs;
+        // (the record after the last level: same abscissa, weight 0 - see level_table_kernel)
+        const double t2 = poly7(xc, nxt.xv);
+        const double du1 = t2 - u_last, hs1 = nxt.hs;
         u_last = t2;
         const double w_top = fma(hs1, fabs(du1), hs * fabs(du));
-        npkz = __builtin_amdgcn_readfirstlane(rec[1].npkz);
         finish_into(top, w_top, acc_w, acc_h);
         u_k += du; du = du1; hs = hs1;
-        np = npkz & 0x1ffff; kz = npkz >> 17;
-        ++rec;
+        np = nxt.npkz & 0x1ffff; kz = nxt.npkz >> 17;
+        cur = nxt;
     }
 }
 
@@ -1489,7 +1542,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
         if (sl != slice) {                                 // (workgroup-uniform) the slice's level table and integration partition
             slice = sl;
             K = fill_levels(c.nz, m, P.hts ? P.hts[sl] : P.ht, P.zref);
-            const SlicePartition part = fill_partition<!SLOW && !PR>(P, m, c.nz, sl, K);
+            const SlicePartition part = fill_partition(P, m, sl, K);
             poison = part.poison; clamp_lo = part.clamp_lo; clamp_hi = part.clamp_hi;
             clamp_any = clamp_lo | clamp_hi;
         }
@@ -1518,10 +1571,13 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
             const double u0r = w[(int64_t)WS_U0 * ns], u1r = w[(int64_t)WS_U1 * ns];
             const EpochCubes<T2, 1> one{{c.v}};
             const unsigned long long live = __builtin_amdgcn_ballot_w64(active && mine);
+            // the slice's records of the level table (per tile, from the scalar slice index: a pointer kept across the slice test would
+            // not be wave-uniform for the compiler, and the records would come through vector loads)
+            const LevelRec* const lev = PR ? nullptr : P.lev + (int64_t)__builtin_amdgcn_readfirstlane(sl) * (c.nz + 1);
             auto run = [&](auto nochk) {
                 constexpr bool NC = decltype(nochk)::value;
                 if constexpr (PR) march_ray_height_levels<T2, 1, NC>(c, one, m, q, xc, u0r, u1r, K, k0, lo_first, clamp_lo, clamp_hi, &acc_w, &acc_h);
-                else march_slice_levels<T2, 1, NC>(c, one, m, q, xc, u0r, u1r, K, clamp_lo, clamp_hi, live, &acc_w, &acc_h);
+                else march_slice_levels<T2, 1, NC>(c, one, m, q, xc, lev, u0r, u1r, K, clamp_lo, clamp_hi, live, &acc_w, &acc_h);
             };
             // the wave-wide no-check proof (lane_nocheck): bounds of the cell search from the polynomial coefficients
             bool lane_safe = false;

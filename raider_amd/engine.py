@@ -13,6 +13,11 @@ from . import _pinned
 from ._lib import Context, check, f64, ptr
 
 
+# one record of the level table of pass 2 (Cube.level_table; include/raider_hip.h: rdr_level_table), 80 bytes
+LEVEL_REC = np.dtype([('xv', '<f8'), ('hs', '<f8'), ('step', '<f8'), ('zmid', '<f8'), ('r0', '<f8'), ('r1', '<f8'), ('gk', '<f8'), ('rk', '<f8'),
+                      ('npkz', '<i4'), ('pad', '<i4', (3,))])
+
+
 def _is_dev(a):
     return hasattr(a, 'data_ptr')
 
@@ -401,6 +406,26 @@ class Cube:
         lo, hi, kz = np.empty(nz), np.empty(nz), np.empty(nz, dtype=np.int32)
         check(self.ctx.lib.rdr_ray_levels(self.handle, float(ht), float(zref), C.byref(K), ptr(lo), ptr(hi), ptr(kz)), self.ctx.handle)
         return lo[:K.value].copy(), hi[:K.value].copy(), kz[:K.value].copy()
+
+    def level_table(self, hts, zref, nparts=None, maxlen=None, max_seg=1000.0):
+        """The level table pass 2 of the light slice marcher reads for slices at `hts` (a scalar: one slice), as the device kernel
+        writes it before every pass 2: a structured array [S, nz+1] with the fields of LEVEL_REC (include/raider_hip.h:
+        rdr_level_table) - per slice its K levels, the weight-0 sentinel behind the last, zeros after it.  The partition is given
+        as nparts[S, >= nz-1] (int) or as per-level length maxima maxlen[S, >= nz-1] with max_seg."""
+        hts = f64(np.atleast_1d(hts)).ravel()
+        nz = self.shape[2]
+        if (nparts is None) == (maxlen is None):
+            raise ValueError('exactly one of nparts / maxlen')
+        if nparts is not None:
+            rows = np.ascontiguousarray(np.atleast_2d(nparts), dtype=np.int32)
+        else:
+            rows = np.ascontiguousarray(np.atleast_2d(maxlen), dtype=np.float64)
+        if rows.shape[0] != hts.size:
+            raise ValueError(f'{hts.size} slices, {rows.shape[0]} partition rows')
+        out = np.zeros((hts.size, nz + 1), dtype=LEVEL_REC)
+        check(self.ctx.lib.rdr_level_table(self.ctx.handle, self.handle, ptr(hts), hts.size, float(zref), ptr(rows) if nparts is not None else None,
+                                           None if nparts is not None else ptr(rows), rows.shape[1], float(max_seg), ptr(out)), self.ctx.handle)
+        return out
 
     def ray_prepass(self, rays, ht, zref):
         rays.adopt_stream(self.ctx)

@@ -1,6 +1,7 @@
 # One gpurun call = one full profile set of the current kernels:  gpurun -- 'PROFILE_TAG=v13 bash tools/profile_round.sh'
 # then (here)  python tools/profile_digest.py gpurun_out/v13   ->  profiles/r02_v13_*   (bench.py reads r02_v13_counters.json)
-set -x
+# A step that fails or runs into its time limit ends the script: nothing more is started on a GPU that has just faulted or hung.
+set -ex
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
 O=$R/gpurun_out/${PROFILE_TAG:-v13}; mkdir -p $O
@@ -12,7 +13,7 @@ import bench, torch
 print(json.dumps(dict(source_hash=bench.kernel_source_hash(), cube='$CUBE', sq_scene=[2000, 2000], hbm_scene=[4000, 4000],
                       device=torch.cuda.get_device_name(0))))
 PY
-python $R/bench.py --full --cube $CUBE > $O/bench.json 2> $O/bench.err
+timeout 600 python $R/bench.py --full --cube $CUBE > $O/bench.json 2> $O/bench.err
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python $R/bench.py --full --cube $CUBE --steps 10 --warmup 3 --cpu-sample 0 --no-e2e --no-secondary > $O/kt.log 2>&1
 timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -- python $R/tools/pmc_probe.py $CUBE > $O/fetch.log 2>&1
 timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -- python $R/tools/pmc_probe.py $CUBE > $O/write.log 2>&1
