@@ -612,6 +612,15 @@ int rdr_tiff_predict(rdr_ctx* ctx, const void* in, int sample_bytes, int64_t hei
 int64_t rdr_deflate_bound(int64_t n);
 int rdr_deflate_encode(rdr_ctx* ctx, const void* src, int64_t src_bytes, const int64_t* seg_offset, const int64_t* seg_bytes, int64_t nseg,
                        void* out, int64_t out_capacity, int64_t* out_offset, int loc);
+/* rdr_deflate_encode_tables: rdr_deflate_encode with a choice of tables - the same contract, errors and bound.  RDR_DEFL_FIXED is
+ * rdr_deflate_encode, byte for byte.  RDR_DEFL_DYNAMIC: every sub-block is the smallest of a stored block, a fixed-Huffman block and a
+ * dynamic-Huffman block (BTYPE 10) over the same tokens, chosen on the device from the tokens' symbol counts (ties: stored, then
+ * fixed); the code lengths are optimal under RFC 1951's limits of 15 and 7 bits.  Any other `tables` is RDR_ERR_INVALID before the
+ * device is touched.  block_counts (HOST, 3, may be NULL): the stored, fixed and dynamic sub-blocks of the call. */
+#define RDR_DEFL_FIXED 0
+#define RDR_DEFL_DYNAMIC 1
+int rdr_deflate_encode_tables(rdr_ctx* ctx, const void* src, int64_t src_bytes, const int64_t* seg_offset, const int64_t* seg_bytes,
+                              int64_t nseg, int tables, void* out, int64_t out_capacity, int64_t* out_offset, int64_t* block_counts, int loc);
 /* rdr_h5_chunks: a C-ordered array of `ndim` <= 4 axes (shape, HOST) of elem_bytes 1 / 2 / 4 / 8 cut into chunks (chunk, HOST) in
  * row-major chunk order.  Every chunk is full size: elements beyond the array's edge are `fill` (HOST, elem_bytes bytes).  shuffle:
  * each chunk is byte-transposed as HDF5's shuffle filter does, out[j * n + i] = in[i * elem_bytes + j] over the chunk's n elements.

@@ -19,6 +19,7 @@ RDR_F32, RDR_F64, RDR_I16 = 0, 1, 2
 RASTER_NEAREST, RASTER_LINEAR = 0, 1
 RDR_BYTESWAPPED = 0x100
 RDR_HOST, RDR_DEVICE = 0, 1
+RDR_DEFL_FIXED, RDR_DEFL_DYNAMIC = 0, 1
 ORIGIN_GRID, ORIGIN_LLH, ORIGIN_XYZ = 0, 1, 2
 RDR_PROJ_LCC, RDR_PROJ_STERE, RDR_GRID_TM = 1, 2, 3
 LOS_VEC, LOS_INC_HD, LOS_INC_HD_SCALAR, LOS_ZENITH = 0, 1, 2, 3
@@ -155,6 +156,7 @@ SYMBOLS = [
     ('rdr_tiff_predict', C.c_int, [_VP, _VP, C.c_int, C.c_int64, C.c_int64, _VP, C.c_int]),
     ('rdr_deflate_bound', C.c_int64, [C.c_int64]),
     ('rdr_deflate_encode', C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int]),
+    ('rdr_deflate_encode_tables', C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int, _VP, C.c_int64, _VP, _VP, C.c_int]),
     ('rdr_h5_chunks', C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, _VP, C.c_int]),
 ]
 

@@ -35,7 +35,7 @@ constexpr int MAX_SLICES = 512;   // height slices per rdr_raytrace_slices call
 
 enum { SLOT_IN0 = 0, SLOT_IN1, SLOT_IN2, SLOT_IN3, SLOT_IN4, SLOT_IN5, SLOT_IN6, SLOT_OUT0, SLOT_OUT1, SLOT_OUT2, SLOT_AUX,
        SLOT_PT0, SLOT_PT1, SLOT_PT2, SLOT_PT3, SLOT_PT4, SLOT_PT5, SLOT_TMPCUBE, SLOT_TMPAXES,      // rdr_point_delays: points, delays, the intermediate cube
-       SLOT_DEFL,                                                                                    // rdr_deflate_encode: the sub-blocks' slots
+       SLOT_DEFL, SLOT_DEFL_TOK,                                                                     // rdr_deflate_encode: the sub-blocks' slots; the workgroups' token scratch
        NSLOT };
 
 struct rdr_ctx {
@@ -3654,10 +3654,11 @@ int64_t rdr_deflate_bound(int64_t n) {
     return n + 5 * ((n + DEFL_SUB - 1) / DEFL_SUB) + 6;        // a stored block per sub-block, 78 01 and the Adler-32
 }
 
-int rdr_deflate_encode(rdr_ctx* c, const void* src, int64_t src_bytes, const int64_t* seg_offset, const int64_t* seg_bytes, int64_t nseg, void* out,
-                       int64_t out_capacity, int64_t* out_offset, int loc) {
+int rdr_deflate_encode_tables(rdr_ctx* c, const void* src, int64_t src_bytes, const int64_t* seg_offset, const int64_t* seg_bytes, int64_t nseg, int tables,
+                              void* out, int64_t out_capacity, int64_t* out_offset, int64_t* block_counts, int loc) {
     if (!c || !src || !seg_offset || !seg_bytes || !out || !out_offset) return fail(c, RDR_ERR_INVALID, "rdr_deflate_encode: NULL argument");
     if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, "rdr_deflate_encode: loc must be RDR_HOST or RDR_DEVICE");
+    if (tables != RDR_DEFL_FIXED && tables != RDR_DEFL_DYNAMIC) return fail(c, RDR_ERR_INVALID, "rdr_deflate_encode: tables must be RDR_DEFL_FIXED or RDR_DEFL_DYNAMIC");
     if (src_bytes <= 0 || src_bytes > ((int64_t)1 << 40) || nseg <= 0 || nseg > (1 << 24))
         return fail(c, RDR_ERR_INVALID, "rdr_deflate_encode: need a non-empty buffer (at most 2^40 bytes) and 1 .. 2^24 segments");
     int64_t need = 0, nsub = 0;
@@ -3688,8 +3689,15 @@ int rdr_deflate_encode(rdr_ctx* c, const void* src, int64_t src_bytes, const int
     rc = ensure(c, SLOT_OUT1, (size_t)nsub * sizeof(DeflResult), &dres); if (rc) return rc;
     rc = upload(c, dsubs, subs.data(), (size_t)nsub * sizeof(DeflSub)); if (rc) return rc;
     // one wave per sub-block; a compute unit holds three of these 53 KB workgroups, the grid strides over the rest
-    hipLaunchKernelGGL(deflate_encode_kernel, dim3((unsigned)std::min<int64_t>(nsub, (int64_t)c->num_cus * 3)), dim3(64), 0, c->stream, (const uint8_t*)dsrc,
-                       (const DeflSub*)dsubs, nsub, (uint8_t*)dslots, (DeflResult*)dres);
+    const unsigned grid = (unsigned)std::min<int64_t>(nsub, (int64_t)c->num_cus * 3);
+    if (tables == RDR_DEFL_DYNAMIC) {
+        void* dtok;
+        rc = ensure(c, SLOT_DEFL_TOK, (size_t)grid * DEFL_SUB * sizeof(uint32_t), &dtok); if (rc) return rc;
+        hipLaunchKernelGGL(deflate_encode_dyn_kernel, dim3(grid), dim3(64), 0, c->stream, (const uint8_t*)dsrc, (const DeflSub*)dsubs, nsub, (uint8_t*)dslots,
+                           (DeflResult*)dres, (uint32_t*)dtok);
+    } else
+        hipLaunchKernelGGL(deflate_encode_kernel, dim3(grid), dim3(64), 0, c->stream, (const uint8_t*)dsrc, (const DeflSub*)dsubs, nsub, (uint8_t*)dslots,
+                           (DeflResult*)dres);
     HIPCHECK(c, hipGetLastError());
     std::vector<DeflResult> res((size_t)nsub);
     HIPCHECK(c, hipMemcpyAsync(res.data(), dres, (size_t)nsub * sizeof(DeflResult), hipMemcpyDeviceToHost, c->stream));
@@ -3697,6 +3705,7 @@ int rdr_deflate_encode(rdr_ctx* c, const void* src, int64_t src_bytes, const int
     // sizes -> offsets; the sub-blocks' Adler sums -> the streams' (A' = A + s1, B' = B + n A + s2: adler32_combine's rule)
     int64_t pos = 0, seg = 0;
     uint32_t A = 1u, B = 0u;
+    int64_t kinds[3] = {0, 0, 0};                                  // stored, fixed, dynamic sub-blocks
     for (int64_t k = 0; k < nsub; ++k) {
         DeflSub& d = subs[(size_t)k];
         const DeflResult& r = res[(size_t)k];
@@ -3704,6 +3713,7 @@ int rdr_deflate_encode(rdr_ctx* c, const void* src, int64_t src_bytes, const int
         if (d.flags & 1) { out_offset[seg] = pos; A = 1u; B = 0u; }
         d.dst_off = pos;
         d.fixed_bytes = r.fixed_bytes;
+        ++kinds[r.fixed_bytes > 0 ? (r.pad == 2 ? 2 : 1) : 0];
         B = (uint32_t)((B + (uint64_t)d.n % 65521u * A + r.s2) % 65521u);
         A = (A + r.s1) % 65521u;
         pos += ((d.flags & 1) ? 2 : 0) + (r.fixed_bytes > 0 ? r.fixed_bytes : d.n + 5) + ((d.flags & 2) ? 4 : 0);
@@ -3718,7 +3728,13 @@ int rdr_deflate_encode(rdr_ctx* c, const void* src, int64_t src_bytes, const int
     HIPCHECK(c, hipGetLastError());
     rc = finish_out(c, out, dout, (size_t)pos, loc); if (rc) return rc;
     HIPCHECK(c, hipStreamSynchronize(c->stream));
+    if (block_counts) { block_counts[0] = kinds[0]; block_counts[1] = kinds[1]; block_counts[2] = kinds[2]; }
     return RDR_OK;
+}
+
+int rdr_deflate_encode(rdr_ctx* c, const void* src, int64_t src_bytes, const int64_t* seg_offset, const int64_t* seg_bytes, int64_t nseg, void* out,
+                       int64_t out_capacity, int64_t* out_offset, int loc) {
+    return rdr_deflate_encode_tables(c, src, src_bytes, seg_offset, seg_bytes, nseg, RDR_DEFL_FIXED, out, out_capacity, out_offset, nullptr, loc);
 }
 
 int rdr_tiff_predict(rdr_ctx* c, const void* in, int sample_bytes, int64_t height, int64_t width, void* out, int loc) {

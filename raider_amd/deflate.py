@@ -1,7 +1,8 @@
 """zlib streams written on the GPU (rdr_deflate_encode) and the chunk cutter of the NetCDF-4 writer (rdr_h5_chunks).
 
 The encoder turns independent byte ranges of one buffer into complete zlib streams, one wave per 32 KiB sub-block, with fixed-Huffman
-and stored blocks only.  NumPy arrays go up and come back in one transfer each; device tensors stay where they are.
+and stored blocks; with tables='dynamic' every sub-block is the smallest of a stored, a fixed-Huffman and a
+dynamic-Huffman block.  NumPy arrays go up and come back in one transfer each; device tensors stay where they are.
 There is no CPU fallback: the writers that want host zlib call zlib."""
 import numpy as np
 
@@ -23,10 +24,29 @@ def require_gpu(what):
         raise RuntimeError(f'{what} runs on the GPU; no GPU is visible and there is no CPU fallback')
 
 
-def deflate_segments(buf, offsets, sizes):
+TABLES = {'fixed': L.RDR_DEFL_FIXED, 'dynamic': L.RDR_DEFL_DYNAMIC}
+_last_counts = (0, 0, 0)
+
+
+def tables_mode(tables):
+    """The library's value of the `tables` keyword; anything but 'fixed' and 'dynamic' is a ValueError."""
+    if tables not in TABLES:
+        raise ValueError(f"tables must be 'fixed' or 'dynamic', not {tables!r}")
+    return TABLES[tables]
+
+
+def last_block_counts():
+    """(stored, fixed, dynamic): the sub-blocks of each kind in the last deflate_segments call of this process."""
+    return _last_counts
+
+
+def deflate_segments(buf, offsets, sizes, tables='fixed'):
     """(packed, out_offsets): the byte ranges buf[offsets[i] : offsets[i] + sizes[i]] as zlib streams packed back to back; stream i is
     packed[out_offsets[i] : out_offsets[i + 1]].  buf: a C-contiguous NumPy array or device tensor of any element type (taken as bytes);
-    packed is a uint8 array / tensor of the same kind, out_offsets an int64 NumPy array of len(sizes) + 1."""
+    packed is a uint8 array / tensor of the same kind, out_offsets an int64 NumPy array of len(sizes) + 1.  tables: 'fixed' (stored and
+    fixed-Huffman blocks) or 'dynamic' (dynamic-Huffman blocks too, wherever they are the smallest)."""
+    global _last_counts
+    mode = tables_mode(tables)
     so = np.ascontiguousarray(offsets, dtype=np.int64).ravel()
     sb = np.ascontiguousarray(sizes, dtype=np.int64).ravel()
     if so.size != sb.size:
@@ -37,6 +57,7 @@ def deflate_segments(buf, offsets, sizes):
         raise ValueError('deflate_segments: every segment needs at least one byte')
     cap = sum(bound(int(v)) * int(c) for v, c in zip(*np.unique(sb, return_counts=True)))
     oo = np.zeros(so.size + 1, dtype=np.int64)
+    kinds = np.zeros(3, dtype=np.int64)
     if _is_tensor(buf):
         import torch
         if not buf.is_cuda or not buf.is_contiguous():
@@ -45,13 +66,17 @@ def deflate_segments(buf, offsets, sizes):
         out = torch.empty(cap, dtype=torch.uint8, device=buf.device)
         ctx = L.Context.default()
         ctx.adopt_torch_stream(src)
-        L.check(ctx.lib.rdr_deflate_encode(ctx.handle, L.ptr(src), src.numel(), L.ptr(so), L.ptr(sb), so.size, L.ptr(out), cap, L.ptr(oo), L.RDR_DEVICE), ctx.handle)
+        L.check(ctx.lib.rdr_deflate_encode_tables(ctx.handle, L.ptr(src), src.numel(), L.ptr(so), L.ptr(sb), so.size, mode, L.ptr(out), cap, L.ptr(oo), L.ptr(kinds),
+                                                  L.RDR_DEVICE), ctx.handle)
+        _last_counts = tuple(int(k) for k in kinds)
         return out[:int(oo[-1])], oo
     require_gpu('deflate_segments (rdr_deflate_encode)')
     src = np.ascontiguousarray(buf).reshape(-1).view(np.uint8)
     out = np.empty(cap, dtype=np.uint8)
     ctx = L.Context.default()
-    L.check(ctx.lib.rdr_deflate_encode(ctx.handle, L.ptr(src), src.size, L.ptr(so), L.ptr(sb), so.size, L.ptr(out), cap, L.ptr(oo), L.RDR_HOST), ctx.handle)
+    L.check(ctx.lib.rdr_deflate_encode_tables(ctx.handle, L.ptr(src), src.size, L.ptr(so), L.ptr(sb), so.size, mode, L.ptr(out), cap, L.ptr(oo), L.ptr(kinds), L.RDR_HOST),
+            ctx.handle)
+    _last_counts = tuple(int(k) for k in kinds)
     return out[:int(oo[-1])], oo
 
 
@@ -113,13 +138,14 @@ def h5_chunks_host(array, chunk, fill, shuffle=True):
     return np.concatenate(out)
 
 
-def compress_chunks(array, chunk, fill, shuffle=True):
+def compress_chunks(array, chunk, fill, shuffle=True, tables='fixed'):
     """(packed bytes as a NumPy uint8 array, offsets): `array` cut into chunks, shuffled and deflated on the device - what
-    h5write takes as a chunked variable's data.  One download, of the packed streams."""
+    h5write takes as a chunked variable's data.  One download, of the packed streams.  tables: as deflate_segments."""
+    tables_mode(tables)
     raw = h5_chunks(array, chunk, fill, shuffle)
     n = int(np.prod(chunk_grid(tuple(array.shape), chunk), dtype=np.int64))
     cb = (raw.numel() if _is_tensor(raw) else raw.size) // n
-    packed, oo = deflate_segments(raw, np.arange(n, dtype=np.int64) * cb, np.full(n, cb, dtype=np.int64))
+    packed, oo = deflate_segments(raw, np.arange(n, dtype=np.int64) * cb, np.full(n, cb, dtype=np.int64), tables=tables)
     if _is_tensor(packed):
         packed = packed.cpu().numpy()
     return packed, oo

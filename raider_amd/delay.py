@@ -232,8 +232,9 @@ def gunw_chunks(shape):
     return (nz, max(1, ny // 3), max(1, nx // 3))
 
 
-def _compressed(data, chunks, fill):
-    """A cube (NumPy or device tensor) as h5write.ChunkedData: cut into chunks, shuffled and deflated on the device."""
+def _compressed(data, chunks, fill, tables='fixed'):
+    """A cube (NumPy or device tensor) as h5write.ChunkedData: cut into chunks, shuffled and deflated on the device (tables: the
+    encoder's Huffman tables, 'fixed' or 'dynamic')."""
     from . import deflate
     from .h5write import ChunkedData
     shape = tuple(int(s) for s in data.shape)
@@ -241,7 +242,7 @@ def _compressed(data, chunks, fill):
         raise ValueError(f'a compressed cube has three axes, not shape {shape}')
     chunks = gunw_chunks(shape) if chunks is None else tuple(int(c) for c in chunks)
     dtype = np.dtype(str(data.dtype).replace('torch.', ''))
-    packed, offsets = deflate.compress_chunks(data, chunks, fill, shuffle=True)
+    packed, offsets = deflate.compress_chunks(data, chunks, fill, shuffle=True, tables=tables)
     return ChunkedData(shape, dtype, chunks, packed, offsets, filters=('shuffle', 'deflate'), level=1)
 
 
@@ -262,15 +263,21 @@ class DelayCube:
         except KeyError:
             raise AttributeError(k)
 
-    def to_netcdf(self, path, format='NETCDF4', compress=False, chunks=None):
+    def to_netcdf(self, path, format='NETCDF4', compress=False, chunks=None, tables='fixed'):
         """The delay-cube file of delay.py:329-401 / cli/raider.py:373-398 (`ds.to_netcdf`): dims z, y, x; variables wet, hydro (f64,
         units m, grid_mapping crs), coordinate variables, the integer `crs` grid-mapping variable and the global attributes.
         format='NETCDF4' (what the reference writes): HDF5 through raider_amd.h5write; 'NETCDF3_64BIT': classic format through
         scipy.  (When xarray is installed writeResultsToXarray returns a real Dataset instead of this class.)
         compress=True (NETCDF4 only, needs the GPU): wet and hydro are written chunked + shuffle + deflate, cut, shuffled and deflated
         on the device (raider_amd.deflate); `chunks` defaults to the reference's GUNW rule (nz, max(1, ny // 3), max(1, nx // 3))
-        (aria/calcGUNW.py:65-72), at most 16 chunks.  Coordinates and crs stay contiguous.  compress=False writes what it always wrote."""
+        (aria/calcGUNW.py:65-72), at most 16 chunks.  Coordinates and crs stay contiguous.  compress=False writes what it always wrote.
+        tables='dynamic' (with compress=True): the encoder writes dynamic-Huffman blocks wherever they are the smallest - smaller files,
+        read by the same readers; 'fixed' writes the bytes it always wrote."""
         v = self.variables
+        if tables not in ('fixed', 'dynamic'):
+            raise ValueError(f"tables must be 'fixed' or 'dynamic', not {tables!r}")
+        if tables == 'dynamic' and not compress:
+            raise ValueError("tables='dynamic' belongs to compress=True")
         if compress and not format.upper().startswith('NETCDF4'):
             raise ValueError('compress=True needs format NETCDF4 (the classic format has no filters)')
         degrees = self.attrs.get('_degrees', True)
@@ -287,7 +294,7 @@ class DelayCube:
             for name, long in (('wet', 'wet'), ('hydro', 'hydrostatic')):
                 data = v[name].double() if hasattr(v[name], 'data_ptr') else np.asarray(v[name], dtype=np.float64)
                 if compress:
-                    data = _compressed(data, chunks, np.nan)
+                    data = _compressed(data, chunks, np.nan, tables)
                 elif hasattr(data, 'data_ptr'):
                     data = data.cpu().numpy()
                 variables[name] = (('z', 'y', 'x'), data, dict(units='m', description=f'{long} {desc} delay', grid_mapping='crs'))

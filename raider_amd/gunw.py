@@ -114,11 +114,14 @@ def compute_delays_slc(cube_paths, wavelength, ctx=None):
     return ds
 
 
-def write_delays_slc(ds_slc, path):
+def write_delays_slc(ds_slc, path, tables='fixed'):
     """The object compute_delays_slc returns as a standalone NetCDF-4 file: the four layers as float32 with _FillValue 0.0 and chunks
     (nz, max(1, ny // 3), max(1, nx // 3)) (calcGUNW.py:65-72), cut, shuffled and deflated on the device; float32 coordinate
-    variables heightsMeta / latitudeMeta / longitudeMeta; the per-layer attributes compute_delays_slc collected."""
+    variables heightsMeta / latitudeMeta / longitudeMeta; the per-layer attributes compute_delays_slc collected.  tables: the
+    encoder's Huffman tables, 'fixed' (the bytes it always wrote) or 'dynamic' (smaller chunks, the same readers)."""
     from .delay import _compressed, gunw_chunks
+    if tables not in ('fixed', 'dynamic'):
+        raise ValueError(f"tables must be 'fixed' or 'dynamic', not {tables!r}")
     from .h5write import write_netcdf4
     v = ds_slc.variables
     dims = {d: int(np.size(v[d])) for d in DIM_NAMES}
@@ -130,7 +133,7 @@ def write_delays_slc(ds_slc, path):
             data = v[layer].float() if hasattr(v[layer], 'data_ptr') else np.asarray(v[layer], dtype=np.float32)
             attrs = {k: (val if isinstance(val, (str, int, float, np.number)) else str(val)) for k, val in layer_attrs.get(layer, {}).items() if val is not None}
             attrs['_FillValue'] = np.float32(0.0)
-            variables[layer] = (tuple(DIM_NAMES), _compressed(data, gunw_chunks(data.shape), 0.0), attrs)
+            variables[layer] = (tuple(DIM_NAMES), _compressed(data, gunw_chunks(data.shape), 0.0, tables), attrs)
     gattrs = {k: str(val) for k, val in getattr(ds_slc, 'attrs', {}).items() if val is not None and not k.startswith('_')}
     write_netcdf4(path, dims, variables, gattrs)
     return str(path)

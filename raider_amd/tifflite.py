@@ -498,9 +498,9 @@ def _is_geographic(epsg):
     return 4000 <= epsg <= 4999
 
 
-def _device_strips(array, h, w, itemsize, rps, predictor):
+def _device_strips(array, h, w, itemsize, rps, predictor, tables):
     """The strips of `array` (NumPy or device tensor) as zlib streams from the device encoder: the predictor as a kernel of its own
-    (rdr_tiff_predict), every strip in ONE rdr_deflate_encode call, one download of the packed streams."""
+    (rdr_tiff_predict), every strip in ONE rdr_deflate_encode_tables call, one download of the packed streams."""
     import torch
     from . import _lib as L
     from . import deflate as D
@@ -519,17 +519,18 @@ def _device_strips(array, h, w, itemsize, rps, predictor):
     row_bytes = w * itemsize
     offs = np.arange(0, h, rps, dtype=np.int64) * row_bytes
     sizes = np.minimum(rps, h - np.arange(0, h, rps, dtype=np.int64)) * row_bytes
-    packed, oo = D.deflate_segments(t, offs, sizes)
+    packed, oo = D.deflate_segments(t, offs, sizes, tables=tables)
     packed = packed.cpu().numpy()
     return [packed[oo[i]:oo[i + 1]] for i in range(offs.size)]
 
 
-def write(path, array, transform=None, crs=None, nodata=None, compress=None, rows_per_strip=None, predictor=None, encoder='host'):
+def write(path, array, transform=None, crs=None, nodata=None, compress=None, rows_per_strip=None, predictor=None, encoder='host', tables='fixed'):
     """One band as a GeoTIFF in strips: classic TIFF, BigTIFF when the pixels pass 4 GiB; little-endian; compress None or 'deflate'
     (zlib).  array: 2-D uint16 / int16 / float32 / float64 (and uint8, what the delay writers make of integer arrays).  transform: GDAL's six numbers (north-up); crs: an EPSG code (see _epsg_of);
     nodata: written as GDAL_NODATA.  predictor: None, or 2 (with 'deflate': every row differenced along x in the unsigned integer type
     of the sample width, tag 317 - what the readers undo).  encoder: 'host' (zlib level 6), or 'device' (with 'deflate': the strips
-    are deflated on the GPU in one call; array may then be a device tensor, and no GPU is an error by name)."""
+    are deflated on the GPU in one call; array may then be a device tensor, and no GPU is an error by name).  tables: 'fixed', or
+    'dynamic' (with encoder='device': dynamic-Huffman blocks wherever they are the smallest)."""
     if compress not in (None, 'none', 'deflate', 'DEFLATE'):
         raise ValueError(f"compress must be None or 'deflate', not {compress!r}")
     deflate = compress in ('deflate', 'DEFLATE')
@@ -540,6 +541,10 @@ def write(path, array, transform=None, crs=None, nodata=None, compress=None, row
         raise ValueError(f"encoder must be 'host' or 'device', not {encoder!r}")
     if (predictor or encoder == 'device') and not deflate:
         raise ValueError("predictor=2 and encoder='device' belong to compress='deflate'")
+    if tables not in ('fixed', 'dynamic'):
+        raise ValueError(f"tables must be 'fixed' or 'dynamic', not {tables!r}")
+    if tables == 'dynamic' and encoder != 'device':
+        raise ValueError("tables='dynamic' belongs to encoder='device'")
     tensor = type(array).__module__.split('.')[0] == 'torch'
     if tensor and encoder != 'device':
         array = array.cpu().numpy()
@@ -561,7 +566,7 @@ def write(path, array, transform=None, crs=None, nodata=None, compress=None, row
     rps = int(rows_per_strip) if rows_per_strip else max(1, (1 << 16) // row_bytes)
     rps = min(max(rps, 1), h)
     if encoder == 'device':
-        strips = _device_strips(array if tensor else a, h, w, dtype.itemsize, rps, predictor)
+        strips = _device_strips(array if tensor else a, h, w, dtype.itemsize, rps, predictor, tables)
     else:
         strips = []
         for y in range(0, h, rps):
