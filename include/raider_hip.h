@@ -628,6 +628,34 @@ int rdr_deflate_encode_tables(rdr_ctx* ctx, const void* src, int64_t src_bytes, 
 int rdr_h5_chunks(rdr_ctx* ctx, const void* array, int elem_bytes, int ndim, const int64_t* shape, const int64_t* chunk, const void* fill,
                   int shuffle, void* out, int loc);
 
+/* ---- zlib streams decoded on the device (raider_amd/deflate.py, tifflite.py, h5lite.py) -------------------------------------------
+ * rdr_inflate_decode: `nseg` independent zlib streams (RFC 1950 wrapper, RFC 1951 body) out of one byte buffer `src` of `src_bytes`:
+ * stream i is src[seg_offset[i] .. + seg_bytes[i]), at any byte offset, and is written to out + i * out_stride, at most
+ * seg_out_bytes[i] <= out_stride bytes of it.  status[i] is one of RDR_INFL_*; it is RDR_INFL_OK exactly when zlib 1.2.11's inflate
+ * (as zlib.decompress drives it) accepts the stream and its output fits the slot, and then the slot's bytes are zlib's.  Bytes behind
+ * the Adler-32 are ignored.  A bad stream sets its status and stops: nothing outside its segment is read, nothing outside
+ * [slot, slot + seg_out_bytes[i]) is written, and slot bytes the stream does not reach keep their value.  produced[i] (may be NULL):
+ * the bytes written to slot i.  src, out, status and produced live at `loc`; the three int64 tables are HOST arrays.  One wave per
+ * stream, the 32 KiB history a ring in LDS from which the output is flushed: the output is never read back.  RDR_ERR_INVALID, before
+ * the device is touched: NULL, src_bytes / nseg / out_stride <= 0, nseg > 2^24, a segment outside src or of 2 GiB or more, a slot
+ * beyond out_stride, out_stride >= 2 GiB, nseg * out_stride > 2^40.  seg_bytes[i] == 0 is NOT an error of the call (as for
+ * rdr_tiff_lzw_decode: a file may hold an empty segment beside good ones): that stream gets RDR_INFL_SHORT. */
+#define RDR_INFL_OK 0        /* the final block ended, the Adler-32 matches, the output fits the slot */
+#define RDR_INFL_SHORT 1     /* the input ended before the final block or its trailer */
+#define RDR_INFL_OVERFLOW 2  /* the stream holds more than the slot takes */
+#define RDR_INFL_INVALID 3   /* bad CMF / FLG, a preset dictionary, block type 3, LEN != ~NLEN, a bad code set or symbol, a distance too far back */
+#define RDR_INFL_CHECKSUM 4  /* Adler-32 mismatch */
+int rdr_inflate_decode(rdr_ctx* ctx, const void* src, int64_t src_bytes, const int64_t* seg_offset, const int64_t* seg_bytes, int64_t nseg,
+                       const int64_t* seg_out_bytes, void* out, int64_t out_stride, int32_t* status, int64_t* produced, int loc);
+/* rdr_h5_unchunk: the inverse of rdr_h5_chunks.  `npresent` decoded chunks, chunk k at chunks + k * chunk_stride and chunk_index[k]
+ * (HOST) its row-major index in the chunk grid ceil(shape / chunk), each index at most once -> the C-ordered array out of `shape`.
+ * Edge chunks are clipped, the shuffle is undone (`shuffle`), bytes are reversed within an element (`swap`); elements of chunks
+ * that are not in the table are 0.  chunks and out live at `loc`; shape, chunk and chunk_index are HOST arrays.  RDR_ERR_INVALID:
+ * NULL, elem_bytes / ndim / sizes out of range, more than 2^36 elements, npresent outside 1 .. the grid's chunk count, an index
+ * outside the grid or given twice, chunk_stride below one chunk. */
+int rdr_h5_unchunk(rdr_ctx* ctx, const void* chunks, int64_t chunk_stride, const int64_t* chunk_index, int64_t npresent, int elem_bytes, int ndim,
+                   const int64_t* shape, const int64_t* chunk, int shuffle, int swap, void* out, int loc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@ RASTER_NEAREST, RASTER_LINEAR = 0, 1
 RDR_BYTESWAPPED = 0x100
 RDR_HOST, RDR_DEVICE = 0, 1
 RDR_DEFL_FIXED, RDR_DEFL_DYNAMIC = 0, 1
+RDR_INFL_OK, RDR_INFL_SHORT, RDR_INFL_OVERFLOW, RDR_INFL_INVALID, RDR_INFL_CHECKSUM = 0, 1, 2, 3, 4
 ORIGIN_GRID, ORIGIN_LLH, ORIGIN_XYZ = 0, 1, 2
 RDR_PROJ_LCC, RDR_PROJ_STERE, RDR_GRID_TM = 1, 2, 3
 LOS_VEC, LOS_INC_HD, LOS_INC_HD_SCALAR, LOS_ZENITH = 0, 1, 2, 3
@@ -158,6 +159,8 @@ SYMBOLS = [
     ('rdr_deflate_encode', C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int]),
     ('rdr_deflate_encode_tables', C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int, _VP, C.c_int64, _VP, _VP, C.c_int]),
     ('rdr_h5_chunks', C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, _VP, C.c_int]),
+    ('rdr_inflate_decode', C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, C.c_int]),
+    ('rdr_h5_unchunk', C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, C.c_int]),
 ]
 
 

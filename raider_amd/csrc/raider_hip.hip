@@ -342,6 +342,7 @@ static hipError_t launch_lds(void (*kern)(KArgs...), dim3 g, dim3 b, size_t sm, 
 #include "raster_kernels.h"
 #include "tiff_kernels.h"
 #include "deflate_kernels.h"
+#include "inflate_kernels.h"
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -3791,6 +3792,96 @@ int rdr_h5_chunks(rdr_ctx* c, const void* array, int elem_bytes, int ndim, const
     hipLaunchKernelGGL(h5_chunks_kernel, dim3(grid_for(L.total_elems, 256, c->num_cus * 16)), dim3(256), 0, c->stream, (const uint8_t*)din, L, (uint8_t*)dout);
     HIPCHECK(c, hipGetLastError());
     rc = finish_out(c, out, dout, (size_t)L.total_elems * elem_bytes, loc); if (rc) return rc;
+    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return RDR_OK;
+}
+
+
+// ---- zlib streams decoded on the device, and chunks put back into an array (inflate_kernels.h) -------------------------------------
+int rdr_inflate_decode(rdr_ctx* c, const void* src, int64_t src_bytes, const int64_t* seg_offset, const int64_t* seg_bytes, int64_t nseg,
+                       const int64_t* seg_out_bytes, void* out, int64_t out_stride, int32_t* status, int64_t* produced, int loc) {
+    if (!c || !src || !seg_offset || !seg_bytes || !seg_out_bytes || !out || !status) return fail(c, RDR_ERR_INVALID, "rdr_inflate_decode: NULL argument");
+    if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, "rdr_inflate_decode: loc must be RDR_HOST or RDR_DEVICE");
+    if (src_bytes <= 0 || nseg <= 0 || nseg > (1 << 24)) return fail(c, RDR_ERR_INVALID, "rdr_inflate_decode: need a non-empty buffer and 1 .. 2^24 segments");
+    if (out_stride <= 0 || out_stride > ((int64_t)1 << 31) - 256 || nseg * out_stride > ((int64_t)1 << 40))
+        return fail(c, RDR_ERR_INVALID, "rdr_inflate_decode: out_stride must be positive and below 2 GiB (at most 2^40 bytes in all)");
+    for (int64_t i = 0; i < nseg; ++i) {
+        if (seg_offset[i] < 0 || seg_bytes[i] < 0 || seg_offset[i] > src_bytes || seg_bytes[i] > src_bytes - seg_offset[i])
+            return fail(c, RDR_ERR_INVALID, "rdr_inflate_decode: segment " + std::to_string(i) + " does not lie inside the source buffer");
+        if (seg_bytes[i] >= ((int64_t)1 << 31) - 256) return fail(c, RDR_ERR_INVALID, "rdr_inflate_decode: segment " + std::to_string(i) + " is 2 GiB or longer");
+        if (seg_out_bytes[i] < 0 || seg_out_bytes[i] > out_stride)
+            return fail(c, RDR_ERR_INVALID, "rdr_inflate_decode: segment " + std::to_string(i) + " would write beyond its slot of out_stride bytes");
+    }
+    HIPCHECK(c, hipSetDevice(c->device));
+    const void* dsrc; void *dtab, *dout, *dstat, *dprod = nullptr;
+    int rc = stage_in(c, SLOT_IN0, src, (size_t)src_bytes, loc, &dsrc); if (rc) return rc;
+    rc = ensure(c, SLOT_IN1, (size_t)nseg * 24, &dtab); if (rc) return rc;
+    int64_t* tab = (int64_t*)dtab;                            // the three tables are host arrays whatever `loc` says: offsets | bytes | out bytes
+    rc = upload(c, tab, seg_offset, (size_t)nseg * 8); if (rc) return rc;
+    rc = upload(c, tab + nseg, seg_bytes, (size_t)nseg * 8); if (rc) return rc;
+    rc = upload(c, tab + 2 * nseg, seg_out_bytes, (size_t)nseg * 8); if (rc) return rc;
+    rc = stage_out(c, SLOT_OUT0, out, (size_t)(nseg * out_stride), loc, &dout); if (rc) return rc;
+    rc = stage_out(c, SLOT_OUT1, status, (size_t)nseg * 4, loc, &dstat); if (rc) return rc;
+    if (produced) { rc = stage_out(c, SLOT_OUT2, produced, (size_t)nseg * 8, loc, &dprod); if (rc) return rc; }
+    // bytes of a slot the stream does not reach keep their value: a host `out` goes up first
+    if (loc == RDR_HOST) { rc = upload(c, dout, out, (size_t)(nseg * out_stride)); if (rc) return rc; }
+    // one wave per stream; a compute unit holds three of these 44 KB workgroups, the grid strides over the rest
+    const int grid = (int)std::min<int64_t>(nseg, (int64_t)c->num_cus * 3);
+    hipLaunchKernelGGL(inflate_kernel, dim3(grid), dim3(64), 0, c->stream, (const uint8_t*)dsrc, src_bytes, (const int64_t*)tab, (const int64_t*)(tab + nseg),
+                       (const int64_t*)(tab + 2 * nseg), (int)nseg, (uint8_t*)dout, out_stride, (int32_t*)dstat, (int64_t*)dprod);
+    HIPCHECK(c, hipGetLastError());
+    rc = finish_out(c, out, dout, (size_t)(nseg * out_stride), loc); if (rc) return rc;
+    rc = finish_out(c, status, dstat, (size_t)nseg * 4, loc); if (rc) return rc;
+    if (produced) { rc = finish_out(c, produced, dprod, (size_t)nseg * 8, loc); if (rc) return rc; }
+    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return RDR_OK;
+}
+
+int rdr_h5_unchunk(rdr_ctx* c, const void* chunks, int64_t chunk_stride, const int64_t* chunk_index, int64_t npresent, int elem_bytes, int ndim,
+                   const int64_t* shape, const int64_t* chunk, int shuffle, int swap, void* out, int loc) {
+    if (!c || !chunks || !chunk_index || !shape || !chunk || !out) return fail(c, RDR_ERR_INVALID, "rdr_h5_unchunk: NULL argument");
+    if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, "rdr_h5_unchunk: loc must be RDR_HOST or RDR_DEVICE");
+    if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) return fail(c, RDR_ERR_INVALID, "rdr_h5_unchunk: elements of 1, 2, 4 or 8 bytes");
+    if (ndim < 1 || ndim > 4) return fail(c, RDR_ERR_INVALID, "rdr_h5_unchunk: 1 .. 4 dimensions");
+    H5UnchunkLayout L{};
+    int64_t out_elems = 1, nchunks = 1;
+    L.chunk_elems = 1;
+    for (int d = 0; d < 4; ++d) { L.shape[d] = L.chunk[d] = L.nchunk[d] = 1; }
+    for (int d = 0; d < ndim; ++d) {
+        const int64_t s = shape[d], k = chunk[d];
+        if (s <= 0 || k <= 0 || s > ((int64_t)1 << 31) || k > ((int64_t)1 << 31)) return fail(c, RDR_ERR_INVALID, "rdr_h5_unchunk: shape and chunk sizes must be positive (below 2^31)");
+        const int e = 4 - ndim + d;
+        L.shape[e] = s; L.chunk[e] = k; L.nchunk[e] = (s + k - 1) / k;
+        if (out_elems > ((int64_t)1 << 36) / s || L.chunk_elems > ((int64_t)1 << 36) / k) return fail(c, RDR_ERR_INVALID, "rdr_h5_unchunk: more than 2^36 elements");
+        out_elems *= s; L.chunk_elems *= k;
+        nchunks *= L.nchunk[e];
+        if (nchunks > ((int64_t)1 << 36) / L.chunk_elems) return fail(c, RDR_ERR_INVALID, "rdr_h5_unchunk: more than 2^36 elements");
+    }
+    if (npresent <= 0 || npresent > nchunks) return fail(c, RDR_ERR_INVALID, "rdr_h5_unchunk: 1 .. " + std::to_string(nchunks) + " chunks may be present");
+    if (chunk_stride < L.chunk_elems * elem_bytes || chunk_stride > ((int64_t)1 << 40) / npresent)
+        return fail(c, RDR_ERR_INVALID, "rdr_h5_unchunk: chunk_stride must hold one decoded chunk (at most 2^40 bytes in all)");
+    try {                                                       // each index inside the grid and at most once: a sorted copy of the table, never the grid
+        std::vector<int64_t> sorted(chunk_index, chunk_index + npresent);
+        std::sort(sorted.begin(), sorted.end());
+        if (sorted.front() < 0 || sorted.back() >= nchunks) return fail(c, RDR_ERR_INVALID, "rdr_h5_unchunk: a chunk index lies outside the chunk grid");
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(c, RDR_ERR_INVALID, "rdr_h5_unchunk: a chunk index is given twice");
+    } catch (const std::bad_alloc&) {
+        return fail(c, RDR_ERR_OOM, "rdr_h5_unchunk: no host memory to check the chunk table");
+    }
+    L.total_elems = npresent * L.chunk_elems;
+    L.chunk_stride = chunk_stride;
+    L.es = elem_bytes; L.shuffle = shuffle != 0; L.swap = swap != 0;
+    HIPCHECK(c, hipSetDevice(c->device));
+    const void* din; void *dout, *dtab;
+    int rc = stage_in(c, SLOT_IN0, chunks, (size_t)(npresent * chunk_stride), loc, &din); if (rc) return rc;
+    rc = ensure(c, SLOT_IN1, (size_t)npresent * 8, &dtab); if (rc) return rc;
+    rc = upload(c, dtab, chunk_index, (size_t)npresent * 8); if (rc) return rc;
+    rc = stage_out(c, SLOT_OUT0, out, (size_t)out_elems * elem_bytes, loc, &dout); if (rc) return rc;
+    if (npresent < nchunks) HIPCHECK(c, hipMemsetAsync(dout, 0, (size_t)out_elems * elem_bytes, c->stream));      // absent chunks read as 0
+    hipLaunchKernelGGL(h5_unchunk_kernel, dim3(grid_for(L.total_elems, 256, c->num_cus * 16)), dim3(256), 0, c->stream, (const uint8_t*)din, (const int64_t*)dtab, L,
+                       (uint8_t*)dout);
+    HIPCHECK(c, hipGetLastError());
+    rc = finish_out(c, out, dout, (size_t)out_elems * elem_bytes, loc); if (rc) return rc;
     if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
     return RDR_OK;
 }

@@ -1,4 +1,5 @@
-"""zlib streams written on the GPU (rdr_deflate_encode) and the chunk cutter of the NetCDF-4 writer (rdr_h5_chunks).
+"""zlib streams written on the GPU (rdr_deflate_encode) and read back there (rdr_inflate_decode), the chunk cutter of the NetCDF-4
+writer (rdr_h5_chunks) and its inverse (rdr_h5_unchunk).
 
 The encoder turns independent byte ranges of one buffer into complete zlib streams, one wave per 32 KiB sub-block, with fixed-Huffman
 and stored blocks; with tables='dynamic' every sub-block is the smallest of a stored, a fixed-Huffman and a
@@ -149,3 +150,122 @@ def compress_chunks(array, chunk, fill, shuffle=True, tables='fixed'):
     if _is_tensor(packed):
         packed = packed.cpu().numpy()
     return packed, oo
+
+
+# ---- the way back: zlib streams decoded on the device (rdr_inflate_decode), chunks put back into an array (rdr_h5_unchunk) -----------
+def inflate_mode(inflate):
+    """The `inflate` keyword of the readers, validated: 'auto', 'host' or 'device'."""
+    if inflate not in ('auto', 'host', 'device'):
+        raise ValueError(f"inflate must be 'auto', 'host' or 'device', not {inflate!r}")
+    return inflate
+
+
+def inflate_segments(buf, offsets, sizes, out_sizes, out_stride=None, out=None):
+    """(out, status, produced): the zlib streams buf[offsets[i] : offsets[i] + sizes[i]] decoded on the device, stream i into
+    out[i * out_stride : i * out_stride + out_sizes[i]].  buf: a C-contiguous NumPy array or device tensor (taken as bytes); out is a
+    uint8 array / tensor of the same kind of len(sizes) * out_stride bytes (out_stride: max(out_sizes) rounded up to 16 when None),
+    status an int32 and produced an int64 array / tensor.  status[i] is one of RDR_INFL_*: 0 exactly when zlib.decompress accepts the
+    stream and its output fits the slot.  `out`: an existing buffer to decode into - slot bytes a stream does not reach keep their value
+    (a new buffer is zeroed).  One transfer each way for NumPy, none for tensors."""
+    so = np.ascontiguousarray(offsets, dtype=np.int64).ravel()
+    sb = np.ascontiguousarray(sizes, dtype=np.int64).ravel()
+    cap = np.ascontiguousarray(out_sizes, dtype=np.int64).ravel()
+    n = so.size
+    if sb.size != n or cap.size != n:
+        raise ValueError('offsets, sizes and out_sizes differ in length')
+    if n == 0:
+        raise ValueError('inflate_segments: no segments')
+    if out_stride is None:
+        out_stride = max(16, (int(cap.max()) + 15) // 16 * 16)
+    out_stride = int(out_stride)
+    tensor = _is_tensor(buf)
+    if tensor:
+        import torch
+        if not buf.is_cuda or not buf.is_contiguous():
+            raise TypeError('inflate_segments: a tensor must be contiguous and live on the GPU')
+        src = buf.reshape(-1).view(torch.uint8)
+        nsrc = src.numel()
+        if out is None:
+            out = torch.zeros(n * out_stride, dtype=torch.uint8, device=buf.device)
+        elif not _is_tensor(out) or out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < n * out_stride:
+            raise TypeError(f'inflate_segments: out must be a contiguous uint8 tensor on the GPU of {n} slots of {out_stride} bytes')
+        status = torch.full((n,), -1, dtype=torch.int32, device=buf.device)
+        produced = torch.zeros(n, dtype=torch.int64, device=buf.device)
+        loc = L.RDR_DEVICE
+    else:
+        require_gpu('inflate_segments (rdr_inflate_decode)')
+        src = np.ascontiguousarray(buf).reshape(-1).view(np.uint8)
+        nsrc = src.size
+        if out is None:
+            out = np.zeros(n * out_stride, dtype=np.uint8)
+        elif not isinstance(out, np.ndarray) or out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < n * out_stride:
+            raise TypeError(f'inflate_segments: out must be a C-contiguous uint8 array of {n} slots of {out_stride} bytes')
+        status = np.full(n, -1, dtype=np.int32)
+        produced = np.zeros(n, dtype=np.int64)
+        loc = L.RDR_HOST
+    ctx = L.Context.default()
+    if tensor:
+        ctx.adopt_torch_stream(src)
+    L.check(ctx.lib.rdr_inflate_decode(ctx.handle, L.ptr(src), nsrc, L.ptr(so), L.ptr(sb), n, L.ptr(cap), L.ptr(out), out_stride, L.ptr(status), L.ptr(produced), loc),
+            ctx.handle)
+    return out, status, produced
+
+
+def h5_unchunk(chunks, chunk_stride, chunk_index, dtype, shape, chunk, shuffle=True, swap=False):
+    """The inverse of h5_chunks: decoded chunks (uint8 array / device tensor, chunk k at k * chunk_stride, its row-major index in the
+    chunk grid chunk_index[k]) -> the C-ordered array / tensor of `shape` and `dtype` (native byte order; `swap`: the chunks hold
+    the other one).  Elements of chunks that are not listed are 0."""
+    dt = np.dtype(dtype).newbyteorder('=')
+    shape = tuple(int(s) for s in shape)
+    chunk = tuple(int(c) for c in chunk)
+    idx = np.ascontiguousarray(chunk_index, dtype=np.int64).ravel()
+    if len(chunk) != len(shape) or not 1 <= len(shape) <= 4:
+        raise ValueError(f'h5_unchunk: chunk {chunk} does not fit an array of shape {shape} (1 to 4 axes)')
+    if idx.size == 0:
+        raise ValueError('h5_unchunk: no chunks')
+    sh, ck = np.array(shape, dtype=np.int64), np.array(chunk, dtype=np.int64)
+    nbytes = int(np.prod(sh)) * dt.itemsize
+    ctx = L.Context.default()
+    if _is_tensor(chunks):
+        import torch
+        if not chunks.is_cuda or not chunks.is_contiguous() or chunks.numel() * chunks.element_size() < idx.size * int(chunk_stride):
+            raise TypeError('h5_unchunk: a tensor must be contiguous, live on the GPU and hold every chunk')
+        out = torch.empty(nbytes, dtype=torch.uint8, device=chunks.device)
+        ctx.adopt_torch_stream(chunks)
+        loc = L.RDR_DEVICE
+    else:
+        require_gpu('h5_unchunk (rdr_h5_unchunk)')
+        chunks = np.ascontiguousarray(chunks).reshape(-1).view(np.uint8)
+        if chunks.size < idx.size * int(chunk_stride):
+            raise ValueError('h5_unchunk: the buffer does not hold every chunk')
+        out = np.empty(nbytes, dtype=np.uint8)
+        loc = L.RDR_HOST
+    L.check(ctx.lib.rdr_h5_unchunk(ctx.handle, L.ptr(chunks), int(chunk_stride), L.ptr(idx), idx.size, dt.itemsize, len(shape), L.ptr(sh), L.ptr(ck), int(bool(shuffle)),
+                                   int(bool(swap)), L.ptr(out), loc), ctx.handle)
+    if _is_tensor(out):
+        import torch
+        if not hasattr(torch, dt.name):
+            raise TypeError(f'h5_unchunk: this torch build has no tensor type for {dt.name}')
+        return out.view(getattr(torch, dt.name)).reshape(shape)
+    return out.view(dt).reshape(shape)
+
+
+def h5_unchunk_host(chunks, chunk_stride, chunk_index, dtype, shape, chunk, shuffle=True, swap=False):
+    """NumPy restatement of rdr_h5_unchunk (what the tests compare it with)."""
+    dt = np.dtype(dtype).newbyteorder('=')
+    src_dt = dt.newbyteorder('S') if swap else dt
+    shape = tuple(int(s) for s in shape)
+    chunk = tuple(int(c) for c in chunk)
+    grid = chunk_grid(shape, chunk)
+    n = int(np.prod(chunk, dtype=np.int64))
+    raw = np.ascontiguousarray(chunks).reshape(-1).view(np.uint8)
+    out = np.zeros(shape, dtype=dt)
+    for k, ci in enumerate(np.asarray(chunk_index, dtype=np.int64).ravel()):
+        b = raw[k * int(chunk_stride):k * int(chunk_stride) + n * dt.itemsize]
+        if shuffle:
+            b = b.reshape(dt.itemsize, n).T
+        blk = np.ascontiguousarray(b).reshape(-1).view(src_dt).reshape(chunk)
+        offs = tuple(int(i) * c for i, c in zip(np.unravel_index(int(ci), grid), chunk))
+        sel = tuple(slice(o, min(o + c, s)) for o, c, s in zip(offs, chunk, shape))
+        out[sel] = blk[tuple(slice(0, s.stop - s.start) for s in sel)]
+    return out

@@ -89,8 +89,16 @@ class _Var:
     `data` may be a zero-argument loader: the array is then read from the file on first use (a ray-traced run never touches
     the f64 `*_total` fields, two thirds of a processed-cube file)."""
 
-    def __init__(self, data, attrs, raw=None):
-        self._data, self.attrs, self._raw = data, attrs, raw
+    def __init__(self, data, attrs, raw=None, device=None):
+        self._data, self.attrs, self._raw, self._device = data, attrs, raw, device
+
+    def read_device(self):
+        """The variable as a device tensor decoded on the GPU (a chunked, deflated variable: h5lite.Dataset.read_device), or None when
+        the file does not allow it or no GPU is visible (then `data`)."""
+        if self._device is None:
+            return None
+        import torch
+        return self._device() if torch.cuda.is_available() else None
 
     def raw(self):
         """The variable as it lies in the file - a read-only, possibly other-endian view of the file mapping, no copy - or None when
@@ -147,7 +155,8 @@ def _read_cube_file(path):
         obj = f[k]
         if isinstance(obj, h5lite.Dataset) and obj.dtype is not None and obj.dtype.kind in 'fiu':
             out[k] = _Var(obj.read, {n: v for n, v in obj.attrs.items() if not n.startswith('_N') and n not in ('CLASS', 'NAME')},
-                          obj.raw if obj.dtype.kind == 'f' else None)
+                          obj.raw if obj.dtype.kind == 'f' else None,
+                          obj.read_device if obj.dtype.kind == 'f' and obj.dtype.itemsize in (4, 8) else None)      # (what a Cube takes as it is)
     return out
 
 
@@ -197,9 +206,17 @@ def getInterpolators(wm_file, kind='pointwise', shared=False, ctx=None):
         # they lie there, byte-swapped and NaN-scanned on the device - no host pass over 58 MB (ERA5-sized) to 400 MB (HRRR-sized)
         v = var[name]
         r = v.raw() if hasattr(v, 'raw') else None
+        if r is None and hasattr(v, 'read_device'):
+            r = v.read_device()                                    # chunked + deflated: inflated and put together on the device
         return r if r is not None else get(name)
     wet = field('wet_total' if kind == 'total' else 'wet')
     hydro = field('hydro_total' if kind == 'total' else 'hydro')
+    if hasattr(wet, 'is_cuda') != hasattr(hydro, 'is_cuda'):       # one field decoded on the device, the other not: both go there
+        import torch
+        up = lambda a, like: a if hasattr(a, 'is_cuda') else torch.from_numpy(np.array(a, dtype=np.asarray(a).dtype.newbyteorder('='))).to(like.device)
+        wet, hydro = up(wet, hydro), up(hydro, wet)
+    if hasattr(wet, 'is_cuda') and hydro.dtype != wet.dtype:
+        hydro = hydro.to(wet.dtype)
     cube = Cube(ys, xs, zs, wet, hydro, order='zyx', ctx=ctx)      # no host transpose (delayFcns.py:40-41 does one)
     if cube.has_nan():                                             # delayFcns.py:50-52, answered by the packing kernel
         from .logger import logger

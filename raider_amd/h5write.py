@@ -37,10 +37,14 @@ def _pad8(b):
 
 
 # ---- datatype messages -------------------------------------------------------------------------------------------------
-def _dt_numeric(dt):
+def _dt_numeric(dt, big_endian_ok=False):
     dt = np.dtype(dt)
     if dt.byteorder == '>':
-        raise ValueError('big-endian arrays are not written')
+        if not big_endian_ok:
+            raise ValueError('big-endian arrays are not written')
+        msg = bytearray(_dt_numeric(dt.newbyteorder('<')))
+        msg[1] |= 1                                    # byte order: big-endian (a ChunkedData whose caller stored its chunks so)
+        return bytes(msg)
     if dt.kind == 'f':
         if dt.itemsize == 4:
             props = struct.pack('<HHBBBBI', 0, 32, 23, 8, 0, 23, 127); bits = bytes([0x20, 31, 0])
@@ -144,7 +148,9 @@ def _object_header(messages):
 class ChunkedData:
     """The data of a chunked, filtered variable, compressed by the CALLER: this writer lays the file out and never compresses.
     shape / dtype: the variable's; chunks: the chunk shape (every chunk is stored full size, edge chunks padded with the fill
-    value); filters: ('shuffle', 'deflate'), ('deflate',) or () in HDF5's pipeline order; packed: the chunks' stored bytes back to
+    value); filters: ('shuffle', 'deflate'), ('deflate',) or () in HDF5's pipeline order, 'fletcher32' last when the caller put the four
+    checksum bytes behind every chunk (this writer neither computes nor checks them: a file whose bytes are not HDF5's Fletcher-32 of
+    the chunk is refused by libhdf5, while h5lite drops them unverified); a big-endian dtype says the caller stored the elements so; packed: the chunks' stored bytes back to
     back in row-major chunk order (a uint8 array or bytes), chunk k being packed[offsets[k]:offsets[k + 1]].  raider_amd.deflate
     .compress_chunks makes (packed, offsets) on the device; NumPy shuffle + zlib.compress make the same on the host."""
 
@@ -160,8 +166,8 @@ class ChunkedData:
             raise ValueError(f'chunks {self.chunks} do not fit a variable of shape {self.shape}')
         if any(c <= 0 or c > s for c, s in zip(self.chunks, self.shape)):
             raise ValueError(f'chunk sizes must lie in 1 .. the dimension size: chunks {self.chunks}, shape {self.shape}')
-        if any(f not in ('shuffle', 'deflate') for f in self.filters):
-            raise ValueError(f"filters are 'shuffle' and 'deflate', not {self.filters}")
+        if any(f not in ('shuffle', 'deflate', 'fletcher32') for f in self.filters):
+            raise ValueError(f"filters are 'shuffle', 'deflate' and 'fletcher32', not {self.filters}")
         self.grid = tuple(-(-s // c) for s, c in zip(self.shape, self.chunks))
         self.nchunks = int(np.prod(self.grid))
         if self.offsets.size != self.nchunks + 1 or self.offsets[0] != 0 or np.any(np.diff(self.offsets) <= 0) or self.offsets[-1] != self.packed.size:
@@ -171,7 +177,7 @@ class ChunkedData:
 
 
 _CHUNK_K = 32         # superblock version 0 implies it: one leaf of the chunk B-tree holds 2 * K chunks
-_FILTER_IDS = {'deflate': 1, 'shuffle': 2}
+_FILTER_IDS = {'deflate': 1, 'shuffle': 2, 'fletcher32': 3}
 
 
 class _Dataset:
@@ -182,7 +188,7 @@ class _Dataset:
             if self.chunked.nchunks > 2 * _CHUNK_K:
                 raise ValueError(f'variable {name!r} needs {self.chunked.nchunks} chunks; one B-tree leaf holds {2 * _CHUNK_K} '
                                  '(multi-level chunk trees are not written: choose larger chunks)')
-            _dt_numeric(self.chunked.dtype)
+            _dt_numeric(self.chunked.dtype, big_endian_ok=True)
             self.data = None
             self.shape, self.dtype = self.chunked.shape, self.chunked.dtype
         else:
@@ -220,7 +226,7 @@ class _Dataset:
 
     def header(self, addr_of, gcol_addr):
         c = self.chunked
-        msgs = [_message(0x01, _dataspace(self.shape)), _message(0x03, _dt_numeric(self.dtype), flags=1)]
+        msgs = [_message(0x01, _dataspace(self.shape)), _message(0x03, _dt_numeric(self.dtype, big_endian_ok=c is not None), flags=1)]
         alloc = 2 if c is None else 3                                        # late for contiguous, incremental for chunked storage: libhdf5's defaults
         if self.fill is not None:
             fv = np.asarray(self.fill, dtype=self.dtype).tobytes()
@@ -234,8 +240,9 @@ class _Dataset:
             if c.filters:
                 body = struct.pack('<BB6x', 1, len(c.filters))
                 for f in c.filters:
-                    client = [self.dtype.itemsize] if f == 'shuffle' else [c.level]
-                    body += struct.pack('<HHHH', _FILTER_IDS[f], 8, 1, len(client)) + _pad8(f.encode() + b'\0')   # optional filter, named as libhdf5 names it
+                    client = [self.dtype.itemsize] if f == 'shuffle' else [c.level] if f == 'deflate' else []
+                    name = _pad8(f.encode() + b'\0')
+                    body += struct.pack('<HHHH', _FILTER_IDS[f], len(name), 1, len(client)) + name                # optional filter, named as libhdf5 names it
                     body += struct.pack(f'<{len(client)}I', *client) + (b'\0' * 4 if len(client) % 2 else b'')
                 msgs.append(_message(0x0B, body))
             dims = list(c.chunks) + [self.dtype.itemsize]

@@ -5,7 +5,8 @@ in later ones are ignored) of a classic (magic 42) or BigTIFF (magic 43) file in
 samples of uint8/16/32, int8/16/32, float32/64 in any band count; compression 1 (none), 5 (LZW), 8 / 32946 (deflate), 32773
 (PackBits); predictor 1 and 2.  Everything else is refused BY NAME (`UnsupportedTIFFFeature`), as h5lite refuses what it does not read.
 
-Where the bytes are decoded: deflate (zlib) and PackBits on the host; LZW on the GPU (rdr_tiff_lzw_decode: the compressed segments go
+Where the bytes are decoded: PackBits on the host; deflate on the host (zlib) or, for files of many segments read with `device=`
+(and whenever inflate='device' asks for it), on the GPU (rdr_inflate_decode, one wave per segment); LZW on the GPU (rdr_tiff_lzw_decode: the compressed segments go
 up as they are, one wave decodes each) - there is no host LZW decoder here, a pure-Python one needs minutes for a real DEM.  With
 `device=` the decoded segments are put together there too (rdr_tiff_assemble: padding clipped, bytes swapped, predictor undone) and
 the raster never exists on the host; without it, and without LZW, everything is NumPy and no GPU is needed.  The writer deflates its
@@ -377,7 +378,8 @@ def _gpu_device(device):
     import torch
     if device is None:
         if not torch.cuda.is_available():
-            raise RuntimeError('LZW-compressed GeoTIFFs are decoded on the GPU (rdr_tiff_lzw_decode); no GPU is visible and there is no CPU fallback')
+            raise RuntimeError("LZW-compressed GeoTIFFs, and deflate ones read with inflate='device', are decoded on the GPU (rdr_tiff_lzw_decode, "
+                               'rdr_inflate_decode); no GPU is visible and there is no CPU fallback')
         return torch.device('cuda', torch.cuda.current_device())
     device = torch.device(device)
     if device.type != 'cuda':
@@ -385,8 +387,15 @@ def _gpu_device(device):
     return device
 
 
-def _read_device(info, band, device):
-    """The decode through the two kernels; a uint8 tensor holding the raster's bytes, and its shape."""
+# inflate='auto': deflate segments from which the device route is taken.  Measured (tools/bench_inflate.py, profiles/r24_inflate.json): a
+# 4000 x 4000 int16 DEM read to a device tensor in 64 segments takes 119 ms on the device route against 71 ms through zlib, in 256
+# segments 32 ms against 80 ms - one wave decodes one segment, so the route pays only once a few hundred waves run side by side.
+_INFLATE_MIN_SEGMENTS = 256
+
+
+def _read_device(info, band, device, inflate='host'):
+    """The decode through the two kernels; a uint8 tensor holding the raster's bytes, and its shape.  inflate: where deflate segments
+    are decoded, 'host' or 'device'."""
     import torch
     nseg = len(info.offsets)
     full = info.tile_h * info.tile_w * info.spp_seg * info.dtype.itemsize
@@ -403,6 +412,19 @@ def _read_device(info, band, device):
         if bad.size:
             what = {1: 'ends early or holds more than the segment takes', 2: 'holds a code beyond the string table'}.get(int(status[bad[0]]), 'failed')
             raise NotATIFF(f'{info.path}: the LZW stream of segment {int(bad[0])} {what} ({bad.size} of {nseg} segments damaged)')
+    elif info.compression in (8, 32946) and inflate == 'device':
+        # the file's bytes go up, rdr_inflate_decode writes the (zeroed) slots; a segment it does not accept is decoded again on the
+        # host and patched in, so that the host route's result - a truncated over-long stream - or its exception stands
+        from . import deflate
+        whole = np.fromfile(info.path, dtype=np.uint8)
+        src = torch.from_numpy(whole).to(device)
+        need = np.array([info.seg_bytes(k) for k in range(nseg)], dtype=np.int64)
+        segs, status, _ = deflate.inflate_segments(src, info.offsets, info.bytecounts, need, out_stride=stride)
+        for k in np.nonzero(status.cpu().numpy())[0]:
+            k = int(k)
+            o = int(info.offsets[k])
+            d = _host_segment(info, whole[o:o + int(info.bytecounts[k])].tobytes(), k)
+            segs[k * stride:k * stride + len(d)] = torch.from_numpy(np.frombuffer(d, dtype=np.uint8).copy()).to(device)
     else:
         buf = np.zeros(nseg * stride, dtype=np.uint8)
         with open(info.path, 'rb') as f:
@@ -414,16 +436,23 @@ def _read_device(info, band, device):
     return assemble_device(segs, stride, info.height, info.width, info.tile_h, info.tile_w, info.predictor, info.swap, info.dtype, info.planar, info.count, band)
 
 
-def read(path, band=None, device=None):
+def read(path, band=None, device=None, inflate='auto'):
     """(array, profile) of the first image of a GeoTIFF.  band: 1-based, None = every band ((H, W) for a one-band file, else (bands, H, W)).
     device: a torch GPU device - the array is a tensor there and the decoded raster never exists on the host; None - a NumPy array
-    (LZW files still pass through the GPU, which decodes them; all others are read without one)."""
+    (LZW files still pass through the GPU, which decodes them; all others are read without one).  inflate: where deflate segments
+    are decoded - 'host' (zlib), 'device' (rdr_inflate_decode; with device=None the result is downloaded) or 'auto' (the device when
+    `device` is given and the file has at least _INFLATE_MIN_SEGMENTS segments).  Both routes give the same pixels and errors."""
+    from .deflate import inflate_mode
+    inflate = inflate_mode(inflate)
     info = TiffInfo(path)
     if band is not None and not 1 <= int(band) <= info.count:
         raise IndexError(f'{path}: band {band} of {info.count}')
     b0 = None if band is None else int(band) - 1
-    if device is not None or info.compression == 5:
-        raw, shape = _read_device(info, b0, _gpu_device(device))
+    deflated = info.compression in (8, 32946)
+    if inflate == 'auto':
+        inflate = 'device' if deflated and device is not None and len(info.offsets) >= _INFLATE_MIN_SEGMENTS else 'host'
+    if device is not None or info.compression == 5 or (deflated and inflate == 'device'):
+        raw, shape = _read_device(info, b0, _gpu_device(device), inflate)
         if device is not None:
             arr = raw.view(_torch_dtype(info.dtype)).reshape(shape)
         else:
