@@ -667,9 +667,13 @@ __global__ __launch_bounds__(256) void tiff_predict_kernel(const U* __restrict__
     }
 }
 
-struct H5ChunkLayout {
+// an array cut into chunks: what h5_chunks_kernel and its inverse (h5_unchunk_kernel, inflate_kernels.h) both walk
+struct H5ChunkGrid {
     int64_t shape[4], chunk[4], nchunk[4];         // padded to four axes with ones in front
-    int64_t chunk_elems, total_elems;              // elements of one chunk; of all chunks
+    int64_t chunk_elems, total_elems;              // elements of one chunk; of all chunks the kernel walks
+};
+
+struct H5ChunkLayout : H5ChunkGrid {
     int es, shuffle;
     uint8_t fill[8];
 };

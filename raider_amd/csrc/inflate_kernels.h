@@ -29,6 +29,7 @@
 
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
+#include "deflate_kernels.h"   // H5ChunkGrid
 #define INFL_HD __host__ __device__ inline
 #else
 #define INFL_HD inline
@@ -551,9 +552,7 @@ __global__ __launch_bounds__(64) void inflate_kernel(const uint8_t* __restrict__
 }
 
 // ---- the inverse of h5_chunks_kernel ---------------------------------------------------------------------------------------------
-struct H5UnchunkLayout {
-    int64_t shape[4], chunk[4], nchunk[4];         // padded to four axes with ones in front
-    int64_t chunk_elems, total_elems;              // elements of one chunk; of all PRESENT chunks
+struct H5UnchunkLayout : H5ChunkGrid {             // (deflate_kernels.h; total_elems counts the PRESENT chunks)
     int64_t chunk_stride;                          // bytes between decoded chunks
     int es, shuffle, swap;
 };

@@ -224,6 +224,7 @@ static int upload_parts(rdr_ctx* ctx, void* dst, const HostPart* parts, int npar
     size_t bytes = 0;
     for (int i = 0; i < nparts; ++i) bytes += parts[i].bytes;
     if (bytes == 0) return RDR_OK;
+    if (nparts == 1) return upload(ctx, dst, parts[0].p, bytes);
     if (bytes > rdr_ctx::PIN_MAX) {               // too large for the ring: piece by piece
         size_t o = 0;
         for (int i = 0; i < nparts; ++i) { const int rc = upload(ctx, static_cast<char*>(dst) + o, parts[i].p, parts[i].bytes); if (rc) return rc; o += parts[i].bytes; }
@@ -289,6 +290,66 @@ static int finish_out(rdr_ctx* ctx, void* dst, const void* dev, size_t bytes, in
     HIPCHECK(ctx, hipMemcpyAsync(dst, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
     return RDR_OK;
 }
+
+// The stage / launch check / download / synchronise sequence of ONE call of an entry point, over the four functions above.  Every argument
+// is named once, with its size: in() and out() hand out SLOT_IN0.. and SLOT_OUT0.. in the order of the calls (an absent - NULL - argument
+// still takes its turn, so the others keep their slots), an explicit slot is for the few calls that deviate; finish() downloads what out()
+// and inout() staged, with the sizes they were given.  The first failure is kept in `rc` and turns every later method into a no-op that
+// returns NULL: an entry point tests `rc` once, before it launches.  Fixed arrays only, and no HIP call that the four functions do not make.
+struct Staged {
+    rdr_ctx* c; int loc, oloc; int rc = RDR_OK;
+    int nin = 0, nout = 0, ndown = 0;
+    struct { void* host; const void* dev; size_t bytes; } down[6];
+    Staged(rdr_ctx* ctx, int loc_) : c(ctx), loc(loc_), oloc(loc_) {}
+    Staged(rdr_ctx* ctx, int loc_, int out_loc) : c(ctx), loc(loc_), oloc(out_loc) {}   // outputs in another place than the inputs
+
+    template <typename T> const T* in(const T* p, size_t bytes, int slot = -1) {
+        const void* d = nullptr;
+        if (slot < 0) slot = SLOT_IN0 + nin++;
+        if (!rc) rc = stage_in(c, slot, p, bytes, loc, &d);
+        return rc ? nullptr : static_cast<const T*>(d);
+    }
+    template <typename T> T* out(T* p, size_t bytes, int slot = -1) {      // p == NULL: an optional output that was not asked for
+        void* d = nullptr;
+        if (slot < 0) slot = SLOT_OUT0 + nout++;
+        if (!p || rc) return nullptr;
+        rc = stage_out(c, slot, p, bytes, oloc, &d);
+        return rc ? nullptr : static_cast<T*>(download(p, d, bytes));
+    }
+    template <typename T> T* inout(T* p, size_t bytes, int slot) {         // staged up as an input, downloaded as an output
+        const void* d = nullptr;
+        if (!p || rc) return nullptr;
+        rc = stage_in(c, slot, p, bytes, loc, &d);
+        return rc ? nullptr : static_cast<T*>(download(p, const_cast<void*>(d), bytes));
+    }
+    template <typename T> T* scratch(int slot, size_t bytes) {             // device-only working memory of the call
+        void* d = nullptr;
+        if (!rc) rc = ensure(c, slot, bytes, &d);
+        return rc ? nullptr : static_cast<T*>(d);
+    }
+    // a small table that comes from the HOST whatever `loc` says: its parts land back to back in `slot`, as one copy, and are consumed on return
+    template <typename T> T* table(int slot, const HostPart* parts, int nparts) {
+        size_t bytes = 0;
+        for (int i = 0; i < nparts; ++i) bytes += parts[i].bytes;
+        T* d = scratch<T>(slot, bytes);
+        if (!rc) rc = upload_parts(c, d, parts, nparts);
+        return rc ? nullptr : d;
+    }
+    // after the launch: its error, the downloads in the order they were staged, the host's wait when the outputs are its own (or `always`)
+    int finish(bool always_sync = false) {
+        if (rc) return rc;
+        HIPCHECK(c, hipGetLastError());
+        for (int i = 0; i < ndown; ++i) { rc = finish_out(c, down[i].host, down[i].dev, down[i].bytes, oloc); if (rc) return rc; }
+        if (oloc == RDR_HOST || always_sync) HIPCHECK(c, hipStreamSynchronize(c->stream));
+        return RDR_OK;
+    }
+private:
+    void* download(void* host, void* dev, size_t bytes) {
+        if (ndown == 6) { rc = fail(c, RDR_ERR_INVALID, "Staged: more than 6 outputs in one call"); return nullptr; }
+        down[ndown++] = {host, dev, bytes};
+        return dev;
+    }
+};
 
 struct KTimer {
     rdr_ctx* c; int which; hipEvent_t stop = nullptr;
@@ -943,18 +1004,12 @@ int rdr_transform_cone(rdr_ctx* c, int kind, const double* p, int np, int direct
     if (n < 0) return fail(c, RDR_ERR_INVALID, "rdr_transform_cone: negative count");
     if (n == 0) return RDR_OK;
     HIPCHECK(c, hipSetDevice(c->device));
-    const void *da, *db; void *oa, *ob;
-    rc = stage_in(c, SLOT_IN0, in_a, (size_t)n * 8, loc, &da); if (rc) return rc;
-    rc = stage_in(c, SLOT_IN1, in_b, (size_t)n * 8, loc, &db); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, out_a, (size_t)n * 8, loc, &oa); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT1, out_b, (size_t)n * 8, loc, &ob); if (rc) return rc;
-    hipLaunchKernelGGL(cone_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, L, direction, (const double*)da, (const double*)db, n,
-                       (double*)oa, (double*)ob);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, out_a, oa, (size_t)n * 8, loc); if (rc) return rc;
-    rc = finish_out(c, out_b, ob, (size_t)n * 8, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    Staged S(c, loc);
+    const double *da = S.in(in_a, (size_t)n * 8), *db = S.in(in_b, (size_t)n * 8);
+    double *oa = S.out(out_a, (size_t)n * 8), *ob = S.out(out_b, (size_t)n * 8);
+    if (S.rc) return S.rc;
+    hipLaunchKernelGGL(cone_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, L, direction, da, db, n, oa, ob);
+    return S.finish();
 }
 
 int rdr_project_points(rdr_ctx* c, const rdr_cube* q, const double* lat, const double* lon, int64_t n, double* y, double* x, int loc) {
@@ -970,18 +1025,12 @@ int rdr_project_points(rdr_ctx* c, const rdr_cube* q, const double* lat, const d
         if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
         return RDR_OK;
     }
-    const void *a, *b; void *oy, *ox;
-    int rc = stage_in(c, SLOT_IN0, lat, (size_t)n * 8, loc, &a); if (rc) return rc;
-    rc = stage_in(c, SLOT_IN1, lon, (size_t)n * 8, loc, &b); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, y, (size_t)n * 8, loc, &oy); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT1, x, (size_t)n * 8, loc, &ox); if (rc) return rc;
-    hipLaunchKernelGGL(lcc_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, q->proj, (const double*)a, (const double*)b, n,
-                       (double*)oy, (double*)ox);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, y, oy, (size_t)n * 8, loc); if (rc) return rc;
-    rc = finish_out(c, x, ox, (size_t)n * 8, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    Staged S(c, loc);
+    const double *a = S.in(lat, (size_t)n * 8), *b = S.in(lon, (size_t)n * 8);
+    double *oy = S.out(y, (size_t)n * 8), *ox = S.out(x, (size_t)n * 8);
+    if (S.rc) return S.rc;
+    hipLaunchKernelGGL(lcc_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, q->proj, a, b, n, oy, ox);
+    return S.finish();
 }
 
 int rdr_transform_tm(rdr_ctx* c, const double* p, int np, int direction, const double* in_a, const double* in_b, int64_t n, double* out_a,
@@ -993,18 +1042,12 @@ int rdr_transform_tm(rdr_ctx* c, const double* p, int np, int direction, const d
     if (n == 0) return RDR_OK;
     HIPCHECK(c, hipSetDevice(c->device));
     const TmParams T = tm_setup(p[0], p[1], p[2], p[3], p[4], p[5], p[6]);
-    const void *da, *db; void *oa, *ob;
-    int rc = stage_in(c, SLOT_IN0, in_a, (size_t)n * 8, loc, &da); if (rc) return rc;
-    rc = stage_in(c, SLOT_IN1, in_b, (size_t)n * 8, loc, &db); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, out_a, (size_t)n * 8, loc, &oa); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT1, out_b, (size_t)n * 8, loc, &ob); if (rc) return rc;
-    hipLaunchKernelGGL(tm_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, T, direction, (const double*)da, (const double*)db, n,
-                       (double*)oa, (double*)ob);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, out_a, oa, (size_t)n * 8, loc); if (rc) return rc;
-    rc = finish_out(c, out_b, ob, (size_t)n * 8, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    Staged S(c, loc);
+    const double *da = S.in(in_a, (size_t)n * 8), *db = S.in(in_b, (size_t)n * 8);
+    double *oa = S.out(out_a, (size_t)n * 8), *ob = S.out(out_b, (size_t)n * 8);
+    if (S.rc) return S.rc;
+    hipLaunchKernelGGL(tm_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, T, direction, da, db, n, oa, ob);
+    return S.finish();
 }
 
 // ---- output grids in a projected CRS (transformPoints of delay.py:207-209,262-263 on the (ny, nx) meshgrid) -------------------------
@@ -1061,19 +1104,15 @@ int rdr_grid_geodetic(rdr_ctx* c, int grid_kind, const double* params, int npara
     const int64_t n = nx * ny;
     if (n == 0) return RDR_OK;
     HIPCHECK(c, hipSetDevice(c->device));
-    const void *dx, *dy; void *t, *ola, *olo;
-    rc = stage_in(c, SLOT_IN0, xpts, (size_t)nx * 8, loc, &dx); if (rc) return rc;
-    rc = stage_in(c, SLOT_IN1, ypts, (size_t)ny * 8, loc, &dy); if (rc) return rc;
-    rc = ensure(c, SLOT_IN2, (size_t)n * 16, &t); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, lat, (size_t)n * 8, loc, &ola); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT1, lon, (size_t)n * 8, loc, &olo); if (rc) return rc;
+    Staged S(c, loc);
+    const double *dx = S.in(xpts, (size_t)nx * 8), *dy = S.in(ypts, (size_t)ny * 8);
+    double* t = S.scratch<double>(SLOT_IN2, (size_t)n * 16);
+    double *ola = S.out(lat, (size_t)n * 8), *olo = S.out(lon, (size_t)n * 8);
+    if (S.rc) return S.rc;
     const double *oy, *ox;
-    rc = grid_nodes(c, g, (const double*)dx, nx, (const double*)dy, ny, nullptr, (double*)t, (double*)t + n, (double*)ola, (double*)olo, &oy, &ox);
+    rc = grid_nodes(c, g, dx, nx, dy, ny, nullptr, t, t + n, ola, olo, &oy, &ox);
     if (rc) return rc;
-    rc = finish_out(c, lat, ola, (size_t)n * 8, loc); if (rc) return rc;
-    rc = finish_out(c, lon, olo, (size_t)n * 8, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    return S.finish();
 }
 
 // the same shape, dtype and axis vectors: what the two-epoch blends and the blended point gathers ask of their cubes
@@ -1140,16 +1179,16 @@ int rdr_inverse_time_weights(rdr_ctx* c, const double* az, int64_t n, const doub
     if (n < 0) return fail(c, RDR_ERR_INVALID, "rdr_inverse_time_weights: negative count");
     if (n == 0) return RDR_OK;
     HIPCHECK(c, hipSetDevice(c->device));
-    const void* da; void* dw;
-    int rc = stage_in(c, SLOT_IN0, az, (size_t)n * 8, loc, &da); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, weights, (size_t)n * nd * 8, loc, &dw); if (rc) return rc;
+    Staged S(c, loc);
+    const double* da = S.in(az, (size_t)n * 8);
+    double* dw = S.out(weights, (size_t)n * nd * 8);
+    if (S.rc) return S.rc;
     HIPCHECK(c, hipMemsetAsync(c->d_flags, 0, sizeof(int), c->stream));
-    hipLaunchKernelGGL(time_weights_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, D, (const double*)da, n, (double*)dw, c->d_flags);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, weights, dw, (size_t)n * nd * 8, loc); if (rc) return rc;
+    hipLaunchKernelGGL(time_weights_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, D, da, n, dw, c->d_flags);
     int f = 0;
     HIPCHECK(c, hipMemcpyAsync(&f, c->d_flags, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    const int rc = S.finish(true);                       // (always waits: the flag is read here)
+    if (rc) return rc;
     if (!f) return fail(c, RDR_ERR_INVALID, "No dates provided are within temporal window");
     return RDR_OK;
 }
@@ -1212,22 +1251,17 @@ int rdr_delays_to_phase(rdr_ctx* c, const void* wet, const void* hydro, int64_t 
     if (n == 0) return RDR_OK;
     HIPCHECK(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)n * (dtype == RDR_F32 ? 4 : 8);
-    const void *dw, *dh; void *ow, *oh;
-    int rc = stage_in(c, SLOT_IN0, wet, bytes, loc, &dw); if (rc) return rc;
-    rc = stage_in(c, SLOT_IN1, hydro, bytes, loc, &dh); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, wet_out, bytes, loc, &ow); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT1, hydro_out, bytes, loc, &oh); if (rc) return rc;
+    Staged S(c, loc);
+    const void *dw = S.in(wet, bytes), *dh = S.in(hydro, bytes);
+    void *ow = S.out(wet_out, bytes), *oh = S.out(hydro_out, bytes);
+    if (S.rc) return S.rc;
     const double phase2range = (-4.0 * 3.141592653589793) / wavelength;       // calcGUNW.py:54
     const int g = grid_for(n, 256, c->num_cus * 8);
     if (dtype == RDR_F32)
         hipLaunchKernelGGL(phase_kernel<float>, dim3(g), dim3(256), 0, c->stream, (const float*)dw, (const float*)dh, n, (float)phase2range, (float*)ow, (float*)oh);
     else
         hipLaunchKernelGGL(phase_kernel<double>, dim3(g), dim3(256), 0, c->stream, (const double*)dw, (const double*)dh, n, phase2range, (double*)ow, (double*)oh);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, wet_out, ow, bytes, loc); if (rc) return rc;
-    rc = finish_out(c, hydro_out, oh, bytes, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    return S.finish();
 }
 
 int rdr_cube_read(rdr_ctx* c, const rdr_cube* q, void* wet, void* hydro) {
@@ -1800,17 +1834,12 @@ static int project_impl(rdr_ctx* c, const char* who, double* wet, double* hydro,
     if (n < 0) return fail(c, RDR_ERR_INVALID, std::string(who) + ": negative count");
     if (n == 0) return RDR_OK;
     HIPCHECK(c, hipSetDevice(c->device));
-    const void *di, *dwi = nullptr, *dhi = nullptr;
-    int rc = stage_in(c, SLOT_IN0, proj, (size_t)n * 8, loc, &di); if (rc) return rc;
-    if (wet) { rc = stage_in(c, SLOT_OUT0, wet, (size_t)n * 8, loc, &dwi); if (rc) return rc; }
-    if (hydro) { rc = stage_in(c, SLOT_OUT1, hydro, (size_t)n * 8, loc, &dhi); if (rc) return rc; }
-    hipLaunchKernelGGL(project_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, (double*)dwi, (double*)dhi, pmode,
-                       (const double*)di, 0.0, n);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, wet, dwi, (size_t)n * 8, loc); if (rc) return rc;
-    rc = finish_out(c, hydro, dhi, (size_t)n * 8, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    Staged S(c, loc);
+    const double* di = S.in(proj, (size_t)n * 8);
+    double *dwi = S.inout(wet, (size_t)n * 8, SLOT_OUT0), *dhi = S.inout(hydro, (size_t)n * 8, SLOT_OUT1);   // divided in place
+    if (S.rc) return S.rc;
+    hipLaunchKernelGGL(project_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, dwi, dhi, pmode, di, 0.0, n);
+    return S.finish();
 }
 
 int rdr_project_cosinc(rdr_ctx* c, double* wet, double* hydro, const double* inc, int64_t n, int loc) {
@@ -3007,17 +3036,12 @@ int rdr_top_of_atmosphere(rdr_ctx* c, const double* xyz, const double* los, int6
     if (n < 0) return fail(c, RDR_ERR_INVALID, "rdr_top_of_atmosphere: negative count");
     if (n == 0) return RDR_OK;
     HIPCHECK(c, hipSetDevice(c->device));
-    const void *dx, *dl, *df; void* dp;
-    int rc = stage_in(c, SLOT_IN0, xyz, (size_t)n * 24, loc, &dx); if (rc) return rc;
-    rc = stage_in(c, SLOT_IN1, los, (size_t)n * 24, loc, &dl); if (rc) return rc;
-    rc = stage_in(c, SLOT_IN2, factor, (size_t)n * 8, loc, &df); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, pos, (size_t)n * 24, loc, &dp); if (rc) return rc;
-    hipLaunchKernelGGL(toa_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, (const double*)dx, (const double*)dl, n, h,
-                       (const double*)df, (double*)dp);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, pos, dp, (size_t)n * 24, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    Staged S(c, loc);
+    const double *dx = S.in(xyz, (size_t)n * 24), *dl = S.in(los, (size_t)n * 24), *df = S.in(factor, (size_t)n * 8);   // (factor is optional)
+    double* dp = S.out(pos, (size_t)n * 24);
+    if (S.rc) return S.rc;
+    hipLaunchKernelGGL(toa_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, dx, dl, n, h, df, dp);
+    return S.finish();
 }
 
 int rdr_build_ray(rdr_ctx* c, const double* model_zs, int64_t nz, double ht, const double* xyz, const double* los, int64_t n,
@@ -3032,24 +3056,14 @@ int rdr_build_ray(rdr_ctx* c, const double* model_zs, int64_t nz, double ht, con
     if (n < 0) return fail(c, RDR_ERR_INVALID, "rdr_build_ray: negative count");
     if (n == 0) return RDR_OK;
     HIPCHECK(c, hipSetDevice(c->device));
-    const void *dx, *dl; void *dlen, *dlo, *dhi, *dtab;
-    int rc = stage_in(c, SLOT_IN0, xyz, (size_t)n * 24, loc, &dx); if (rc) return rc;
-    rc = stage_in(c, SLOT_IN1, los, (size_t)n * 24, loc, &dl); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, lengths, (size_t)K * n * 8, loc, &dlen); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT1, low, (size_t)K * n * 24, loc, &dlo); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT2, high, (size_t)K * n * 24, loc, &dhi); if (rc) return rc;
-    rc = ensure(c, SLOT_AUX, (size_t)2 * K * 8, &dtab); if (rc) return rc;
-    std::vector<double> tab(lo); tab.insert(tab.end(), hi.begin(), hi.end());
-    HIPCHECK(c, hipMemcpyAsync(dtab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipStreamSynchronize(c->stream));
-    hipLaunchKernelGGL(build_ray_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, (const double*)dx, (const double*)dl, n, K,
-                       (const double*)dtab, (double*)dlen, (double*)dlo, (double*)dhi);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, lengths, dlen, (size_t)K * n * 8, loc); if (rc) return rc;
-    rc = finish_out(c, low, dlo, (size_t)K * n * 24, loc); if (rc) return rc;
-    rc = finish_out(c, high, dhi, (size_t)K * n * 24, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    Staged S(c, loc);
+    const double *dx = S.in(xyz, (size_t)n * 24), *dl = S.in(los, (size_t)n * 24);
+    double *dlen = S.out(lengths, (size_t)K * n * 8), *dlo = S.out(low, (size_t)K * n * 24), *dhi = S.out(high, (size_t)K * n * 24);
+    const HostPart tab[2] = {{lo.data(), (size_t)K * 8}, {hi.data(), (size_t)K * 8}};           // the level table: K lower | K upper bounds
+    const double* dtab = S.table<double>(SLOT_AUX, tab, 2);
+    if (S.rc) return S.rc;
+    hipLaunchKernelGGL(build_ray_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, dx, dl, n, K, dtab, dlen, dlo, dhi);
+    return S.finish();
 }
 
 // ---- geodesy ------------------------------------------------------------------------------------------
@@ -3058,17 +3072,12 @@ int rdr_lla2ecef(rdr_ctx* c, const double* lat, const double* lon, const double*
     if (n < 0) return fail(c, RDR_ERR_INVALID, "rdr_lla2ecef: negative count");
     if (n == 0) return RDR_OK;
     HIPCHECK(c, hipSetDevice(c->device));
-    const void *a, *b, *d; void* o;
-    int rc = stage_in(c, SLOT_IN0, lat, (size_t)n * 8, loc, &a); if (rc) return rc;
-    rc = stage_in(c, SLOT_IN1, lon, (size_t)n * 8, loc, &b); if (rc) return rc;
-    rc = stage_in(c, SLOT_IN2, h, (size_t)n * 8, loc, &d); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, xyz, (size_t)n * 24, loc, &o); if (rc) return rc;
-    hipLaunchKernelGGL(lla2ecef_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, (const double*)a, (const double*)b,
-                       (const double*)d, n, (double*)o);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, xyz, o, (size_t)n * 24, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    Staged S(c, loc);
+    const double *a = S.in(lat, (size_t)n * 8), *b = S.in(lon, (size_t)n * 8), *d = S.in(h, (size_t)n * 8);
+    double* o = S.out(xyz, (size_t)n * 24);
+    if (S.rc) return S.rc;
+    hipLaunchKernelGGL(lla2ecef_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, a, b, d, n, o);
+    return S.finish();
 }
 
 int rdr_ecef2lla(rdr_ctx* c, const double* xyz, int64_t n, double* lon, double* lat, double* h, int loc) {
@@ -3076,19 +3085,12 @@ int rdr_ecef2lla(rdr_ctx* c, const double* xyz, int64_t n, double* lon, double* 
     if (n < 0) return fail(c, RDR_ERR_INVALID, "rdr_ecef2lla: negative count");
     if (n == 0) return RDR_OK;
     HIPCHECK(c, hipSetDevice(c->device));
-    const void* a; void *o0, *o1, *o2;
-    int rc = stage_in(c, SLOT_IN0, xyz, (size_t)n * 24, loc, &a); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, lon, (size_t)n * 8, loc, &o0); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT1, lat, (size_t)n * 8, loc, &o1); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT2, h, (size_t)n * 8, loc, &o2); if (rc) return rc;
-    hipLaunchKernelGGL(ecef2lla_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, (const double*)a, n, (double*)o0,
-                       (double*)o1, (double*)o2);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, lon, o0, (size_t)n * 8, loc); if (rc) return rc;
-    rc = finish_out(c, lat, o1, (size_t)n * 8, loc); if (rc) return rc;
-    rc = finish_out(c, h, o2, (size_t)n * 8, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    Staged S(c, loc);
+    const double* a = S.in(xyz, (size_t)n * 24);
+    double *o0 = S.out(lon, (size_t)n * 8), *o1 = S.out(lat, (size_t)n * 8), *o2 = S.out(h, (size_t)n * 8);
+    if (S.rc) return S.rc;
+    hipLaunchKernelGGL(ecef2lla_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, a, n, o0, o1, o2);
+    return S.finish();
 }
 
 int rdr_look_vectors(rdr_ctx* c, const rdr_rays* r, double ht, double* los) {
@@ -3101,13 +3103,11 @@ int rdr_look_vectors(rdr_ctx* c, const rdr_rays* r, double ht, double* los) {
     HIPCHECK(c, hipSetDevice(c->device));
     RayParams P;
     rc = stage_rays(c, r, P); if (rc) return rc;
-    void* o;
-    rc = stage_out(c, SLOT_OUT0, los, (size_t)r->n * 24, r->loc, &o); if (rc) return rc;
-    hipLaunchKernelGGL(look_kernel, dim3(grid_for(r->n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, P, (double*)o);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, los, o, (size_t)r->n * 24, r->loc); if (rc) return rc;
-    if (r->loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    Staged S(c, r->loc);
+    double* o = S.out(los, (size_t)r->n * 24);
+    if (S.rc) return S.rc;
+    hipLaunchKernelGGL(look_kernel, dim3(grid_for(r->n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, P, o);
+    return S.finish();
 }
 
 int rdr_cubes_from_model_levels(rdr_ctx* c, const double* ys, int64_t ny, const double* xs, int64_t nx, const double* zs3, const double* p,
@@ -3184,27 +3184,17 @@ int rdr_ecmwf_model_levels(rdr_ctx* c, const float* z_surf, const float* lnsp, c
     HIPCHECK(c, hipSetDevice(c->device));
     const int64_t ncol = ny * nx;
     // the small tables (latitudes, a, b) always come from the host; the fields and the outputs follow `loc`
-    void* aux;
-    int rc = ensure(c, SLOT_AUX, (size_t)(2 * (nlev + 1)) * 8 + (size_t)ny * 4, &aux); if (rc) return rc;
-    double* da = (double*)aux; double* db = da + (nlev + 1); float* dl = (float*)(db + (nlev + 1));
-    HIPCHECK(c, hipMemcpyAsync(da, a, (size_t)(nlev + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(db, b, (size_t)(nlev + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(dl, lats, (size_t)ny * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipStreamSynchronize(c->stream));
-    const void *dz, *ds, *dt_, *dq; void *dp, *dh;
-    rc = stage_in(c, SLOT_IN0, z_surf, (size_t)ncol * 4, loc, &dz); if (rc) return rc;
-    rc = stage_in(c, SLOT_IN1, lnsp, (size_t)ncol * 4, loc, &ds); if (rc) return rc;
-    rc = stage_in(c, SLOT_IN2, t, (size_t)ncol * nlev * 4, loc, &dt_); if (rc) return rc;
-    rc = stage_in(c, SLOT_IN3, q, (size_t)ncol * nlev * 4, loc, &dq); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, p_out, (size_t)ncol * nlev * 8, loc, &dp); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT1, zs_out, (size_t)ncol * nlev * 8, loc, &dh); if (rc) return rc;
-    hipLaunchKernelGGL(ecmwf_levels_kernel, dim3(grid_for(ncol, 256, c->num_cus * 8)), dim3(256), 0, c->stream, (const float*)dz, (const float*)ds,
-                       (const float*)dt_, (const float*)dq, dl, da, db, (int)nlev, ny, nx, R_d, (double*)dp, (double*)dh);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, p_out, dp, (size_t)ncol * nlev * 8, loc); if (rc) return rc;
-    rc = finish_out(c, zs_out, dh, (size_t)ncol * nlev * 8, loc); if (rc) return rc;
-    HIPCHECK(c, hipStreamSynchronize(c->stream));       // the tables in SLOT_AUX must outlive the kernel
-    return RDR_OK;
+    Staged S(c, loc);
+    const HostPart tab[3] = {{a, (size_t)(nlev + 1) * 8}, {b, (size_t)(nlev + 1) * 8}, {lats, (size_t)ny * 4}};
+    const double* da = S.table<double>(SLOT_AUX, tab, 3);
+    const float *dz = S.in(z_surf, (size_t)ncol * 4), *ds = S.in(lnsp, (size_t)ncol * 4);
+    const float *dt_ = S.in(t, (size_t)ncol * nlev * 4), *dq = S.in(q, (size_t)ncol * nlev * 4);
+    double *dp = S.out(p_out, (size_t)ncol * nlev * 8), *dh = S.out(zs_out, (size_t)ncol * nlev * 8);
+    if (S.rc) return S.rc;
+    const double* db = da + (nlev + 1); const float* dl = (const float*)(db + (nlev + 1));
+    hipLaunchKernelGGL(ecmwf_levels_kernel, dim3(grid_for(ncol, 256, c->num_cus * 8)), dim3(256), 0, c->stream, dz, ds, dt_, dq, dl, da, db, (int)nlev, ny, nx,
+                       R_d, dp, dh);
+    return S.finish(true);                              // (always waits: the tables in SLOT_AUX must outlive the kernel)
 }
 
 int rdr_pressure_level_state(rdr_ctx* c, const double* height, int height_kind, const double* p, int p_ndim, const double* t, const double* hum,
@@ -3224,31 +3214,21 @@ int rdr_pressure_level_state(rdr_ctx* c, const double* height, int height_kind, 
     HIPCHECK(c, hipSetDevice(c->device));
     const size_t nb = (size_t)nlev * ny * nx * 8;
     PressureLevelParams P;
-    const void* d;
-    int rc;
-    rc = stage_in(c, SLOT_IN0, height, nb, loc, &d); if (rc) return rc; P.height = (const double*)d;
-    rc = stage_in(c, SLOT_IN1, p, p_ndim == 3 ? nb : (size_t)nlev * 8, loc, &d); if (rc) return rc; P.p = (const double*)d;
-    rc = stage_in(c, SLOT_IN2, t, nb, loc, &d); if (rc) return rc; P.t = (const double*)d;
-    rc = stage_in(c, SLOT_IN3, hum, nb, loc, &d); if (rc) return rc; P.hum = (const double*)d;
-    rc = stage_in(c, SLOT_IN4, lats, (size_t)ny * (lat_ndim == 2 ? nx : 1) * 8, loc, &d); if (rc) return rc; P.lats = (const double*)d;
-    void *dz, *dp, *dt_, *dh;
-    rc = stage_out(c, SLOT_OUT0, zs_out, nb, out_loc, &dz); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT1, p_out, nb, out_loc, &dp); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT2, t_out, nb, out_loc, &dt_); if (rc) return rc;
-    rc = stage_out(c, SLOT_AUX, hum_out, nb, out_loc, &dh); if (rc) return rc;
+    Staged S(c, loc, out_loc);
+    P.height = S.in(height, nb);
+    P.p = S.in(p, p_ndim == 3 ? nb : (size_t)nlev * 8);
+    P.t = S.in(t, nb);
+    P.hum = S.in(hum, nb);
+    P.lats = S.in(lats, (size_t)ny * (lat_ndim == 2 ? nx : 1) * 8);
+    P.zs_out = S.out(zs_out, nb); P.p_out = S.out(p_out, nb); P.t_out = S.out(t_out, nb);
+    P.hum_out = S.out(hum_out, nb, SLOT_AUX);            // (a fourth output: there are three output slots)
+    if (S.rc) return S.rc;
     P.nlev = nlev; P.ny = ny; P.nx = nx;
     P.height_kind = height_kind; P.p_3d = p_ndim == 3; P.lat_2d = lat_ndim == 2;
     P.top_first = top_first; P.flip_rows = rows_descending; P.flip_cols = cols_descending;
-    P.zs_out = (double*)dz; P.p_out = (double*)dp; P.t_out = (double*)dt_; P.hum_out = (double*)dh;
     const int64_t ntiles = ny * ((nx + 31) / 32) * ((nlev + 31) / 32);
     hipLaunchKernelGGL(pressure_levels_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)c->num_cus * 16))), dim3(256), 0, c->stream, P);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, zs_out, dz, nb, out_loc); if (rc) return rc;
-    rc = finish_out(c, p_out, dp, nb, out_loc); if (rc) return rc;
-    rc = finish_out(c, t_out, dt_, nb, out_loc); if (rc) return rc;
-    rc = finish_out(c, hum_out, dh, nb, out_loc); if (rc) return rc;
-    if (out_loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    return S.finish();
 }
 
 int rdr_orbit_look_vectors(rdr_ctx* c, const double* sv_t, const double* sv_pos, const double* sv_vel, int64_t nsv, const double* xyz,
@@ -3260,33 +3240,23 @@ int rdr_orbit_look_vectors(rdr_ctx* c, const double* sv_t, const double* sv_pos,
     if (n == 0) return RDR_OK;
     HIPCHECK(c, hipSetDevice(c->device));
     // the (small) state-vector table always comes from the host; targets / outputs follow `loc`
-    void* dtab;
-    int rc = ensure(c, SLOT_AUX, (size_t)nsv * 7 * 8, &dtab); if (rc) return rc;
-    double* dt_ = (double*)dtab; double* dp_ = dt_ + nsv; double* dv_ = dp_ + 3 * nsv;
-    HIPCHECK(c, hipMemcpyAsync(dt_, sv_t, (size_t)nsv * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(dp_, sv_pos, (size_t)nsv * 24, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(dv_, sv_vel, (size_t)nsv * 24, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipStreamSynchronize(c->stream));
-    const void* dx; void *dl, *da = nullptr, *dr = nullptr;
-    rc = stage_in(c, SLOT_IN0, xyz, (size_t)n * 24, loc, &dx); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, los, (size_t)n * 24, loc, &dl); if (rc) return rc;
-    if (aztime) { rc = stage_out(c, SLOT_OUT1, aztime, (size_t)n * 8, loc, &da); if (rc) return rc; }
-    if (srange) { rc = stage_out(c, SLOT_OUT2, srange, (size_t)n * 8, loc, &dr); if (rc) return rc; }
+    Staged S(c, loc);
+    const HostPart tab[3] = {{sv_t, (size_t)nsv * 8}, {sv_pos, (size_t)nsv * 24}, {sv_vel, (size_t)nsv * 24}};
+    double* dt_ = S.table<double>(SLOT_AUX, tab, 3);
+    const double* dx = S.in(xyz, (size_t)n * 24);
+    double *dl = S.out(los, (size_t)n * 24), *da = S.out(aztime, (size_t)n * 8), *dr = S.out(srange, (size_t)n * 8);   // (aztime, srange: optional)
+    if (S.rc) return S.rc;
+    double* dp_ = dt_ + nsv; double* dv_ = dp_ + 3 * nsv;
     if (nsv <= ORBIT_LDS_MAX_SV) {
         // state vectors + per-segment reciprocals in LDS, division-free Hermite evaluation (orbit_los_fast_kernel)
         const size_t smem = ((size_t)nsv * 7 + (size_t)(nsv - 3) * 16) * sizeof(double);
         hipLaunchKernelGGL(orbit_los_fast_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), smem, c->stream, dt_, dp_, dv_, (int)nsv,
-                           (const double*)dx, n, threshold, maxiter, (double*)dl, (double*)da, (double*)dr);
+                           dx, n, threshold, maxiter, dl, da, dr);
     } else {
         hipLaunchKernelGGL(orbit_los_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, dt_, dp_, dv_, (int)nsv,
-                           (const double*)dx, n, threshold, maxiter, (double*)dl, (double*)da, (double*)dr);
+                           dx, n, threshold, maxiter, dl, da, dr);
     }
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, los, dl, (size_t)n * 24, loc); if (rc) return rc;
-    if (aztime) { rc = finish_out(c, aztime, da, (size_t)n * 8, loc); if (rc) return rc; }
-    if (srange) { rc = finish_out(c, srange, dr, (size_t)n * 8, loc); if (rc) return rc; }
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    return S.finish();
 }
 
 // ---- azimuth-time-grid combination in one pass (aztime_kernels.h) ------------------------------------------------------------------
@@ -3415,24 +3385,27 @@ int rdr_interp_nd(rdr_ctx* c, int32_t ndim, const double* const* axes, const int
     int64_t s = 1;
     for (int d = ndim - 1; d >= 0; --d) { P.stride[d] = s; s *= axis_len[d]; }
     // axes are always host-side tuples of small 1-D arrays in the reference API; accept device too
-    void* dax;
-    int rc = ensure(c, SLOT_AUX, (size_t)tot_axes * 8, &dax); if (rc) return rc;
-    for (int d = 0; d < ndim; ++d)
-        HIPCHECK(c, hipMemcpyAsync((double*)dax + P.off[d], axes[d], (size_t)axis_len[d] * 8,
-                                   loc == RDR_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
-    const void *dv, *dq; void* dout;
-    rc = stage_in(c, SLOT_IN0, values, (size_t)nvals * 8, loc, &dv); if (rc) return rc;
-    rc = stage_in(c, SLOT_IN1, q, (size_t)n * ndim * 8, loc, &dq); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, out, (size_t)n * 8, loc, &dout); if (rc) return rc;
+    Staged S(c, loc);
+    double* dax;
+    if (loc == RDR_HOST) {
+        HostPart tab[8];
+        for (int d = 0; d < ndim; ++d) tab[d] = HostPart{axes[d], (size_t)axis_len[d] * 8};
+        dax = S.table<double>(SLOT_AUX, tab, ndim);
+    } else {
+        dax = S.scratch<double>(SLOT_AUX, (size_t)tot_axes * 8);
+        if (S.rc) return S.rc;
+        for (int d = 0; d < ndim; ++d)
+            HIPCHECK(c, hipMemcpyAsync(dax + P.off[d], axes[d], (size_t)axis_len[d] * 8, hipMemcpyDeviceToDevice, c->stream));
+    }
+    const double *dv = S.in(values, (size_t)nvals * 8), *dq = S.in(q, (size_t)n * ndim * 8);
+    double* dout = S.out(out, (size_t)n * 8);
+    if (S.rc) return S.rc;
     {
         KTimer t(c, 2);
-        hipLaunchKernelGGL(interp_nd_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, P, (const double*)dax,
-                           (const double*)dv, (const double*)dq, n, has_fill, fill, (double*)dout);
+        hipLaunchKernelGGL(interp_nd_kernel, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream, P, (const double*)dax, dv, dq, n, has_fill, fill,
+                           dout);
     }
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, out, dout, (size_t)n * 8, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    return S.finish();
 }
 
 int rdr_interp_along_axis(rdr_ctx* c, const double* points, const double* values, int64_t ncol, int64_t m, const double* q,
@@ -3442,17 +3415,12 @@ int rdr_interp_along_axis(rdr_ctx* c, const double* points, const double* values
     if (ncol < 0 || mq < 0) return fail(c, RDR_ERR_INVALID, "rdr_interp_along_axis: negative count");
     if (ncol * mq == 0) return RDR_OK;
     HIPCHECK(c, hipSetDevice(c->device));
-    const void *dp, *dv, *dq; void* dout;
-    int rc = stage_in(c, SLOT_IN0, points, (size_t)ncol * m * 8, loc, &dp); if (rc) return rc;
-    rc = stage_in(c, SLOT_IN1, values, (size_t)ncol * m * 8, loc, &dv); if (rc) return rc;
-    rc = stage_in(c, SLOT_IN2, q, (size_t)ncol * mq * 8, loc, &dq); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, out, (size_t)ncol * mq * 8, loc, &dout); if (rc) return rc;
-    hipLaunchKernelGGL(along_axis_kernel, dim3(grid_for(ncol * mq, 256, c->num_cus * 8)), dim3(256), 0, c->stream, (const double*)dp,
-                       (const double*)dv, ncol, m, (const double*)dq, mq, has_fill, fill, (double*)dout);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, out, dout, (size_t)ncol * mq * 8, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    Staged S(c, loc);
+    const double *dp = S.in(points, (size_t)ncol * m * 8), *dv = S.in(values, (size_t)ncol * m * 8), *dq = S.in(q, (size_t)ncol * mq * 8);
+    double* dout = S.out(out, (size_t)ncol * mq * 8);
+    if (S.rc) return S.rc;
+    hipLaunchKernelGGL(along_axis_kernel, dim3(grid_for(ncol * mq, 256, c->num_cus * 8)), dim3(256), 0, c->stream, dp, dv, ncol, m, dq, mq, has_fill, fill, dout);
+    return S.finish();
 }
 
 int64_t rdr_make_points_count(double max_len, double step) {
@@ -3472,19 +3440,15 @@ int rdr_make_points(rdr_ctx* c, double max_len, const double* sp, const double* 
     if (nrays < 0) return fail(c, RDR_ERR_INVALID, "rdr_make_points: negative count");
     if (nrays * npts == 0) return RDR_OK;
     HIPCHECK(c, hipSetDevice(c->device));
-    const void *ds, *dl; void* dout;
-    int rc = stage_in(c, SLOT_IN0, sp, (size_t)nrays * 24, loc, &ds); if (rc) return rc;
-    rc = stage_in(c, SLOT_IN1, slv, (size_t)nrays * 24, loc, &dl); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, out, (size_t)nrays * 3 * npts * 8, loc, &dout); if (rc) return rc;
+    Staged S(c, loc);
+    const double *ds = S.in(sp, (size_t)nrays * 24), *dl = S.in(slv, (size_t)nrays * 24);
+    double* dout = S.out(out, (size_t)nrays * 3 * npts * 8);
+    if (S.rc) return S.rc;
     {
         KTimer t(c, 3);
-        hipLaunchKernelGGL(make_points_kernel, dim3(grid_for(nrays * 3 * npts, 256, c->num_cus * 8)), dim3(256), 0, c->stream,
-                           (const double*)ds, (const double*)dl, nrays, npts, step, (double*)dout);
+        hipLaunchKernelGGL(make_points_kernel, dim3(grid_for(nrays * 3 * npts, 256, c->num_cus * 8)), dim3(256), 0, c->stream, ds, dl, nrays, npts, step, dout);
     }
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, out, dout, (size_t)nrays * 3 * npts * 8, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    return S.finish();
 }
 
 
@@ -3519,18 +3483,15 @@ int rdr_raster_sample(rdr_ctx* c, const void* raster, int dtype, int64_t height,
     if (method == RASTER_LINEAR && (height < 2 || width < 2)) return fail(c, RDR_ERR_INVALID, "rdr_raster_sample: linear sampling needs two pixels per axis");
     HIPCHECK(c, hipSetDevice(c->device));
     const RasterGeo g{height, width, gt6[0], gt6[1], gt6[3], gt6[5]};
-    const void *dr, *dx, *dy; void* dout;
-    int rc = stage_in(c, SLOT_IN0, raster, (size_t)(height * width) * esize, loc, &dr); if (rc) return rc;
-    rc = stage_in(c, SLOT_IN1, x, (size_t)n * 8, loc, &dx); if (rc) return rc;
-    rc = stage_in(c, SLOT_IN2, y, (size_t)n * 8, loc, &dy); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, out, (size_t)n * 8, loc, &dout); if (rc) return rc;
-    if (dtype == RDR_I16) launch_raster_sample<int16_t>(c, method, dr, g, (const double*)dx, (const double*)dy, n, has_nodata != 0, nodata, (double*)dout);
-    else if (dtype == RDR_F32) launch_raster_sample<float>(c, method, dr, g, (const double*)dx, (const double*)dy, n, has_nodata != 0, nodata, (double*)dout);
-    else launch_raster_sample<double>(c, method, dr, g, (const double*)dx, (const double*)dy, n, has_nodata != 0, nodata, (double*)dout);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, out, dout, (size_t)n * 8, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    Staged S(c, loc);
+    const void* dr = S.in(raster, (size_t)(height * width) * esize);
+    const double *dx = S.in(x, (size_t)n * 8), *dy = S.in(y, (size_t)n * 8);
+    double* dout = S.out(out, (size_t)n * 8);
+    if (S.rc) return S.rc;
+    if (dtype == RDR_I16) launch_raster_sample<int16_t>(c, method, dr, g, dx, dy, n, has_nodata != 0, nodata, dout);
+    else if (dtype == RDR_F32) launch_raster_sample<float>(c, method, dr, g, dx, dy, n, has_nodata != 0, nodata, dout);
+    else launch_raster_sample<double>(c, method, dr, g, dx, dy, n, has_nodata != 0, nodata, dout);
+    return S.finish();
 }
 
 template <typename T>
@@ -3545,63 +3506,73 @@ int rdr_raster_bounds(rdr_ctx* c, const void* a, const void* b, int dtype, int64
     if (n <= 0 || n > ((int64_t)1 << 40)) return fail(c, RDR_ERR_INVALID, "rdr_raster_bounds: the element count must be positive (at most 2^40)");
     if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, "rdr_raster_bounds: loc must be RDR_HOST or RDR_DEVICE");
     HIPCHECK(c, hipSetDevice(c->device));
-    const void *da, *db; void *dpart, *dout;
-    int rc = stage_in(c, SLOT_IN0, a, (size_t)n * esize, loc, &da); if (rc) return rc;
-    rc = stage_in(c, SLOT_IN1, b, (size_t)n * esize, loc, &db); if (rc) return rc;
+    Staged S(c, loc);
+    const void *da = S.in(a, (size_t)n * esize), *db = S.in(b, (size_t)n * esize);       // (b is optional)
     // one lane takes 16 bytes per step; the grid is sized from the compute-unit count and strides over the rest
     const int grid = grid_for((n * esize + 15) / 16, 256, c->num_cus * 8);
-    rc = ensure(c, SLOT_AUX, (size_t)grid * 6 * 8, &dpart); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, out6, 6 * 8, loc, &dout); if (rc) return rc;
+    double* dpart = S.scratch<double>(SLOT_AUX, (size_t)grid * 6 * 8);
+    double* dout = S.out(out6, 6 * 8);
+    if (S.rc) return S.rc;
     {
         KTimer t(c, 3);
-        if (dtype == RDR_I16) launch_raster_bounds<int16_t>(c, grid, da, db, n, has_nodata != 0, nodata, (double*)dpart);
-        else if (dtype == RDR_F32) launch_raster_bounds<float>(c, grid, da, db, n, has_nodata != 0, nodata, (double*)dpart);
-        else launch_raster_bounds<double>(c, grid, da, db, n, has_nodata != 0, nodata, (double*)dpart);
-        hipLaunchKernelGGL(raster_bounds_final_kernel, dim3(1), dim3(256), 0, c->stream, (const double*)dpart, grid, (double*)dout);
+        if (dtype == RDR_I16) launch_raster_bounds<int16_t>(c, grid, da, db, n, has_nodata != 0, nodata, dpart);
+        else if (dtype == RDR_F32) launch_raster_bounds<float>(c, grid, da, db, n, has_nodata != 0, nodata, dpart);
+        else launch_raster_bounds<double>(c, grid, da, db, n, has_nodata != 0, nodata, dpart);
+        hipLaunchKernelGGL(raster_bounds_final_kernel, dim3(1), dim3(256), 0, c->stream, (const double*)dpart, grid, dout);
     }
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, out6, dout, 6 * 8, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    return S.finish();
 }
 
 
 // ---- GeoTIFF segments (tiff_kernels.h): LZW decoding and raster assembly -----------------------------------------------------------
-int rdr_tiff_lzw_decode(rdr_ctx* c, const void* src, int64_t src_bytes, const int64_t* seg_offset, const int64_t* seg_bytes, int64_t nseg,
-                        const int64_t* seg_out_bytes, void* out, int64_t out_stride, int32_t* status, int loc) {
-    if (!c || !src || !seg_offset || !seg_bytes || !seg_out_bytes || !out || !status) return fail(c, RDR_ERR_INVALID, "rdr_tiff_lzw_decode: NULL argument");
-    if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, "rdr_tiff_lzw_decode: loc must be RDR_HOST or RDR_DEVICE");
-    if (src_bytes <= 0 || nseg <= 0 || nseg > (1 << 24)) return fail(c, RDR_ERR_INVALID, "rdr_tiff_lzw_decode: need a non-empty buffer and 1 .. 2^24 segments");
+// The shared check of a segment table's entry: `bytes` bytes at `off` lie inside a source buffer of `src_bytes` (decoders and the encoder)
+static int segment_in_source(rdr_ctx* c, const std::string& w, int64_t i, int64_t off, int64_t bytes, int64_t src_bytes) {
+    if (off < 0 || bytes < 0 || off > src_bytes || bytes > src_bytes - off)
+        return fail(c, RDR_ERR_INVALID, w + ": segment " + std::to_string(i) + " does not lie inside the source buffer");
+    return RDR_OK;
+}
+
+// One driver for the two segment decoders (LZW strips / tiles, zlib streams): segment i of `src` is decoded into out + i * out_stride, one
+// wave per segment.  `launch(grid, src, tab, out, status, produced)` starts the kernel; tab = offsets | bytes | out bytes, nseg each.
+template <typename Launch>
+static int decode_segments(rdr_ctx* c, const char* who, const void* src, int64_t src_bytes, const int64_t* seg_offset, const int64_t* seg_bytes, int64_t nseg,
+                           const int64_t* seg_out_bytes, void* out, int64_t out_stride, int32_t* status, int64_t* produced, int loc, int per_cu,
+                           Launch&& launch) {
+    const std::string w(who);
+    if (!c || !src || !seg_offset || !seg_bytes || !seg_out_bytes || !out || !status) return fail(c, RDR_ERR_INVALID, w + ": NULL argument");
+    if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, w + ": loc must be RDR_HOST or RDR_DEVICE");
+    if (src_bytes <= 0 || nseg <= 0 || nseg > (1 << 24)) return fail(c, RDR_ERR_INVALID, w + ": need a non-empty buffer and 1 .. 2^24 segments");
     if (out_stride <= 0 || out_stride > ((int64_t)1 << 31) - 256 || nseg * out_stride > ((int64_t)1 << 40))
-        return fail(c, RDR_ERR_INVALID, "rdr_tiff_lzw_decode: out_stride must be positive and below 2 GiB (at most 2^40 bytes in all)");
+        return fail(c, RDR_ERR_INVALID, w + ": out_stride must be positive and below 2 GiB (at most 2^40 bytes in all)");
     for (int64_t i = 0; i < nseg; ++i) {
-        if (seg_offset[i] < 0 || seg_bytes[i] < 0 || seg_offset[i] > src_bytes || seg_bytes[i] > src_bytes - seg_offset[i])
-            return fail(c, RDR_ERR_INVALID, "rdr_tiff_lzw_decode: segment " + std::to_string(i) + " does not lie inside the source buffer");
-        if (seg_bytes[i] >= ((int64_t)1 << 31) - 256) return fail(c, RDR_ERR_INVALID, "rdr_tiff_lzw_decode: segment " + std::to_string(i) + " is 2 GiB or longer");
+        const int rc = segment_in_source(c, w, i, seg_offset[i], seg_bytes[i], src_bytes); if (rc) return rc;
+        if (seg_bytes[i] >= ((int64_t)1 << 31) - 256) return fail(c, RDR_ERR_INVALID, w + ": segment " + std::to_string(i) + " is 2 GiB or longer");
         if (seg_out_bytes[i] < 0 || seg_out_bytes[i] > out_stride)
-            return fail(c, RDR_ERR_INVALID, "rdr_tiff_lzw_decode: segment " + std::to_string(i) + " would write beyond its slot of out_stride bytes");
+            return fail(c, RDR_ERR_INVALID, w + ": segment " + std::to_string(i) + " would write beyond its slot of out_stride bytes");
     }
     HIPCHECK(c, hipSetDevice(c->device));
-    const void* dsrc; void *dtab, *dout, *dstat;
-    int rc = stage_in(c, SLOT_IN0, src, (size_t)src_bytes, loc, &dsrc); if (rc) return rc;
-    rc = ensure(c, SLOT_IN1, (size_t)nseg * 24, &dtab); if (rc) return rc;
-    int64_t* tab = (int64_t*)dtab;                            // the three tables are host arrays whatever `loc` says: offsets | bytes | out bytes
-    rc = upload(c, tab, seg_offset, (size_t)nseg * 8); if (rc) return rc;
-    rc = upload(c, tab + nseg, seg_bytes, (size_t)nseg * 8); if (rc) return rc;
-    rc = upload(c, tab + 2 * nseg, seg_out_bytes, (size_t)nseg * 8); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, out, (size_t)(nseg * out_stride), loc, &dout); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT1, status, (size_t)nseg * 4, loc, &dstat); if (rc) return rc;
+    Staged S(c, loc);
+    const uint8_t* dsrc = S.in(static_cast<const uint8_t*>(src), (size_t)src_bytes);
+    const HostPart tabs[3] = {{seg_offset, (size_t)nseg * 8}, {seg_bytes, (size_t)nseg * 8}, {seg_out_bytes, (size_t)nseg * 8}};
+    const int64_t* tab = S.table<int64_t>(SLOT_IN1, tabs, 3);   // the three tables are host arrays whatever `loc` says
+    uint8_t* dout = S.out(static_cast<uint8_t*>(out), (size_t)(nseg * out_stride));
+    int32_t* dstat = S.out(status, (size_t)nseg * 4);
+    int64_t* dprod = S.out(produced, (size_t)nseg * 8);         // (optional)
+    if (S.rc) return S.rc;
     // bytes of a slot the stream does not reach keep their value: a host `out` goes up first
-    if (loc == RDR_HOST) { rc = upload(c, dout, out, (size_t)(nseg * out_stride)); if (rc) return rc; }
-    // one wave per segment; a compute unit holds five of these 29 KB workgroups, the grid strides over the rest
-    const int grid = (int)std::min<int64_t>(nseg, (int64_t)c->num_cus * 5);
-    hipLaunchKernelGGL(tiff_lzw_kernel, dim3(grid), dim3(64), 0, c->stream, (const uint8_t*)dsrc, src_bytes, (const int64_t*)tab, (const int64_t*)(tab + nseg),
-                       (const int64_t*)(tab + 2 * nseg), (int)nseg, (uint8_t*)dout, out_stride, (int32_t*)dstat);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, out, dout, (size_t)(nseg * out_stride), loc); if (rc) return rc;
-    rc = finish_out(c, status, dstat, (size_t)nseg * 4, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    if (loc == RDR_HOST) { const int rc = upload(c, dout, out, (size_t)(nseg * out_stride)); if (rc) return rc; }
+    // one wave per segment; a compute unit holds `per_cu` of the kernel's workgroups (by their LDS), the grid strides over the rest
+    launch((int)std::min<int64_t>(nseg, (int64_t)c->num_cus * per_cu), dsrc, tab, dout, dstat, dprod);
+    return S.finish();
+}
+
+int rdr_tiff_lzw_decode(rdr_ctx* c, const void* src, int64_t src_bytes, const int64_t* seg_offset, const int64_t* seg_bytes, int64_t nseg,
+                        const int64_t* seg_out_bytes, void* out, int64_t out_stride, int32_t* status, int loc) {
+    // five of the 29 KB workgroups per compute unit
+    return decode_segments(c, "rdr_tiff_lzw_decode", src, src_bytes, seg_offset, seg_bytes, nseg, seg_out_bytes, out, out_stride, status, nullptr, loc, 5,
+                           [&](int grid, const uint8_t* dsrc, const int64_t* tab, uint8_t* dout, int32_t* dstat, int64_t*) {
+        hipLaunchKernelGGL(tiff_lzw_kernel, dim3(grid), dim3(64), 0, c->stream, dsrc, src_bytes, tab, tab + nseg, tab + 2 * nseg, (int)nseg, dout, out_stride, dstat);
+    });
 }
 
 int rdr_tiff_assemble(rdr_ctx* c, const void* segs, int64_t seg_stride, int64_t height, int64_t width, int64_t tile_h, int64_t tile_w, int predictor,
@@ -3623,10 +3594,11 @@ int rdr_tiff_assemble(rdr_ctx* c, const void* segs, int64_t seg_stride, int64_t 
     const int64_t nsegs = tiles_x * tiles_y * nplanes, nout = band < 0 ? bands : 1;
     if (nsegs > ((int64_t)1 << 42) / seg_stride || nout * height * width > ((int64_t)1 << 40)) return fail(c, RDR_ERR_INVALID, "rdr_tiff_assemble: the raster is beyond 2^40 samples");
     HIPCHECK(c, hipSetDevice(c->device));
-    const void* dsegs; void* dout;
     const size_t out_bytes = (size_t)(nout * height * width) * sample_bytes;
-    int rc = stage_in(c, SLOT_IN0, segs, (size_t)(nsegs * seg_stride), loc, &dsegs); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, out, out_bytes, loc, &dout); if (rc) return rc;
+    Staged S(c, loc);
+    const void* dsegs = S.in(segs, (size_t)(nsegs * seg_stride));
+    void* dout = S.out(out, out_bytes);
+    if (S.rc) return S.rc;
     if ((reinterpret_cast<uintptr_t>(dsegs) | reinterpret_cast<uintptr_t>(dout)) % sample_bytes != 0) return fail(c, RDR_ERR_INVALID, "rdr_tiff_assemble: buffers must be aligned to the sample size");
     if (predictor == 1 && !swap && tiles_x == 1 && tiles_y == 1 && tile_w == width && (bands == 1 || planar == 2)) {
         // one strip (per plane) that is the raster already: a copy per output band
@@ -3641,11 +3613,8 @@ int rdr_tiff_assemble(rdr_ctx* c, const void* segs, int64_t seg_stride, int64_t 
         else if (sample_bytes == 2) hipLaunchKernelGGL(tiff_assemble_kernel<uint16_t>, G, B, 0, c->stream, (const uint8_t*)dsegs, L, (uint16_t*)dout);
         else if (sample_bytes == 4) hipLaunchKernelGGL(tiff_assemble_kernel<uint32_t>, G, B, 0, c->stream, (const uint8_t*)dsegs, L, (uint32_t*)dout);
         else hipLaunchKernelGGL(tiff_assemble_kernel<uint64_t>, G, B, 0, c->stream, (const uint8_t*)dsegs, L, (uint64_t*)dout);
-        HIPCHECK(c, hipGetLastError());
     }
-    rc = finish_out(c, out, dout, out_bytes, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    return S.finish();
 }
 
 
@@ -3665,8 +3634,7 @@ int rdr_deflate_encode_tables(rdr_ctx* c, const void* src, int64_t src_bytes, co
     int64_t need = 0, nsub = 0;
     for (int64_t i = 0; i < nseg; ++i) {
         if (seg_bytes[i] <= 0) return fail(c, RDR_ERR_INVALID, "rdr_deflate_encode: segment " + std::to_string(i) + " is empty");
-        if (seg_offset[i] < 0 || seg_offset[i] > src_bytes || seg_bytes[i] > src_bytes - seg_offset[i])
-            return fail(c, RDR_ERR_INVALID, "rdr_deflate_encode: segment " + std::to_string(i) + " does not lie inside the source buffer");
+        const int rc = segment_in_source(c, "rdr_deflate_encode", i, seg_offset[i], seg_bytes[i], src_bytes); if (rc) return rc;
         need += rdr_deflate_bound(seg_bytes[i]);
         nsub += (seg_bytes[i] + DEFL_SUB - 1) / DEFL_SUB;
         if (need > ((int64_t)1 << 41)) return fail(c, RDR_ERR_INVALID, "rdr_deflate_encode: the segments hold more than 2^40 bytes");
@@ -3683,22 +3651,20 @@ int rdr_deflate_encode_tables(rdr_ctx* c, const void* src, int64_t src_bytes, co
                 subs[(size_t)k] = DeflSub{seg_offset[i] + o, 0, (int32_t)m, (o == 0 ? 1 : 0) | (o + m == seg_bytes[i] ? 2 : 0), 0u, 0};
             }
     }
-    const void* dsrc; void *dsubs, *dslots, *dres, *dout;
-    int rc = stage_in(c, SLOT_IN0, src, (size_t)src_bytes, loc, &dsrc); if (rc) return rc;
-    rc = ensure(c, SLOT_IN1, (size_t)nsub * sizeof(DeflSub), &dsubs); if (rc) return rc;
-    rc = ensure(c, SLOT_DEFL, (size_t)nsub * DEFL_SLOT, &dslots); if (rc) return rc;
-    rc = ensure(c, SLOT_OUT1, (size_t)nsub * sizeof(DeflResult), &dres); if (rc) return rc;
-    rc = upload(c, dsubs, subs.data(), (size_t)nsub * sizeof(DeflSub)); if (rc) return rc;
+    Staged S(c, loc);
+    const uint8_t* dsrc = S.in(static_cast<const uint8_t*>(src), (size_t)src_bytes);
+    const HostPart sub_table{subs.data(), (size_t)nsub * sizeof(DeflSub)};
+    const DeflSub* dsubs = S.table<DeflSub>(SLOT_IN1, &sub_table, 1);
+    uint8_t* dslots = S.scratch<uint8_t>(SLOT_DEFL, (size_t)nsub * DEFL_SLOT);
+    DeflResult* dres = S.scratch<DeflResult>(SLOT_OUT1, (size_t)nsub * sizeof(DeflResult));
     // one wave per sub-block; a compute unit holds three of these 53 KB workgroups, the grid strides over the rest
     const unsigned grid = (unsigned)std::min<int64_t>(nsub, (int64_t)c->num_cus * 3);
-    if (tables == RDR_DEFL_DYNAMIC) {
-        void* dtok;
-        rc = ensure(c, SLOT_DEFL_TOK, (size_t)grid * DEFL_SUB * sizeof(uint32_t), &dtok); if (rc) return rc;
-        hipLaunchKernelGGL(deflate_encode_dyn_kernel, dim3(grid), dim3(64), 0, c->stream, (const uint8_t*)dsrc, (const DeflSub*)dsubs, nsub, (uint8_t*)dslots,
-                           (DeflResult*)dres, (uint32_t*)dtok);
-    } else
-        hipLaunchKernelGGL(deflate_encode_kernel, dim3(grid), dim3(64), 0, c->stream, (const uint8_t*)dsrc, (const DeflSub*)dsubs, nsub, (uint8_t*)dslots,
-                           (DeflResult*)dres);
+    uint32_t* dtok = tables == RDR_DEFL_DYNAMIC ? S.scratch<uint32_t>(SLOT_DEFL_TOK, (size_t)grid * DEFL_SUB * sizeof(uint32_t)) : nullptr;
+    if (S.rc) return S.rc;
+    if (tables == RDR_DEFL_DYNAMIC)
+        hipLaunchKernelGGL(deflate_encode_dyn_kernel, dim3(grid), dim3(64), 0, c->stream, dsrc, dsubs, nsub, dslots, dres, dtok);
+    else
+        hipLaunchKernelGGL(deflate_encode_kernel, dim3(grid), dim3(64), 0, c->stream, dsrc, dsubs, nsub, dslots, dres);
     HIPCHECK(c, hipGetLastError());
     std::vector<DeflResult> res((size_t)nsub);
     HIPCHECK(c, hipMemcpyAsync(res.data(), dres, (size_t)nsub * sizeof(DeflResult), hipMemcpyDeviceToHost, c->stream));
@@ -3722,13 +3688,13 @@ int rdr_deflate_encode_tables(rdr_ctx* c, const void* src, int64_t src_bytes, co
     }
     out_offset[nseg] = pos;
     if (pos > out_capacity) return fail(c, RDR_ERR_HIP, "rdr_deflate_encode: the streams exceed their bound");       // (cannot happen: every sub-block is at most n + 5)
-    rc = upload(c, dsubs, subs.data(), (size_t)nsub * sizeof(DeflSub)); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, out, (size_t)pos, loc, &dout); if (rc) return rc;
-    hipLaunchKernelGGL(deflate_pack_kernel, dim3((unsigned)std::min<int64_t>(nsub, (int64_t)c->num_cus * 8)), dim3(256), 0, c->stream, (const uint8_t*)dsrc,
-                       (const DeflSub*)dsubs, nsub, (const uint8_t*)dslots, (uint8_t*)dout, pos);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, out, dout, (size_t)pos, loc); if (rc) return rc;
-    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    S.table<DeflSub>(SLOT_IN1, &sub_table, 1);                       // (the same table again, with the offsets, sizes and checksums filled in)
+    uint8_t* dout = S.out(static_cast<uint8_t*>(out), (size_t)pos);
+    if (S.rc) return S.rc;
+    hipLaunchKernelGGL(deflate_pack_kernel, dim3((unsigned)std::min<int64_t>(nsub, (int64_t)c->num_cus * 8)), dim3(256), 0, c->stream, dsrc, dsubs, nsub,
+                       (const uint8_t*)dslots, dout, pos);
+    const int rc = S.finish(true);                                   // (always waits, as the size pass above did)
+    if (rc) return rc;
     if (block_counts) { block_counts[0] = kinds[0]; block_counts[1] = kinds[1]; block_counts[2] = kinds[2]; }
     return RDR_OK;
 }
@@ -3747,18 +3713,39 @@ int rdr_tiff_predict(rdr_ctx* c, const void* in, int sample_bytes, int64_t heigh
     if (in == out) return fail(c, RDR_ERR_INVALID, "rdr_tiff_predict: in and out must be different buffers");
     HIPCHECK(c, hipSetDevice(c->device));
     const int64_t n = height * width;
-    const void* din; void* dout;
-    int rc = stage_in(c, SLOT_IN0, in, (size_t)n * sample_bytes, loc, &din); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, out, (size_t)n * sample_bytes, loc, &dout); if (rc) return rc;
+    Staged S(c, loc);
+    const void* din = S.in(in, (size_t)n * sample_bytes);
+    void* dout = S.out(out, (size_t)n * sample_bytes);
+    if (S.rc) return S.rc;
     if ((reinterpret_cast<uintptr_t>(din) | reinterpret_cast<uintptr_t>(dout)) % sample_bytes != 0) return fail(c, RDR_ERR_INVALID, "rdr_tiff_predict: buffers must be aligned to the sample size");
     const dim3 G(grid_for(n, 256, c->num_cus * 16)), Bk(256);
     if (sample_bytes == 1) hipLaunchKernelGGL(tiff_predict_kernel<uint8_t>, G, Bk, 0, c->stream, (const uint8_t*)din, n, width, (uint8_t*)dout);
     else if (sample_bytes == 2) hipLaunchKernelGGL(tiff_predict_kernel<uint16_t>, G, Bk, 0, c->stream, (const uint16_t*)din, n, width, (uint16_t*)dout);
     else if (sample_bytes == 4) hipLaunchKernelGGL(tiff_predict_kernel<uint32_t>, G, Bk, 0, c->stream, (const uint32_t*)din, n, width, (uint32_t*)dout);
     else hipLaunchKernelGGL(tiff_predict_kernel<uint64_t>, G, Bk, 0, c->stream, (const uint64_t*)din, n, width, (uint64_t*)dout);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, out, dout, (size_t)n * sample_bytes, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return S.finish();
+}
+
+// The chunk grid of an array of `ndim` axes (rdr_h5_chunks and its inverse): shape and chunk padded to four axes with ones in front, every
+// size and product checked (at most 2^36 elements, padding included).  *array_elems: elements of the array; *nchunks: chunks of the grid.
+// G.total_elems is left to the caller - all chunks one way, the present ones the other.
+static int h5_chunk_grid(rdr_ctx* c, const char* who, int elem_bytes, int ndim, const int64_t* shape, const int64_t* chunk, H5ChunkGrid& G, int64_t* array_elems,
+                         int64_t* nchunks) {
+    const std::string w(who);
+    if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) return fail(c, RDR_ERR_INVALID, w + ": elements of 1, 2, 4 or 8 bytes");
+    if (ndim < 1 || ndim > 4) return fail(c, RDR_ERR_INVALID, w + ": 1 .. 4 dimensions");
+    *array_elems = *nchunks = G.chunk_elems = 1;
+    for (int d = 0; d < 4; ++d) { G.shape[d] = G.chunk[d] = G.nchunk[d] = 1; }
+    for (int d = 0; d < ndim; ++d) {
+        const int64_t s = shape[d], k = chunk[d];
+        if (s <= 0 || k <= 0 || s > ((int64_t)1 << 31) || k > ((int64_t)1 << 31)) return fail(c, RDR_ERR_INVALID, w + ": shape and chunk sizes must be positive (below 2^31)");
+        const int e = 4 - ndim + d;
+        G.shape[e] = s; G.chunk[e] = k; G.nchunk[e] = (s + k - 1) / k;
+        if (*array_elems > ((int64_t)1 << 36) / s || G.chunk_elems > ((int64_t)1 << 36) / k) return fail(c, RDR_ERR_INVALID, w + ": more than 2^36 elements");
+        *array_elems *= s; G.chunk_elems *= k;
+        *nchunks *= G.nchunk[e];
+        if (*nchunks > ((int64_t)1 << 36) / G.chunk_elems) return fail(c, RDR_ERR_INVALID, w + ": more than 2^36 elements");
+    }
     return RDR_OK;
 }
 
@@ -3766,97 +3753,40 @@ int rdr_h5_chunks(rdr_ctx* c, const void* array, int elem_bytes, int ndim, const
                   void* out, int loc) {
     if (!c || !array || !shape || !chunk || !fill || !out) return fail(c, RDR_ERR_INVALID, "rdr_h5_chunks: NULL argument");
     if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, "rdr_h5_chunks: loc must be RDR_HOST or RDR_DEVICE");
-    if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) return fail(c, RDR_ERR_INVALID, "rdr_h5_chunks: elements of 1, 2, 4 or 8 bytes");
-    if (ndim < 1 || ndim > 4) return fail(c, RDR_ERR_INVALID, "rdr_h5_chunks: 1 .. 4 dimensions");
     H5ChunkLayout L{};
-    int64_t in_elems = 1, nchunks = 1;
-    L.chunk_elems = 1;
-    for (int d = 0; d < 4; ++d) { L.shape[d] = L.chunk[d] = L.nchunk[d] = 1; }
-    for (int d = 0; d < ndim; ++d) {
-        const int64_t s = shape[d], k = chunk[d];
-        if (s <= 0 || k <= 0 || s > ((int64_t)1 << 31) || k > ((int64_t)1 << 31)) return fail(c, RDR_ERR_INVALID, "rdr_h5_chunks: shape and chunk sizes must be positive (below 2^31)");
-        const int e = 4 - ndim + d;
-        L.shape[e] = s; L.chunk[e] = k; L.nchunk[e] = (s + k - 1) / k;
-        if (in_elems > ((int64_t)1 << 36) / s || L.chunk_elems > ((int64_t)1 << 36) / k) return fail(c, RDR_ERR_INVALID, "rdr_h5_chunks: more than 2^36 elements");
-        in_elems *= s; L.chunk_elems *= k;
-        nchunks *= L.nchunk[e];
-        if (nchunks > ((int64_t)1 << 36) / L.chunk_elems) return fail(c, RDR_ERR_INVALID, "rdr_h5_chunks: more than 2^36 elements");
-    }
+    int64_t in_elems, nchunks;
+    const int rc = h5_chunk_grid(c, "rdr_h5_chunks", elem_bytes, ndim, shape, chunk, L, &in_elems, &nchunks); if (rc) return rc;
     L.total_elems = nchunks * L.chunk_elems;
     L.es = elem_bytes; L.shuffle = shuffle != 0;
     std::memcpy(L.fill, fill, (size_t)elem_bytes);
     HIPCHECK(c, hipSetDevice(c->device));
-    const void* din; void* dout;
-    int rc = stage_in(c, SLOT_IN0, array, (size_t)in_elems * elem_bytes, loc, &din); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, out, (size_t)L.total_elems * elem_bytes, loc, &dout); if (rc) return rc;
-    hipLaunchKernelGGL(h5_chunks_kernel, dim3(grid_for(L.total_elems, 256, c->num_cus * 16)), dim3(256), 0, c->stream, (const uint8_t*)din, L, (uint8_t*)dout);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, out, dout, (size_t)L.total_elems * elem_bytes, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    Staged S(c, loc);
+    const uint8_t* din = S.in(static_cast<const uint8_t*>(array), (size_t)in_elems * elem_bytes);
+    uint8_t* dout = S.out(static_cast<uint8_t*>(out), (size_t)L.total_elems * elem_bytes);
+    if (S.rc) return S.rc;
+    hipLaunchKernelGGL(h5_chunks_kernel, dim3(grid_for(L.total_elems, 256, c->num_cus * 16)), dim3(256), 0, c->stream, din, L, dout);
+    return S.finish();
 }
 
 
 // ---- zlib streams decoded on the device, and chunks put back into an array (inflate_kernels.h) -------------------------------------
 int rdr_inflate_decode(rdr_ctx* c, const void* src, int64_t src_bytes, const int64_t* seg_offset, const int64_t* seg_bytes, int64_t nseg,
                        const int64_t* seg_out_bytes, void* out, int64_t out_stride, int32_t* status, int64_t* produced, int loc) {
-    if (!c || !src || !seg_offset || !seg_bytes || !seg_out_bytes || !out || !status) return fail(c, RDR_ERR_INVALID, "rdr_inflate_decode: NULL argument");
-    if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, "rdr_inflate_decode: loc must be RDR_HOST or RDR_DEVICE");
-    if (src_bytes <= 0 || nseg <= 0 || nseg > (1 << 24)) return fail(c, RDR_ERR_INVALID, "rdr_inflate_decode: need a non-empty buffer and 1 .. 2^24 segments");
-    if (out_stride <= 0 || out_stride > ((int64_t)1 << 31) - 256 || nseg * out_stride > ((int64_t)1 << 40))
-        return fail(c, RDR_ERR_INVALID, "rdr_inflate_decode: out_stride must be positive and below 2 GiB (at most 2^40 bytes in all)");
-    for (int64_t i = 0; i < nseg; ++i) {
-        if (seg_offset[i] < 0 || seg_bytes[i] < 0 || seg_offset[i] > src_bytes || seg_bytes[i] > src_bytes - seg_offset[i])
-            return fail(c, RDR_ERR_INVALID, "rdr_inflate_decode: segment " + std::to_string(i) + " does not lie inside the source buffer");
-        if (seg_bytes[i] >= ((int64_t)1 << 31) - 256) return fail(c, RDR_ERR_INVALID, "rdr_inflate_decode: segment " + std::to_string(i) + " is 2 GiB or longer");
-        if (seg_out_bytes[i] < 0 || seg_out_bytes[i] > out_stride)
-            return fail(c, RDR_ERR_INVALID, "rdr_inflate_decode: segment " + std::to_string(i) + " would write beyond its slot of out_stride bytes");
-    }
-    HIPCHECK(c, hipSetDevice(c->device));
-    const void* dsrc; void *dtab, *dout, *dstat, *dprod = nullptr;
-    int rc = stage_in(c, SLOT_IN0, src, (size_t)src_bytes, loc, &dsrc); if (rc) return rc;
-    rc = ensure(c, SLOT_IN1, (size_t)nseg * 24, &dtab); if (rc) return rc;
-    int64_t* tab = (int64_t*)dtab;                            // the three tables are host arrays whatever `loc` says: offsets | bytes | out bytes
-    rc = upload(c, tab, seg_offset, (size_t)nseg * 8); if (rc) return rc;
-    rc = upload(c, tab + nseg, seg_bytes, (size_t)nseg * 8); if (rc) return rc;
-    rc = upload(c, tab + 2 * nseg, seg_out_bytes, (size_t)nseg * 8); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, out, (size_t)(nseg * out_stride), loc, &dout); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT1, status, (size_t)nseg * 4, loc, &dstat); if (rc) return rc;
-    if (produced) { rc = stage_out(c, SLOT_OUT2, produced, (size_t)nseg * 8, loc, &dprod); if (rc) return rc; }
-    // bytes of a slot the stream does not reach keep their value: a host `out` goes up first
-    if (loc == RDR_HOST) { rc = upload(c, dout, out, (size_t)(nseg * out_stride)); if (rc) return rc; }
-    // one wave per stream; a compute unit holds three of these 44 KB workgroups, the grid strides over the rest
-    const int grid = (int)std::min<int64_t>(nseg, (int64_t)c->num_cus * 3);
-    hipLaunchKernelGGL(inflate_kernel, dim3(grid), dim3(64), 0, c->stream, (const uint8_t*)dsrc, src_bytes, (const int64_t*)tab, (const int64_t*)(tab + nseg),
-                       (const int64_t*)(tab + 2 * nseg), (int)nseg, (uint8_t*)dout, out_stride, (int32_t*)dstat, (int64_t*)dprod);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, out, dout, (size_t)(nseg * out_stride), loc); if (rc) return rc;
-    rc = finish_out(c, status, dstat, (size_t)nseg * 4, loc); if (rc) return rc;
-    if (produced) { rc = finish_out(c, produced, dprod, (size_t)nseg * 8, loc); if (rc) return rc; }
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    // three of the 44 KB workgroups per compute unit
+    return decode_segments(c, "rdr_inflate_decode", src, src_bytes, seg_offset, seg_bytes, nseg, seg_out_bytes, out, out_stride, status, produced, loc, 3,
+                           [&](int grid, const uint8_t* dsrc, const int64_t* tab, uint8_t* dout, int32_t* dstat, int64_t* dprod) {
+        hipLaunchKernelGGL(inflate_kernel, dim3(grid), dim3(64), 0, c->stream, dsrc, src_bytes, tab, tab + nseg, tab + 2 * nseg, (int)nseg, dout, out_stride, dstat,
+                           dprod);
+    });
 }
 
 int rdr_h5_unchunk(rdr_ctx* c, const void* chunks, int64_t chunk_stride, const int64_t* chunk_index, int64_t npresent, int elem_bytes, int ndim,
                    const int64_t* shape, const int64_t* chunk, int shuffle, int swap, void* out, int loc) {
     if (!c || !chunks || !chunk_index || !shape || !chunk || !out) return fail(c, RDR_ERR_INVALID, "rdr_h5_unchunk: NULL argument");
     if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, "rdr_h5_unchunk: loc must be RDR_HOST or RDR_DEVICE");
-    if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) return fail(c, RDR_ERR_INVALID, "rdr_h5_unchunk: elements of 1, 2, 4 or 8 bytes");
-    if (ndim < 1 || ndim > 4) return fail(c, RDR_ERR_INVALID, "rdr_h5_unchunk: 1 .. 4 dimensions");
     H5UnchunkLayout L{};
-    int64_t out_elems = 1, nchunks = 1;
-    L.chunk_elems = 1;
-    for (int d = 0; d < 4; ++d) { L.shape[d] = L.chunk[d] = L.nchunk[d] = 1; }
-    for (int d = 0; d < ndim; ++d) {
-        const int64_t s = shape[d], k = chunk[d];
-        if (s <= 0 || k <= 0 || s > ((int64_t)1 << 31) || k > ((int64_t)1 << 31)) return fail(c, RDR_ERR_INVALID, "rdr_h5_unchunk: shape and chunk sizes must be positive (below 2^31)");
-        const int e = 4 - ndim + d;
-        L.shape[e] = s; L.chunk[e] = k; L.nchunk[e] = (s + k - 1) / k;
-        if (out_elems > ((int64_t)1 << 36) / s || L.chunk_elems > ((int64_t)1 << 36) / k) return fail(c, RDR_ERR_INVALID, "rdr_h5_unchunk: more than 2^36 elements");
-        out_elems *= s; L.chunk_elems *= k;
-        nchunks *= L.nchunk[e];
-        if (nchunks > ((int64_t)1 << 36) / L.chunk_elems) return fail(c, RDR_ERR_INVALID, "rdr_h5_unchunk: more than 2^36 elements");
-    }
+    int64_t out_elems, nchunks;
+    const int rc = h5_chunk_grid(c, "rdr_h5_unchunk", elem_bytes, ndim, shape, chunk, L, &out_elems, &nchunks); if (rc) return rc;
     if (npresent <= 0 || npresent > nchunks) return fail(c, RDR_ERR_INVALID, "rdr_h5_unchunk: 1 .. " + std::to_string(nchunks) + " chunks may be present");
     if (chunk_stride < L.chunk_elems * elem_bytes || chunk_stride > ((int64_t)1 << 40) / npresent)
         return fail(c, RDR_ERR_INVALID, "rdr_h5_unchunk: chunk_stride must hold one decoded chunk (at most 2^40 bytes in all)");
@@ -3872,16 +3802,13 @@ int rdr_h5_unchunk(rdr_ctx* c, const void* chunks, int64_t chunk_stride, const i
     L.chunk_stride = chunk_stride;
     L.es = elem_bytes; L.shuffle = shuffle != 0; L.swap = swap != 0;
     HIPCHECK(c, hipSetDevice(c->device));
-    const void* din; void *dout, *dtab;
-    int rc = stage_in(c, SLOT_IN0, chunks, (size_t)(npresent * chunk_stride), loc, &din); if (rc) return rc;
-    rc = ensure(c, SLOT_IN1, (size_t)npresent * 8, &dtab); if (rc) return rc;
-    rc = upload(c, dtab, chunk_index, (size_t)npresent * 8); if (rc) return rc;
-    rc = stage_out(c, SLOT_OUT0, out, (size_t)out_elems * elem_bytes, loc, &dout); if (rc) return rc;
+    Staged S(c, loc);
+    const uint8_t* din = S.in(static_cast<const uint8_t*>(chunks), (size_t)(npresent * chunk_stride));
+    const HostPart index{chunk_index, (size_t)npresent * 8};      // (a host array whatever `loc` says)
+    const int64_t* dtab = S.table<int64_t>(SLOT_IN1, &index, 1);
+    uint8_t* dout = S.out(static_cast<uint8_t*>(out), (size_t)out_elems * elem_bytes);
+    if (S.rc) return S.rc;
     if (npresent < nchunks) HIPCHECK(c, hipMemsetAsync(dout, 0, (size_t)out_elems * elem_bytes, c->stream));      // absent chunks read as 0
-    hipLaunchKernelGGL(h5_unchunk_kernel, dim3(grid_for(L.total_elems, 256, c->num_cus * 16)), dim3(256), 0, c->stream, (const uint8_t*)din, (const int64_t*)dtab, L,
-                       (uint8_t*)dout);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, out, dout, (size_t)out_elems * elem_bytes, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    hipLaunchKernelGGL(h5_unchunk_kernel, dim3(grid_for(L.total_elems, 256, c->num_cus * 16)), dim3(256), 0, c->stream, din, dtab, L, dout);
+    return S.finish();
 }

@@ -41,6 +41,48 @@ def last_block_counts():
     return _last_counts
 
 
+class _Route:
+    """How one buffer goes through the library, NumPy array or device tensor alike: its C-contiguous form (`array`), that as bytes
+    (`bytes`), the `loc` that goes with it, the context - on torch's current stream for a tensor - and buffers of the same kind (`new`).
+    A tensor that is not on the GPU (or not contiguous, unless `make_contiguous`) is a TypeError of `need`; an array without a GPU
+    is require_gpu's RuntimeError."""
+
+    def __init__(self, buf, who, entry, need='a tensor must be contiguous and live on the GPU', make_contiguous=False):
+        self.tensor = _is_tensor(buf)
+        if self.tensor:
+            import torch
+            if not buf.is_cuda or not (make_contiguous or buf.is_contiguous()):
+                raise TypeError(f'{who}: {need}')
+            self.array = buf.contiguous()
+            self.bytes = self.array.reshape(-1).view(torch.uint8)
+            self.loc = L.RDR_DEVICE
+        else:
+            require_gpu(f'{who} ({entry})')
+            self.array = np.ascontiguousarray(buf)
+            self.bytes = self.array.reshape(-1).view(np.uint8)
+            self.loc = L.RDR_HOST
+        self.nbytes = self.bytes.numel() if self.tensor else self.bytes.size
+        self.ctx = L.Context.default()
+        if self.tensor:
+            self.ctx.adopt_torch_stream(self.bytes)
+
+    def new(self, n, dtype=np.uint8, fill=None):
+        """`n` elements of `dtype` where the buffer lives: filled with `fill`, or uninitialised.  (Zeros come from zeros(): a memset on
+        the device, untouched pages on the host.)"""
+        if self.tensor:
+            import torch
+            kw = dict(dtype=getattr(torch, np.dtype(dtype).name), device=self.array.device)
+            return torch.empty(n, **kw) if fill is None else torch.zeros(n, **kw) if fill == 0 else torch.full((n,), fill, **kw)
+        return np.empty(n, dtype=dtype) if fill is None else np.zeros(n, dtype=dtype) if fill == 0 else np.full(n, fill, dtype=dtype)
+
+    def owns(self, out):
+        """`out` is a contiguous uint8 buffer of the buffer's own kind."""
+        if self.tensor:
+            import torch
+            return _is_tensor(out) and out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous()
+        return isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous
+
+
 def deflate_segments(buf, offsets, sizes, tables='fixed'):
     """(packed, out_offsets): the byte ranges buf[offsets[i] : offsets[i] + sizes[i]] as zlib streams packed back to back; stream i is
     packed[out_offsets[i] : out_offsets[i + 1]].  buf: a C-contiguous NumPy array or device tensor of any element type (taken as bytes);
@@ -59,24 +101,10 @@ def deflate_segments(buf, offsets, sizes, tables='fixed'):
     cap = sum(bound(int(v)) * int(c) for v, c in zip(*np.unique(sb, return_counts=True)))
     oo = np.zeros(so.size + 1, dtype=np.int64)
     kinds = np.zeros(3, dtype=np.int64)
-    if _is_tensor(buf):
-        import torch
-        if not buf.is_cuda or not buf.is_contiguous():
-            raise TypeError('deflate_segments: a tensor must be contiguous and live on the GPU')
-        src = buf.reshape(-1).view(torch.uint8)
-        out = torch.empty(cap, dtype=torch.uint8, device=buf.device)
-        ctx = L.Context.default()
-        ctx.adopt_torch_stream(src)
-        L.check(ctx.lib.rdr_deflate_encode_tables(ctx.handle, L.ptr(src), src.numel(), L.ptr(so), L.ptr(sb), so.size, mode, L.ptr(out), cap, L.ptr(oo), L.ptr(kinds),
-                                                  L.RDR_DEVICE), ctx.handle)
-        _last_counts = tuple(int(k) for k in kinds)
-        return out[:int(oo[-1])], oo
-    require_gpu('deflate_segments (rdr_deflate_encode)')
-    src = np.ascontiguousarray(buf).reshape(-1).view(np.uint8)
-    out = np.empty(cap, dtype=np.uint8)
-    ctx = L.Context.default()
-    L.check(ctx.lib.rdr_deflate_encode_tables(ctx.handle, L.ptr(src), src.size, L.ptr(so), L.ptr(sb), so.size, mode, L.ptr(out), cap, L.ptr(oo), L.ptr(kinds), L.RDR_HOST),
-            ctx.handle)
+    r = _Route(buf, 'deflate_segments', 'rdr_deflate_encode')
+    out = r.new(cap)
+    L.check(r.ctx.lib.rdr_deflate_encode_tables(r.ctx.handle, L.ptr(r.bytes), r.nbytes, L.ptr(so), L.ptr(sb), so.size, mode, L.ptr(out), cap, L.ptr(oo), L.ptr(kinds),
+                                                r.loc), r.ctx.handle)
     _last_counts = tuple(int(k) for k in kinds)
     return out[:int(oo[-1])], oo
 
@@ -90,18 +118,9 @@ def h5_chunks(array, chunk, fill, shuffle=True):
     """`array` (NumPy or device tensor, at most 4-D) cut into full-size chunks in row-major chunk order, edge chunks padded with `fill`,
     each chunk byte-shuffled as HDF5's shuffle filter does when `shuffle`.  Returns a uint8 array / tensor of
     n_chunks * prod(chunk) * itemsize bytes: chunk k is bytes [k * chunk_bytes, (k + 1) * chunk_bytes)."""
-    tensor = _is_tensor(array)
-    if tensor:
-        import torch
-        if not array.is_cuda:
-            raise TypeError('h5_chunks: a tensor must live on the GPU')
-        a = array.contiguous()
-        dt = np.dtype(str(a.dtype).replace('torch.', ''))
-        shape = tuple(a.shape)
-    else:
-        require_gpu('h5_chunks (rdr_h5_chunks)')
-        a = np.ascontiguousarray(array)
-        dt, shape = a.dtype, a.shape
+    r = _Route(array, 'h5_chunks', 'rdr_h5_chunks', need='a tensor must live on the GPU', make_contiguous=True)
+    dt = np.dtype(str(r.array.dtype).replace('torch.', '')) if r.tensor else r.array.dtype
+    shape = tuple(r.array.shape)
     chunk = tuple(int(c) for c in chunk)
     if len(chunk) != len(shape) or not 1 <= len(shape) <= 4:
         raise ValueError(f'h5_chunks: chunk {chunk} does not fit an array of shape {shape} (1 to 4 axes)')
@@ -110,15 +129,9 @@ def h5_chunks(array, chunk, fill, shuffle=True):
     nbytes = int(np.prod(chunk_grid(shape, chunk), dtype=np.int64) * np.prod(chunk, dtype=np.int64)) * dt.itemsize
     fv = np.array([fill], dtype=dt)
     sh, ck = np.array(shape, dtype=np.int64), np.array(chunk, dtype=np.int64)
-    ctx = L.Context.default()
-    if tensor:
-        out = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
-        ctx.adopt_torch_stream(a)
-        loc = L.RDR_DEVICE
-    else:
-        out = np.empty(nbytes, dtype=np.uint8)
-        loc = L.RDR_HOST
-    L.check(ctx.lib.rdr_h5_chunks(ctx.handle, L.ptr(a), dt.itemsize, len(shape), L.ptr(sh), L.ptr(ck), L.ptr(fv), int(bool(shuffle)), L.ptr(out), loc), ctx.handle)
+    out = r.new(nbytes)
+    L.check(r.ctx.lib.rdr_h5_chunks(r.ctx.handle, L.ptr(r.bytes), dt.itemsize, len(shape), L.ptr(sh), L.ptr(ck), L.ptr(fv), int(bool(shuffle)), L.ptr(out), r.loc),
+            r.ctx.handle)
     return out
 
 
@@ -178,36 +191,16 @@ def inflate_segments(buf, offsets, sizes, out_sizes, out_stride=None, out=None):
     if out_stride is None:
         out_stride = max(16, (int(cap.max()) + 15) // 16 * 16)
     out_stride = int(out_stride)
-    tensor = _is_tensor(buf)
-    if tensor:
-        import torch
-        if not buf.is_cuda or not buf.is_contiguous():
-            raise TypeError('inflate_segments: a tensor must be contiguous and live on the GPU')
-        src = buf.reshape(-1).view(torch.uint8)
-        nsrc = src.numel()
-        if out is None:
-            out = torch.zeros(n * out_stride, dtype=torch.uint8, device=buf.device)
-        elif not _is_tensor(out) or out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() < n * out_stride:
-            raise TypeError(f'inflate_segments: out must be a contiguous uint8 tensor on the GPU of {n} slots of {out_stride} bytes')
-        status = torch.full((n,), -1, dtype=torch.int32, device=buf.device)
-        produced = torch.zeros(n, dtype=torch.int64, device=buf.device)
-        loc = L.RDR_DEVICE
-    else:
-        require_gpu('inflate_segments (rdr_inflate_decode)')
-        src = np.ascontiguousarray(buf).reshape(-1).view(np.uint8)
-        nsrc = src.size
-        if out is None:
-            out = np.zeros(n * out_stride, dtype=np.uint8)
-        elif not isinstance(out, np.ndarray) or out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < n * out_stride:
-            raise TypeError(f'inflate_segments: out must be a C-contiguous uint8 array of {n} slots of {out_stride} bytes')
-        status = np.full(n, -1, dtype=np.int32)
-        produced = np.zeros(n, dtype=np.int64)
-        loc = L.RDR_HOST
-    ctx = L.Context.default()
-    if tensor:
-        ctx.adopt_torch_stream(src)
-    L.check(ctx.lib.rdr_inflate_decode(ctx.handle, L.ptr(src), nsrc, L.ptr(so), L.ptr(sb), n, L.ptr(cap), L.ptr(out), out_stride, L.ptr(status), L.ptr(produced), loc),
-            ctx.handle)
+    r = _Route(buf, 'inflate_segments', 'rdr_inflate_decode')
+    if out is None:
+        out = r.new(n * out_stride, fill=0)
+    elif not r.owns(out) or (out.numel() if r.tensor else out.size) < n * out_stride:
+        kind = 'contiguous uint8 tensor on the GPU' if r.tensor else 'C-contiguous uint8 array'
+        raise TypeError(f'inflate_segments: out must be a {kind} of {n} slots of {out_stride} bytes')
+    status = r.new(n, np.int32, fill=-1)
+    produced = r.new(n, np.int64, fill=0)
+    L.check(r.ctx.lib.rdr_inflate_decode(r.ctx.handle, L.ptr(r.bytes), r.nbytes, L.ptr(so), L.ptr(sb), n, L.ptr(cap), L.ptr(out), out_stride, L.ptr(status),
+                                         L.ptr(produced), r.loc), r.ctx.handle)
     return out, status, produced
 
 
@@ -225,24 +218,15 @@ def h5_unchunk(chunks, chunk_stride, chunk_index, dtype, shape, chunk, shuffle=T
         raise ValueError('h5_unchunk: no chunks')
     sh, ck = np.array(shape, dtype=np.int64), np.array(chunk, dtype=np.int64)
     nbytes = int(np.prod(sh)) * dt.itemsize
-    ctx = L.Context.default()
-    if _is_tensor(chunks):
-        import torch
-        if not chunks.is_cuda or not chunks.is_contiguous() or chunks.numel() * chunks.element_size() < idx.size * int(chunk_stride):
+    r = _Route(chunks, 'h5_unchunk', 'rdr_h5_unchunk', need='a tensor must be contiguous, live on the GPU and hold every chunk')
+    if r.nbytes < idx.size * int(chunk_stride):
+        if r.tensor:
             raise TypeError('h5_unchunk: a tensor must be contiguous, live on the GPU and hold every chunk')
-        out = torch.empty(nbytes, dtype=torch.uint8, device=chunks.device)
-        ctx.adopt_torch_stream(chunks)
-        loc = L.RDR_DEVICE
-    else:
-        require_gpu('h5_unchunk (rdr_h5_unchunk)')
-        chunks = np.ascontiguousarray(chunks).reshape(-1).view(np.uint8)
-        if chunks.size < idx.size * int(chunk_stride):
-            raise ValueError('h5_unchunk: the buffer does not hold every chunk')
-        out = np.empty(nbytes, dtype=np.uint8)
-        loc = L.RDR_HOST
-    L.check(ctx.lib.rdr_h5_unchunk(ctx.handle, L.ptr(chunks), int(chunk_stride), L.ptr(idx), idx.size, dt.itemsize, len(shape), L.ptr(sh), L.ptr(ck), int(bool(shuffle)),
-                                   int(bool(swap)), L.ptr(out), loc), ctx.handle)
-    if _is_tensor(out):
+        raise ValueError('h5_unchunk: the buffer does not hold every chunk')
+    out = r.new(nbytes)
+    L.check(r.ctx.lib.rdr_h5_unchunk(r.ctx.handle, L.ptr(r.bytes), int(chunk_stride), L.ptr(idx), idx.size, dt.itemsize, len(shape), L.ptr(sh), L.ptr(ck),
+                                     int(bool(shuffle)), int(bool(swap)), L.ptr(out), r.loc), r.ctx.handle)
+    if r.tensor:
         import torch
         if not hasattr(torch, dt.name):
             raise TypeError(f'h5_unchunk: this torch build has no tensor type for {dt.name}')
