@@ -508,6 +508,51 @@ struct RayParams {
                                        // out (0: never; != 0 only on a launch that allocated skip_smem_bytes); such waves are counted in nslow[1]
 };
 
+// The argument block of the two ray kernels as the kernarg segment holds it.  The light instantiations read their uniform parameters from
+// there AT THE POINT OF USE, through the constant address space (scalar loads) and a pointer made opaque per site (ray_args): a field
+// read this way is a short-lived SGPR next to its use.  Read from the by-value arguments, all of them - some 110 dwords - are kept live
+// across the whole tile loop, more than the scalar file holds, and the surplus is parked in lanes of two vector registers: one
+// v_readlane_b32 per use, in the vector ALU's issue slots (profiles/r26_tile_body_regs.txt).  What the level loops read as SGPR operands
+// stays with the by-value arguments.  Nothing is written through this pointer and the arguments keep arriving as kernel arguments.
+template <typename T2> struct RayKernArgs { CubeView<T2> c; RayParams P; LccParams proj; };
+static_assert(offsetof(RayKernArgs<float2>, P) == sizeof(CubeView<float2>) && offsetof(RayKernArgs<float2>, proj) == sizeof(CubeView<float2>) + sizeof(RayParams) &&
+              sizeof(CubeView<float2>) % 8 == 0 && sizeof(CubeView<double2>) == sizeof(CubeView<float2>) && sizeof(RayParams) % 8 == 0,
+              "RayKernArgs mirrors the kernarg layout of (CubeView, RayParams, LccParams): consecutive 8-byte aligned structs");
+template <typename T2>
+__device__ __forceinline__ const __attribute__((address_space(4))) RayKernArgs<T2>* ray_args() {
+    const __attribute__((address_space(4))) RayKernArgs<T2>* p = (const __attribute__((address_space(4))) RayKernArgs<T2>*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));        // (opaque: no load through it is merged with another site's or hoisted out of the tile loop)
+    return p;
+}
+
+// A tile's records and outputs through scalar bases.  Field f of thread tl of local tile lt is ws[f * nslots + lt * BLOCK + tl]: everything
+// but tl is wave-uniform, so the 64-bit part of the address is formed on the scalar unit - base = ws + lt * BLOCK, stepped by nslots per
+// field - and the vector part is the thread's constant tl * 8 (< 2 KiB): the access takes the saddr + 32-bit voffset form, no 64-bit vector
+// add per field.  No product with nslots ever enters the 32-bit offset (29 * 8 * nslots passes 4 GiB at 19 M rays).
+__device__ __forceinline__ int64_t wave_uniform(int64_t v) {                  // v is the same in every lane: as a scalar
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32));
+    return (int64_t)(((unsigned long long)hi << 32) | lo);
+}
+typedef __attribute__((address_space(1))) double GlobalF64;       // (the workspace is device memory: global accesses, not flat ones,
+typedef __attribute__((address_space(1))) char GlobalByte;        //  also behind a base the compiler cannot look through)
+struct TileRecords {
+    GlobalByte* base; int64_t fstride; unsigned voff;
+    // ws: the workspace (may be null: nothing is accessed then); lt: the tile (wave-uniform); tl: the thread
+    __device__ __forceinline__ TileRecords(double* ws, int64_t nslots, int64_t lt, int tl)
+        : base((GlobalByte*)(ws + wave_uniform(lt) * BLOCK)), fstride(nslots * (int64_t)sizeof(double)), voff((unsigned)tl * (unsigned)sizeof(double)) {}
+    // (each field's base is pinned to scalar registers: left to itself the compiler reassociates the chain of addresses into 64-bit VECTOR
+    // multiply-adds, quarter-rate instructions, from one field to the next)
+    __device__ __forceinline__ GlobalF64& operator[](int f) const { GlobalByte* b = base + f * fstride; asm("" : "+s"(b)); return *(GlobalF64*)(b + voff); }
+    // consecutive fields f, f + 1, ...: one scalar 64-bit add per field
+    struct Run {
+        GlobalByte* b; int64_t fstride; unsigned voff;
+        __device__ __forceinline__ GlobalF64& next() { asm("" : "+s"(b)); GlobalF64& r = *(GlobalF64*)(b + voff); b += fstride; return r; }
+    };
+    __device__ __forceinline__ Run run(int f) const { return Run{base + f * fstride, fstride, voff}; }
+};
+static_assert(WS_POLY_LAT == WS_POLY_H + PN && WS_POLY_LON == WS_POLY_LAT + PN && WS_XPOLY == WS_POLY_LON + PN && WS_SCALE == WS_XPOLY + PX && WS_U1 == WS_U0 + 1,
+              "the runs of consecutive record fields both passes walk (TileRecords::Run)");
+
 // The slice-uniform level table of build_ray (losreader.py:785-808), computed by one thread into LDS from the LDS z table.
 __device__ inline int build_levels(const double2* ez, int nz, double ht, double zref, double* s_lo, double* s_hi, int* s_kz) {
     int K = 0;
@@ -733,8 +778,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
     static_assert(!SLOW || (OM == 0 && !PR), "the generic kernel takes every input form");
     const bool per_ray = PR || (SLOW && P.ht_ray != nullptr);
     if (SLOW && *P.nslow == 0) return;
-    const int origin_mode = OM != 0 ? 0 : P.origin_mode;
-    const int los_mode = OM == 1 ? 0 : P.los_mode;
+    // The uniform parameters as the tile loop reads them: the light instantiations through the kernarg segment, afresh at every site
+    // (RayKernArgs); the generic kernel from its by-value arguments.
+    auto Pk = [&]() -> decltype(auto) { if constexpr (SLOW) return (P); else return (ray_args<T2>()->P); };
+    auto Ck = [&]() -> decltype(auto) { if constexpr (SLOW) return (c); else return (ray_args<T2>()->c); };
+    auto Jk = [&]() -> decltype(auto) { if constexpr (SLOW) return (proj); else return (ray_args<T2>()->proj); };
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const RaySmem m = carve_smem(smem_raw, c.ny, c.nx, c.nz, c.exact_y, c.exact_x);
     // The instantiations whose waves may skip the per-level length loop (below): not the per-ray-height ones (their loop starts per lane), and
@@ -743,9 +791,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
     if (SKIPPABLE && threadIdx.x == 0) m.K[3] = 0;        // the workgroup's count of waves that skipped (before the barrier of fill_axes)
     fill_axes(c, m);
     const int tid = threadIdx.x;
-    const bool reduce = P.maxlen_bits != nullptr;
-    // (kernel-uniform; read through an opaque copy at every use, so that no flag of it is carried across the tile body)
-    auto skip_on = [&]() { if (!SKIPPABLE || !reduce) return false; int on = P.skip_levels; asm volatile("" : "+s"(on)); return on != 0; };
+    // (kernel-uniform; read afresh at every use, so that no flag of them is carried across the tile body)
+    auto reduce_on = [&]() { return Pk().maxlen_bits != nullptr; };
+    auto skip_on = [&]() { if (!SKIPPABLE) return false; const auto& a = Pk(); return a.maxlen_bits != nullptr && a.skip_levels != 0; };
     // per-level maximum of the ray length over a slice (delay.py:283): every lane folds its length into column lane%16 of
     // the workgroup's LDS table with one ds_max_u64 (non-negative doubles order like their bit patterns); the columns are
     // combined when the workgroup leaves the slice (flush).  NaN lengths are left out here and reported through the flags,
@@ -754,7 +802,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
     int K = 0, slice = -1;
     double ht = P.ht;
     auto flush = [&]() {                                   // called by every thread of the workgroup
-        if (!reduce || slice < 0) return;
+        const auto& a = Pk();
+        if (a.maxlen_bits == nullptr || slice < 0) return;
         __syncthreads();
         int tf = threadIdx.x;
         asm volatile("" : "+v"(tf));                       // (opaque: no address derived from it is kept live across the tile loop)
@@ -762,43 +811,47 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
             unsigned long long v = 0ULL;
 #pragma unroll
             for (int cc = 0; cc < MXCOLS; ++cc) v = max(v, m.mxcol[k * MXCOLS + cc]);
-            atomicMax(&P.maxlen_bits[(int64_t)slice * MAX_LEVELS + k], v);
+            atomicMax(&a.maxlen_bits[(int64_t)slice * MAX_LEVELS + k], v);
         }
         int f = my_flags;
         for (int off = 32; off > 0; off >>= 1) f |= __shfl_xor(f, off, 64);
-        if ((tf & 63) == 0 && f) atomicOr(P.flags + slice, f);
+        if ((tf & 63) == 0 && f) atomicOr(a.flags + slice, f);
         my_flags = 0;
     };
     TileWalk walk(P.tile_count, P.tile_ctr, m.K + 2);
     int64_t lt;
-    while (walk.next(P.tile_count, lt)) {
-        const int64_t tg = P.tile_begin + lt;              // tile of the batch; t: tile within its slice
-        const int sl = (int)(tg / P.tiles_per_slice);
-        const int64_t t = tg - (int64_t)sl * P.tiles_per_slice;
+    while (walk.next(Pk().tile_count, lt)) {
+        const auto& pa = Pk();                             // (this site: the tile's place in the batch and its rays)
+        const int origin_mode = OM != 0 ? 0 : pa.origin_mode;
+        const int los_mode = OM == 1 ? 0 : pa.los_mode;
+        const int64_t tg = pa.tile_begin + lt;             // tile of the batch; t: tile within its slice
+        const int sl = (int)(tg / pa.tiles_per_slice);
+        const int64_t t = tg - (int64_t)sl * pa.tiles_per_slice;
         if (sl != slice) {                                 // (workgroup-uniform) first tile, or the walk has reached the next slice
             flush();
             slice = sl;
-            ht = P.hts ? P.hts[sl] : P.ht;
-            K = fill_levels(c.nz, m, ht, P.zref);
+            ht = pa.hts ? pa.hts[sl] : pa.ht;
+            K = fill_levels(Ck().nz, m, ht, pa.zref);
             int tz = threadIdx.x;
             asm volatile("" : "+v"(tz));
-            if (reduce) for (int k = tz; k < K * MXCOLS; k += BLOCK) m.mxcol[k] = 0ULL;
+            if (reduce_on()) for (int k = tz; k < K * MXCOLS; k += BLOCK) m.mxcol[k] = 0ULL;
             if (skip_on()) {
                 double* const dabs = skip_dabs(m);
-                unsigned long long* const flr = skip_floor(m, c.nz);
+                const int nz = Ck().nz;
+                unsigned long long* const flr = skip_floor(m, nz);
                 // the slice's table of the wave bound (below): |v_k^n - v_(k-1)^n| for the levels the bound is used for, and a floor of 0
                 for (int k = tz; k < K; k += BLOCK) {
                     const double v1 = m.xv[k], v0 = k >= 2 ? m.xv[k - 1] : v1;
                     double p1 = v1, p0 = v0;
 #pragma unroll
-                    for (int n = 0; n < 7; ++n) { dabs[n * c.nz + k] = fabs(p1 - p0); p1 *= v1; p0 *= v0; }
+                    for (int n = 0; n < 7; ++n) { dabs[n * nz + k] = fabs(p1 - p0); p1 *= v1; p0 *= v0; }
                     flr[k] = 0ULL;
                 }
             }
             __syncthreads();
         }
         if (skip_on()) {
-            unsigned long long* const flr = skip_floor(m, c.nz);
+            unsigned long long* const flr = skip_floor(m, Ck().nz);
             // the floor of this tile's skip decisions: what the workgroup's earlier tiles have folded into the columns (the barriers of
             // walk.next() are behind us).  It only ever trails the columns, and a stale floor merely skips less.  GRID origins have the
             // barrier of the tile's sines / cosines between this store and the decisions that read it; list origins have none: a wave
@@ -818,33 +871,32 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
         // pointers, row / column offsets) is hoisted out of the tile loop and kept live - or spilled - across the polynomial fit.
         int tl = threadIdx.x;
         asm volatile("" : "+v"(tl));
-        const int64_t lbase = (int64_t)sl * P.los_stride;  // this slice's block of the look-vector / incidence arrays
         int64_t i, row = 0, col = 0; bool active;
         if (origin_mode == 0) {
-            const int64_t ty = t / P.tiles_x, tx = t - ty * P.tiles_x;
+            const int64_t ty = t / pa.tiles_x, tx = t - ty * pa.tiles_x;
             row = ty * TILE + (tl >> 4); col = tx * TILE + (tl & 15);
-            active = row < P.ny && col < P.nx;
-            i = row * P.nx + col;
+            active = row < pa.ny && col < pa.nx;
+            i = row * pa.nx + col;
         } else {
             i = t * BLOCK + tl;
-            active = i < P.n;
+            active = i < pa.n;
         }
         // ---- origin: llh -> ECEF (delay.py:262-267)
         double lat = 0, lon = 0, ox = qnan(), oy = qnan(), oz = qnan();
         double hti = ht;                                   // the ray's origin height: the slice's, or its own
-        if (PR || SLOW) { if (per_ray && active) hti = P.ht_ray[i]; }
+        if (PR || SLOW) { if (per_ray && active) hti = pa.ht_ray[i]; }
         RayBase base;
         if (!SLOW && origin_mode == 0) {
             // a tile has 16 distinct latitudes and 16 distinct longitudes: 32 lanes take the sines / cosines for everybody
             // (the previous tile's readers are past the barriers of walk.next())
             if (tl < 32) {
-                const int64_t ty = t / P.tiles_x, tx = t - ty * P.tiles_x;
+                const int64_t ty = t / pa.tiles_x, tx = t - ty * pa.tiles_x;
                 const int64_t r = ty * TILE + (tl & 15), cc = tx * TILE + (tl & 15);
-                const double v = tl < 16 ? (r < P.ny ? P.ypts[r] : 0.0) : (cc < P.nx ? P.xpts[cc] : 0.0);
+                const double v = tl < 16 ? (r < pa.ny ? pa.ypts[r] : 0.0) : (cc < pa.nx ? pa.xpts[cc] : 0.0);
                 tile_trig<LCC>(v, tl, proj, m.trig);
             }
             __syncthreads();
-            if (active) { lat = P.ypts[row]; lon = P.xpts[col]; }
+            if (active) { lat = pa.ypts[row]; lon = pa.xpts[col]; }
             base.lat0 = lat; base.lon0 = lon;
             base.s0 = active ? m.trig[2 * (tl >> 4)] : 0.0; base.c0 = active ? m.trig[2 * (tl >> 4) + 1] : 1.0;
             base.sl0 = active ? m.trig[32 + 2 * (tl & 15)] : 0.0; base.cl0 = active ? m.trig[33 + 2 * (tl & 15)] : 1.0;
@@ -856,11 +908,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
             }
         } else {
             if (active) {
-                if (origin_mode == 0) { lat = P.ypts[row]; lon = P.xpts[col]; }
-                else if (P.lat) { lat = P.lat[i]; lon = P.lon[i]; }
+                if (origin_mode == 0) { lat = pa.ypts[row]; lon = pa.xpts[col]; }
+                else if (pa.lat) { lat = pa.lat[i]; lon = pa.lon[i]; }
                 if (origin_mode == 2) {
-                    ox = P.xyz[3 * i]; oy = P.xyz[3 * i + 1]; oz = P.xyz[3 * i + 2];
-                    if (!P.lat) { double h0_; ecef2lla(ox, oy, oz, lon, lat, h0_); }   // frame for the delta lat/lon formulas
+                    ox = pa.xyz[3 * i]; oy = pa.xyz[3 * i + 1]; oz = pa.xyz[3 * i + 2];
+                    if (!pa.lat) { double h0_; ecef2lla(ox, oy, oz, lon, lat, h0_); }   // frame for the delta lat/lon formulas
                 } else lla2ecef(lat, lon, hti, ox, oy, oz);
             }
             base = make_base(lat, lon);
@@ -868,10 +920,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
         // ---- look vector (delay.py:270)
         double lx = qnan(), ly = qnan(), lz = qnan();
         if (active) {
+            const auto& la = Pk();                         // (this site: the look vectors)
+            const int64_t lbase = (int64_t)sl * la.los_stride;  // this slice's block of the look-vector / incidence arrays
             // (inc / heading: the origin's own sines / cosines are the ones inc_hd_to_ecef would compute again)
-            if (los_mode == 0) { const double* lp = P.los + 3 * (lbase + i); lx = lp[0]; ly = lp[1]; lz = lp[2]; }
-            else if (los_mode == 1) inc_hd_to_ecef_sc(P.inc[lbase + i], P.hd ? P.hd[lbase + i] : P.hd0, base.s0, base.c0, base.sl0, base.cl0, lx, ly, lz);
-            else if (los_mode == 2) inc_hd_to_ecef_sc(P.inc0, P.hd0, base.s0, base.c0, base.sl0, base.cl0, lx, ly, lz);
+            if (los_mode == 0) { const double* lp = la.los + 3 * (lbase + i); lx = lp[0]; ly = lp[1]; lz = lp[2]; }
+            else if (los_mode == 1) inc_hd_to_ecef_sc(la.inc[lbase + i], la.hd ? la.hd[lbase + i] : la.hd0, base.s0, base.c0, base.sl0, base.cl0, lx, ly, lz);
+            else if (los_mode == 2) inc_hd_to_ecef_sc(la.inc0, la.hd0, base.s0, base.c0, base.sl0, base.cl0, lx, ly, lz);
             else { lx = base.c0 * base.cl0; ly = base.c0 * base.sl0; lz = base.s0; }   // zenith (losreader.py:302-316)
         }
         // |l| (1 for unit look vectors): ray length between two crossings = (t_hi - t_lo) * |l|   (losreader.py:821)
@@ -884,7 +938,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
         // on the ground (tools/ray_poly_probe.py), which moves delays by < 1e-10 m - and must not reach the +-180 meridian
         // (the light path does not wrap longitudes).
         const double cosi = (lx * base.c0 * base.cl0 + ly * base.c0 * base.sl0 + lz * base.s0) / nl;
-        const double gam = (P.zref - hti) / (cosi * 6.3e6);
+        const double zref = Pk().zref;
+        const double gam = (zref - hti) / (cosi * 6.3e6);
         // LCC cubes: spherical cones only (HRRR), and the node projections use short series in log(t/t_origin) <= gam / cos(lat)
         // (geodesy_fast.h); an ellipsoidal cone goes to the generic kernels (lcc_forward) ray by ray.
         // The +-180 deg meridian: the light path carries longitude UNWRAPPED (origin + small delta), the reference wraps every
@@ -896,20 +951,23 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
         // Aleutians) then stay on the light path.  On a conic / polar-stereographic cube only the cone's own cut meridian
         // lam0 +- 180 matters (theta = n (lam - lam0) is wrapped there); geographic +-180 is an ordinary meridian.
         bool lon_ok;
-        if (proj.kind == 1) {
-            double dl = lon - proj.lam0 * RAD_TO_DEG;
+        const auto& ja = Jk();
+        const int proj_kind = ja.kind;
+        if (proj_kind == 1) {
+            double dl = lon - ja.lam0 * RAD_TO_DEG;
             dl -= 360.0 * rint(dl * (1.0 / 360.0));
             lon_ok = fabs(dl) + 12.0 < 180.0;
         } else {
-            const bool wrap_pos = (c.x_hi <= 180.0) & (c.x_lo > -168.0), wrap_neg = (c.x_lo >= -180.0) & (c.x_hi < 168.0);
+            const auto& ca = Ck();
+            const double x_lo = ca.x_lo, x_hi = ca.x_hi;
+            const bool wrap_pos = (x_hi <= 180.0) & (x_lo > -168.0), wrap_neg = (x_lo >= -180.0) & (x_hi < 168.0);
             lon_ok = (fabs(lon) + 5.0 < 180.0) || ((fabs(lon) <= 180.0) && (lon > 0.0 ? wrap_pos : wrap_neg));
         }
         const bool fast_ok = !active || ((cosi > 0.05) && (base.c0 > gam + 0.02) && (gam < 0.2 * (base.c0 - gam)) && (gam < 0.035) &&
-                                         lon_ok && (proj.kind != 1 || (proj.e == 0.0 && gam < 0.09 * base.c0)));   // (run-time test: the generic kernels must classify identically)
-        const int64_t slot = lt * BLOCK + tl;
+                                         lon_ok && (proj_kind != 1 || (ja.e == 0.0 && gam < 0.09 * base.c0)));   // (run-time test: the generic kernels must classify identically)
         if (!SLOW) {
             const unsigned long long slow_mask = __ballot(!fast_ok);
-            if (slow_mask && (tl & 63) == 0) atomicAdd(P.nslow, (int)__popcll(slow_mask));
+            if (slow_mask && (tl & 63) == 0) atomicAdd(Pk().nslow, (int)__popcll(slow_mask));
         }
         const bool mine = SLOW ? !fast_ok : fast_ok;      // lanes this instantiation is responsible for
         if (SLOW && !__any(mine)) continue;               // (wave-uniform) nothing to mop up in this wave
@@ -919,7 +977,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
         int k0 = 0; double lo_first = K > 0 ? m.lo[0] : 0.0;
         if (PR || SLOW) {
             if (per_ray) {
-                k0 = first_level(m.ax.ez, c.nz, m.lo, m.hi, m.kz, K, hti, lo_first);
+                k0 = first_level(m.ax.ez, Ck().nz, m.lo, m.hi, m.kz, K, hti, lo_first);
                 if (active && mine && hti < ht) my_flags |= 32;
             }
         }
@@ -929,9 +987,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
         int mxcol_idx = tl & (MXCOLS - 1);
         asm volatile("" : "+v"(mxcol_idx));
         unsigned long long* const mxc = m.mxcol + mxcol_idx;
-        double* const w = P.ws ? P.ws + slot : nullptr;
-        const int64_t ns = P.nslots;
         if constexpr (SLOW) {
+            double* const w = P.ws ? P.ws + (lt * BLOCK + tl) : nullptr;
+            const int64_t ns = P.nslots;
+            const bool reduce = reduce_on();
             // a column of the side buffer for this ray's K+1 crossings: one device atomic per wave, columns handed out in lane
             // order; -1 when the buffer is full (pass 2 then recomputes the crossings)
             int64_t sidx = -1;
@@ -990,9 +1049,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
             // (>= ht) and move monotonically to the crossing, which lies in [0, (zref - ht)/cos(inc)].
             // (an origin ABOVE zref inside zref's model interval - the reference's one reversed segment, low_ht = ht > high_ht = zref - starts its
             // iterates at t0 = ht and ends them at a NEGATIVE ray parameter: both belong to the range.  Unchanged for ht <= zref.)
-            const double t_end = (P.zref - hti) / (cosi * nl);
+            const double t_end = (zref - hti) / (cosi * nl);
             const double t_a = fmin(fmin(0.0, hti), t_end) - 1.0;
-            const double t_b = fmax(fmax(P.zref, hti), t_end) + 1.0;
+            const double t_b = fmax(fmax(zref, hti), t_end) + 1.0;
             const double half = 0.5 * (t_b - t_a), mid = 0.5 * (t_b + t_a);
             const double su = 1.0 / half, ou = -mid * su;
             RayPoly q;
@@ -1001,25 +1060,33 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
             if (shared_lcc) { lorg.rho = m.trig[64 + (tl >> 4)]; lorg.st = m.trig[80 + 2 * (tl & 15)]; lorg.ct = m.trig[81 + 2 * (tl & 15)]; }
             fit_ray_poly<LCC>(base, ox, oy, oz, lx, ly, lz, mid, half, proj, shared_lcc ? &lorg : nullptr, q);
             const double scale = nl * half;                           // ray length per unit of u
-            if (w && mine) {
+            // The record's stores (TileRecords), at each of the three places they stand; the base is formed afresh each time.
+            auto records = [&]() { const auto& a = Pk(); return TileRecords(a.ws, a.nslots, lt, tl); };
+            auto has_ws = [&]() { return Pk().ws != nullptr; };
+            if (has_ws() && mine) {
                 // exact-uniform axes: hand pass 2 the INDEX-space coordinate (v - g0) * (n-1)/(g[n-1]-g0) directly (cell_xy<true>)
-                if (c.exact_y) {
-                    q.lat[0] = (q.lat[0] - c.y_lo) * c.inv_dy;
+                const auto& ca = Ck();
+                if (ca.exact_y) {
+                    const double inv_dy = ca.inv_dy;
+                    q.lat[0] = (q.lat[0] - ca.y_lo) * inv_dy;
 #pragma unroll
-                    for (int n = 1; n < PN; ++n) q.lat[n] *= c.inv_dy;
+                    for (int n = 1; n < PN; ++n) q.lat[n] *= inv_dy;
                 }
-                if (c.exact_x) {
-                    q.lon[0] = (q.lon[0] - c.x_lo) * c.inv_dx;
+                if (ca.exact_x) {
+                    const double inv_dx = ca.inv_dx;
+                    q.lon[0] = (q.lon[0] - ca.x_lo) * inv_dx;
 #pragma unroll
-                    for (int n = 1; n < PN; ++n) q.lon[n] *= c.inv_dx;
+                    for (int n = 1; n < PN; ++n) q.lon[n] *= inv_dx;
                 }
+                const TileRecords w = records();
+                TileRecords::Run r = w.run(WS_POLY_H);
 #pragma unroll
-                for (int n = 0; n < PN; ++n) {
-                    w[(int64_t)(WS_POLY_H + n) * ns] = q.h[n];
-                    w[(int64_t)(WS_POLY_LAT + n) * ns] = q.lat[n];
-                    w[(int64_t)(WS_POLY_LON + n) * ns] = q.lon[n];
-                }
-                w[(int64_t)WS_SCALE * ns] = scale;
+                for (int n = 0; n < PN; ++n) r.next() = q.h[n];
+#pragma unroll
+                for (int n = 0; n < PN; ++n) r.next() = q.lat[n];
+#pragma unroll
+                for (int n = 0; n < PN; ++n) r.next() = q.lon[n];
+                w[WS_SCALE] = scale;
             }
             // getTopOfAtmosphere carried on u: u0 = u(h); u += (h - H(u)) * su / factor   (losreader.py:724-731)
             // Level 0 (ten plain Newton steps per end, losreader.py:770-777) sets the gain of every later level.
@@ -1038,19 +1105,21 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
                                                                                                // interval gives ONE reversed segment (low_ht = ht > high_ht = zref) of positive length
                 last_len = L;
                 gain = su * (L / (hi - lo));                                                   // su / cos_factor, losreader.py:824-825
-                if (w && mine) { w[(int64_t)WS_U0 * ns] = u_lo; w[(int64_t)WS_U1 * ns] = u_hi; }
-                if (reduce) {
+                if (has_ws() && mine) { TileRecords::Run r = records().run(WS_U0); r.next() = u_lo; r.next() = u_hi; }
+                if (reduce_on()) {
                     atomicMax(&mxc[PR ? k0 * MXCOLS : 0], (unsigned long long)__double_as_longlong((cnt && L > 0.0) ? L : 0.0));
-                    if (cnt && !(poly5(q.h, u_lo) < c.z_lo)) my_flags |= 4;                    // first sample of the ray
+                    if (cnt && !(poly5(q.h, u_lo) < Ck().z_lo)) my_flags |= 4;                    // first sample of the ray
                 }
             }
             // Later levels: the three-iteration crossing as a polynomial of the level height (fit_crossing_poly)
             double xc[PX];
             fit_crossing_poly(q.h, su, ou, gain, m.xmap[0], m.xmap[1], xc);
-            if (w && mine) {
+            if (has_ws() && mine) {
+                TileRecords::Run r = records().run(WS_XPOLY);
 #pragma unroll
-                for (int n = 0; n < PX; ++n) w[(int64_t)(WS_XPOLY + n) * ns] = xc[n];
+                for (int n = 0; n < PX; ++n) r.next() = xc[n];
             }
+            const bool reduce = reduce_on();
             if (reduce) {
                 // The level abscissae are read from LDS ahead of the ds_max of the previous pair: LDS operations complete in
                 // order, so a read issued after an atomic would wait for it.
@@ -1095,8 +1164,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
                 bool skip = false;
                 if constexpr (SKIPPABLE) {
                     if (K > 2 && K <= 128 && skip_on()) {
+                        const int nz = Ck().nz;
                         const double* const dabs = skip_dabs(m);
-                        const unsigned long long* const flr = skip_floor(m, c.nz);
+                        const unsigned long long* const flr = skip_floor(m, nz);
                         double S = fabs(xm[0]);
 #pragma unroll
                         for (int n = 1; n < PX; ++n) S += fabs(xm[n]);
@@ -1111,8 +1181,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
 #pragma unroll
                             for (int n = 1; n < PX; ++n) {
                                 const double an = (double)wave_max_nonneg(cnt ? float_above_abs(xm[n]) : 0.0f);
-                                Ba = fma(an, dabs[(n - 1) * c.nz + ka], Ba);
-                                if (K > 64) Bb = fma(an, dabs[(n - 1) * c.nz + kb], Bb);
+                                Ba = fma(an, dabs[(n - 1) * nz + ka], Ba);
+                                if (K > 64) Bb = fma(an, dabs[(n - 1) * nz + kb], Bb);
                             }
                             const double margin = fma((double)a0, 0x1p-44, 0x1p-120);
                             Ba = fma(Ba, 1.0 + 0x1p-30, margin);
@@ -1144,7 +1214,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
                     atomicMax(&mxc[k * MXCOLS], (unsigned long long)__double_as_longlong(fmax(fabs(L), 0.0)));
                 }
                 if (PR ? (k0 + 1 < K) : (K > 1)) last_len = u_end * scale;                    // (only its NaN-ness is used)
-                if (K > 0 && cnt && !(poly5(q.h, u_end) > c.z_hi)) my_flags |= 8;              // last sample of the ray
+                if (K > 0 && cnt && !(poly5(q.h, u_end) > Ck().z_hi)) my_flags |= 8;         // last sample of the ray
             }
             if (reduce && cnt && K > 0) my_flags |= (last_len != last_len) ? 1 : 2;
         }
@@ -1152,7 +1222,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
     flush();
     if (skip_on()) {
         __syncthreads();
-        if (threadIdx.x == 0 && m.K[3] > 0) atomicAdd(P.nslow + 1, m.K[3]);
+        if (threadIdx.x == 0 && m.K[3] > 0) atomicAdd(Pk().nslow + 1, m.K[3]);
     }
 }
 
@@ -1165,7 +1235,9 @@ struct SlicePartition {
 
 // nParts of level k of slice sl (delay.py:283) from the given partition or the slice's length maxima; diverged: the lengths ask for
 // fewer than 2 or more than MAX_NPARTS parts (e.g. look vectors far from unit length) - the loops run with 2, the caller flags it.
-__device__ __forceinline__ int level_nparts(const RayParams& P, int sl, int k, bool& diverged) {
+// (RP: RayParams, by value or in the kernarg segment - RayKernArgs; so below)
+template <typename RP>
+__device__ __forceinline__ int level_nparts(const RP& P, int sl, int k, bool& diverged) {
     int np;
     if (P.nparts_override) np = P.nparts_override[(int64_t)sl * MAX_LEVELS + k];
     else {
@@ -1181,7 +1253,8 @@ __device__ __forceinline__ double level_half_weight(double step) { return 0.5e-6
 // Integration partition of slice sl, after fill_levels (workgroup-uniform; called by every thread): the separate LDS arrays the
 // per-ray-height loops and the generic kernel read, and what the partition decides for every ray of the slice.  (The light slice
 // loop reads the same values from the level table: level_table_kernel.)
-__device__ __forceinline__ SlicePartition fill_partition(const RayParams& P, const RaySmem& m, int sl, int K) {
+template <typename RP>
+__device__ __forceinline__ SlicePartition fill_partition(const RP& P, const RaySmem& m, int sl, int K) {
     int tz = threadIdx.x;
     asm volatile("" : "+v"(tz));                   // (opaque: nothing derived from it is hoisted out of the tile loop and spilled)
     if (tz == 0) m.K[1] = 0;
@@ -1256,7 +1329,8 @@ __global__ __launch_bounds__(BLOCK) void level_table_kernel(CubeView<T2> c, RayP
 }
 
 // Thread tl of tile t (within its slice) -> ray i of the batch; active: the ray exists (false: tile padding).
-__device__ __forceinline__ void tile_ray(const RayParams& P, int64_t t, int tl, int64_t& i, bool& active) {
+template <typename RP>
+__device__ __forceinline__ void tile_ray(const RP& P, int64_t t, int tl, int64_t& i, bool& active) {
     if (P.origin_mode == 0) {
         const int64_t ty = t / P.tiles_x, tx = t - ty * P.tiles_x;
         const int64_t row = ty * TILE + (tl >> 4), col = tx * TILE + (tl & 15);
@@ -1271,15 +1345,19 @@ __device__ __forceinline__ void tile_ray(const RayParams& P, int64_t t, int tl, 
 // A light ray's record (w: the ray's slot of the workspace, ns: its field stride): the three ray polynomials and the crossing
 // polynomial.  The level crossings come from the latter as the loop reaches them (7 FMAs, no global loads inside the loop besides
 // the gathers, so the only memory waits are on a sample's own corners).
+// A record is read once per pass 2 and there are 232 B of it per ray - 3.7 GB on the headline step, against a cube of 58 MB that every
+// sample gathers from: the loads are marked nontemporal (record_field), so that the stream of records does not push the cube's lines
+// out of the L2.  Same values, so same bits.
+__device__ __forceinline__ double record_field(const double* w, int64_t ns, int f) { return __builtin_nontemporal_load(&w[(int64_t)f * ns]); }
 __device__ __forceinline__ void load_ray_record(const double* w, int64_t ns, RayPoly& q, double (&xc)[PX]) {
 #pragma unroll
     for (int n = 0; n < PN; ++n) {
-        q.h[n] = w[(int64_t)(WS_POLY_H + n) * ns];
-        q.lat[n] = w[(int64_t)(WS_POLY_LAT + n) * ns];
-        q.lon[n] = w[(int64_t)(WS_POLY_LON + n) * ns];
+        q.h[n] = record_field(w, ns, WS_POLY_H + n);
+        q.lat[n] = record_field(w, ns, WS_POLY_LAT + n);
+        q.lon[n] = record_field(w, ns, WS_POLY_LON + n);
     }
 #pragma unroll
-    for (int n = 0; n < PX; ++n) xc[n] = w[(int64_t)(WS_XPOLY + n) * ns];
+    for (int n = 0; n < PX; ++n) xc[n] = record_field(w, ns, WS_XPOLY + n);
 }
 
 // The no-check proof of a lane (REGULAR grids; the kernels take it wave-wide: __all); u0r, u1r: fields WS_U0, WS_U1 of its record,
@@ -1517,6 +1595,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
     static_assert(!SLOW || !PR, "the generic kernel looks at P.ht_ray at run time");
     if (SLOW && *P.nslow == 0) return;
     const bool per_ray = PR || (SLOW && P.ht_ray != nullptr);
+    // (the uniform parameters of the tile body: crossings_kernel.  The cube view stays by value: the level loops read it as SGPR operands)
+    auto Pk = [&]() -> decltype(auto) { if constexpr (SLOW) return (P); else return (ray_args<T2>()->P); };
     constexpr bool REGULAR = GRID == 1;
     CubeView<T2> c = c_in;
     if (REGULAR) { c.exact_y = 1; c.exact_x = 1; c.small = 1; }
@@ -1535,24 +1615,25 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
     bool clamp_lo = false, clamp_hi = false, clamp_any = false;
     TileWalk walk(P.tile_count, P.tile_ctr, m.K + 2);
     int64_t lt;
-    while (walk.next(P.tile_count, lt)) {
-        const int64_t tg = P.tile_begin + lt;              // tile of the batch; t: tile within its slice
-        const int sl = (int)(tg / P.tiles_per_slice);
-        const int64_t t = tg - (int64_t)sl * P.tiles_per_slice;
+    while (walk.next(Pk().tile_count, lt)) {
+        const auto& pa = Pk();                             // (this site: the tile's place in the batch, its rays and their records)
+        const int64_t tg = pa.tile_begin + lt;             // tile of the batch; t: tile within its slice
+        const int sl = (int)(tg / pa.tiles_per_slice);
+        const int64_t t = tg - (int64_t)sl * pa.tiles_per_slice;
         if (sl != slice) {                                 // (workgroup-uniform) the slice's level table and integration partition
             slice = sl;
-            K = fill_levels(c.nz, m, P.hts ? P.hts[sl] : P.ht, P.zref);
-            const SlicePartition part = fill_partition(P, m, sl, K);
+            K = fill_levels(c.nz, m, pa.hts ? pa.hts[sl] : pa.ht, pa.zref);
+            const SlicePartition part = fill_partition(pa, m, sl, K);
             poison = part.poison; clamp_lo = part.clamp_lo; clamp_hi = part.clamp_hi;
             clamp_any = clamp_lo | clamp_hi;
         }
         int tl = threadIdx.x;
         asm volatile("" : "+v"(tl));                       // per-tile opaque copy of the thread index (see crossings_kernel)
         int64_t i; bool active;
-        tile_ray(P, t, tl, i, active);
-        const double* w = P.ws + (lt * BLOCK + tl);
-        const int64_t ns = P.nslots;
-        const double scale_rec = w[(int64_t)WS_SCALE * ns];         // light ray: ray length per unit of u (> 0 or NaN); generic ray: 0
+        tile_ray(pa, t, tl, i, active);
+        const double* w = pa.ws + (lt * BLOCK + tl);
+        const int64_t ns = pa.nslots;
+        const double scale_rec = SLOW ? w[(int64_t)WS_SCALE * ns] : record_field(w, ns, WS_SCALE);   // light ray: ray length per unit of u (> 0 or NaN); generic ray: 0
         const bool fast_ok = !active || scale_rec != 0.0;
         const bool mine = SLOW ? !fast_ok : fast_ok;
         if (SLOW && !__any(mine)) continue;
@@ -1560,7 +1641,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
         // per-ray heights: the ray's first level of the slice table, found exactly as pass 1 found it (idle lanes: none)
         int k0 = 0; double lo_first = K > 0 ? m.lo[0] : 0.0;
         if (PR || SLOW) {
-            if (per_ray) k0 = (active && mine) ? first_level(m.ax.ez, c.nz, m.lo, m.hi, m.kz, K, P.ht_ray[i], lo_first) : K;
+            if (per_ray) k0 = (active && mine) ? first_level(m.ax.ez, c.nz, m.lo, m.hi, m.kz, K, pa.ht_ray[i], lo_first) : K;
         }
         if constexpr (!SLOW) {
             // ---- light rays: the two level loops above, on this one cube ------------------------------------------------
@@ -1568,12 +1649,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
             double xc[PX];
             load_ray_record(w, ns, q, xc);
             const double scale = scale_rec;
-            const double u0r = w[(int64_t)WS_U0 * ns], u1r = w[(int64_t)WS_U1 * ns];
+            const double u0r = record_field(w, ns, WS_U0), u1r = record_field(w, ns, WS_U1);
             const EpochCubes<T2, 1> one{{c.v}};
             const unsigned long long live = __builtin_amdgcn_ballot_w64(active && mine);
             // the slice's records of the level table (per tile, from the scalar slice index: a pointer kept across the slice test would
             // not be wave-uniform for the compiler, and the records would come through vector loads)
-            const LevelRec* const lev = PR ? nullptr : P.lev + (int64_t)__builtin_amdgcn_readfirstlane(sl) * (c.nz + 1);
+            const LevelRec* const lev = PR ? nullptr : pa.lev + (int64_t)__builtin_amdgcn_readfirstlane(sl) * (c.nz + 1);
             auto run = [&](auto nochk) {
                 constexpr bool NC = decltype(nochk)::value;
                 if constexpr (PR) march_ray_height_levels<T2, 1, NC>(c, one, m, q, xc, u0r, u1r, K, k0, lo_first, clamp_lo, clamp_hi, &acc_w, &acc_h);
@@ -1705,7 +1786,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
             };
             if (REGULAR && __all(lane_safe)) {
                 if constexpr (STAGED) {
-                    if (P.stage_f64 && c.ny >= 4 && c.nx >= 4 && c.nz >= 3) run_staged();      // (the staged block holds z entries zb .. zb+2, zb >= 0)
+                    if (Pk().stage_f64 && c.ny >= 4 && c.nx >= 4 && c.nz >= 3) run_staged();      // (the staged block holds z entries zb .. zb+2, zb >= 0)
                     else run(std::integral_constant<bool, true>{});
                 } else run(std::integral_constant<bool, true>{});
             }
@@ -1767,7 +1848,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
                 }
             }
         }
-        if (active && mine) { const int64_t o = (int64_t)sl * P.n + i; P.wet[o] = acc_w + poison; P.hyd[o] = acc_h + poison; }
+        if (active && mine) { const auto& oa = Pk(); const int64_t o = (int64_t)sl * oa.n + i; oa.wet[o] = acc_w + poison; oa.hyd[o] = acc_h + poison; }
     }
 }
 
