@@ -1,7 +1,8 @@
 // libraider_hip.so - C ABI (include/raider_hip.h) + the remaining kernels.  gfx950 only.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC raider_hip.hip -o libraider_hip.so
-// The point path (launch_interp, launch_interp_epochs, the paired blend of interp3_impl) picks its kernels' element type with by_dtype and
-// checks two cubes' grids with same_grid_dtype, both above rdr_cube_blend; the gathers' one device body is gather_points (cube_kernels.h).
+// Every launcher of a kernel templated on the cube's element type (the point path, the two ray passes, the cube build) picks it with by_dtype
+// (beside launch_lds); two cubes' grids are compared with same_grid_dtype (above rdr_cube_blend); the gathers' one device body is gather_points
+// (cube_kernels.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -200,15 +201,21 @@ static int dev_malloc(rdr_ctx* ctx, void** p, size_t bytes) {
     return RDR_OK;
 }
 
+// `b` holds at least `bytes` (a new allocation: at least min_cap).  Too small: the context stream is waited for - work on it may still
+// use the old buffer -, the old buffer is freed, the new one allocated, in that order (the device never holds both).
+static int grow(rdr_ctx* ctx, DevBuf& b, size_t bytes, size_t min_cap = 0) {
+    if (b.cap >= bytes) return RDR_OK;
+    if (b.p) { HIPCHECK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHECK(ctx, hipFree(b.p)); b.p = nullptr; b.cap = 0; }
+    const size_t cap = std::max(bytes, min_cap);
+    const int rc = dev_malloc(ctx, &b.p, cap); if (rc) return rc;
+    b.cap = cap;
+    return RDR_OK;
+}
+
 static int ensure(rdr_ctx* ctx, int s, size_t bytes, void** out) {
     DevBuf& b = ctx->slot[s];
     if (bytes > ((size_t)1 << 46)) return fail(ctx, RDR_ERR_INVALID, "a size argument is negative or beyond 64 TiB");
-    if (b.cap < bytes) {
-        if (b.p) { HIPCHECK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHECK(ctx, hipFree(b.p)); b.p = nullptr; b.cap = 0; }
-        size_t cap = std::max(bytes, (size_t)1 << 16);
-        int rc = dev_malloc(ctx, &b.p, cap); if (rc) return rc;
-        b.cap = cap;
-    }
+    const int rc = grow(ctx, b, bytes, (size_t)1 << 16); if (rc) return rc;
     *out = b.p;
     return RDR_OK;
 }
@@ -390,6 +397,13 @@ static hipError_t launch_lds(void (*kern)(KArgs...), dim3 g, dim3 b, size_t sm, 
     }
     hipLaunchKernelGGL(kern, g, b, sm, s, std::forward<Args>(args)...);
     return hipGetLastError();
+}
+
+// f(float2()) or f(double2()) by the cube's dtype, and what f returns: a generic lambda takes the element type of its kernel from the tag
+template <typename F>
+static auto by_dtype(const rdr_cube* q, F&& f) -> decltype(f(float2())) {
+    if (q->dtype == RDR_F32) return f(float2());
+    return f(double2());
 }
 
 // ---- kernels other than the two ray passes (raider_kernels.h) ---------------------------------------------------------
@@ -1120,12 +1134,6 @@ static bool same_grid_dtype(const rdr_cube* a, const rdr_cube* b) {
     return a->ny == b->ny && a->nx == b->nx && a->nz == b->nz && a->dtype == b->dtype && a->ys == b->ys && a->xs == b->xs && a->zs == b->zs;
 }
 
-// f(float2()) or f(double2()) by the cube's dtype: a generic lambda takes the element type of its kernel from the tag (the point path)
-template <typename F>
-static void by_dtype(const rdr_cube* q, F&& f) {
-    if (q->dtype == RDR_F32) f(float2()); else f(double2());
-}
-
 int rdr_cube_blend(rdr_ctx* c, const rdr_cube* a, double w1, const rdr_cube* b, double w2, rdr_cube** out) {
     if (!c || !a || !b || !out) return fail(c, RDR_ERR_INVALID, "rdr_cube_blend: NULL argument");
     note_use(c, a); note_use(c, b);
@@ -1145,12 +1153,10 @@ int rdr_cube_blend(rdr_ctx* c, const rdr_cube* a, double w1, const rdr_cube* b, 
     const int g = grid_for((nscal / vec + 3) / 4, 256, 1 << 22);
     {
         KTimer t(c, 3);
-        if (a->dtype == RDR_F32)
-            hipLaunchKernelGGL((blend_kernel<float>), dim3(g), dim3(256), 0, c->stream, (const float*)a->d_vals, (float)w1,
-                               (const float*)b->d_vals, (float)w2, (float*)q->d_vals, nscal);
-        else
-            hipLaunchKernelGGL((blend_kernel<double>), dim3(g), dim3(256), 0, c->stream, (const double*)a->d_vals, w1,
-                               (const double*)b->d_vals, w2, (double*)q->d_vals, nscal);
+        by_dtype(a, [&](auto tag) {
+            typedef decltype(tag.x) T;
+            hipLaunchKernelGGL((blend_kernel<T>), dim3(g), dim3(256), 0, c->stream, (const T*)a->d_vals, (T)w1, (const T*)b->d_vals, (T)w2, (T*)q->d_vals, nscal);
+        });
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { rdr_cube_destroy(q); return fail(c, RDR_ERR_HIP, hipGetErrorString(e)); }
@@ -1218,10 +1224,7 @@ int rdr_cube_blend_weighted(rdr_ctx* c, const rdr_cube* const* cubes, int32_t nd
     const int g = grid_for(total, 256, c->num_cus * 8);
     {
         KTimer t(c, 3);
-        if (a->dtype == RDR_F32)
-            hipLaunchKernelGGL((blend_weighted_kernel<float2>), dim3(g), dim3(256), 0, c->stream, S, (const double*)dwt, a->ny, a->nx, a->nz, (double2*)q->d_vals);
-        else
-            hipLaunchKernelGGL((blend_weighted_kernel<double2>), dim3(g), dim3(256), 0, c->stream, S, (const double*)dwt, a->ny, a->nx, a->nz, (double2*)q->d_vals);
+        by_dtype(a, [&](auto t) { hipLaunchKernelGGL((blend_weighted_kernel<decltype(t)>), dim3(g), dim3(256), 0, c->stream, S, (const double*)dwt, a->ny, a->nx, a->nz, (double2*)q->d_vals); });
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1274,10 +1277,10 @@ int rdr_cube_read(rdr_ctx* c, const rdr_cube* q, void* wet, void* hydro) {
     int rc = ensure(c, SLOT_OUT0, total * esz, &dw); if (rc) return rc;
     rc = ensure(c, SLOT_OUT1, total * esz, &dh); if (rc) return rc;
     const int g = grid_for(total, 256, c->num_cus * 8);
-    if (q->dtype == RDR_F32)
-        hipLaunchKernelGGL((unpack_cube_kernel<float, float2>), dim3(g), dim3(256), 0, c->stream, (const float2*)q->d_vals, (float*)dw, (float*)dh, total);
-    else
-        hipLaunchKernelGGL((unpack_cube_kernel<double, double2>), dim3(g), dim3(256), 0, c->stream, (const double2*)q->d_vals, (double*)dw, (double*)dh, total);
+    by_dtype(q, [&](auto tag) {
+        typedef decltype(tag) T2; typedef decltype(tag.x) T;
+        hipLaunchKernelGGL((unpack_cube_kernel<T, T2>), dim3(g), dim3(256), 0, c->stream, (const T2*)q->d_vals, (T*)dw, (T*)dh, total);
+    });
     HIPCHECK(c, hipGetLastError());
     HIPCHECK(c, hipMemcpyAsync(wet, dw, total * esz, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipMemcpyAsync(hydro, dh, total * esz, hipMemcpyDeviceToHost, c->stream));
@@ -1306,8 +1309,7 @@ static int quad_build(rdr_ctx* c, const rdr_cube* q_any) {
                  ~Pub() { if (ok) { q->quad_bytes = need; q->quad_nblk = nblk; q->d_quad = p; } else (void)hipFree(p); } } pub{q, dq, need, nblk};
     const int64_t parts = (int64_t)(need / 16);
     const int g = (grid_for(parts, 256, c->num_cus * 32) + 7) / 8 * 8;       // a multiple of 8: one share of the ranges per XCD (quad_build_kernel)
-    if (q->dtype == RDR_F32) hipLaunchKernelGGL((quad_build_kernel<float2>), dim3(g), dim3(256), 0, c->stream, (const float2*)q->d_vals, (int)q->ny, (int)q->nx, (int)q->nz, nblk, (uint4*)dq);
-    else hipLaunchKernelGGL((quad_build_kernel<double2>), dim3(g), dim3(256), 0, c->stream, (const double2*)q->d_vals, (int)q->ny, (int)q->nx, (int)q->nz, nblk, (uint4*)dq);
+    by_dtype(q, [&](auto t) { hipLaunchKernelGGL((quad_build_kernel<decltype(t)>), dim3(g), dim3(256), 0, c->stream, (const decltype(t)*)q->d_vals, (int)q->ny, (int)q->nx, (int)q->nz, nblk, (uint4*)dq); });
     HIPCHECK(c, hipGetLastError());
     // one-time, like rdr_cube_create: the copy must be complete before it is PUBLISHED - any other stream (a context switched to
     // torch's stream, a second context sharing the cube) may read it from then on.  0.7 ms of a build that happens once per cube.
@@ -1395,6 +1397,21 @@ struct StreamsQuiesce {
     }
 };
 
+// The events of one pipelined call, destroyed on every exit path.  Declared BEFORE the call's StreamsQuiesce: they are then destroyed
+// only once the streams are idle.
+struct EventList {
+    std::vector<hipEvent_t> v;
+    ~EventList() { for (auto& e : v) if (e) (void)hipEventDestroy(e); }
+    bool add(size_t n) {                        // n more events (no timing); false: one of them could not be created
+        for (size_t i = 0; i < n; ++i) {
+            hipEvent_t e = nullptr;
+            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return false;
+            v.push_back(e);
+        }
+        return true;
+    }
+};
+
 // Large HOST point sets: the points go up (copy stream) and the delays come down (download stream) in chunks, the download of chunk k
 // under the upload of chunk k+1 (PCIe is full duplex), the gathers on the ctx stream in between - 40-48 B per point cross the link,
 // which is all such a call costs (the gather itself: 0.03 ms per 10^6 points).  Uploads on their OWN stream also run under whatever
@@ -1421,10 +1438,8 @@ static int interp_pipeline_impl(rdr_ctx* c, const char* who, const rdr_cube* q, 
     if (hydro) { rc = ensure(c, slots[5], (size_t)n * D * 8, &dh); if (rc) return rc; }
     // chunks of >= 512 k points (a copy call costs 10-20 us: 1 MB copies would spend as long on calls as on bytes), at most 8
     const int nchunk = (int)std::max<int64_t>(1, std::min<int64_t>(8, n >> 19));
-    struct EventList { std::vector<hipEvent_t> v; ~EventList() { for (auto& e : v) if (e) (void)hipEventDestroy(e); } } evs;
-    evs.v.assign((size_t)2 * nchunk, nullptr);
-    for (auto& e : evs.v)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(c, RDR_ERR_HIP, std::string(who) + ": event creation failed");
+    EventList evs;
+    if (!evs.add((size_t)2 * nchunk)) return fail(c, RDR_ERR_HIP, std::string(who) + ": event creation failed");
     StreamsQuiesce quiesce(c);                  // (declared after the events: they are destroyed only once the streams are idle)
     auto up = [&](void* dst, const void* src, size_t bytes) {
         c->point_upload_bytes += (int64_t)bytes;
@@ -1484,6 +1499,41 @@ static int stage_points_in(rdr_ctx* ctx, int s, const void* src, size_t bytes, i
     return stage_in(ctx, s, src, bytes, loc, dev);
 }
 
+// the pipelined gather's scratch (y, x, z, proj, wet, hydro) of the gather entries, and of the point-delay drivers (whose build holds the others)
+static const int k_gather_slots[6] = {SLOT_IN0, SLOT_IN1, SLOT_IN2, SLOT_IN3, SLOT_OUT0, SLOT_OUT1};
+static const int k_point_slots[6] = {SLOT_PT0, SLOT_PT1, SLOT_PT2, SLOT_PT3, SLOT_PT4, SLOT_PT5};
+
+static PointQuery make_query(int pmode, double inc0) {
+    PointQuery Q; std::memset(&Q, 0, sizeof(Q));
+    Q.pmode = pmode; Q.inc0 = inc0;
+    return Q;
+}
+
+// The gather of n points at `loc` for D dates, NOT pipelined, in this order: y, x, z and the divisors (pstride == n: D blocks of them)
+// through stage_points_in - so counted - into SLOT_IN0..3, the [D][n] outputs staged in SLOT_OUT0 / 1, launch(Q, dw, dh) and its error,
+// the downloads, the host's wait when the outputs are its own.
+template <typename Launch>
+static int gather_staged(rdr_ctx* c, PointQuery Q, const double* y, const double* x, const double* z, const double* proj, int64_t pstride, int64_t n, int D,
+                         double* wet, double* hydro, int loc, Launch&& launch) {
+    const size_t ystride = x ? 1 : 3;                                  // doubles per point behind `y`
+    const size_t np = pstride ? (size_t)D : 1, obytes = (size_t)n * (size_t)D * 8;
+    const void* d; void *dw = nullptr, *dh = nullptr;
+    int rc = stage_points_in(c, SLOT_IN0, y, (size_t)n * ystride * 8, loc, &d); if (rc) return rc; Q.y = (const double*)d;
+    if (x) {
+        rc = stage_points_in(c, SLOT_IN1, x, (size_t)n * 8, loc, &d); if (rc) return rc; Q.x = (const double*)d;
+        rc = stage_points_in(c, SLOT_IN2, z, (size_t)n * 8, loc, &d); if (rc) return rc; Q.z = (const double*)d;
+    }
+    if (Q.pmode == 1 || Q.pmode == 3) { rc = stage_points_in(c, SLOT_IN3, proj, (size_t)n * np * 8, loc, &d); if (rc) return rc; Q.proj = (const double*)d; }
+    if (wet) { rc = stage_out(c, SLOT_OUT0, wet, obytes, loc, &dw); if (rc) return rc; }
+    if (hydro) { rc = stage_out(c, SLOT_OUT1, hydro, obytes, loc, &dh); if (rc) return rc; }
+    launch(Q, (double*)dw, (double*)dh);
+    HIPCHECK(c, hipGetLastError());
+    rc = finish_out(c, wet, dw, obytes, loc); if (rc) return rc;
+    rc = finish_out(c, hydro, dh, obytes, loc); if (rc) return rc;
+    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return RDR_OK;
+}
+
 // the point query behind rdr_interp3 / rdr_interp3_project: y/x/z three arrays (x != NULL) or y = packed (n,3); pmode / proj / inc0 as
 // PointQuery (cube_kernels.h); either output may be NULL (it is then neither written nor downloaded)
 static int interp3_impl(rdr_ctx* c, const char* who, const rdr_cube* q, const double* y, const double* x, const double* z, int64_t n, int pmode,
@@ -1519,31 +1569,14 @@ static int interp3_impl(rdr_ctx* c, const char* who, const rdr_cube* q, const do
         HIPCHECK(c, hipGetLastError());
         B.pair = dp;
     }
-    PointQuery Q; std::memset(&Q, 0, sizeof(Q));
-    Q.pmode = pmode; Q.inc0 = inc0;
-    const bool has_proj = pmode == 1 || pmode == 3;
-    const size_t ystride = x ? 1 : 3;                                  // doubles per point behind `y`
+    const PointQuery Q = make_query(pmode, inc0);
     const bool quad = !B.vb && quad_wanted(c, q, n);
     if (quad) { rc = quad_build(c, q); if (rc) return rc; }
     if (loc == RDR_HOST && n >= (1 << 18) && pipelining()) {
-        static const int slots[6] = {SLOT_IN0, SLOT_IN1, SLOT_IN2, SLOT_IN3, SLOT_OUT0, SLOT_OUT1};
-        return interp_pipeline(c, who, q, quad, y, x, z, n, Q, proj, wet, hydro, slots, B);
+        return interp_pipeline(c, who, q, quad, y, x, z, n, Q, proj, wet, hydro, k_gather_slots, B);
     }
-    const void* d; void *dw = nullptr, *dh = nullptr;
-    rc = stage_points_in(c, SLOT_IN0, y, (size_t)n * ystride * 8, loc, &d); if (rc) return rc; Q.y = (const double*)d;
-    if (x) {
-        rc = stage_points_in(c, SLOT_IN1, x, (size_t)n * 8, loc, &d); if (rc) return rc; Q.x = (const double*)d;
-        rc = stage_points_in(c, SLOT_IN2, z, (size_t)n * 8, loc, &d); if (rc) return rc; Q.z = (const double*)d;
-    }
-    if (has_proj) { rc = stage_points_in(c, SLOT_IN3, proj, (size_t)n * 8, loc, &d); if (rc) return rc; Q.proj = (const double*)d; }
-    if (wet) { rc = stage_out(c, SLOT_OUT0, wet, (size_t)n * 8, loc, &dw); if (rc) return rc; }
-    if (hydro) { rc = stage_out(c, SLOT_OUT1, hydro, (size_t)n * 8, loc, &dh); if (rc) return rc; }
-    launch_interp(c, q, Q, n, (double*)dw, (double*)dh, quad, B);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, wet, dw, (size_t)n * 8, loc); if (rc) return rc;
-    rc = finish_out(c, hydro, dh, (size_t)n * 8, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    return gather_staged(c, Q, y, x, z, proj, 0, n, 1, wet, hydro, loc,
+                         [&](const PointQuery& Qd, double* dw, double* dh) { launch_interp(c, q, Qd, n, dw, dh, quad, B); });
 }
 
 int rdr_interp3(rdr_ctx* c, const rdr_cube* q, const double* pts, int64_t n, double* wet, double* hydro, int loc) {
@@ -1623,28 +1656,20 @@ static int build_cube_impl(rdr_ctx* c, const rdr_cube* q, const double* xpts, in
         const int gs = grid_for(nodes + nz, 256, c->num_cus * 8);
         const double *qy = nullptr, *qx = nullptr;
         if (grid) { rc = grid_nodes(c, *grid, (const double*)dx, nx, (const double*)dy, ny, &q->proj, tbl, tbl + nodes, tbl + 2 * nodes, tbl + 3 * nodes, &qy, &qx); if (rc) return rc; }
-        hipError_t e;
-        if (q->dtype == RDR_F32) {
+        const hipError_t e = by_dtype(q, [&](auto tag) {
+            typedef decltype(tag) T2;
+            hipError_t e_;
             if (grid)
-                e = launch_lds(build_cube_setup_table_kernel<float2>, dim3(gs), dim3(256), axes_smem(q), c->stream, make_view<float2>(q), qy, qx, nodes,
-                               (const double*)dz, nz, (BuildNode*)dn, (BuildLevel*)dl, (int)axes_fit_lds(q));
+                e_ = launch_lds(build_cube_setup_table_kernel<T2>, dim3(gs), dim3(256), axes_smem(q), c->stream, make_view<T2>(q), qy, qx, nodes,
+                                (const double*)dz, nz, (BuildNode*)dn, (BuildLevel*)dl, (int)axes_fit_lds(q));
             else
-                e = launch_lds(build_cube_setup_kernel<float2>, dim3(gs), dim3(256), axes_smem(q), c->stream, make_view<float2>(q), q->proj, (const double*)dx, nx,
-                               (const double*)dy, ny, (const double*)dz, nz, (BuildNode*)dn, (BuildLevel*)dl, (int)axes_fit_lds(q));
-            if (e == hipSuccess)
-                e = launch_lds(build_cube_kernel<float2>, g, dim3(256), sm, c->stream, (const float2*)q->d_vals, (int)q->ny, (int)q->nx, (int)q->nz,
-                               (const BuildNode*)dn, (const BuildLevel*)dl, nx, ny, nz, zchunk, (double*)dw, (double*)dh);
-        } else {
-            if (grid)
-                e = launch_lds(build_cube_setup_table_kernel<double2>, dim3(gs), dim3(256), axes_smem(q), c->stream, make_view<double2>(q), qy, qx, nodes,
-                               (const double*)dz, nz, (BuildNode*)dn, (BuildLevel*)dl, (int)axes_fit_lds(q));
-            else
-                e = launch_lds(build_cube_setup_kernel<double2>, dim3(gs), dim3(256), axes_smem(q), c->stream, make_view<double2>(q), q->proj, (const double*)dx, nx,
-                               (const double*)dy, ny, (const double*)dz, nz, (BuildNode*)dn, (BuildLevel*)dl, (int)axes_fit_lds(q));
-            if (e == hipSuccess)
-                e = launch_lds(build_cube_kernel<double2>, g, dim3(256), sm, c->stream, (const double2*)q->d_vals, (int)q->ny, (int)q->nx, (int)q->nz,
-                               (const BuildNode*)dn, (const BuildLevel*)dl, nx, ny, nz, zchunk, (double*)dw, (double*)dh);
-        }
+                e_ = launch_lds(build_cube_setup_kernel<T2>, dim3(gs), dim3(256), axes_smem(q), c->stream, make_view<T2>(q), q->proj, (const double*)dx, nx,
+                                (const double*)dy, ny, (const double*)dz, nz, (BuildNode*)dn, (BuildLevel*)dl, (int)axes_fit_lds(q));
+            if (e_ == hipSuccess)
+                e_ = launch_lds(build_cube_kernel<T2>, g, dim3(256), sm, c->stream, (const T2*)q->d_vals, (int)q->ny, (int)q->nx, (int)q->nz,
+                                (const BuildNode*)dn, (const BuildLevel*)dl, nx, ny, nz, zchunk, (double*)dw, (double*)dh);
+            return e_;
+        });
         if (e != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("build_cube_kernel launch: ") + hipGetErrorString(e));
     }
     if (keep) { keep[0] = (double*)dw; keep[1] = (double*)dh; return RDR_OK; }
@@ -1743,6 +1768,30 @@ static int scratch_cube_init(rdr_cube& tmp, rdr_ctx* c, const double* xpts, int6
     return 0;
 }
 
+// what the point-delay drivers ask of their output grid
+static int point_grid_args(rdr_ctx* c, const std::string& w, int64_t nx, int64_t ny, int64_t nz) {
+    if (nx < 2 || ny < 2 || nz < 2) return fail(c, RDR_ERR_INVALID, w + ": the delay cube needs two nodes per axis");
+    if (nz > MAX_LEVELS) return fail(c, RDR_ERR_INVALID, w + ": more than 512 height levels");
+    if (ny + nx + nz > 100000) return fail(c, RDR_ERR_INVALID, w + ": axes too long");
+    return RDR_OK;
+}
+
+// The intermediate cube(s) of the point-delay drivers, in this order: `tmp` described (scratch_cube_init), hipSetDevice, D value regions
+// in SLOT_TMPCUBE (tmp.d_vals: the first), the axes' slot (tmp.d_axes), and ax = ys | xs | zs - which the CALLER sends up, on its
+// stream and under its StreamsQuiesce.  Scratch objects: values and axes live in context slots, nothing is ever destroyed.
+static int scratch_cube_setup(rdr_ctx* c, rdr_cube& tmp, const double* xpts, int64_t nx, const double* ypts, int64_t ny, const double* zpts, int64_t nz,
+                              int D, int* fy, int* fx, int* fz, std::vector<double>& ax) {
+    if (scratch_cube_init(tmp, c, xpts, nx, ypts, ny, zpts, nz, fy, fx, fz))
+        return fail(c, RDR_ERR_INVALID, "The points in each dimension must be strictly ascending or descending (and >= 2)");
+    HIPCHECK(c, hipSetDevice(c->device));
+    void *dvals, *daxes;
+    int rc = ensure(c, SLOT_TMPCUBE, (size_t)ny * nx * nz * sizeof(double2) * (size_t)D, &dvals); if (rc) return rc;
+    rc = ensure(c, SLOT_TMPAXES, (size_t)(ny + nx + nz) * 8, &daxes); if (rc) return rc;
+    tmp.d_vals = dvals; tmp.d_axes = (double*)daxes;
+    ax.insert(ax.end(), tmp.ys.begin(), tmp.ys.end()); ax.insert(ax.end(), tmp.xs.begin(), tmp.xs.end()); ax.insert(ax.end(), tmp.zs.begin(), tmp.zs.end());
+    return RDR_OK;
+}
+
 // planar (z, y, x) build results -> the interleaved (y, x, z) values of the intermediate cube, NaN verdict into *nf
 static void pack_planar(rdr_ctx* c, double* const* planar, double2* dvals, int64_t ny, int64_t nx, int64_t nz, int fy, int fx, int fz, int* nf) {
     if (nx >= 8 && nz >= 8)        // x is contiguous - the LDS-transposing packer (cube_kernels.h)
@@ -1770,41 +1819,26 @@ static void scratch_trim_point_delays(rdr_ctx* c) {
 static int point_delays_impl(rdr_ctx* c, const char* who, const rdr_cube* q, const GridCrs* grid, const double* xpts, int64_t nx, const double* ypts,
                              int64_t ny, const double* zpts, int64_t nz, const double* y, const double* x, const double* z, int64_t n, int proj_mode,
                              const double* proj, double inc0, double* wet, double* hydro, int32_t* cube_has_nan) {
-    const std::string w(who);
-    if (nx < 2 || ny < 2 || nz < 2) return fail(c, RDR_ERR_INVALID, w + ": the delay cube needs two nodes per axis");
-    if (nz > MAX_LEVELS) return fail(c, RDR_ERR_INVALID, w + ": more than 512 height levels");
-    if (ny + nx + nz > 100000) return fail(c, RDR_ERR_INVALID, w + ": axes too long");
-    int rc = point_query_args(c, who, y, x, z, n, proj_mode, proj, wet, hydro); if (rc) return rc;
-    // the intermediate cube: a scratch object (values and axes in context slots), never destroyed
+    int rc = point_grid_args(c, who, nx, ny, nz); if (rc) return rc;
+    rc = point_query_args(c, who, y, x, z, n, proj_mode, proj, wet, hydro); if (rc) return rc;
     int fy, fx, fz;
     rdr_cube tmp;
-    if (scratch_cube_init(tmp, c, xpts, nx, ypts, ny, zpts, nz, &fy, &fx, &fz))
-        return fail(c, RDR_ERR_INVALID, "The points in each dimension must be strictly ascending or descending (and >= 2)");
-    HIPCHECK(c, hipSetDevice(c->device));
-    const size_t total = (size_t)ny * nx * nz;
-    void *dvals, *daxes;
-    rc = ensure(c, SLOT_TMPCUBE, total * sizeof(double2), &dvals); if (rc) return rc;
-    rc = ensure(c, SLOT_TMPAXES, (size_t)(ny + nx + nz) * 8, &daxes); if (rc) return rc;
-    tmp.d_vals = dvals; tmp.d_axes = (double*)daxes;
     std::vector<double> ax;
-    ax.insert(ax.end(), tmp.ys.begin(), tmp.ys.end()); ax.insert(ax.end(), tmp.xs.begin(), tmp.xs.end()); ax.insert(ax.end(), tmp.zs.begin(), tmp.zs.end());
+    rc = scratch_cube_setup(c, tmp, xpts, nx, ypts, ny, zpts, nz, 1, &fy, &fx, &fz, ax); if (rc) return rc;
     StreamsQuiesce quiesce(c);                  // (`ax`, the caller's points and outputs: nothing may still be copying when an error returns)
-    HIPCHECK(c, hipMemcpyAsync(daxes, ax.data(), ax.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(tmp.d_axes, ax.data(), ax.size() * 8, hipMemcpyHostToDevice, c->stream));
     double* planar[2] = {nullptr, nullptr};
     rc = build_cube_impl(c, q, xpts, nx, ypts, ny, zpts, nz, nullptr, nullptr, RDR_HOST, planar, nullptr, grid); if (rc) return rc;
     int* const nf = c->d_flags + MAX_SLICES + 2;
     HIPCHECK(c, hipMemsetAsync(nf, 0, sizeof(int), c->stream));
-    pack_planar(c, planar, (double2*)dvals, ny, nx, nz, fy, fx, fz, nf);
+    pack_planar(c, planar, (double2*)tmp.d_vals, ny, nx, nz, fy, fx, fz, nf);
     HIPCHECK(c, hipGetLastError());
     // (into a page-locked word: a pageable destination would stall the host here until the cube is built - and the upload of the
     // points, which is to run UNDER that build, with it)
     c->h_word[0] = 0;
     HIPCHECK(c, hipMemcpyAsync(&c->h_word[0], nf, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     if (n > 0) {
-        PointQuery Q; std::memset(&Q, 0, sizeof(Q));
-        Q.pmode = proj_mode; Q.inc0 = inc0;
-        static const int slots[6] = {SLOT_PT0, SLOT_PT1, SLOT_PT2, SLOT_PT3, SLOT_PT4, SLOT_PT5};
-        rc = interp_pipeline(c, who, &tmp, false, y, x, z, n, Q, proj, wet, hydro, slots); if (rc) return rc;
+        rc = interp_pipeline(c, who, &tmp, false, y, x, z, n, make_query(proj_mode, inc0), proj, wet, hydro, k_point_slots); if (rc) return rc;
     } else HIPCHECK(c, hipStreamSynchronize(c->stream));
     quiesce.armed = false;                      // (both branches have synchronised)
     if (cube_has_nan) *cube_has_nan = c->h_word[0] != 0;
@@ -1867,6 +1901,10 @@ static int levels_host(const std::vector<double>& zs, double ht, double zref, st
     return (int)lo.size();
 }
 
+static int fail_no_levels(rdr_ctx* c) {
+    return fail(c, RDR_ERR_NO_LEVELS, "no weather-model interval contributes to the ray integral (build_ray -> None)");
+}
+
 int rdr_ray_levels(const rdr_cube* q, double ht, double zref, int32_t* K, double* lo, double* hi, int32_t* kz) {
     if (!q || !K) return fail(nullptr, RDR_ERR_INVALID, "rdr_ray_levels: NULL argument");
     std::vector<double> l, h; std::vector<int> z;
@@ -1874,7 +1912,7 @@ int rdr_ray_levels(const rdr_cube* q, double ht, double zref, int32_t* K, double
     if (lo) std::copy(l.begin(), l.end(), lo);
     if (hi) std::copy(h.begin(), h.end(), hi);
     if (kz) std::copy(z.begin(), z.end(), kz);
-    if (*K == 0) return fail(q->ctx, RDR_ERR_NO_LEVELS, "no weather-model interval contributes to the ray integral (build_ray -> None)");
+    if (*K == 0) return fail_no_levels(q->ctx);
     return RDR_OK;
 }
 
@@ -1998,19 +2036,10 @@ static int64_t ws_chunk_tiles(rdr_ctx* c, int K) {
 // Reserve records for `tiles` tiles and point P at them (records, side buffer, side counter).
 static int ws_reserve(rdr_ctx* c, int64_t tiles, int K, RayParams& P) {
     const size_t need = (size_t)tiles * ws_tile_bytes();
-    if (c->ws.cap < need) {
-        if (c->ws.p) { HIPCHECK(c, hipStreamSynchronize(c->stream)); HIPCHECK(c, hipFree(c->ws.p)); c->ws.p = nullptr; c->ws.cap = 0; }
-        { const int rc_ = dev_malloc(c, &c->ws.p, need); if (rc_) return rc_; }
-        c->ws.cap = need;
-    }
+    int rc = grow(c, c->ws, need); if (rc) return rc;
     const size_t budget = ws_budget(c);
     const int64_t cols = side_columns(c, tiles * BLOCK, K, budget > need ? budget - need : 0);
-    const size_t sneed = (size_t)cols * (K + 1) * sizeof(double);
-    if (c->side.cap < sneed) {
-        if (c->side.p) { HIPCHECK(c, hipStreamSynchronize(c->stream)); HIPCHECK(c, hipFree(c->side.p)); c->side.p = nullptr; c->side.cap = 0; }
-        { const int rc_ = dev_malloc(c, &c->side.p, sneed); if (rc_) return rc_; }
-        c->side.cap = sneed;
-    }
+    rc = grow(c, c->side, (size_t)cols * (K + 1) * sizeof(double)); if (rc) return rc;
     c->side_cap = cols;
     P.ws = (double*)c->ws.p;
     P.side = cols > 0 ? (double*)c->side.p : nullptr; P.side_cap = cols; P.side_ctr = c->d_sidectr;
@@ -2100,14 +2129,12 @@ static int launch_crossings(rdr_ctx* c, const rdr_cube* q, RayParams P, int64_t 
         // input form of the batch, fixed at compile time for the two hot ones (crossings_kernel's OM parameter)
         const int om = P.origin_mode != RDR_ORIGIN_GRID ? 0 : (P.los_mode == RDR_LOS_VEC ? 1 : 2);
         const dim3 G(g), B(BLOCK);
-        e = q->dtype == RDR_F32 ? launch_lds(crossings_fn<float2>(lcc, om, P.ht_ray != nullptr), G, B, sm_light, c->stream, make_view<float2>(q), P, q->proj)
-                                : launch_lds(crossings_fn<double2>(lcc, om, P.ht_ray != nullptr), G, B, sm_light, c->stream, make_view<double2>(q), P, q->proj);
+        e = by_dtype(q, [&](auto t) { return launch_lds(crossings_fn<decltype(t)>(lcc, om, P.ht_ray != nullptr), G, B, sm_light, c->stream, make_view<decltype(t)>(q), P, q->proj); });
     }
     if (e != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("crossings_kernel launch: ") + hipGetErrorString(e));
     // generic-geodesy mop-up of the rays the classification rejected (returns at once when there are none)
     P.tile_ctr = c->d_tilectr + 8;
-    if (q->dtype == RDR_F32) e = launch_lds(crossings_kernel<float2, true>, dim3(g), dim3(BLOCK), sm, c->stream, make_view<float2>(q), P, q->proj);
-    else e = launch_lds(crossings_kernel<double2, true>, dim3(g), dim3(BLOCK), sm, c->stream, make_view<double2>(q), P, q->proj);
+    e = by_dtype(q, [&](auto t) { return launch_lds(crossings_kernel<decltype(t), true>, dim3(g), dim3(BLOCK), sm, c->stream, make_view<decltype(t)>(q), P, q->proj); });
     if (e != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("crossings_kernel launch: ") + hipGetErrorString(e));
     return RDR_OK;
 }
@@ -2128,12 +2155,7 @@ static int march_grid(const rdr_cube* q, bool per_ray) {
 static int launch_level_table(rdr_ctx* c, const rdr_cube* q, RayParams& P, int64_t s0, int64_t ns) {
     P.lev = nullptr;
     if (P.ht_ray || ns <= 0) return RDR_OK;
-    const size_t need = (size_t)P.nslices * (size_t)(q->nz + 1) * sizeof(LevelRec);
-    if (c->lev.cap < need) {
-        if (c->lev.p) { HIPCHECK(c, hipStreamSynchronize(c->stream)); HIPCHECK(c, hipFree(c->lev.p)); c->lev.p = nullptr; c->lev.cap = 0; }
-        { const int rc_ = dev_malloc(c, &c->lev.p, need); if (rc_) return rc_; }
-        c->lev.cap = need;
-    }
+    { const int rc = grow(c, c->lev, (size_t)P.nslices * (size_t)(q->nz + 1) * sizeof(LevelRec)); if (rc) return rc; }
     P.lev = (const LevelRec*)c->lev.p;
     hipError_t e;
     {
@@ -2156,9 +2178,7 @@ static int check_level_table(rdr_ctx* c, const RayParams& P) {
 static int launch_march_generic(rdr_ctx* c, const rdr_cube* q, RayParams P, dim3 G, dim3 B, size_t sm, bool zero_ctr) {
     if (zero_ctr) HIPCHECK(c, hipMemsetAsync(c->d_tilectr + 24, 0, 8 * sizeof(int), c->stream));
     P.tile_ctr = c->d_tilectr + 24;
-    hipError_t e;
-    if (q->dtype == RDR_F32) e = launch_lds(march_kernel<float2, true>, G, B, sm, c->stream, make_view<float2>(q), P, q->proj);
-    else e = launch_lds(march_kernel<double2, true>, G, B, sm, c->stream, make_view<double2>(q), P, q->proj);
+    const hipError_t e = by_dtype(q, [&](auto t) { return launch_lds(march_kernel<decltype(t), true>, G, B, sm, c->stream, make_view<decltype(t)>(q), P, q->proj); });
     if (e != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("march_kernel launch: ") + hipGetErrorString(e));
     return RDR_OK;
 }
@@ -2178,8 +2198,7 @@ static int launch_march(rdr_ctx* c, const rdr_cube* q, RayParams P, int64_t tb, 
         KTimer t(c, 1);
         const bool per_ray = P.ht_ray != nullptr;
         const int grid = march_grid(q, per_ray);
-        e = q->dtype == RDR_F32 ? launch_lds(march_fn<float2>(grid, per_ray), G, B, sm, c->stream, make_view<float2>(q), P, q->proj)
-                                : launch_lds(march_fn<double2>(grid, per_ray), G, B, sm, c->stream, make_view<double2>(q), P, q->proj);
+        e = by_dtype(q, [&](auto t) { return launch_lds(march_fn<decltype(t)>(grid, per_ray), G, B, sm, c->stream, make_view<decltype(t)>(q), P, q->proj); });
     }
     if (e != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("march_kernel launch: ") + hipGetErrorString(e));
     return launch_march_generic(c, q, P, G, B, sm, false);
@@ -2240,8 +2259,9 @@ static int launch_march_epochs(rdr_ctx* c, const rdr_cube* const* qs, int D, Ray
         hipError_t err = hipSuccess;
         {
             KTimer t(c, 1);
-            if (q->dtype == RDR_F32) err = ge == 4 ? launch_stacked<float2, 4>(c, qs + e, grid, Pe, estride, G, B, sm) : launch_stacked<float2, 2>(c, qs + e, grid, Pe, estride, G, B, sm);
-            else err = ge == 4 ? launch_stacked<double2, 4>(c, qs + e, grid, Pe, estride, G, B, sm) : launch_stacked<double2, 2>(c, qs + e, grid, Pe, estride, G, B, sm);
+            err = by_dtype(q, [&](auto t) {
+                return ge == 4 ? launch_stacked<decltype(t), 4>(c, qs + e, grid, Pe, estride, G, B, sm) : launch_stacked<decltype(t), 2>(c, qs + e, grid, Pe, estride, G, B, sm);
+            });
         }
         if (err != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("march_epochs_kernel launch: ") + hipGetErrorString(err));
         for (int j = 0; j < ge; ++j) {                  // generic rays, epoch by epoch, on the same records and side buffer
@@ -2259,16 +2279,16 @@ static int launch_march_epochs(rdr_ctx* c, const rdr_cube* const* qs, int D, Ray
 int rdr_ray_kernel_attributes(rdr_ctx* c, const rdr_cube* q, int which, int32_t* vgprs, int32_t* static_lds, int32_t* dynamic_lds,
                               int32_t* scratch, int32_t* max_threads) {
     if (!c || !q || which < 0 || which > 7) return fail(c, RDR_ERR_INVALID, "rdr_ray_kernel_attributes: bad argument");
-    const void* fn = nullptr;
     const bool lcc = q->proj.kind == 1;
     const bool pr = which == 2 || which == 3 || which >= 6;      // 2 / 3: the per-ray-height instantiations of pass 1 / pass 2; 6 / 7: of the stacked march
     const int grid = march_grid(q, pr);
-    const bool f32 = q->dtype == RDR_F32;
-    if (which >= 4) {                              // 4 / 5 (sliced), 6 / 7 (per-ray heights): the stacked march (march_epochs_kernel), E = 2 / 4
-        if ((which & 1) != 0) fn = f32 ? (const void*)march_epochs_fn<float2, 4>(grid, pr) : (const void*)march_epochs_fn<double2, 4>(grid, pr);
-        else fn = f32 ? (const void*)march_epochs_fn<float2, 2>(grid, pr) : (const void*)march_epochs_fn<double2, 2>(grid, pr);
-    } else if ((which & 1) == 0) fn = f32 ? (const void*)crossings_fn<float2>(lcc, 1, pr) : (const void*)crossings_fn<double2>(lcc, 1, pr);
-    else fn = f32 ? (const void*)march_fn<float2>(grid, pr) : (const void*)march_fn<double2>(grid, pr);
+    const void* const fn = by_dtype(q, [&](auto tag) -> const void* {
+        typedef decltype(tag) T2;
+        // 4 / 5 (sliced), 6 / 7 (per-ray heights): the stacked march (march_epochs_kernel), E = 2 / 4
+        if (which >= 4) return (which & 1) != 0 ? (const void*)march_epochs_fn<T2, 4>(grid, pr) : (const void*)march_epochs_fn<T2, 2>(grid, pr);
+        if ((which & 1) == 0) return (const void*)crossings_fn<T2>(lcc, 1, pr);
+        return (const void*)march_fn<T2>(grid, pr);
+    });
     hipFuncAttributes a;
     HIPCHECK(c, hipFuncGetAttributes(&a, fn));
     if (vgprs) *vgprs = a.numRegs;
@@ -2325,10 +2345,86 @@ static int ray_passes(rdr_ctx* c, const rdr_cube* q, const RayParams& P, int K, 
     return RDR_OK;
 }
 
+// What the five one-batch ray entries do before their own work.  check(): every cube noted as used, max_seg, check_rays, device arrays
+// where the entry insists on them (`device_only`: its message), the levels K of (ht, zref) on cube 0 - none is RDR_ERR_NO_LEVELS.
+// stage(): hipSetDevice, stage_rays of the batch it is GIVEN (raytrace_impl holds arrays back for its chunked upload), P.ht / zref /
+// max_seg.  Between the two an entry puts its empty-batch return and samples wsig_match - before stage(), always.
+struct RayCall {
+    int K = 0;
+    RayParams P;
+    double ht = 0, zref = 0, max_seg = 0;
+    int check(rdr_ctx* c, const char* who, const rdr_cube* const* qs, int D, const rdr_rays* r, double ht_, double zref_, double max_seg_,
+              const char* device_only = nullptr) {
+        for (int e = 0; e < D; ++e) note_use(c, qs[e]);
+        if (!(max_seg_ > 0)) return fail(c, RDR_ERR_INVALID, std::string(who) + ": MAX_SEGMENT_LENGTH must be positive");
+        const int rc = check_rays(c, r); if (rc) return rc;
+        if (device_only && r->loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, std::string(who) + device_only);
+        std::vector<double> lo, hi; std::vector<int> kz;
+        K = levels_host(qs[0]->zs, ht_, zref_, lo, hi, kz);
+        if (K == 0) return fail_no_levels(c);
+        ht = ht_; zref = zref_; max_seg = max_seg_;
+        return RDR_OK;
+    }
+    int stage(rdr_ctx* c, const rdr_rays* r) {
+        HIPCHECK(c, hipSetDevice(c->device));
+        const int rc = stage_rays(c, r, P); if (rc) return rc;
+        P.ht = ht; P.zref = zref; P.max_seg = max_seg;
+        return RDR_OK;
+    }
+};
+
+// A fresh partition for `nslices` slices: their length maxima and flags zeroed on the stream, in that order; the stored ray records
+// belong to the old one.
+static int partition_reset(rdr_ctx* c, int64_t nslices) {
+    HIPCHECK(c, hipMemsetAsync(c->d_maxlen, 0, (size_t)nslices * MAX_LEVELS * sizeof(unsigned long long), c->stream));
+    HIPCHECK(c, hipMemsetAsync(c->d_flags, 0, (size_t)nslices * sizeof(int), c->stream));
+    c->wsig.valid = false;
+    return RDR_OK;
+}
+
+// Pass 1 of a whole batch for the two prepass entries (nothing for an empty one).  Device arrays whose records all fit: they are kept
+// for the march that normally follows - ws_reserve before the launch, wsig_set after it.
+static int prepass_records(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, RayCall& R) {
+    if (r->n <= 0) return RDR_OK;
+    const bool keep = r->loc == RDR_DEVICE && R.P.ntiles <= ws_chunk_tiles(c, R.K);
+    int rc;
+    if (keep) { rc = ws_reserve(c, R.P.ntiles, R.K, R.P); if (rc) return rc; }
+    rc = launch_crossings(c, q, R.P, 0, R.P.ntiles); if (rc) return rc;
+    if (keep) wsig_set(c, q, r, R.ht, R.zref, R.K, true);
+    return RDR_OK;
+}
+
+// Pass 2 of the two march entries on a partition that is already on the device.  reuse (wsig_match, sampled before the rays were staged):
+// the stored records of the same batch - attach, level table, march; else ray_passes re-runs a store-only pass 1.  Either way the records
+// are spent afterwards.
+static int march_on_records(rdr_ctx* c, const rdr_cube* q, RayCall& R, bool reuse) {
+    int rc;
+    if (reuse) { ws_attach(c, R.P); rc = launch_level_table(c, q, R.P, 0, 1); if (!rc) rc = launch_march(c, q, R.P, 0, R.P.ntiles); }
+    else rc = ray_passes(c, q, R.P, R.K, R.P.ntiles, 1, ws_chunk_tiles(c, R.K), 1, false);
+    c->wsig.valid = false;
+    return rc;
+}
+
+// The partition back on the host: `nmax` length maxima, `nflags` slice flags, `more` (a slice series' epoch flags; may be absent), the
+// slow-ray counter - and the skipped-wave counter behind it for `nskip` - copied in that order, ONE wait, last_nslow (last_nskip) set.
+static int partition_read(rdr_ctx* c, double* maxlen, size_t nmax, int* flags, size_t nflags, bool nskip, void* more = nullptr, const void* d_more = nullptr,
+                          size_t more_bytes = 0) {
+    int ctr[2] = {0, 0};
+    HIPCHECK(c, hipMemcpyAsync(maxlen, c->d_maxlen, nmax * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(flags, c->d_flags, nflags * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (more_bytes) HIPCHECK(c, hipMemcpyAsync(more, d_more, more_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(ctr, c->d_nslow, (nskip ? 2 : 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    c->last_nslow = ctr[0];
+    if (nskip) c->last_nskip = ctr[1];
+    return RDR_OK;
+}
+
 // Host-buffer ray tracing with the PCIe transfers overlapped: the look vectors (24 B per ray, the bulk of the input) go up in
 // row chunks on the copy stream while pass 1 runs on the chunks that have arrived; after the last chunk the slice-level
 // partition is complete, pass 2 runs chunk by chunk and each chunk's outputs come down while the next is integrated.
 // (hipMemcpyAsync from pageable memory blocks the HOST thread, not the device: kernels launched before it keep running.)
+// An error return waits for all three streams (StreamsQuiesce): nothing is left copying into or out of the caller's arrays.
 static int raytrace_pipelined(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, RayParams P, int K, double* d_los, double* d_hts, double* dw, double* dh,
                               double* wet, double* hydro) {
     const int64_t tile_rows = P.ntiles / P.tiles_x;
@@ -2338,45 +2434,42 @@ static int raytrace_pipelined(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, 
     const int64_t nslots_total = P.ntiles * BLOCK;
     if (d_los) P.los = d_los;                  // (else the look vectors come from inc / heading or zenith: nothing to upload)
     if (d_hts) P.ht_ray = d_hts;               // per-pixel heights travel with the look vectors, chunk by chunk
-    std::vector<hipEvent_t> ev(2 * nchunk, nullptr);
+    EventList ev;                              // [0, nchunk): a chunk's upload; [nchunk, 2 nchunk): its pass 2
+    if (!ev.add((size_t)2 * nchunk)) return fail(c, RDR_ERR_HIP, "pipelined ray tracing: event creation failed");
+    StreamsQuiesce quiesce(c);
+    const auto ok = [](hipError_t e) { return e == hipSuccess; };
     auto range = [&](int k, int64_t& tb, int64_t& tc, int64_t& r0, int64_t& cnt) {
         const int64_t t0 = tile_rows * k / nchunk, t1 = tile_rows * (k + 1) / nchunk;
         tb = t0 * P.tiles_x; tc = (t1 - t0) * P.tiles_x;
         if (r->origin_mode == RDR_ORIGIN_GRID) { r0 = t0 * TILE * r->nx; cnt = std::min<int64_t>(t1 * TILE, r->ny) * r->nx - r0; }
         else { r0 = tb * BLOCK; cnt = std::min<int64_t>((tb + tc) * BLOCK, r->n) - r0; }
     };
-    int status = RDR_OK;
-    auto cleanup = [&]() { for (auto& e : ev) if (e) (void)hipEventDestroy(e); };
-    for (auto& e : ev)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { cleanup(); return fail(c, RDR_ERR_HIP, "pipelined ray tracing: event creation failed"); }
-    for (int k = 0; k < nchunk && status == RDR_OK; ++k) {
+    for (int k = 0; k < nchunk; ++k) {
         int64_t tb, tc, r0, cnt; range(k, tb, tc, r0, cnt);
-        if ((d_los && hipMemcpyAsync(d_los + 3 * r0, r->los + 3 * r0, (size_t)cnt * 24, hipMemcpyHostToDevice, c->copy_stream) != hipSuccess) ||
-            (d_hts && hipMemcpyAsync(d_hts + r0, r->hts + r0, (size_t)cnt * 8, hipMemcpyHostToDevice, c->copy_stream) != hipSuccess) ||
-            ((d_los || d_hts) && (hipEventRecord(ev[k], c->copy_stream) != hipSuccess || hipStreamWaitEvent(c->stream, ev[k], 0) != hipSuccess))) {
-            status = fail(c, RDR_ERR_HIP, "pipelined ray tracing: look-vector / height upload failed"); break;
-        }
+        if ((d_los && !ok(hipMemcpyAsync(d_los + 3 * r0, r->los + 3 * r0, (size_t)cnt * 24, hipMemcpyHostToDevice, c->copy_stream))) ||
+            (d_hts && !ok(hipMemcpyAsync(d_hts + r0, r->hts + r0, (size_t)cnt * 8, hipMemcpyHostToDevice, c->copy_stream))) ||
+            ((d_los || d_hts) && (!ok(hipEventRecord(ev.v[k], c->copy_stream)) || !ok(hipStreamWaitEvent(c->stream, ev.v[k], 0)))))
+            return fail(c, RDR_ERR_HIP, "pipelined ray tracing: look-vector / height upload failed");
         RayParams Pk = P; Pk.ws = ws + tb * BLOCK;
-        status = launch_crossings(c, q, Pk, tb, tc, nslots_total, k == 0);
+        rc = launch_crossings(c, q, Pk, tb, tc, nslots_total, k == 0); if (rc) return rc;
     }
-    if (status == RDR_OK) status = launch_level_table(c, q, P, 0, 1);      // (every chunk's pass 1 is enqueued: the partition is complete)
-    for (int k = 0; k < nchunk && status == RDR_OK; ++k) {
+    rc = launch_level_table(c, q, P, 0, 1); if (rc) return rc;      // (every chunk's pass 1 is enqueued: the partition is complete)
+    for (int k = 0; k < nchunk; ++k) {
         int64_t tb, tc, r0, cnt; range(k, tb, tc, r0, cnt);
         RayParams Pk = P; Pk.ws = ws + tb * BLOCK;
-        status = launch_march(c, q, Pk, tb, tc, nslots_total);
-        if (status == RDR_OK && hipEventRecord(ev[nchunk + k], c->stream) != hipSuccess) status = fail(c, RDR_ERR_HIP, "pipelined ray tracing: event");
+        rc = launch_march(c, q, Pk, tb, tc, nslots_total); if (rc) return rc;
+        if (!ok(hipEventRecord(ev.v[nchunk + k], c->stream))) return fail(c, RDR_ERR_HIP, "pipelined ray tracing: event");
     }
-    for (int k = 0; k < nchunk && status == RDR_OK; ++k) {
+    for (int k = 0; k < nchunk; ++k) {
         int64_t tb, tc, r0, cnt; range(k, tb, tc, r0, cnt);
-        if (hipStreamWaitEvent(c->copy_stream, ev[nchunk + k], 0) != hipSuccess ||
-            hipMemcpyAsync(wet + r0, dw + r0, (size_t)cnt * 8, hipMemcpyDeviceToHost, c->copy_stream) != hipSuccess ||
-            hipMemcpyAsync(hydro + r0, dh + r0, (size_t)cnt * 8, hipMemcpyDeviceToHost, c->copy_stream) != hipSuccess)
-            status = fail(c, RDR_ERR_HIP, "pipelined ray tracing: output download failed");
+        if (!ok(hipStreamWaitEvent(c->copy_stream, ev.v[nchunk + k], 0)) ||
+            !ok(hipMemcpyAsync(wet + r0, dw + r0, (size_t)cnt * 8, hipMemcpyDeviceToHost, c->copy_stream)) ||
+            !ok(hipMemcpyAsync(hydro + r0, dh + r0, (size_t)cnt * 8, hipMemcpyDeviceToHost, c->copy_stream)))
+            return fail(c, RDR_ERR_HIP, "pipelined ray tracing: output download failed");
     }
-    if (hipStreamSynchronize(c->copy_stream) != hipSuccess && status == RDR_OK) status = fail(c, RDR_ERR_HIP, "pipelined ray tracing: sync");
-    if (hipStreamSynchronize(c->stream) != hipSuccess && status == RDR_OK) status = fail(c, RDR_ERR_HIP, "pipelined ray tracing: sync");
-    cleanup();
-    return status;
+    if (!ok(hipStreamSynchronize(c->copy_stream)) || !ok(hipStreamSynchronize(c->stream))) return fail(c, RDR_ERR_HIP, "pipelined ray tracing: sync");
+    quiesce.armed = false;
+    return RDR_OK;
 }
 
 static int flags_to_status(rdr_ctx* c, int flags) {
@@ -2389,57 +2482,25 @@ static int flags_to_status(rdr_ctx* c, int flags) {
 
 int rdr_ray_prepass(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, double ht, double zref, double* maxlen, int32_t* flags) {
     if (!c || !q || !maxlen) return fail(c, RDR_ERR_INVALID, "rdr_ray_prepass: NULL argument");
-    note_use(c, q);
-    int rc = check_rays(c, r); if (rc) return rc;
-    std::vector<double> lo, hi; std::vector<int> kz;
-    const int K = levels_host(q->zs, ht, zref, lo, hi, kz);
-    if (K == 0) return fail(c, RDR_ERR_NO_LEVELS, "no weather-model interval contributes to the ray integral (build_ray -> None)");
-    HIPCHECK(c, hipSetDevice(c->device));
-    RayParams P;
-    rc = stage_rays(c, r, P); if (rc) return rc;
-    P.ht = ht; P.zref = zref; P.max_seg = 1000.0;
-    HIPCHECK(c, hipMemsetAsync(c->d_maxlen, 0, MAX_LEVELS * sizeof(unsigned long long), c->stream));
-    HIPCHECK(c, hipMemsetAsync(c->d_flags, 0, sizeof(int), c->stream));
-    c->wsig.valid = false;
-    if (r->n > 0) {
-        // keep the ray records for the rdr_ray_march that normally follows (same device arrays, whole batch fits)
-        const bool keep = r->loc == RDR_DEVICE && P.ntiles <= ws_chunk_tiles(c, K);
-        if (keep) { rc = ws_reserve(c, P.ntiles, K, P); if (rc) return rc; }
-        rc = launch_crossings(c, q, P, 0, P.ntiles); if (rc) return rc;
-        if (keep) wsig_set(c, q, r, ht, zref, K, true);
-    }
-    int f = 0, nslow[2] = {0, 0};
-    HIPCHECK(c, hipMemcpyAsync(maxlen, c->d_maxlen, (size_t)K * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(&f, c->d_flags, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(nslow, c->d_nslow, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipStreamSynchronize(c->stream));
-    c->last_nslow = nslow[0]; c->last_nskip = nslow[1];
+    RayCall R;                                   // (no empty-batch return: an empty batch still delivers its zeroed partition)
+    int rc = R.check(c, "rdr_ray_prepass", &q, 1, r, ht, zref, 1000.0); if (rc) return rc;
+    rc = R.stage(c, r); if (rc) return rc;
+    rc = partition_reset(c, 1); if (rc) return rc;
+    rc = prepass_records(c, q, r, R); if (rc) return rc;
+    int f = 0;
+    rc = partition_read(c, maxlen, (size_t)R.K, &f, 1, true); if (rc) return rc;
     if (flags) *flags = f;
     return RDR_OK;
 }
 
 int rdr_ray_prepass_device(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, double ht, double zref, double* partition) {
     if (!c || !q || !partition) return fail(c, RDR_ERR_INVALID, "rdr_ray_prepass_device: NULL argument");
-    note_use(c, q);
-    int rc = check_rays(c, r); if (rc) return rc;
-    if (r->loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, "rdr_ray_prepass_device: rays must be device arrays");
-    std::vector<double> lo, hi; std::vector<int> kz;
-    const int K = levels_host(q->zs, ht, zref, lo, hi, kz);
-    if (K == 0) return fail(c, RDR_ERR_NO_LEVELS, "no weather-model interval contributes to the ray integral (build_ray -> None)");
-    HIPCHECK(c, hipSetDevice(c->device));
-    RayParams P;
-    rc = stage_rays(c, r, P); if (rc) return rc;
-    P.ht = ht; P.zref = zref; P.max_seg = 1000.0;
-    HIPCHECK(c, hipMemsetAsync(c->d_maxlen, 0, MAX_LEVELS * sizeof(unsigned long long), c->stream));
-    HIPCHECK(c, hipMemsetAsync(c->d_flags, 0, sizeof(int), c->stream));
-    c->wsig.valid = false;
-    if (r->n > 0) {
-        const bool keep = P.ntiles <= ws_chunk_tiles(c, K);
-        if (keep) { rc = ws_reserve(c, P.ntiles, K, P); if (rc) return rc; }
-        rc = launch_crossings(c, q, P, 0, P.ntiles); if (rc) return rc;
-        if (keep) wsig_set(c, q, r, ht, zref, K, true);
-    }
-    hipLaunchKernelGGL(pack_partition_kernel, dim3(1), dim3(256), 0, c->stream, c->d_maxlen, c->d_flags, K, partition);
+    RayCall R;                                   // (no empty-batch return, as in rdr_ray_prepass)
+    int rc = R.check(c, "rdr_ray_prepass_device", &q, 1, r, ht, zref, 1000.0, ": rays must be device arrays"); if (rc) return rc;
+    rc = R.stage(c, r); if (rc) return rc;
+    rc = partition_reset(c, 1); if (rc) return rc;
+    rc = prepass_records(c, q, r, R); if (rc) return rc;
+    hipLaunchKernelGGL(pack_partition_kernel, dim3(1), dim3(256), 0, c->stream, c->d_maxlen, c->d_flags, R.K, partition);
     HIPCHECK(c, hipGetLastError());
     return RDR_OK;
 }
@@ -2447,26 +2508,15 @@ int rdr_ray_prepass_device(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, dou
 int rdr_ray_march_device(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, double ht, double zref, double max_seg, const double* partition,
                          double* wet, double* hydro) {
     if (!c || !q || !partition || !wet || !hydro) return fail(c, RDR_ERR_INVALID, "rdr_ray_march_device: NULL argument");
-    note_use(c, q);
-    if (!(max_seg > 0)) return fail(c, RDR_ERR_INVALID, "rdr_ray_march_device: MAX_SEGMENT_LENGTH must be positive");
-    int rc = check_rays(c, r); if (rc) return rc;
-    if (r->loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, "rdr_ray_march_device: rays and outputs must be device arrays");
-    std::vector<double> lo, hi; std::vector<int> kz;
-    const int K = levels_host(q->zs, ht, zref, lo, hi, kz);
-    if (K == 0) return fail(c, RDR_ERR_NO_LEVELS, "no weather-model interval contributes to the ray integral (build_ray -> None)");
+    RayCall R;
+    int rc = R.check(c, "rdr_ray_march_device", &q, 1, r, ht, zref, max_seg, ": rays and outputs must be device arrays"); if (rc) return rc;
     if (r->n == 0) return RDR_OK;
-    HIPCHECK(c, hipSetDevice(c->device));
-    const bool reuse = wsig_match(c, q, r, ht, zref, K);
-    RayParams P;
-    rc = stage_rays(c, r, P); if (rc) return rc;
-    P.ht = ht; P.zref = zref; P.max_seg = max_seg;
-    P.wet = wet; P.hyd = hydro;
-    hipLaunchKernelGGL(unpack_partition_kernel, dim3(1), dim3(256), 0, c->stream, partition, K, c->d_maxlen, c->d_flags);
+    const bool reuse = wsig_match(c, q, r, ht, zref, R.K);
+    rc = R.stage(c, r); if (rc) return rc;
+    R.P.wet = wet; R.P.hyd = hydro;
+    hipLaunchKernelGGL(unpack_partition_kernel, dim3(1), dim3(256), 0, c->stream, partition, R.K, c->d_maxlen, c->d_flags);
     HIPCHECK(c, hipGetLastError());
-    if (reuse) { ws_attach(c, P); rc = launch_level_table(c, q, P, 0, 1); if (!rc) rc = launch_march(c, q, P, 0, P.ntiles); }
-    else rc = ray_passes(c, q, P, K, P.ntiles, 1, ws_chunk_tiles(c, K), 1, false);
-    c->wsig.valid = false;
-    return rc;
+    return march_on_records(c, q, R, reuse);
 }
 
 // The level table pass 2 would read for slices at hts[] with the given partition, back on the host (tests, diagnostics): the same kernel
@@ -2507,18 +2557,14 @@ int rdr_level_table(rdr_ctx* c, const rdr_cube* q, const double* hts, int32_t ns
 int rdr_ray_march(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, double ht, double zref, const int32_t* nparts, int32_t flags,
                   double* wet, double* hydro) {
     if (!c || !q || !nparts || !wet || !hydro) return fail(c, RDR_ERR_INVALID, "rdr_ray_march: NULL argument");
-    note_use(c, q);
-    int rc = check_rays(c, r); if (rc) return rc;
-    std::vector<double> lo, hi; std::vector<int> kz;
-    const int K = levels_host(q->zs, ht, zref, lo, hi, kz);
-    if (K == 0) return fail(c, RDR_ERR_NO_LEVELS, "no weather-model interval contributes to the ray integral (build_ray -> None)");
+    RayCall R;
+    int rc = R.check(c, "rdr_ray_march", &q, 1, r, ht, zref, 1000.0); if (rc) return rc;
+    const int K = R.K;
     for (int k = 0; k < K; ++k) if (nparts[k] < 2 || nparts[k] > MAX_NPARTS) return fail(c, RDR_ERR_INVALID, "rdr_ray_march: nparts out of range (2..65536)");
     if (r->n == 0) return RDR_OK;
-    HIPCHECK(c, hipSetDevice(c->device));
     const bool reuse = wsig_match(c, q, r, ht, zref, K);
-    RayParams P;
-    rc = stage_rays(c, r, P); if (rc) return rc;
-    P.ht = ht; P.zref = zref; P.max_seg = 1000.0;
+    rc = R.stage(c, r); if (rc) return rc;
+    RayParams& P = R.P;
     HIPCHECK(c, hipMemcpyAsync(c->d_nparts, nparts, (size_t)K * sizeof(int), hipMemcpyHostToDevice, c->stream));
     int f = flags;
     HIPCHECK(c, hipMemcpyAsync(c->d_flags, &f, sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -2528,10 +2574,7 @@ int rdr_ray_march(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, double ht, d
     rc = stage_out(c, SLOT_OUT0, wet, (size_t)r->n * 8, r->loc, &dw); if (rc) return rc;
     rc = stage_out(c, SLOT_OUT1, hydro, (size_t)r->n * 8, r->loc, &dh); if (rc) return rc;
     P.wet = (double*)dw; P.hyd = (double*)dh;
-    if (reuse) { ws_attach(c, P); rc = launch_level_table(c, q, P, 0, 1); if (!rc) rc = launch_march(c, q, P, 0, P.ntiles); }
-    else rc = ray_passes(c, q, P, K, P.ntiles, 1, ws_chunk_tiles(c, K), 1, false);
-    c->wsig.valid = false;
-    if (rc) return rc;
+    rc = march_on_records(c, q, R, reuse); if (rc) return rc;
     rc = finish_out(c, wet, dw, (size_t)r->n * 8, r->loc); if (rc) return rc;
     rc = finish_out(c, hydro, dh, (size_t)r->n * 8, r->loc); if (rc) return rc;
     if (r->loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
@@ -2544,15 +2587,11 @@ int rdr_ray_march(rdr_ctx* c, const rdr_cube* q, const rdr_rays* r, double ht, d
 static int raytrace_impl(rdr_ctx* c, const char* who, const rdr_cube* const* qs, int32_t D, const rdr_rays* r, double ht, double zref,
                          double max_seg, double* wet, double* hydro, int32_t* nparts_out, int32_t* flags_out) {
     const rdr_cube* q = qs[0];
-    for (int32_t e = 0; e < D; ++e) note_use(c, qs[e]);
-    if (!(max_seg > 0)) return fail(c, RDR_ERR_INVALID, std::string(who) + ": MAX_SEGMENT_LENGTH must be positive");
-    int rc = check_rays(c, r); if (rc) return rc;
-    std::vector<double> lo, hi; std::vector<int> kz;
-    const int K = levels_host(q->zs, ht, zref, lo, hi, kz);
-    if (K == 0) return fail(c, RDR_ERR_NO_LEVELS, "no weather-model interval contributes to the ray integral (build_ray -> None)");
+    RayCall R;
+    int rc = R.check(c, who, qs, D, r, ht, zref, max_seg); if (rc) return rc;
     if (r->n == 0) return RDR_OK;
-    HIPCHECK(c, hipSetDevice(c->device));
-    RayParams P;
+    const int K = R.K;
+    RayParams& P = R.P;
     // one epoch, large host-buffer batches with per-ray look vectors: overlap the PCIe transfers with the two passes (raytrace_pipelined)
     bool pipelined = D == 1 && r->loc == RDR_HOST && r->n >= (1 << 21) && pipelining();
     const bool los_chunks = pipelined && r->los_mode == RDR_LOS_VEC;
@@ -2560,7 +2599,7 @@ static int raytrace_impl(rdr_ctx* c, const char* who, const rdr_cube* const* qs,
     rdr_rays rr = *r;
     if (los_chunks) rr.los = nullptr;                      // the look vectors are uploaded chunk by chunk below
     if (hts_chunks) rr.hts = nullptr;                      // ... and so are per-pixel heights
-    rc = stage_rays(c, &rr, P); if (rc) return rc;
+    rc = R.stage(c, &rr); if (rc) return rc;
     if (pipelined && P.ntiles > ws_chunk_tiles(c, K)) {   // records do not fit: ordinary (chunked-march) path
         const void* d;
         if (los_chunks) {
@@ -2573,15 +2612,12 @@ static int raytrace_impl(rdr_ctx* c, const char* who, const rdr_cube* const* qs,
         }
         pipelined = false;
     }
-    P.ht = ht; P.zref = zref; P.max_seg = max_seg;
     const size_t bytes = (size_t)r->n * (size_t)D * 8;
     void *dw, *dh;
     rc = stage_out(c, SLOT_OUT0, wet, bytes, r->loc, &dw); if (rc) return rc;
     rc = stage_out(c, SLOT_OUT1, hydro, bytes, r->loc, &dh); if (rc) return rc;
     P.wet = (double*)dw; P.hyd = (double*)dh;
-    HIPCHECK(c, hipMemsetAsync(c->d_maxlen, 0, MAX_LEVELS * sizeof(unsigned long long), c->stream));
-    HIPCHECK(c, hipMemsetAsync(c->d_flags, 0, sizeof(int), c->stream));
-    c->wsig.valid = false;
+    rc = partition_reset(c, 1); if (rc) return rc;
     if (pipelined) {
         void *dl = nullptr, *dhts = nullptr;
         if (los_chunks) { rc = ensure(c, SLOT_IN3, (size_t)r->n * 24, &dl); if (rc) return rc; }
@@ -2598,12 +2634,8 @@ static int raytrace_impl(rdr_ctx* c, const char* who, const rdr_cube* const* qs,
     const bool need_sync = r->loc == RDR_HOST || nparts_out || flags_out;
     if (need_sync) {
         std::vector<double> ml(K);
-        int f = 0, nslow = 0;
-        HIPCHECK(c, hipMemcpyAsync(ml.data(), c->d_maxlen, (size_t)K * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHECK(c, hipMemcpyAsync(&f, c->d_flags, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHECK(c, hipMemcpyAsync(&nslow, c->d_nslow, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHECK(c, hipStreamSynchronize(c->stream));
-        c->last_nslow = nslow;
+        int f = 0;
+        rc = partition_read(c, ml.data(), (size_t)K, &f, 1, false); if (rc) return rc;
         if (nparts_out) rdr_nparts(ml.data(), K, max_seg, nparts_out);
         if (flags_out) *flags_out = f;
         return flags_to_status(c, f);
@@ -2719,31 +2751,14 @@ int rdr_interp3_project_epochs(rdr_ctx* c, const rdr_cube* const* cubes, int32_t
     const int D = ncubes;
     std::vector<const void*> vals((size_t)D);
     for (int e = 0; e < D; ++e) vals[(size_t)e] = cubes[e]->d_vals;
-    PointQuery Q; std::memset(&Q, 0, sizeof(Q));
-    Q.pmode = proj_mode; Q.inc0 = inc0;
-    const bool has_proj = proj_mode == 1 || proj_mode == 3;
-    const int64_t pstride = has_proj ? proj_stride : 0;
-    const int64_t np = pstride ? D : 1;
-    const size_t ystride = x ? 1 : 3;
+    const PointQuery Q = make_query(proj_mode, inc0);
+    const int64_t pstride = (proj_mode == 1 || proj_mode == 3) ? proj_stride : 0;
     if (loc == RDR_HOST && n >= (1 << 18) && pipelining()) {
-        static const int slots[6] = {SLOT_IN0, SLOT_IN1, SLOT_IN2, SLOT_IN3, SLOT_OUT0, SLOT_OUT1};
-        return interp_pipeline_impl(c, who, q, false, BlendSpec(), vals.data(), D, y, x, z, n, Q, proj, pstride, wet, hydro, slots);
+        return interp_pipeline_impl(c, who, q, false, BlendSpec(), vals.data(), D, y, x, z, n, Q, proj, pstride, wet, hydro, k_gather_slots);
     }
-    const void* d; void *dw = nullptr, *dh = nullptr;
-    rc = stage_points_in(c, SLOT_IN0, y, (size_t)n * ystride * 8, loc, &d); if (rc) return rc; Q.y = (const double*)d;
-    if (x) {
-        rc = stage_points_in(c, SLOT_IN1, x, (size_t)n * 8, loc, &d); if (rc) return rc; Q.x = (const double*)d;
-        rc = stage_points_in(c, SLOT_IN2, z, (size_t)n * 8, loc, &d); if (rc) return rc; Q.z = (const double*)d;
-    }
-    if (has_proj) { rc = stage_points_in(c, SLOT_IN3, proj, (size_t)n * np * 8, loc, &d); if (rc) return rc; Q.proj = (const double*)d; }
-    if (wet) { rc = stage_out(c, SLOT_OUT0, wet, (size_t)n * D * 8, loc, &dw); if (rc) return rc; }
-    if (hydro) { rc = stage_out(c, SLOT_OUT1, hydro, (size_t)n * D * 8, loc, &dh); if (rc) return rc; }
-    launch_interp_epochs(c, q, vals.data(), D, Q, pstride, n, n, (double*)dw, (double*)dh);
-    HIPCHECK(c, hipGetLastError());
-    rc = finish_out(c, wet, dw, (size_t)n * D * 8, loc); if (rc) return rc;
-    rc = finish_out(c, hydro, dh, (size_t)n * D * 8, loc); if (rc) return rc;
-    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return RDR_OK;
+    return gather_staged(c, Q, y, x, z, proj, pstride, n, D, wet, hydro, loc, [&](const PointQuery& Qd, double* dw, double* dh) {
+        launch_interp_epochs(c, q, vals.data(), D, Qd, pstride, n, n, dw, dh);
+    });
 }
 
 int64_t rdr_point_upload_bytes(const rdr_ctx* c) { return c ? c->point_upload_bytes : -1; }
@@ -2767,31 +2782,23 @@ int rdr_point_delays_epochs(rdr_ctx* c, const rdr_cube* const* cubes, int32_t nc
     rc = epochs_point_args(c, who, y, x, z, n, proj_mode, proj, proj_stride, wet, hydro); if (rc) return rc;
     c->point_upload_bytes = 0;
     if (ncubes == 1) return point_delays_impl(c, who, cubes[0], grid, xpts, nx, ypts, ny, zpts, nz, y, x, z, n, proj_mode, proj, inc0, wet, hydro, cube_has_nan);
-    if (nx < 2 || ny < 2 || nz < 2) return fail(c, RDR_ERR_INVALID, w + ": the delay cube needs two nodes per axis");
-    if (nz > MAX_LEVELS) return fail(c, RDR_ERR_INVALID, w + ": more than 512 height levels");
-    if (ny + nx + nz > 100000) return fail(c, RDR_ERR_INVALID, w + ": axes too long");
-    // the intermediate cubes: ONE scratch description (shape, axes), D value regions
-    int fy, fx, fz;
-    rdr_cube tmp;
-    if (scratch_cube_init(tmp, c, xpts, nx, ypts, ny, zpts, nz, &fy, &fx, &fz))
-        return fail(c, RDR_ERR_INVALID, "The points in each dimension must be strictly ascending or descending (and >= 2)");
-    HIPCHECK(c, hipSetDevice(c->device));
+    rc = point_grid_args(c, w, nx, ny, nz); if (rc) return rc;
+    // the intermediate cubes: ONE scratch description (shape, axes), D value regions (they do not fit: RDR_ERR_OOM, the caller goes date by date)
     const int D = ncubes;
     const size_t total = (size_t)ny * nx * nz;
-    void *dvals, *daxes, *dnan;
-    rc = ensure(c, SLOT_TMPCUBE, total * sizeof(double2) * (size_t)D, &dvals); if (rc) return rc;      // (does not fit: RDR_ERR_OOM, the caller goes date by date)
-    rc = ensure(c, SLOT_TMPAXES, (size_t)(ny + nx + nz) * 8, &daxes); if (rc) return rc;
-    rc = ensure(c, SLOT_OUT2, (size_t)D * sizeof(int), &dnan); if (rc) return rc;
-    tmp.d_vals = dvals; tmp.d_axes = (double*)daxes;
+    int fy, fx, fz;
+    rdr_cube tmp;
     std::vector<double> ax;
-    ax.insert(ax.end(), tmp.ys.begin(), tmp.ys.end()); ax.insert(ax.end(), tmp.xs.begin(), tmp.xs.end()); ax.insert(ax.end(), tmp.zs.begin(), tmp.zs.end());
+    rc = scratch_cube_setup(c, tmp, xpts, nx, ypts, ny, zpts, nz, D, &fy, &fx, &fz, ax); if (rc) return rc;
+    void* dnan;
+    rc = ensure(c, SLOT_OUT2, (size_t)D * sizeof(int), &dnan); if (rc) return rc;
     std::vector<const void*> vals((size_t)D);
     std::vector<int> nanw((size_t)D, 0);
     StreamsQuiesce quiesce(c);                  // (`ax`, `nanw`, the caller's points and outputs: nothing may still be copying when an error returns)
-    HIPCHECK(c, hipMemcpyAsync(daxes, ax.data(), ax.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(tmp.d_axes, ax.data(), ax.size() * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(c, hipMemsetAsync(dnan, 0, (size_t)D * sizeof(int), c->stream));
     for (int e = 0; e < D; ++e) {
-        double2* dv = (double2*)dvals + (size_t)e * total;
+        double2* dv = (double2*)tmp.d_vals + (size_t)e * total;
         vals[(size_t)e] = dv;
         int* const nf = (int*)dnan + e;
         double* planar[2] = {nullptr, nullptr};
@@ -2800,11 +2807,9 @@ int rdr_point_delays_epochs(rdr_ctx* c, const rdr_cube* const* cubes, int32_t nc
         HIPCHECK(c, hipGetLastError());
     }
     if (n > 0) {
-        PointQuery Q; std::memset(&Q, 0, sizeof(Q));
-        Q.pmode = proj_mode; Q.inc0 = inc0;
         const int64_t pstride = (proj_mode == 1 || proj_mode == 3) ? proj_stride : 0;
-        static const int slots[6] = {SLOT_PT0, SLOT_PT1, SLOT_PT2, SLOT_PT3, SLOT_PT4, SLOT_PT5};
-        rc = interp_pipeline_impl(c, who, &tmp, false, BlendSpec(), vals.data(), D, y, x, z, n, Q, proj, pstride, wet, hydro, slots); if (rc) return rc;
+        rc = interp_pipeline_impl(c, who, &tmp, false, BlendSpec(), vals.data(), D, y, x, z, n, make_query(proj_mode, inc0), proj, pstride, wet, hydro, k_point_slots);
+        if (rc) return rc;
     }
     // the D NaN words, after everything else has been enqueued (a pageable destination: the host waits here, with nothing left to overlap)
     HIPCHECK(c, hipMemcpyAsync(nanw.data(), dnan, (size_t)D * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -2863,10 +2868,8 @@ static int raytrace_slices_impl(rdr_ctx* c, const char* who, const rdr_cube* con
     P.ntiles = per * nslices;
     P.ht = hts[0]; P.zref = zref; P.max_seg = max_seg;
     P.wet = (double*)dw; P.hyd = (double*)dh;
-    HIPCHECK(c, hipMemsetAsync(c->d_maxlen, 0, (size_t)nslices * MAX_LEVELS * sizeof(unsigned long long), c->stream));
-    HIPCHECK(c, hipMemsetAsync(c->d_flags, 0, (size_t)nslices * sizeof(int), c->stream));
+    rc = partition_reset(c, nslices); if (rc) return rc;
     if (D > 1) HIPCHECK(c, hipMemsetAsync(dnan, 0, (size_t)D * nslices * sizeof(int), c->stream));
-    c->wsig.valid = false;
     const int K = std::max(Kmax, 1);
     const int64_t fit = ws_chunk_tiles(c, K);
     // Host outputs of a large one-epoch batch come down slice group by slice group on the copy stream while the next groups are
@@ -2879,11 +2882,7 @@ static int raytrace_slices_impl(rdr_ctx* c, const char* who, const rdr_cube* con
         HIPCHECK(c, hipGetLastError());
         return RDR_OK;
     };
-    struct EventList {                                   // (destroyed on every exit path)
-        std::vector<hipEvent_t> v;
-        ~EventList() { for (auto& e : v) if (e) (void)hipEventDestroy(e); }
-    } gev_owner;
-    std::vector<hipEvent_t>& gev = gev_owner.v;
+    EventList gev;                                       // one per finished group
     std::vector<std::pair<int64_t, int64_t>> groups;
     // groups of whole slices: usually one; up to 8 when the outputs are downloaded group by group
     rc = ray_passes(c, q, P, K, per, nslices, fit, pipe ? std::max<int64_t>(1, (nslices + 7) / 8) : nslices, true,
@@ -2891,12 +2890,8 @@ static int raytrace_slices_impl(rdr_ctx* c, const char* who, const rdr_cube* con
                     [&](int64_t s0, int64_t ns) {
                         if (!pipe) return RDR_OK;
                         const int rc_ = nan_scan(s0, ns); if (rc_) return rc_;
-                        hipEvent_t e = nullptr;
-                        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess || hipEventRecord(e, c->stream) != hipSuccess) {
-                            if (e) (void)hipEventDestroy(e);
-                            return fail(c, RDR_ERR_HIP, w + ": event");
-                        }
-                        gev.push_back(e); groups.emplace_back(s0, ns);
+                        if (!gev.add(1) || hipEventRecord(gev.v.back(), c->stream) != hipSuccess) return fail(c, RDR_ERR_HIP, w + ": event");
+                        groups.emplace_back(s0, ns);
                         return RDR_OK;
                     });
     if (rc) return rc;
@@ -2904,7 +2899,7 @@ static int raytrace_slices_impl(rdr_ctx* c, const char* who, const rdr_cube* con
         int status = RDR_OK;
         for (size_t k = 0; k < groups.size() && status == RDR_OK; ++k) {
             const size_t off = (size_t)groups[k].first * r->n, cnt = (size_t)groups[k].second * r->n;
-            if (hipStreamWaitEvent(c->copy_stream, gev[k], 0) != hipSuccess ||
+            if (hipStreamWaitEvent(c->copy_stream, gev.v[k], 0) != hipSuccess ||
                 hipMemcpyAsync(wet + off, (const double*)dw + off, cnt * 8, hipMemcpyDeviceToHost, c->copy_stream) != hipSuccess ||
                 hipMemcpyAsync(hydro + off, (const double*)dh + off, cnt * 8, hipMemcpyDeviceToHost, c->copy_stream) != hipSuccess)
                 status = fail(c, RDR_ERR_HIP, w + ": output download failed");
@@ -2920,13 +2915,7 @@ static int raytrace_slices_impl(rdr_ctx* c, const char* who, const rdr_cube* con
     if (need_sync) {
         std::vector<double> ml((size_t)nslices * MAX_LEVELS);
         std::vector<int> f(nslices), ef(D > 1 ? (size_t)D * nslices : 0);
-        int nslow = 0;
-        HIPCHECK(c, hipMemcpyAsync(ml.data(), c->d_maxlen, ml.size() * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHECK(c, hipMemcpyAsync(f.data(), c->d_flags, (size_t)nslices * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        if (D > 1) HIPCHECK(c, hipMemcpyAsync(ef.data(), dnan, ef.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHECK(c, hipMemcpyAsync(&nslow, c->d_nslow, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHECK(c, hipStreamSynchronize(c->stream));
-        c->last_nslow = nslow;
+        rc = partition_read(c, ml.data(), ml.size(), f.data(), (size_t)nslices, false, ef.data(), dnan, ef.size() * sizeof(int)); if (rc) return rc;
         for (int s = 0; s < nslices; ++s) {
             if (nparts_out) rdr_nparts(ml.data() + (size_t)s * MAX_LEVELS, Ks[s], max_seg, nparts_out + (size_t)s * ld);
             if (flags_out)
@@ -3051,7 +3040,7 @@ int rdr_build_ray(rdr_ctx* c, const double* model_zs, int64_t nz, double ht, con
     std::vector<double> zs(model_zs, model_zs + nz), lo, hi; std::vector<int> kz;
     const int K = levels_host(zs, ht, zref, lo, hi, kz);
     *K_out = K;
-    if (K == 0) return fail(c, RDR_ERR_NO_LEVELS, "no weather-model interval contributes to the ray integral (build_ray -> None)");
+    if (K == 0) return fail_no_levels(c);
     if (!lengths || !low || !high) return RDR_OK;   // size query
     if (n < 0) return fail(c, RDR_ERR_INVALID, "rdr_build_ray: negative count");
     if (n == 0) return RDR_OK;
