@@ -77,9 +77,9 @@ __device__ __forceinline__ GeoF geo_fast(double x, double y, double z) {
 }
 
 // asin(s) for the small angles between a fit node and the ray origin: odd series through s^11.  The static classification
-// admits only rays that turn by less than LON_TRAVEL_MAX = 0.2 rad in longitude (0.035 rad in latitude), where the truncation
-// (231/13312 s^13) is < 1.4e-11 rad (9e-5 m on the ground at the far end of the longest admitted ray).  Used only at the six
-// fit nodes of a ray, never per sample.
+// admits only rays that turn by less than 0.12 rad in longitude (0.035 rad in latitude; raider_kernels.h: fast_ok), where the
+// truncation (231/13312 s^13) is < 2e-14 rad; it stays < 1.4e-11 rad (9e-5 m on the ground) up to 0.2 rad, the limit the series
+// was sized for.  Used only at the six fit nodes of a ray, never per sample.
 __device__ __forceinline__ double asin_small(double s) {
     const double s2 = s * s;
     double q = fma(s2, 63.0 / 2816.0, 35.0 / 1152.0);
@@ -106,10 +106,14 @@ __device__ __forceinline__ RayBase make_base(double lat_deg, double lon_deg) {
 
 // ---- ray polynomials ------------------------------------------------------------------------------------------------
 // Along a straight ray o + t l the geodetic height, latitude and longitude are smooth functions of t: over the rays the
-// static classification admits (angular travel < 0.035 rad, < 0.2 rad of longitude, away from the poles) their degree-5
-// interpolants at the 6 Chebyshev nodes of the ray's parameter range reproduce them to < 3e-7 m (h) and < 2.2e-5 m on the
-// ground (lat, lon) in the worst admitted case, and to 5e-9 m / 5e-6 m for rays shorter than 100 km
-// (sweep: tools/ray_poly_probe.py).  The ray kernels therefore evaluate the full geodesy 6 times per ray and replace
+// static classification admits (angular travel < 0.035 rad, < 0.12 rad of longitude, away from the poles) their degree-5
+// interpolants at the 6 Chebyshev nodes of the ray's parameter range reproduce them to 2.5e-7 m (h), 5.9e-5 m (lat) and
+// 1.5e-4 m (lon, on the ground) in the worst admitted case - rays on the longitude-travel limit - and to 2e-9 m, 3.1e-5 m
+// and 9.4e-5 m for rays shorter than 100 km (a longitude limit of 0.2 rad gives 6.3e-4 m and 1.8e-3 m, one of 0.08 rad 7e-6 m
+// and 2.2e-5 m).  tests/test_ray_poly_bounds.py measures these figures over the rays of tools/ray_poly_probe.py and rays placed
+// on each clause's limit, and asserts bounds above them; tests/test_gpu_ray_geometry.py holds the device to this design at
+// rounding level (1e-8 m class).
+// The ray kernels therefore evaluate the full geodesy 6 times per ray and replace
 // every later evaluation (3 per model level in the Newton level crossings, 1 per integration sample) by 5 FMAs per
 // quantity.  u = su * t + ou maps the range to [-1, 1]; coefficients are monomial in u (well conditioned on [-1, 1]).
 constexpr int PN = 6;

@@ -933,10 +933,15 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
         const double nl = nl2 * rsq_nr<2>(nl2);
         // Static classification: may the ray polynomials be used along the WHOLE ray?  gam bounds the angular travel
         // (t_max <= (zref-ht)/cos(inc) because the local zenith angle of a straight ray decreases with height); the ray must
-        // stay clear of the poles (cos(lat) > gam + 0.02), turn by less than 0.2 rad in longitude (gam / (cos(lat) - gam)) and
-        // be shorter than 0.035 rad - inside that region the degree-5 interpolants are good to 1e-7 m in height and 2e-5 m
-        // on the ground (tools/ray_poly_probe.py), which moves delays by < 1e-10 m - and must not reach the +-180 meridian
-        // (the light path does not wrap longitudes).
+        // stay clear of the poles (cos(lat) > gam + 0.02), turn by less than 0.12 rad in longitude (gam / (cos(lat) - gam)) and
+        // be shorter than 0.035 rad - inside that region the degree-5 interpolants are good to 2.5e-7 m in height and, on the
+        // ground, to 5.9e-5 m (lat) and 1.5e-4 m (lon) at worst, 3.1e-5 m and 9.4e-5 m on rays shorter than 100 km
+        // (tests/test_ray_poly_bounds.py).  The longitude limit is set by what that interpolation error does to a delay: a field
+        // LINEAR in longitude with the strongest horizontal gradient of the synthetic cube (62 N-units per degree at 75-80 deg N)
+        // held through a whole 41 km column moves a delay by 8.8e-10 m at 70 deg incidence, under the 1e-9 m of the parity suites;
+        // at 0.2 rad, the limit before, it was 3.9e-9 m (tests/test_gpu_ray_geometry.py, which measures this part apart from the
+        // offset of the level crossings against the reference's height: that one does not depend on the classification).
+        // The ray must not reach the +-180 meridian either (the light path does not wrap longitudes).
         const double cosi = (lx * base.c0 * base.cl0 + ly * base.c0 * base.sl0 + lz * base.s0) / nl;
         const double zref = Pk().zref;
         const double gam = (zref - hti) / (cosi * 6.3e6);
@@ -944,7 +949,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
         // (geodesy_fast.h); an ellipsoidal cone goes to the generic kernels (lcc_forward) ray by ray.
         // The +-180 deg meridian: the light path carries longitude UNWRAPPED (origin + small delta), the reference wraps every
         // sample into (-180, 180] (atan2).  The two agree whenever no sample crosses the meridian (origin more than 5 deg away from
-        // it - a ray travels < 0.2 rad = 11.5 deg only at high latitude, where the other clauses bite first... kept as before), and
+        // it - a ray travels < 0.12 rad = 6.9 deg only at high latitude, where the other clauses bite first... kept as before), and
         // ALSO when a crossing sample is outside the cube either way: a lon/lat cube whose x axis ends at or before +180 and starts
         // more than 12 deg after -180 (wrap_pos) gives NaN for an unwrapped 180.x (beyond the axis) and for the reference's
         // wrapped -179.x (before it) alike; mirrored for origins near -180 (wrap_neg).  Dateline scenes (Fiji, Chukotka, the
@@ -963,7 +968,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
             const bool wrap_pos = (x_hi <= 180.0) & (x_lo > -168.0), wrap_neg = (x_lo >= -180.0) & (x_hi < 168.0);
             lon_ok = (fabs(lon) + 5.0 < 180.0) || ((fabs(lon) <= 180.0) && (lon > 0.0 ? wrap_pos : wrap_neg));
         }
-        const bool fast_ok = !active || ((cosi > 0.05) && (base.c0 > gam + 0.02) && (gam < 0.2 * (base.c0 - gam)) && (gam < 0.035) &&
+        const bool fast_ok = !active || ((cosi > 0.05) && (base.c0 > gam + 0.02) && (gam < 0.12 * (base.c0 - gam)) && (gam < 0.035) &&
                                          lon_ok && (proj_kind != 1 || (ja.e == 0.0 && gam < 0.09 * base.c0)));   // (run-time test: the generic kernels must classify identically)
         if (!SLOW) {
             const unsigned long long slow_mask = __ballot(!fast_ok);

@@ -206,8 +206,8 @@ def test_ray_polynomial_stress(R, case):
         c = O.synthetic_cube(60, 90, 40, seed=8, ztop=80000.0, y0=64.0, y1=79.0, x0=-175.0, x1=-130.0)
         ypts = np.linspace(75.0, 69.0, 10); xpts = np.linspace(-158.0, -150.0, 12)
         inc = rng.uniform(25, 45, (10, 12)); hd = rng.uniform(-180, 180, (10, 12)); ht = 0.0
-    elif case == 'polar_80km':        # 79-85.5 deg N: up to the classification's 0.2 rad of longitude travel (the hand-over to the generic
-        c = O.synthetic_cube(90, 120, 40, seed=8, ztop=80000.0, y0=70.0, y1=89.5, x0=-175.0, x1=-95.0)       # kernels sits near 84.5 deg N here)
+    elif case == 'polar_80km':        # 79-85.5 deg N: up to the classification's 0.12 rad of longitude travel (the hand-over to the generic
+        c = O.synthetic_cube(90, 120, 40, seed=8, ztop=80000.0, y0=70.0, y1=89.5, x0=-175.0, x1=-95.0)       # kernels sits near 82 deg N here)
         ypts = np.linspace(85.5, 79.0, 14); xpts = np.linspace(-150.0, -120.0, 10)
         inc = rng.uniform(25, 46, (14, 10)); hd = rng.uniform(-180, 180, (14, 10)); ht = 0.0
     else:
@@ -255,7 +255,7 @@ def test_diverged_lengths_are_refused(R, c1):
 
 def test_generic_ray_side_buffer_full_partial_and_absent(R):
     """The level crossings of generic-geodesy rays travel from pass 1 to pass 2 in a compact side buffer; a ray that finds it
-    full has them recomputed by pass 2.  A polar scene (every ray generic) and a scene straddling the 84.4 deg hand-over
+    full has them recomputed by pass 2.  A polar scene (every ray generic) and a scene straddling the hand-over near 82 deg
     (mixed) must give bit-identical delays with an ample buffer, one that holds a fraction of the generic rays, and none."""
     ctx = R.Context.default()
     c = O.synthetic_cube(40, 44, 36, seed=7, y0=78.0, y1=89.9, x0=-60.0, x1=60.0)

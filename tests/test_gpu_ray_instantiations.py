@@ -98,7 +98,7 @@ def _generic_rays(proj, xs, lat, lon, los, hts, zref):
         wrap_pos = xs.max() <= 180.0 and xs.min() > -168.0
         wrap_neg = xs.min() >= -180.0 and xs.max() < 168.0
         ok = (np.abs(lon) + 5.0 < 180.0) | ((np.abs(lon) <= 180.0) & np.where(lon > 0.0, wrap_pos, wrap_neg))
-    fast = (cosi > 0.05) & (c0 > gam + 0.02) & (gam < 0.2 * (c0 - gam)) & (gam < 0.035) & ok
+    fast = (cosi > 0.05) & (c0 > gam + 0.02) & (gam < 0.12 * (c0 - gam)) & (gam < 0.035) & ok
     return int((~fast).sum())
 
 

@@ -26,7 +26,7 @@ wet, hyd, nparts, _ = cube.raytrace(R.Rays.grid(xpts, ypts, los=np.ascontiguousa
 print('nparts equal:', np.array_equal(nparts, onp[0]), ' NaN pattern equal:', np.array_equal(np.isnan(hyd), np.isnan(oh[0])), ' finite:', np.isfinite(oh[0]).mean())
 gam = (zref - ht) / (np.cos(np.radians(inc)) * 6.3e6)
 c0 = np.cos(np.radians(yy))
-light = (c0 > gam + 0.02) & (gam < 0.2 * (c0 - gam)) & (gam < 0.035)
+light = (c0 > gam + 0.02) & (gam < 0.12 * (c0 - gam)) & (gam < 0.035)
 for a in np.arange(lat_lo, lat_hi, 1.0):
     m = (yy >= a) & (yy < a + 1.0)
     dw = np.nanmax(np.abs(wet - ow[0])[m]); dh = np.nanmax(np.abs(hyd - oh[0])[m])
