@@ -656,6 +656,25 @@ int rdr_inflate_decode(rdr_ctx* ctx, const void* src, int64_t src_bytes, const i
 int rdr_h5_unchunk(rdr_ctx* ctx, const void* chunks, int64_t chunk_stride, const int64_t* chunk_index, int64_t npresent, int elem_bytes, int ndim,
                    const int64_t* shape, const int64_t* chunk, int shuffle, int swap, void* out, int loc);
 
+/* ---- exact all-pair empirical variograms of a station series (raider_amd/variogram.py; csrc/variogram_kernels.h) -------------------
+ * The core of raiderStats (cli/statsPlot.py:573-659) over ALL n (n - 1) / 2 pairs of n points, where the reference samples 1000.
+ * x, y [n]: metres.  values [nd][n]: one row per date, NaN = missing.  A pair i < j counts on a date when both its values are not
+ * NaN; its lag is h = sqrt(dx * dx + dy * dy), evaluated without contraction (the value NumPy gets), its semivariance
+ * g = 0.5 * (v_i - v_j)^2.
+ * rdr_pair_distance_max: hmax[d] = the largest h over the pairs of date d, NaN for a date with fewer than two valid points (the
+ * reference's default bins end at 0.67 of it, :638).
+ * rdr_pair_variogram: edges [nedge_rows][nbins + 1], finite and strictly ascending, one row for all dates (nedge_rows = 1) or one
+ * per date (nedge_rows = nd).  A pair goes to the bin b with edges[b] < h <= edges[b + 1] (:644); h <= edges[0] and h > edges[nbins]
+ * are dropped.  count [nd][nbins] is exact; lag_sum and gamma_sum [nd][nbins] are f64 sums of h and g, added in an order that may
+ * differ between calls (within (m - 1) * 2^-53 relative of the exact sum of a bin of m pairs); an empty bin gives 0, 0.0, 0.0.
+ * Dates run in groups of at most four per launch, which share the pair distances.  No floating-point atomic touches global memory.
+ * Every array lives at `loc`; a call with host outputs synchronises.  RDR_ERR_INVALID, before the device is touched and with the
+ * outputs unwritten: NULL, a wrong loc, n outside 2 .. 2^20, nd outside 1 .. 4096, nbins outside 1 .. 64, nedge_rows not 1 or nd, an
+ * edge row that is not finite or not strictly ascending (a row on the device is read back for this check). */
+int rdr_pair_distance_max(rdr_ctx* ctx, const double* x, const double* y, int64_t n, const double* values, int nd, double* hmax, int loc);
+int rdr_pair_variogram(rdr_ctx* ctx, const double* x, const double* y, int64_t n, const double* values, int nd, const double* edges, int nedge_rows,
+                       int nbins, int64_t* count, double* lag_sum, double* gamma_sum, int loc);
+
 #ifdef __cplusplus
 }
 #endif

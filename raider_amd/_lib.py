@@ -161,6 +161,8 @@ SYMBOLS = [
     ('rdr_h5_chunks', C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, _VP, C.c_int]),
     ('rdr_inflate_decode', C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, C.c_int]),
     ('rdr_h5_unchunk', C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, C.c_int]),
+    ('rdr_pair_distance_max', C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int, _VP, C.c_int]),
+    ('rdr_pair_variogram', C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int, _VP, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int]),
 ]
 
 

@@ -418,6 +418,7 @@ static auto by_dtype(const rdr_cube* q, F&& f) -> decltype(f(float2())) {
 #include "tiff_kernels.h"
 #include "deflate_kernels.h"
 #include "inflate_kernels.h"
+#include "variogram_kernels.h"
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -3799,5 +3800,101 @@ int rdr_h5_unchunk(rdr_ctx* c, const void* chunks, int64_t chunk_stride, const i
     if (S.rc) return S.rc;
     if (npresent < nchunks) HIPCHECK(c, hipMemsetAsync(dout, 0, (size_t)out_elems * elem_bytes, c->stream));      // absent chunks read as 0
     hipLaunchKernelGGL(h5_unchunk_kernel, dim3(grid_for(L.total_elems, 256, c->num_cus * 16)), dim3(256), 0, c->stream, din, dtab, L, dout);
+    return S.finish();
+}
+
+
+// ---- all-pair variograms of a station series (variogram_kernels.h; raider_amd/variogram.py) ----------------------------------------
+// what both entries refuse before the device is touched
+static int pair_args(rdr_ctx* c, const char* who, bool null_arg, int64_t n, int nd, int loc) {
+    const std::string w(who);
+    if (null_arg) return fail(c, RDR_ERR_INVALID, w + ": NULL argument");
+    if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, w + ": loc must be RDR_HOST or RDR_DEVICE");
+    if (n < 2 || n > ((int64_t)1 << 20)) return fail(c, RDR_ERR_INVALID, w + ": n must be 2 .. 2^20 points (got " + std::to_string(n) + ")");
+    if (nd < 1 || nd > 4096) return fail(c, RDR_ERR_INVALID, w + ": nd must be 1 .. 4096 dates (got " + std::to_string(nd) + ")");
+    return RDR_OK;
+}
+
+// workgroups of a pair launch: one per tile pair, at most four per compute unit (RAIDER_HIP_VARIOGRAM_GRID: another cap, for tests)
+static int pair_grid(const rdr_ctx* c, int64_t n) {
+    const int64_t nt = (n + VG_TILE - 1) / VG_TILE, ntp = nt * (nt + 1) / 2;
+    int64_t cap = (int64_t)c->num_cus * 4;
+    if (const char* e = std::getenv("RAIDER_HIP_VARIOGRAM_GRID")) { const long v = std::atol(e); if (v >= 1 && v <= 4096) cap = v; }
+    return (int)std::min(ntp, cap);
+}
+
+// date groups of 4, then 2, then 1 (engine.epoch_groups): f(first date, dates)
+template <typename F>
+static void pair_date_groups(int nd, F&& f) {
+    for (int d0 = 0; d0 < nd;) {
+        const int g = nd - d0 >= 4 ? 4 : nd - d0 >= 2 ? 2 : 1;
+        f(d0, g);
+        d0 += g;
+    }
+}
+
+int rdr_pair_distance_max(rdr_ctx* c, const double* x, const double* y, int64_t n, const double* values, int nd, double* hmax, int loc) {
+    const int bad = pair_args(c, "rdr_pair_distance_max", !c || !x || !y || !values || !hmax, n, nd, loc); if (bad) return bad;
+    HIPCHECK(c, hipSetDevice(c->device));
+    Staged S(c, loc);
+    const double *dx = S.in(x, (size_t)n * 8), *dy = S.in(y, (size_t)n * 8), *dv = S.in(values, (size_t)nd * n * 8);
+    double* dh = S.out(hmax, (size_t)nd * 8);
+    unsigned long long* dm = S.scratch<unsigned long long>(SLOT_AUX, (size_t)nd * 8);
+    if (S.rc) return S.rc;
+    HIPCHECK(c, hipMemsetAsync(dm, 0, (size_t)nd * 8, c->stream));
+    const int grid = pair_grid(c, n);
+    pair_date_groups(nd, [&](int d0, int g) {
+        if (g == 4) hipLaunchKernelGGL(pair_hmax_kernel<4>, dim3(grid), dim3(VG_TILE), 0, c->stream, dx, dy, dv, (int)n, d0, dm);
+        else if (g == 2) hipLaunchKernelGGL(pair_hmax_kernel<2>, dim3(grid), dim3(VG_TILE), 0, c->stream, dx, dy, dv, (int)n, d0, dm);
+        else hipLaunchKernelGGL(pair_hmax_kernel<1>, dim3(grid), dim3(VG_TILE), 0, c->stream, dx, dy, dv, (int)n, d0, dm);
+    });
+    hipLaunchKernelGGL(pair_hmax_finish_kernel, dim3((nd + 255) / 256), dim3(256), 0, c->stream, dm, nd, dh);
+    return S.finish();
+}
+
+int rdr_pair_variogram(rdr_ctx* c, const double* x, const double* y, int64_t n, const double* values, int nd, const double* edges, int nedge_rows,
+                       int nbins, int64_t* count, double* lag_sum, double* gamma_sum, int loc) {
+    static const char* who = "rdr_pair_variogram";
+    const int bad = pair_args(c, who, !c || !x || !y || !values || !edges || !count || !lag_sum || !gamma_sum, n, nd, loc); if (bad) return bad;
+    if (nbins < 1 || nbins > VG_MAXB) return fail(c, RDR_ERR_INVALID, std::string(who) + ": nbins must be 1 .. 64 (got " + std::to_string(nbins) + ")");
+    if (nedge_rows != 1 && nedge_rows != nd)
+        return fail(c, RDR_ERR_INVALID, std::string(who) + ": nedge_rows must be 1 or nd = " + std::to_string(nd) + " (got " + std::to_string(nedge_rows) + ")");
+    const size_t ne = (size_t)nbins + 1, nedges = (size_t)nedge_rows * ne;
+    // edge rows: finite and strictly ascending (a row on the device is read back for the check: at most 65 numbers per row)
+    std::vector<double> back;
+    const double* he = edges;
+    if (loc == RDR_DEVICE) {
+        HIPCHECK(c, hipSetDevice(c->device));
+        back.resize(nedges);
+        HIPCHECK(c, hipMemcpyAsync(back.data(), edges, nedges * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(c, hipStreamSynchronize(c->stream));
+        he = back.data();
+    }
+    for (int r = 0; r < nedge_rows; ++r)
+        for (size_t k = 0; k < ne; ++k) {
+            const double e = he[r * ne + k];
+            if (!std::isfinite(e)) return fail(c, RDR_ERR_INVALID, std::string(who) + ": edge row " + std::to_string(r) + " holds a value that is not finite");
+            if (k && !(e > he[r * ne + k - 1]))
+                return fail(c, RDR_ERR_INVALID, std::string(who) + ": edge row " + std::to_string(r) + " is not strictly ascending at index " + std::to_string(k));
+        }
+    HIPCHECK(c, hipSetDevice(c->device));
+    const size_t nout = (size_t)nd * nbins;
+    const int grid = pair_grid(c, n);
+    Staged S(c, loc);
+    const double *dx = S.in(x, (size_t)n * 8), *dy = S.in(y, (size_t)n * 8), *dv = S.in(values, (size_t)nd * n * 8), *de = S.in(edges, nedges * 8);
+    long long* dc = reinterpret_cast<long long*>(S.out(count, nout * 8));
+    double *dl = S.out(lag_sum, nout * 8), *dg = S.out(gamma_sum, nout * 8);
+    const size_t part = (size_t)grid * 4 * nbins;                 // elements of one partial array of the largest date group
+    double* dpart = S.scratch<double>(SLOT_AUX, 3 * part * 8);
+    if (S.rc) return S.rc;
+    unsigned long long* pc = reinterpret_cast<unsigned long long*>(dpart);
+    double *pl = dpart + part, *pg = dpart + 2 * part;
+    const int per_date = nedge_rows > 1 ? 1 : 0;
+    pair_date_groups(nd, [&](int d0, int g) {
+        if (g == 4) hipLaunchKernelGGL(pair_variogram_kernel<4>, dim3(grid), dim3(VG_TILE), 0, c->stream, dx, dy, dv, (int)n, d0, de, per_date, nbins, pc, pl, pg);
+        else if (g == 2) hipLaunchKernelGGL(pair_variogram_kernel<2>, dim3(grid), dim3(VG_TILE), 0, c->stream, dx, dy, dv, (int)n, d0, de, per_date, nbins, pc, pl, pg);
+        else hipLaunchKernelGGL(pair_variogram_kernel<1>, dim3(grid), dim3(VG_TILE), 0, c->stream, dx, dy, dv, (int)n, d0, de, per_date, nbins, pc, pl, pg);
+        hipLaunchKernelGGL(pair_reduce_kernel, dim3((g * nbins + 63) / 64), dim3(64), 0, c->stream, pc, pl, pg, grid, g * nbins, (long long)d0 * nbins, dc, dl, dg);
+    });
     return S.finish();
 }
