@@ -675,6 +675,38 @@ int rdr_pair_distance_max(rdr_ctx* ctx, const double* x, const double* y, int64_
 int rdr_pair_variogram(rdr_ctx* ctx, const double* x, const double* y, int64_t n, const double* values, int nd, const double* edges, int nedge_rows,
                        int nbins, int64_t* count, double* lag_sum, double* gamma_sum, int loc);
 
+/* rdr_cell_variogram: the all-pair variograms of EVERY grid cell and date in one pass (cli/statsPlot.py:721-814, _append_variogram
+ * without its sampling; csrc/cell_variogram_kernels.h).  x, y [n], values [nd][n]: as above, the stations SORTED BY CELL - cell c owns
+ * the stations cell_start[c] .. cell_start[c + 1] - 1 (cell_start [ncells + 1], ascending, first 0, last n; an empty cell is allowed).
+ * Per slice (cell c, date d), over the pairs of the cell's stations valid on the date:
+ *   nvalid [ncells][nd]   the valid stations;
+ *   status [ncells][nd]   0 done; 1 skipped: nvalid < min_valid; 2 (deramp only) the plane is numerically singular - the determinant of
+ *                         the centred 2 x 2 normal matrix is not above 1e-12 (Sxx + Syy)^2: fewer than three stations, stations at one
+ *                         place or within 1e-6 of their extent of one line - and the slice is left to the caller's lstsq.  A slice with status != 0 has count 0, sums 0.0,
+ *                         hmax NaN and, with deramp, NaN residuals;
+ *   deramp = 1            the plane a x + b y + c fitted to the valid stations (centred normal equations, f64, a fixed summation order)
+ *                         is removed before the pairs are formed; residuals (NULL or [nd][n], NaN where values is) receives the result.
+ *                         residuals must not overlap values, and is refused without deramp;
+ *   hmax [ncells][nd]     the largest h, NaN without a valid pair;
+ *   edges = NULL          the reference's default row per slice, np.linspace(0, 0.67 * hmax, nbins + 1) bit for bit (:638);
+ *   edges != NULL         [ncells][nbins + 1], one finite, strictly ascending row per cell, for all its dates;
+ *   edges_out             NULL or [ncells][nd][nbins + 1]: the row of each slice (NaN for a default row without a pair);
+ *   count, lag_sum, gamma_sum [ncells][nd][nbins]: as rdr_pair_variogram's, the same bin rule and the same bound on the sums;
+ *   tot_count, tot_lag, tot_gamma  NULL (all three) or [ncells][nbins], given edges only: the slices of a cell with status 0 added in
+ *                         date order - with all pairs kept, _binned_vario of the dates' concatenated raw arrays (:793-801).
+ * One workgroup owns a (cell, group of 4 / 2 / 1 dates): three launches at most, no partials, no floating-point atomic on global memory,
+ * counts identical between calls.  A cell of up to 512 stations is staged in LDS; a larger one runs from global memory in ONE
+ * workgroup (no limit but n, and no speed to expect beyond some thousand stations per cell).  Every array lives at `loc`; with deramp
+ * and residuals = NULL a work array of nd * n doubles is taken from the context.  RDR_ERR_INVALID, before any launch and with the outputs
+ * unwritten: NULL (x, y, cell_start, values, nvalid, hmax, status, count, lag_sum, gamma_sum), a wrong loc, n outside 2 .. 2^20, nd
+ * outside 1 .. 4096, nbins outside 1 .. 64, ncells outside 1 .. 2^20, min_valid < 0, deramp not 0 or 1, residuals without deramp, some
+ * but not all of tot_*, totals without edges, cell_start not starting at 0, not ending at n or not ascending, an edge row that is not
+ * finite or not strictly ascending (arrays on the device are read back for these checks). */
+int rdr_cell_variogram(rdr_ctx* ctx, const double* x, const double* y, int64_t n, const int64_t* cell_start, int ncells, const double* values, int nd,
+                       int deramp, int min_valid, const double* edges, int nbins, int64_t* nvalid, double* hmax, int32_t* status, int64_t* count,
+                       double* lag_sum, double* gamma_sum, double* edges_out, double* residuals, int64_t* tot_count, double* tot_lag, double* tot_gamma,
+                       int loc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,7 @@ SYMBOLS = [
     ('rdr_h5_unchunk', C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, C.c_int]),
     ('rdr_pair_distance_max', C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int, _VP, C.c_int]),
     ('rdr_pair_variogram', C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int, _VP, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int]),
+    ('rdr_cell_variogram', C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int] + [_VP] * 11 + [C.c_int]),
 ]
 
 

@@ -419,6 +419,7 @@ static auto by_dtype(const rdr_cube* q, F&& f) -> decltype(f(float2())) {
 #include "deflate_kernels.h"
 #include "inflate_kernels.h"
 #include "variogram_kernels.h"
+#include "cell_variogram_kernels.h"
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -3897,4 +3898,87 @@ int rdr_pair_variogram(rdr_ctx* c, const double* x, const double* y, int64_t n, 
         hipLaunchKernelGGL(pair_reduce_kernel, dim3((g * nbins + 63) / 64), dim3(64), 0, c->stream, pc, pl, pg, grid, g * nbins, (long long)d0 * nbins, dc, dl, dg);
     });
     return S.finish();
+}
+
+// ---- per-grid-cell variograms in one pass (cell_variogram_kernels.h; raider_amd/variogram.py: grid_variograms) ----------------------
+int rdr_cell_variogram(rdr_ctx* c, const double* x, const double* y, int64_t n, const int64_t* cell_start, int ncells, const double* values, int nd,
+                       int deramp, int min_valid, const double* edges, int nbins, int64_t* nvalid, double* hmax, int32_t* status, int64_t* count,
+                       double* lag_sum, double* gamma_sum, double* edges_out, double* residuals, int64_t* tot_count, double* tot_lag, double* tot_gamma,
+                       int loc) {
+    static const char* who = "rdr_cell_variogram";
+    const std::string w(who);
+    const int bad = pair_args(c, who, !c || !x || !y || !cell_start || !values || !nvalid || !hmax || !status || !count || !lag_sum || !gamma_sum, n, nd, loc);
+    if (bad) return bad;
+    if (nbins < 1 || nbins > VG_MAXB) return fail(c, RDR_ERR_INVALID, w + ": nbins must be 1 .. 64 (got " + std::to_string(nbins) + ")");
+    if (ncells < 1 || ncells > (1 << 20)) return fail(c, RDR_ERR_INVALID, w + ": ncells must be 1 .. 2^20 cells (got " + std::to_string(ncells) + ")");
+    if (min_valid < 0) return fail(c, RDR_ERR_INVALID, w + ": min_valid must not be negative (got " + std::to_string(min_valid) + ")");
+    if (deramp != 0 && deramp != 1) return fail(c, RDR_ERR_INVALID, w + ": deramp must be 0 or 1 (got " + std::to_string(deramp) + ")");
+    if (residuals && !deramp) return fail(c, RDR_ERR_INVALID, w + ": residuals are written only with deramp = 1");
+    const bool totals = tot_count || tot_lag || tot_gamma;
+    if (totals && !(tot_count && tot_lag && tot_gamma)) return fail(c, RDR_ERR_INVALID, w + ": tot_count, tot_lag and tot_gamma come together or not at all");
+    if (totals && !edges) return fail(c, RDR_ERR_INVALID, w + ": totals need given edges (one row per cell)");
+    const size_t ne = (size_t)nbins + 1, nedges = edges ? (size_t)ncells * ne : 0;
+    // cell_start and the edge rows are checked on the host (arrays on the device are read back: ncells + 1 and ncells * (nbins + 1) numbers)
+    std::vector<int64_t> back_cs; std::vector<double> back_e;
+    const int64_t* hcs = cell_start; const double* he = edges;
+    if (loc == RDR_DEVICE) {
+        HIPCHECK(c, hipSetDevice(c->device));
+        back_cs.resize((size_t)ncells + 1);
+        HIPCHECK(c, hipMemcpyAsync(back_cs.data(), cell_start, ((size_t)ncells + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        if (edges) { back_e.resize(nedges); HIPCHECK(c, hipMemcpyAsync(back_e.data(), edges, nedges * 8, hipMemcpyDeviceToHost, c->stream)); }
+        HIPCHECK(c, hipStreamSynchronize(c->stream));
+        hcs = back_cs.data(); if (edges) he = back_e.data();
+    }
+    if (hcs[0] != 0) return fail(c, RDR_ERR_INVALID, w + ": cell_start[0] must be 0 (got " + std::to_string(hcs[0]) + ")");
+    if (hcs[ncells] != n) return fail(c, RDR_ERR_INVALID, w + ": cell_start[ncells] must be n = " + std::to_string(n) + " (got " + std::to_string(hcs[ncells]) + ")");
+    for (int k = 0; k < ncells; ++k)
+        if (hcs[k + 1] < hcs[k]) return fail(c, RDR_ERR_INVALID, w + ": cell_start is not ascending at index " + std::to_string(k + 1));
+    for (int r = 0; edges && r < ncells; ++r)
+        for (size_t k = 0; k < ne; ++k) {
+            const double e = he[r * ne + k];
+            if (!std::isfinite(e)) return fail(c, RDR_ERR_INVALID, w + ": edge row " + std::to_string(r) + " holds a value that is not finite");
+            if (k && !(e > he[r * ne + k - 1]))
+                return fail(c, RDR_ERR_INVALID, w + ": edge row " + std::to_string(r) + " is not strictly ascending at index " + std::to_string(k));
+        }
+    HIPCHECK(c, hipSetDevice(c->device));
+    const size_t cd = (size_t)ncells * nd, vbytes = (size_t)nd * n * 8;
+    const void* d;
+    CellVgArgs A{};
+    int rc = stage_in(c, SLOT_IN0, x, (size_t)n * 8, loc, &d); if (rc) return rc; A.x = (const double*)d;
+    rc = stage_in(c, SLOT_IN1, y, (size_t)n * 8, loc, &d); if (rc) return rc; A.y = (const double*)d;
+    rc = stage_in(c, SLOT_IN2, cell_start, ((size_t)ncells + 1) * 8, loc, &d); if (rc) return rc; A.cell_start = (const long long*)d;
+    rc = stage_in(c, SLOT_IN3, values, vbytes, loc, &d); if (rc) return rc; A.values = (const double*)d;
+    rc = stage_in(c, SLOT_IN4, edges, nedges * 8, loc, &d); if (rc) return rc; A.edges = (const double*)d;
+    // the outputs: where they are (loc = device), or back to back in one slot from which they are downloaded (loc = host)
+    struct Out { void* host; size_t bytes; void* dev; };
+    Out outs[11] = {{nvalid, cd * 8, nullptr}, {hmax, cd * 8, nullptr}, {status, cd * 4, nullptr}, {count, cd * nbins * 8, nullptr},
+                    {lag_sum, cd * nbins * 8, nullptr}, {gamma_sum, cd * nbins * 8, nullptr}, {edges_out, cd * ne * 8, nullptr}, {residuals, vbytes, nullptr},
+                    {tot_count, (size_t)ncells * nbins * 8, nullptr}, {tot_lag, (size_t)ncells * nbins * 8, nullptr}, {tot_gamma, (size_t)ncells * nbins * 8, nullptr}};
+    if (loc == RDR_DEVICE) {
+        for (Out& o : outs) o.dev = o.host;
+    } else {
+        size_t total = 0;
+        for (Out& o : outs) if (o.host) total += (o.bytes + 15) & ~(size_t)15;
+        void* base; rc = ensure(c, SLOT_OUT0, total, &base); if (rc) return rc;
+        size_t off = 0;
+        for (Out& o : outs) if (o.host) { o.dev = static_cast<char*>(base) + off; off += (o.bytes + 15) & ~(size_t)15; }
+    }
+    A.n = n; A.nd = nd; A.deramp = deramp; A.min_valid = min_valid; A.nbins = nbins;
+    A.nvalid = (long long*)outs[0].dev; A.hmax = (double*)outs[1].dev; A.status = (int*)outs[2].dev; A.count = (long long*)outs[3].dev;
+    A.lag = (double*)outs[4].dev; A.gamma = (double*)outs[5].dev; A.edges_out = (double*)outs[6].dev; A.resid = (double*)outs[7].dev;
+    if (deramp && !A.resid) { void* t; rc = ensure(c, SLOT_AUX, vbytes, &t); if (rc) return rc; A.resid = (double*)t; }   // (cells beyond LDS read them back)
+    // date groups of 4, then 2, then 1: one launch per group size, a workgroup per (cell, group)
+    const int n4 = nd / 4, d2 = n4 * 4, n2 = (nd - d2) / 2, d1 = d2 + n2 * 2, n1 = nd - d1;
+    if (n4) hipLaunchKernelGGL(cell_variogram_kernel<4>, dim3((unsigned)ncells * n4), dim3(VG_TILE), 0, c->stream, A, 0, n4);
+    if (n2) hipLaunchKernelGGL(cell_variogram_kernel<2>, dim3((unsigned)ncells * n2), dim3(VG_TILE), 0, c->stream, A, d2, n2);
+    if (n1) hipLaunchKernelGGL(cell_variogram_kernel<1>, dim3((unsigned)ncells * n1), dim3(VG_TILE), 0, c->stream, A, d1, n1);
+    if (totals) {
+        const long long nt = (long long)ncells * nbins;
+        hipLaunchKernelGGL(cell_totals_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, c->stream, A.count, A.lag, A.gamma, A.status, ncells, nd, nbins,
+                           (long long*)outs[8].dev, (double*)outs[9].dev, (double*)outs[10].dev);
+    }
+    HIPCHECK(c, hipGetLastError());
+    for (Out& o : outs) { rc = finish_out(c, o.host, o.dev, o.bytes, loc); if (rc) return rc; }
+    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return RDR_OK;
 }

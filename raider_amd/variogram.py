@@ -265,3 +265,241 @@ def station_variograms(lon, lat, values, deramp=True, edges=None, nbins=19, mode
         binned.append((h, g))
         fits.append(fit_variogram(h, g, model) if (fit and h.size) else None)
     return StationVariograms(pv, binned, fits, x, y)
+
+
+# ---- per-grid-cell variograms: the gridding of raiderStats and _append_variogram over all cells and dates in one device pass ---------
+StationGrid = namedtuple('StationGrid', 'extent spacing grid_dim gridpoints cell order start')
+
+
+def station_grid(lon, lat, spacing=1.0, bbox=None):
+    """The grid of `RaiderStats._get_extent` (cli/statsPlot.py:1291-1368) and the cell of every station -> StationGrid.
+
+    extent [W, E, S, N] = floor / ceil of the stations' bounds, or of `bbox` = [S, N, W, E] (which must overlap the stations' extent
+    and stay within +-180 / +-90: the reference's two exceptions, here ValueError with its messages); clamped to +-180 / +-90.  A
+    spacing that does not divide both extents is reset to 1 with a warning (:1339).  grid_dim = [nx, ny].  gridpoints [G, 2] (lon, lat
+    of the cell centres) in the reference's order: cell g = ix * ny + (ny - 1 - iy), ix counted from the west, iy from the south, so a
+    map is a[g].reshape(nx, ny).T with row 0 in the north.
+
+    cell [N]: station i lies in ix = min(floor((lon - W) / spacing), nx - 1), likewise iy - a cell owns its west and south edges, the
+    outer east and north borders belong to the last column and row (the reference resolves a station exactly on an interior edge by
+    R-tree order, which is not a rule); -1 for a station outside the extent (or NaN), which takes part in nothing.  order: a stable
+    argsort of cell without the dropped stations; start [G + 1]: cell g owns order[start[g]:start[g + 1]]."""
+    import warnings
+    lon = np.asarray(lon, dtype=np.float64).reshape(-1); lat = np.asarray(lat, dtype=np.float64).reshape(-1)
+    if lon.size != lat.size or lon.size == 0:
+        raise ValueError('lon and lat must have the same, non-empty length')
+    extent = [np.floor(np.nanmin(lon)), np.ceil(np.nanmax(lon)), np.floor(np.nanmin(lat)), np.ceil(np.nanmax(lat))]
+    if bbox is not None:
+        s, n, w, e = (float(b) for b in bbox)
+        if e < extent[0] or w > extent[1] or n < extent[2] or s > extent[3]:          # closed rectangles: touching counts as overlap
+            raise ValueError('User-specified bounds do not overlap with dataset bounds, adjust bounds and re-run program.')
+        extent = [np.floor(w), np.ceil(e), np.floor(s), np.ceil(n)]
+        if extent[0] < -180.0 or extent[1] > 180.0 or extent[2] < -90.0 or extent[3] > 90.0:
+            raise ValueError('Specified bounds exceed -180/180 lon and/or -90/90 lat, adjust bounds and re-run program.')
+    extent = [max(extent[0], -180.0), min(extent[1], 180.0), max(extent[2], -90.0), min(extent[3], 90.0)]
+    if (extent[1] - extent[0]) % spacing != 0 or (extent[3] - extent[2]) % spacing:
+        warnings.warn(f'spacing {spacing} is not an even multiple of the bounds, reset to 1 degree')
+        spacing = 1
+    nx, ny = int((extent[1] - extent[0]) / spacing), int((extent[3] - extent[2]) / spacing)
+    # centres by the reference's running sums: x from the east edge downwards, y from the south edge upwards, the list then reversed
+    xs, x = [], extent[1] - spacing / 2
+    while x >= extent[0] + spacing / 2:
+        xs.append(x); x -= spacing
+    ys, y = [], extent[2] + spacing / 2
+    while y <= extent[3] - spacing / 2:
+        ys.append(y); y += spacing
+    if len(xs) != nx or len(ys) != ny:
+        raise ValueError(f'the grid of spacing {spacing} over {extent} has {len(xs)} x {len(ys)} centres, not {nx} x {ny}')
+    gridpoints = np.array([[xv, yv] for xv in xs[::-1] for yv in ys[::-1]], dtype=np.float64).reshape(nx * ny, 2)
+    with np.errstate(invalid='ignore'):
+        inside = (lon >= extent[0]) & (lon <= extent[1]) & (lat >= extent[2]) & (lat <= extent[3])
+        ix = np.minimum(np.floor((np.where(inside, lon, extent[0]) - extent[0]) / spacing), nx - 1).astype(np.int64)
+        iy = np.minimum(np.floor((np.where(inside, lat, extent[2]) - extent[2]) / spacing), ny - 1).astype(np.int64)
+    cell = np.where(inside, ix * ny + (ny - 1 - iy), -1).astype(np.int64)
+    order = np.argsort(cell, kind='stable')
+    order = order[cell[order] >= 0]
+    start = np.concatenate([[0], np.cumsum(np.bincount(cell[order], minlength=nx * ny))]).astype(np.int64)
+    return StationGrid(extent, spacing, [nx, ny], gridpoints, cell, order, start)
+
+
+class GridVariograms:
+    """What grid_variograms returns.  grid: the StationGrid; G cells, D dates, B bins.  nvalid, hmax, status [G, D] (status 0 done on
+    the device, 1 skipped - fewer than density_threshold valid stations -, 2 done through the host chain: a singular plane); count,
+    lag_sum, gamma_sum [G, D, B] and edges [G, D, B + 1] per slice; total_count, total_lag, total_gamma [G, B] in total_edges [G, B + 1]:
+    all good dates of a cell binned together; these sums are NumPy arrays or GPU tensors as the inputs were.  Host arrays: params [G, 3]
+    (range, sill, nugget of the total fit) and rmse [G], NaN for a cell without a good date; sparse_grids: the cells that hold stations
+    but no good date; skipped_slices: (cell, date index) of the slices that hold data but fewer than density_threshold stations;
+    grid_range, grid_variance, grid_variogram_rmse [ny, nx]: the maps, row 0 in the north (cli/statsPlot.py:3302-3337);
+    date_fits: {(cell, date index): VariogramFit} when per_date_fits was asked for, else None; x, y: the sorted stations' metres."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def binned(self, c, d):
+        """(hExp, expVario) of cell c on date d, empty bins dropped (_binned_vario)."""
+        n = self.count[c][d]
+        keep = n > 0
+        return self.lag_sum[c][d][keep] / n[keep], self.gamma_sum[c][d][keep] / n[keep]
+
+    def total_binned(self, c):
+        """(hExp, expVario) of all good dates of cell c binned together (:801)."""
+        n = self.total_count[c]
+        keep = n > 0
+        return self.total_lag[c][keep] / n[keep], self.total_gamma[c][keep] / n[keep]
+
+    def map(self, a):
+        """[G] -> [ny, nx], row 0 in the north."""
+        return np.asarray(a).reshape(self.grid.grid_dim).T
+
+
+def _cell_call(ctx, x, y, start, v, deramp, min_valid, edges, nbins, residuals, totals, on_device):
+    """One rdr_cell_variogram call on sorted stations -> dict of outputs (arrays or tensors, as x is)."""
+    nd, n, g = int(v.shape[0]), int(v.shape[1]), int(start.shape[0]) - 1
+    if on_device:
+        import torch
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=v.device)
+        f64, i64, i32 = torch.float64, torch.int64, torch.int32
+    else:
+        new = lambda shape, dtype: np.empty(shape, dtype=dtype)
+        f64, i64, i32 = np.float64, np.int64, np.int32
+    o = dict(nvalid=new((g, nd), i64), hmax=new((g, nd), f64), status=new((g, nd), i32), count=new((g, nd, nbins), i64),
+             lag_sum=new((g, nd, nbins), f64), gamma_sum=new((g, nd, nbins), f64), edges=new((g, nd, nbins + 1), f64),
+             residuals=new((nd, n), f64) if residuals else None)
+    for k in ('total_count', 'total_lag', 'total_gamma'):
+        o[k] = new((g, nbins), i64 if k == 'total_count' else f64) if totals else None
+    check(ctx.lib.rdr_cell_variogram(ctx.handle, ptr(x), ptr(y), n, ptr(start), g, ptr(v), nd, int(bool(deramp)), int(min_valid), ptr(edges), nbins,
+                                     ptr(o['nvalid']), ptr(o['hmax']), ptr(o['status']), ptr(o['count']), ptr(o['lag_sum']), ptr(o['gamma_sum']),
+                                     ptr(o['edges']), ptr(o['residuals']), ptr(o['total_count']), ptr(o['total_lag']), ptr(o['total_gamma']),
+                                     L.RDR_DEVICE if on_device else L.RDR_HOST), ctx.handle)
+    return o
+
+
+def grid_variograms(lon, lat, values, spacing=1.0, bbox=None, density_threshold=10, deramp=True, nbins=19, binned=False, model='exponential',
+                    errlimit=np.inf, fit=True, per_date_fits=False, ctx=None):
+    """`raiderStats --variogramplot` up to its three maps (VariogramAnalysis.create_variograms / _append_variogram, cli/statsPlot.py:721-883,
+    and stats_analyses :3300-3339) for stations lon / lat [N] (degrees) and values [D, N] (NaN = missing), over ALL pairs of every cell
+    -> GridVariograms.  lon, lat, values are all NumPy arrays or all GPU tensors (values then never visits the host; lon and lat do, for
+    the gridding).
+
+      1. station_grid(lon, lat, spacing, bbox); metres in ONE UTM zone per cell, that of the medians of the cell's stations - the rule of
+         station_variograms; the reference takes the medians of each date's valid stations.  Cells are grouped by zone: one transform
+         per zone.
+      2. one device pass (rdr_cell_variogram): per cell and date the plane removal, the largest pair distance, the default bins
+         linspace(0, 0.67 hmax, nbins + 1) and the binned sums.  A slice with fewer than density_threshold valid stations is skipped.
+      3. the few slices whose plane is numerically singular (stations on one line; status 2) are redone through the host chain, `deramp`
+         (np.linalg.lstsq) + pair_variogram, and patched in.
+      4. per cell, one row linspace(0, 0.67 * the largest hmax of its good dates, nbins + 1), and
+      5. a second pass over the residuals in those rows, summed over the good dates: _binned_vario of the concatenated raw arrays (:801).
+      6. per cell with a good date: fit_variogram (host, scipy.optimize.least_squares, as the reference) of the total binned variogram
+         - of the concatenated per-date binned arrays with binned=True (:796-798); rmse = sqrt(nanmean(fun^2)), NaN above errlimit.
+         fit=False leaves params and rmse NaN.  per_date_fits=True also fits every good slice: one host scipy fit per slice, G x D of
+         them - off by default, the maps do not need them."""
+    tensors = [_is_tensor(a) for a in (lon, lat, values)]
+    if any(tensors) and not all(tensors):
+        raise TypeError('lon, lat and values must be all NumPy arrays or all GPU tensors')
+    on_device = all(tensors)
+    nbins = int(nbins)
+    if not 1 <= nbins <= MAX_BINS:
+        raise ValueError(f'nbins must be 1 .. {MAX_BINS} (got {nbins})')
+    if on_device:
+        import torch
+        if not (lon.is_cuda and lat.is_cuda and values.is_cuda):
+            raise TypeError('tensors must live on the GPU')
+        lon_h = lon.detach().to(torch.float64).cpu().numpy().reshape(-1); lat_h = lat.detach().to(torch.float64).cpu().numpy().reshape(-1)
+        v = values if values.ndim == 2 else values[None, :]
+    else:
+        lon_h = np.asarray(lon, dtype=np.float64).reshape(-1); lat_h = np.asarray(lat, dtype=np.float64).reshape(-1)
+        v = np.asarray(values)
+        v = v if v.ndim == 2 else v[None, :]
+    if v.ndim != 2 or v.shape[1] != lon_h.size or lat_h.size != lon_h.size:
+        raise ValueError('lon, lat [N] and values [N] or [D, N] must agree in N')
+    nd = int(v.shape[0])
+    if not 1 <= nd <= MAX_DATES:
+        raise ValueError(f'1 .. {MAX_DATES} dates (got {nd})')
+    grid = station_grid(lon_h, lat_h, spacing, bbox)
+    order, start = grid.order, grid.start
+    n, ng = int(order.size), int(start.size) - 1
+    if not 2 <= n <= MAX_POINTS:
+        raise ValueError(f'2 .. {MAX_POINTS} stations inside the grid (got {n})')
+    # 1. metres, one transform per UTM zone
+    from .delay import transformPoints
+    lo, la = lon_h[order], lat_h[order]
+    full = np.flatnonzero(np.diff(start) > 0)
+    zones = {}
+    for c in full:
+        sl = slice(start[c], start[c + 1])
+        zones.setdefault(utm_zone(np.median(lo[sl]), np.median(la[sl])), []).append(c)
+    x = np.empty(n); y = np.empty(n)
+    for (zone, north), cells in zones.items():
+        idx = np.concatenate([np.arange(start[c], start[c + 1]) for c in cells])
+        p = transformPoints(la[idx], lo[idx], np.zeros(idx.size), 4326, (32600 if north else 32700) + zone)
+        x[idx] = p[..., 1]; y[idx] = p[..., 0]
+    ctx = ctx or Context.default()
+    if on_device:
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(v.device)
+        vs = v.to(torch.float64).index_select(1, dev(order)).contiguous()
+        ctx.adopt_torch_stream(vs)
+        xd, yd, sd = dev(x), dev(y), dev(start)
+        host = lambda a: a.cpu().numpy()
+    else:
+        dev = lambda a: a
+        vs = np.ascontiguousarray(v[:, order], dtype=np.float64)
+        xd, yd, sd = x, y, start
+        host = lambda a: a
+    # 2. the slices
+    o = _cell_call(ctx, xd, yd, sd, vs, deramp, density_threshold, None, nbins, True if deramp else False, False, on_device)
+    status = host(o['status']).copy()
+    resid = o['residuals'] if deramp else vs
+    # 3. singular planes: the host chain on the slice
+    for c, d in zip(*np.nonzero(status == 2)):
+        sl = slice(int(start[c]), int(start[c + 1]))
+        r = _remove_plane(x[sl], y[sl], host(vs[d, sl]))
+        resid[d, sl] = dev(r)
+        if sl.stop - sl.start >= 2:
+            pv = pair_variogram(x[sl], y[sl], r, nbins=nbins, ctx=ctx)
+            for k, a in (('count', pv.count[0]), ('lag_sum', pv.lag_sum[0]), ('gamma_sum', pv.gamma_sum[0]), ('edges', pv.edges[0]), ('hmax', pv.hmax[0:1])):
+                o[k][c, d] = dev(a) if k != 'hmax' else dev(a)[0]
+    hmax = host(o['hmax'])
+    nvalid = host(o['nvalid'])
+    good = status != 1
+    # 4. one row per cell over its good dates
+    with np.errstate(invalid='ignore'):
+        top = np.array([np.nanmax(hmax[c][good[c]]) if (good[c] & ~np.isnan(hmax[c])).any() else np.nan for c in range(ng)])
+    total_edges = default_edges(top, nbins)
+    # 5. the totals
+    t = _cell_call(ctx, xd, yd, sd, resid, False, density_threshold, dev(_usable_rows(total_edges)), nbins, False, True, on_device)
+    # 6. the fits
+    params = np.full((ng, 3), np.nan); rmse = np.full(ng, np.nan)
+    has_good = good.any(axis=1)
+    sparse = [int(c) for c in full if not has_good[c]]
+    skipped = [(int(c), int(d)) for c, d in zip(*np.nonzero((status == 1) & (nvalid > 0)))]
+    res = GridVariograms(grid=grid, nvalid=o['nvalid'], hmax=o['hmax'], status=status, count=o['count'], lag_sum=o['lag_sum'], gamma_sum=o['gamma_sum'],
+                         edges=o['edges'], total_count=t['total_count'], total_lag=t['total_lag'], total_gamma=t['total_gamma'],
+                         total_edges=dev(total_edges), residuals=resid, params=params, rmse=rmse, sparse_grids=sparse, skipped_slices=skipped,
+                         date_fits=None, x=x, y=y)
+    if fit or per_date_fits:
+        cnt = host(o['count']); lag = host(o['lag_sum']); gam = host(o['gamma_sum'])
+        per = lambda c, d: (lag[c, d][cnt[c, d] > 0] / cnt[c, d][cnt[c, d] > 0], gam[c, d][cnt[c, d] > 0] / cnt[c, d][cnt[c, d] > 0])
+    if fit:
+        tc = host(t['total_count']); tl = host(t['total_lag']); tg = host(t['total_gamma'])
+        for c in np.flatnonzero(has_good):
+            if binned:
+                parts = [per(c, d) for d in np.flatnonzero(good[c])]
+                h = np.concatenate([p_[0] for p_ in parts]); g = np.concatenate([p_[1] for p_ in parts])
+            else:
+                keep = tc[c] > 0
+                h = tl[c][keep] / tc[c][keep]; g = tg[c][keep] / tc[c][keep]
+            if h.size == 0:
+                continue
+            f = fit_variogram(h, g, model)
+            params[c] = f.params
+            e = float(np.sqrt(np.nanmean(f.result.fun ** 2)))
+            rmse[c] = e if e <= errlimit else np.nan
+    if per_date_fits:
+        res.date_fits = {}
+        for c, d in zip(*np.nonzero(good)):
+            h, g = per(c, d)
+            if h.size:
+                res.date_fits[(int(c), int(d))] = fit_variogram(h, g, model)
+    res.grid_range = res.map(params[:, 0]); res.grid_variance = res.map(params[:, 1]); res.grid_variogram_rmse = res.map(rmse)
+    return res
