@@ -707,6 +707,32 @@ int rdr_cell_variogram(rdr_ctx* ctx, const double* x, const double* y, int64_t n
                        double* lag_sum, double* gamma_sum, double* edges_out, double* residuals, int64_t* tot_count, double* tot_lag, double* tot_gamma,
                        int loc);
 
+/* rdr_grid_stats: the gridded station statistics of raiderStats (cli/statsPlot.py create_DF, :1571-1794; csrc/grid_stats_kernels.h).
+ * values [nd][n]: one row per date, NaN = no row, every other value - +-inf included - is a value; the stations SORTED BY CELL as for
+ * rdr_cell_variogram (cell_start [ncells + 1], ascending, first 0, last n; an empty cell is allowed).
+ * Per station [n]:
+ *   st_nobs (int64)       its values;
+ *   st_mean, st_median, st_stdev   over them; NaN without a value, st_stdev (ddof = 1) NaN below two.
+ * Per cell [ncells], of its stations:
+ *   nstations (int64)     the stations with a value;
+ *   mean_of_means, mean_of_medians, mean_of_stdevs   the mean of the station statistic over the cell's stations where it is not NaN,
+ *                         added in station order; NaN when none is left.
+ * Per cell [ncells], over all values of its stations at once:
+ *   cell_nobs (int64), abs_mean, abs_median, abs_stdev   as for a station.
+ * A mean is sum / count, a deviation sqrt(sum of (v - mean)^2 / (count - 1)) in a second pass; f64, every sum in a fixed order: two
+ * calls give the same bytes.  A median is (s[(m - 1) / 2] + s[m / 2]) / 2 of the m sorted values, bit for bit, found by exact radix
+ * selection on the order-preserving 64-bit keys (-0 below +0), a byte per pass, without sorting.  No floating-point atomic at all.
+ * Groups: (st_nobs, st_mean, st_stdev), (nstations, mean_of_means, mean_of_stdevs) and (cell_nobs, abs_mean, abs_stdev) are each given
+ * whole or NULL whole - a NULL group is not computed unless another needs it (then in a work array of the context) -; each of the three
+ * medians may be NULL on its own, which skips its selection, and is refused without its group.  A workgroup owns 64 stations, then one
+ * owns a cell: a huge cell runs in ONE workgroup, with no speed to expect.  Every array lives at `loc`; a call with host outputs
+ * synchronises.  RDR_ERR_INVALID, before any launch and with the outputs unwritten: NULL values or cell_start, a wrong loc, n outside
+ * 1 .. 2^20, nd outside 1 .. 4096, ncells outside 1 .. 2^20, a partly NULL group, every group NULL, cell_start not starting at 0, not
+ * ending at n or not ascending (an array on the device is read back for this), a cell of more than 2^31 - 1 slots (nd x its stations). */
+int rdr_grid_stats(rdr_ctx* ctx, const double* values, int64_t n, int nd, const int64_t* cell_start, int ncells, int64_t* st_nobs, double* st_mean,
+                   double* st_median, double* st_stdev, int64_t* nstations, double* mean_of_means, double* mean_of_medians, double* mean_of_stdevs,
+                   int64_t* cell_nobs, double* abs_mean, double* abs_median, double* abs_stdev, int loc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,3 +14,4 @@ from .time_interp import (DatetimeFailed, NoWeatherModelData, WrongNumberOfFiles
                           get_weights_time_interp, getWeatherFile, round_date, round_time, tropo_delay_interp, tropo_delay_interp_series)
 from .variogram import (GridVariograms, PairVariogram, StationGrid, deramp, fit_variogram, grid_variograms, pair_variogram, station_grid,  # noqa: F401
                         station_variograms, utm_common_center)
+from .station_stats import (GridStatistics, grid_statistics, load_gridfile, read_station_csv, save_gridfile, station_table)  # noqa: F401

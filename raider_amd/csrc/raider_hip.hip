@@ -420,6 +420,7 @@ static auto by_dtype(const rdr_cube* q, F&& f) -> decltype(f(float2())) {
 #include "inflate_kernels.h"
 #include "variogram_kernels.h"
 #include "cell_variogram_kernels.h"
+#include "grid_stats_kernels.h"
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -3977,6 +3978,82 @@ int rdr_cell_variogram(rdr_ctx* c, const double* x, const double* y, int64_t n, 
         hipLaunchKernelGGL(cell_totals_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, c->stream, A.count, A.lag, A.gamma, A.status, ncells, nd, nbins,
                            (long long*)outs[8].dev, (double*)outs[9].dev, (double*)outs[10].dev);
     }
+    HIPCHECK(c, hipGetLastError());
+    for (Out& o : outs) { rc = finish_out(c, o.host, o.dev, o.bytes, loc); if (rc) return rc; }
+    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return RDR_OK;
+}
+
+// ---- gridded station statistics (grid_stats_kernels.h; raider_amd/station_stats.py: grid_statistics) --------------------------------
+int rdr_grid_stats(rdr_ctx* c, const double* values, int64_t n, int nd, const int64_t* cell_start, int ncells, int64_t* st_nobs, double* st_mean,
+                   double* st_median, double* st_stdev, int64_t* nstations, double* mean_of_means, double* mean_of_medians, double* mean_of_stdevs,
+                   int64_t* cell_nobs, double* abs_mean, double* abs_median, double* abs_stdev, int loc) {
+    const std::string w("rdr_grid_stats");
+    if (!c || !values || !cell_start) return fail(c, RDR_ERR_INVALID, w + ": NULL argument");
+    if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, w + ": loc must be RDR_HOST or RDR_DEVICE");
+    if (n < 1 || n > ((int64_t)1 << 20)) return fail(c, RDR_ERR_INVALID, w + ": n must be 1 .. 2^20 stations (got " + std::to_string(n) + ")");
+    if (nd < 1 || nd > 4096) return fail(c, RDR_ERR_INVALID, w + ": nd must be 1 .. 4096 dates (got " + std::to_string(nd) + ")");
+    if (ncells < 1 || ncells > (1 << 20)) return fail(c, RDR_ERR_INVALID, w + ": ncells must be 1 .. 2^20 cells (got " + std::to_string(ncells) + ")");
+    // a group comes whole (its median apart) or not at all
+    const bool st_any = st_nobs || st_mean || st_stdev || st_median, st_all = st_nobs && st_mean && st_stdev;
+    const bool of_any = nstations || mean_of_means || mean_of_stdevs || mean_of_medians, of_all = nstations && mean_of_means && mean_of_stdevs;
+    const bool ab_any = cell_nobs || abs_mean || abs_stdev || abs_median, ab_all = cell_nobs && abs_mean && abs_stdev;
+    if (st_any && !st_all) return fail(c, RDR_ERR_INVALID, w + ": st_nobs, st_mean and st_stdev come together or not at all (st_median only with them)");
+    if (of_any && !of_all)
+        return fail(c, RDR_ERR_INVALID, w + ": nstations, mean_of_means and mean_of_stdevs come together or not at all (mean_of_medians only with them)");
+    if (ab_any && !ab_all) return fail(c, RDR_ERR_INVALID, w + ": cell_nobs, abs_mean and abs_stdev come together or not at all (abs_median only with them)");
+    if (!st_any && !of_any && !ab_any) return fail(c, RDR_ERR_INVALID, w + ": every output group is NULL");
+    // cell_start is checked on the host (an array on the device is read back: ncells + 1 numbers)
+    std::vector<int64_t> back_cs;
+    const int64_t* hcs = cell_start;
+    if (loc == RDR_DEVICE) {
+        HIPCHECK(c, hipSetDevice(c->device));
+        back_cs.resize((size_t)ncells + 1);
+        HIPCHECK(c, hipMemcpyAsync(back_cs.data(), cell_start, ((size_t)ncells + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(c, hipStreamSynchronize(c->stream));
+        hcs = back_cs.data();
+    }
+    if (hcs[0] != 0) return fail(c, RDR_ERR_INVALID, w + ": cell_start[0] must be 0 (got " + std::to_string(hcs[0]) + ")");
+    if (hcs[ncells] != n) return fail(c, RDR_ERR_INVALID, w + ": cell_start[ncells] must be n = " + std::to_string(n) + " (got " + std::to_string(hcs[ncells]) + ")");
+    for (int k = 0; k < ncells; ++k) {
+        if (hcs[k + 1] < hcs[k]) return fail(c, RDR_ERR_INVALID, w + ": cell_start is not ascending at index " + std::to_string(k + 1));
+        if ((hcs[k + 1] - hcs[k]) * nd > (int64_t)2147483647)
+            return fail(c, RDR_ERR_INVALID, w + ": cell " + std::to_string(k) + " holds more than 2^31 - 1 slots (" + std::to_string(hcs[k + 1] - hcs[k]) +
+                        " stations x " + std::to_string(nd) + " dates)");
+    }
+    HIPCHECK(c, hipSetDevice(c->device));
+    const void* d;
+    GridStatsArgs A{};
+    int rc = stage_in(c, SLOT_IN0, values, (size_t)nd * n * 8, loc, &d); if (rc) return rc; A.values = (const double*)d;
+    rc = stage_in(c, SLOT_IN1, cell_start, ((size_t)ncells + 1) * 8, loc, &d); if (rc) return rc; A.cell_start = (const long long*)d;
+    // the outputs: where they are (loc = device), or back to back in one slot from which they are downloaded (loc = host)
+    struct Out { void* host; size_t bytes; void* dev; };
+    const size_t sb = (size_t)n * 8, cb = (size_t)ncells * 8;
+    Out outs[12] = {{st_nobs, sb, nullptr}, {st_mean, sb, nullptr}, {st_median, sb, nullptr}, {st_stdev, sb, nullptr},
+                    {nstations, cb, nullptr}, {mean_of_means, cb, nullptr}, {mean_of_medians, cb, nullptr}, {mean_of_stdevs, cb, nullptr},
+                    {cell_nobs, cb, nullptr}, {abs_mean, cb, nullptr}, {abs_median, cb, nullptr}, {abs_stdev, cb, nullptr}};
+    if (loc == RDR_DEVICE) {
+        for (Out& o : outs) o.dev = o.host;
+    } else {
+        size_t total = 0;
+        for (Out& o : outs) if (o.host) total += (o.bytes + 15) & ~(size_t)15;
+        void* base; rc = ensure(c, SLOT_OUT0, total, &base); if (rc) return rc;
+        size_t off = 0;
+        for (Out& o : outs) if (o.host) { o.dev = static_cast<char*>(base) + off; off += (o.bytes + 15) & ~(size_t)15; }
+    }
+    // station statistics that only the cell means read live in a work array of the context
+    void* st[4] = {outs[0].dev, outs[1].dev, outs[2].dev, outs[3].dev};
+    const bool need[4] = {st_any || of_any, st_any || of_any, st_median || mean_of_medians, st_any || of_any};
+    if ((need[0] && !st[0]) || (need[2] && !st[2])) {
+        void* t; rc = ensure(c, SLOT_AUX, 4 * sb, &t); if (rc) return rc;
+        for (int k = 0; k < 4; ++k) if (need[k] && !st[k]) st[k] = static_cast<char*>(t) + k * sb;
+    }
+    A.n = n; A.nd = nd;
+    A.st_nobs = (long long*)st[0]; A.st_mean = (double*)st[1]; A.st_median = need[2] ? (double*)st[2] : nullptr; A.st_stdev = (double*)st[3];
+    A.nstations = (long long*)outs[4].dev; A.mean_of_means = (double*)outs[5].dev; A.mean_of_medians = (double*)outs[6].dev; A.mean_of_stdevs = (double*)outs[7].dev;
+    A.cell_nobs = (long long*)outs[8].dev; A.abs_mean = (double*)outs[9].dev; A.abs_median = (double*)outs[10].dev; A.abs_stdev = (double*)outs[11].dev;
+    if (need[0]) hipLaunchKernelGGL(grid_stats_station_kernel, dim3((unsigned)((n + GS_STATIONS - 1) / GS_STATIONS)), dim3(GS_TILE), 0, c->stream, A);
+    if (of_any || ab_any) hipLaunchKernelGGL(grid_stats_cell_kernel, dim3((unsigned)ncells), dim3(GS_TILE), 0, c->stream, A);
     HIPCHECK(c, hipGetLastError());
     for (Out& o : outs) { rc = finish_out(c, o.host, o.dev, o.bytes, loc); if (rc) return rc; }
     if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));

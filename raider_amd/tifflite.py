@@ -232,7 +232,7 @@ class TiffInfo:
         meta = tags.get(_GDAL_META)
         if isinstance(meta, str):
             for m in re.finditer(r'<Item\s+name="([^"]+)"[^>]*>([^<]*)</Item>', meta):
-                self.tags[m.group(1)] = m.group(2)
+                self.tags[m.group(1)] = m.group(2).replace('&lt;', '<').replace('&gt;', '>').replace('&amp;', '&')
         if 'AREA_OR_POINT' not in self.tags and _geokey(tags, 1025) in (1, 2):
             self.tags['AREA_OR_POINT'] = 'Point' if _geokey(tags, 1025) == 2 else 'Area'
 
@@ -553,13 +553,14 @@ def _device_strips(array, h, w, itemsize, rps, predictor, tables):
     return [packed[oo[i]:oo[i + 1]] for i in range(offs.size)]
 
 
-def write(path, array, transform=None, crs=None, nodata=None, compress=None, rows_per_strip=None, predictor=None, encoder='host', tables='fixed'):
+def write(path, array, transform=None, crs=None, nodata=None, compress=None, rows_per_strip=None, predictor=None, encoder='host', tables='fixed', tags=None):
     """One band as a GeoTIFF in strips: classic TIFF, BigTIFF when the pixels pass 4 GiB; little-endian; compress None or 'deflate'
     (zlib).  array: 2-D uint16 / int16 / float32 / float64 (and uint8, what the delay writers make of integer arrays).  transform: GDAL's six numbers (north-up); crs: an EPSG code (see _epsg_of);
     nodata: written as GDAL_NODATA.  predictor: None, or 2 (with 'deflate': every row differenced along x in the unsigned integer type
     of the sample width, tag 317 - what the readers undo).  encoder: 'host' (zlib level 6), or 'device' (with 'deflate': the strips
     are deflated on the GPU in one call; array may then be a device tensor, and no GPU is an error by name).  tables: 'fixed', or
-    'dynamic' (with encoder='device': dynamic-Huffman blocks wherever they are the smallest)."""
+    'dynamic' (with encoder='device': dynamic-Huffman blocks wherever they are the smallest).  tags: None, or a dict written as the items
+    of GDAL_METADATA (tag 42112) - what `read` hands back as profile['tags']; None leaves the tag out."""
     if compress not in (None, 'none', 'deflate', 'DEFLATE'):
         raise ValueError(f"compress must be None or 'deflate', not {compress!r}")
     deflate = compress in ('deflate', 'DEFLATE')
@@ -633,6 +634,10 @@ def write(path, array, transform=None, crs=None, nodata=None, compress=None, row
         nd = float(nodata)
         txt = 'nan' if nd != nd else (str(int(nd)) if nd == int(nd) and abs(nd) < 1e15 else repr(nd))
         entries.append((_GDAL_NODATA, 2, txt))
+    if tags:
+        from xml.sax.saxutils import escape
+        items = ''.join(f'  <Item name="{escape(str(k), {chr(34): "&quot;"})}">{escape(str(v))}</Item>\n' for k, v in tags.items())
+        entries.append((_GDAL_META, 2, f'<GDALMetadata>\n{items}</GDALMetadata>\n'))
     entries.sort(key=lambda e: e[0])
     head = 16 if big else 8
     pos = head
