@@ -647,6 +647,25 @@ int rdr_h5_chunks(rdr_ctx* ctx, const void* array, int elem_bytes, int ndim, con
 #define RDR_INFL_CHECKSUM 4  /* Adler-32 mismatch */
 int rdr_inflate_decode(rdr_ctx* ctx, const void* src, int64_t src_bytes, const int64_t* seg_offset, const int64_t* seg_bytes, int64_t nseg,
                        const int64_t* seg_out_bytes, void* out, int64_t out_stride, int32_t* status, int64_t* produced, int loc);
+/* rdr_inflate_decode_split: rdr_inflate_decode with long streams decoded by many waves.  Arguments, locations and the RDR_ERR_INVALID
+ * conditions (checked before the device is touched) are rdr_inflate_decode's, and for every stream, good or bad, status[i], produced[i]
+ * and every byte of slot i are exactly what rdr_inflate_decode gives for the same arguments and the same pre-filled `out`.  pieces
+ * (HOST, nseg, may be NULL): the pieces of stream i that separate waves decoded; 1: the stream went through the serial kernel.
+ * A stream is cut where a byte-aligned empty stored block (00 00 FF FF: Z_SYNC_FLUSH, Z_FULL_FLUSH, the close of every 32 KiB
+ * sub-block rdr_deflate_encode does not store) ends: of the marker occurrences that end in the same 1024-byte window of the stream
+ * (window j = stream offsets [1024 j, 1024 j + 1024)) only the first and the last are candidates, so a stream of n bytes has at most
+ * 2 (n / 1024 + 1).
+ * A measure pass decodes every piece without output and records its length, where it ends and how far its matches reach behind its
+ * start; a piece that reaches back is joined with its predecessors (Z_SYNC_FLUSH keeps the history), a false candidate is one no
+ * piece ends on.  A stream whose chain of pieces is not provably clean - an error, no trailer, more output than the slot, a distance
+ * too far back - is decoded by rdr_inflate_decode's kernel, which sets its status as ever.  The call ALWAYS synchronises with the
+ * context's stream, twice on the way (the candidate counts and the measured pieces come to the host, where the plan is made), so
+ * unlike rdr_inflate_decode it does not queue behind device work when loc is RDR_DEVICE.  (A piece that did not decode as it was
+ * measured would give its stream RDR_INFL_INVALID: an internal-consistency status that no input can cause - both passes run the same
+ * decoder over the same bytes - and the one outcome the equality with rdr_inflate_decode does not cover.) */
+int rdr_inflate_decode_split(rdr_ctx* ctx, const void* src, int64_t src_bytes, const int64_t* seg_offset, const int64_t* seg_bytes,
+                             int64_t nseg, const int64_t* seg_out_bytes, void* out, int64_t out_stride, int32_t* status, int64_t* produced,
+                             int64_t* pieces, int loc);
 /* rdr_h5_unchunk: the inverse of rdr_h5_chunks.  `npresent` decoded chunks, chunk k at chunks + k * chunk_stride and chunk_index[k]
  * (HOST) its row-major index in the chunk grid ceil(shape / chunk), each index at most once -> the C-ordered array out of `shape`.
  * Edge chunks are clipped, the shuffle is undone (`shuffle`), bytes are reversed within an element (`swap`); elements of chunks

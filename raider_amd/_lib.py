@@ -160,6 +160,7 @@ SYMBOLS = [
     ('rdr_deflate_encode_tables', C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int, _VP, C.c_int64, _VP, _VP, C.c_int]),
     ('rdr_h5_chunks', C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int, _VP, C.c_int]),
     ('rdr_inflate_decode', C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, C.c_int]),
+    ('rdr_inflate_decode_split', C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int]),
     ('rdr_h5_unchunk', C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, C.c_int]),
     ('rdr_pair_distance_max', C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int, _VP, C.c_int]),
     ('rdr_pair_variogram', C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int, _VP, C.c_int, C.c_int, _VP, _VP, _VP, C.c_int]),

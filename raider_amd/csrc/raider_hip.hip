@@ -3524,12 +3524,9 @@ static int segment_in_source(rdr_ctx* c, const std::string& w, int64_t i, int64_
     return RDR_OK;
 }
 
-// One driver for the two segment decoders (LZW strips / tiles, zlib streams): segment i of `src` is decoded into out + i * out_stride, one
-// wave per segment.  `launch(grid, src, tab, out, status, produced)` starts the kernel; tab = offsets | bytes | out bytes, nseg each.
-template <typename Launch>
-static int decode_segments(rdr_ctx* c, const char* who, const void* src, int64_t src_bytes, const int64_t* seg_offset, const int64_t* seg_bytes, int64_t nseg,
-                           const int64_t* seg_out_bytes, void* out, int64_t out_stride, int32_t* status, int64_t* produced, int loc, int per_cu,
-                           Launch&& launch) {
+// What the segment decoders refuse before the device is touched.
+static int decode_segments_check(rdr_ctx* c, const char* who, const void* src, int64_t src_bytes, const int64_t* seg_offset, const int64_t* seg_bytes, int64_t nseg,
+                                 const int64_t* seg_out_bytes, const void* out, int64_t out_stride, const int32_t* status, int loc) {
     const std::string w(who);
     if (!c || !src || !seg_offset || !seg_bytes || !seg_out_bytes || !out || !status) return fail(c, RDR_ERR_INVALID, w + ": NULL argument");
     if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, w + ": loc must be RDR_HOST or RDR_DEVICE");
@@ -3542,6 +3539,16 @@ static int decode_segments(rdr_ctx* c, const char* who, const void* src, int64_t
         if (seg_out_bytes[i] < 0 || seg_out_bytes[i] > out_stride)
             return fail(c, RDR_ERR_INVALID, w + ": segment " + std::to_string(i) + " would write beyond its slot of out_stride bytes");
     }
+    return RDR_OK;
+}
+
+// One driver for the two segment decoders (LZW strips / tiles, zlib streams): segment i of `src` is decoded into out + i * out_stride, one
+// wave per segment.  `launch(grid, src, tab, out, status, produced)` starts the kernel; tab = offsets | bytes | out bytes, nseg each.
+template <typename Launch>
+static int decode_segments(rdr_ctx* c, const char* who, const void* src, int64_t src_bytes, const int64_t* seg_offset, const int64_t* seg_bytes, int64_t nseg,
+                           const int64_t* seg_out_bytes, void* out, int64_t out_stride, int32_t* status, int64_t* produced, int loc, int per_cu,
+                           Launch&& launch) {
+    { const int rc = decode_segments_check(c, who, src, src_bytes, seg_offset, seg_bytes, nseg, seg_out_bytes, out, out_stride, status, loc); if (rc) return rc; }
     HIPCHECK(c, hipSetDevice(c->device));
     Staged S(c, loc);
     const uint8_t* dsrc = S.in(static_cast<const uint8_t*>(src), (size_t)src_bytes);
@@ -3768,8 +3775,105 @@ int rdr_inflate_decode(rdr_ctx* c, const void* src, int64_t src_bytes, const int
     return decode_segments(c, "rdr_inflate_decode", src, src_bytes, seg_offset, seg_bytes, nseg, seg_out_bytes, out, out_stride, status, produced, loc, 3,
                            [&](int grid, const uint8_t* dsrc, const int64_t* tab, uint8_t* dout, int32_t* dstat, int64_t* dprod) {
         hipLaunchKernelGGL(inflate_kernel, dim3(grid), dim3(64), 0, c->stream, dsrc, src_bytes, tab, tab + nseg, tab + 2 * nseg, (int)nseg, dout, out_stride, dstat,
-                           dprod);
+                           dprod, (const int32_t*)nullptr);
     });
+}
+
+// The same streams with the long ones cut at their flush points (inflate_kernels.h): scan -> the candidates' count comes down -> measure ->
+// the records come down -> the plan, on the host -> the whole streams through inflate_kernel, the pieces through inflate_piece_kernel, the
+// pieces' checksums folded on the device.  A call without a candidate is rdr_inflate_decode's launch behind the scan.  Always synchronises.
+int rdr_inflate_decode_split(rdr_ctx* c, const void* src, int64_t src_bytes, const int64_t* seg_offset, const int64_t* seg_bytes, int64_t nseg,
+                             const int64_t* seg_out_bytes, void* out, int64_t out_stride, int32_t* status, int64_t* produced, int64_t* pieces, int loc) {
+    { const int rc = decode_segments_check(c, "rdr_inflate_decode_split", src, src_bytes, seg_offset, seg_bytes, nseg, seg_out_bytes, out, out_stride, status, loc); if (rc) return rc; }
+    HIPCHECK(c, hipSetDevice(c->device));
+    std::vector<int64_t> base((size_t)nseg + 1);                  // the streams' slots: the start and the candidate windows (infl_slots)
+    std::vector<uint32_t> count((size_t)nseg);
+    std::vector<int64_t> npieces((size_t)nseg, 1);
+    int64_t longest = 0;
+    base[0] = 0;
+    for (int64_t i = 0; i < nseg; ++i) {
+        base[(size_t)i + 1] = base[(size_t)i] + infl_slots(infl_clip32(seg_bytes[i]));
+        longest = std::max(longest, seg_bytes[i]);
+    }
+    const int64_t total = base[(size_t)nseg];
+    Staged S(c, loc);
+    const uint8_t* dsrc = S.in(static_cast<const uint8_t*>(src), (size_t)src_bytes);
+    const HostPart tabs[3] = {{seg_offset, (size_t)nseg * 8}, {seg_bytes, (size_t)nseg * 8}, {seg_out_bytes, (size_t)nseg * 8}};
+    const int64_t* tab = S.table<int64_t>(SLOT_IN1, tabs, 3);
+    uint8_t* dout = S.out(static_cast<uint8_t*>(out), (size_t)(nseg * out_stride));
+    int32_t* dstat = S.out(status, (size_t)nseg * 4);
+    int64_t* dprod = S.out(produced, (size_t)nseg * 8);         // (optional)
+    const HostPart base_part{base.data(), ((size_t)nseg + 1) * 8};
+    const int64_t* dbase = S.table<int64_t>(SLOT_IN2, &base_part, 1);
+    uint32_t* dcand = S.scratch<uint32_t>(SLOT_IN3, (size_t)total * 4);
+    uint32_t* dcount = S.scratch<uint32_t>(SLOT_IN4, (size_t)nseg * 4);
+    if (S.rc) return S.rc;
+    if (loc == RDR_HOST) { const int rc = upload(c, dout, out, (size_t)(nseg * out_stride)); if (rc) return rc; }
+    HIPCHECK(c, hipMemsetAsync(dcand, 0xff, (size_t)total * 4, c->stream));
+    HIPCHECK(c, hipMemsetAsync(dcount, 0, (size_t)nseg * 4, c->stream));
+    {
+        const dim3 G((unsigned)grid_for(longest, 256 * 8, c->num_cus * 4), (unsigned)std::min<int64_t>(nseg, 4096));
+        hipLaunchKernelGGL(infl_scan_kernel, G, dim3(256), 0, c->stream, dsrc, src_bytes, tab, tab + nseg, (int)nseg, dbase, total, dcand, dcount);
+    }
+    HIPCHECK(c, hipGetLastError());
+    HIPCHECK(c, hipMemcpyAsync(count.data(), dcount, (size_t)nseg * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    int64_t with_candidates = 0;
+    for (int64_t i = 0; i < nseg; ++i) with_candidates += count[(size_t)i] != 0u;
+    const int serial_grid = (int)std::min<int64_t>(nseg, (int64_t)c->num_cus * 3);
+    if (with_candidates == 0) {
+        hipLaunchKernelGGL(inflate_kernel, dim3(serial_grid), dim3(64), 0, c->stream, dsrc, src_bytes, tab, tab + nseg, tab + 2 * nseg, (int)nseg, dout, out_stride,
+                           dstat, dprod, (const int32_t*)nullptr);
+    } else {
+        InflPiece* drec = S.scratch<InflPiece>(SLOT_IN5, (size_t)total * sizeof(InflPiece));
+        if (S.rc) return S.rc;
+        HIPCHECK(c, hipMemsetAsync(drec, 0xff, (size_t)total * sizeof(InflPiece), c->stream));
+        hipLaunchKernelGGL(infl_measure_kernel, dim3((unsigned)std::min<int64_t>(total, (int64_t)c->num_cus * 15)), dim3(64), 0, c->stream, dsrc, src_bytes, tab,
+                           tab + nseg, tab + 2 * nseg, (int)nseg, out_stride, dbase, total, dcand, dcount, drec);
+        HIPCHECK(c, hipGetLastError());
+        std::vector<InflPiece> rec;
+        std::vector<InflJob> jobs;
+        std::vector<int32_t> whole;                               // the streams that stay whole
+        try { rec.resize((size_t)total); jobs.reserve((size_t)total); } catch (const std::bad_alloc&) { return fail(c, RDR_ERR_OOM, "rdr_inflate_decode_split: no host memory for the plan"); }
+        HIPCHECK(c, hipMemcpyAsync(rec.data(), drec, (size_t)total * sizeof(InflPiece), hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(c, hipStreamSynchronize(c->stream));
+        for (int64_t i = 0; i < nseg; ++i) {
+            uint32_t n = 0;
+            if (count[(size_t)i]) {
+                const size_t at = jobs.size();
+                const uint32_t nslots = (uint32_t)(base[(size_t)i + 1] - base[(size_t)i]);
+                jobs.resize(at + nslots);
+                n = infl_plan(rec.data() + base[(size_t)i], nslots, infl_clip32(std::min(seg_out_bytes[i], out_stride)), (int32_t)i, jobs.data() + at);
+                if (n < 2) n = 0;                                 // (one piece: the whole stream, which inflate_kernel decodes in one pass)
+                jobs.resize(at + n);
+            }
+            if (n) npieces[(size_t)i] = n; else whole.push_back((int32_t)i);
+        }
+        const int64_t njobs = (int64_t)jobs.size(), nwhole = (int64_t)whole.size();
+        if (nwhole) {
+            const HostPart part{whole.data(), (size_t)nwhole * 4};
+            const int32_t* dlist = S.table<int32_t>(SLOT_IN6, &part, 1);
+            if (S.rc) return S.rc;
+            hipLaunchKernelGGL(inflate_kernel, dim3((unsigned)std::min<int64_t>(nwhole, (int64_t)c->num_cus * 3)), dim3(64), 0, c->stream, dsrc, src_bytes, tab, tab + nseg,
+                               tab + 2 * nseg, (int)nwhole, dout, out_stride, dstat, dprod, dlist);
+            HIPCHECK(c, hipGetLastError());
+        }
+        if (njobs) {
+            const HostPart part{jobs.data(), (size_t)njobs * sizeof(InflJob)};
+            const InflJob* djobs = S.table<InflJob>(SLOT_IN5, &part, 1);          // (the records have come down: their slot is free)
+            InflJobOut* dres = S.scratch<InflJobOut>(SLOT_AUX, (size_t)njobs * sizeof(InflJobOut));
+            if (S.rc) return S.rc;
+            hipLaunchKernelGGL(inflate_piece_kernel, dim3((unsigned)std::min<int64_t>(njobs, (int64_t)c->num_cus * 3)), dim3(64), 0, c->stream, dsrc, src_bytes, tab,
+                               tab + nseg, tab + 2 * nseg, (int)nseg, dout, out_stride, djobs, njobs, dres);
+            HIPCHECK(c, hipGetLastError());
+            hipLaunchKernelGGL(infl_fold_kernel, dim3((unsigned)grid_for(njobs, 256, c->num_cus * 4)), dim3(256), 0, c->stream, djobs, (const InflJobOut*)dres, njobs,
+                               (int)nseg, dstat, dprod);
+        }
+    }
+    const int rc = S.finish(true);
+    if (rc) return rc;
+    if (pieces) std::memcpy(pieces, npieces.data(), (size_t)nseg * 8);
+    return RDR_OK;
 }
 
 int rdr_h5_unchunk(rdr_ctx* c, const void* chunks, int64_t chunk_stride, const int64_t* chunk_index, int64_t npresent, int elem_bytes, int ndim,

@@ -27,6 +27,8 @@ def require_gpu(what):
 
 TABLES = {'fixed': L.RDR_DEFL_FIXED, 'dynamic': L.RDR_DEFL_DYNAMIC}
 _last_counts = (0, 0, 0)
+_last_pieces = np.zeros(0, dtype=np.int64)
+FLUSH_MARKER = b'\x00\x00\xff\xff'
 
 
 def tables_mode(tables):
@@ -173,13 +175,33 @@ def inflate_mode(inflate):
     return inflate
 
 
-def inflate_segments(buf, offsets, sizes, out_sizes, out_stride=None, out=None):
+def last_pieces():
+    """int64 array, one entry per stream of the last inflate_segments(..., split=True) call of this process: the pieces of the stream
+    that separate waves decoded; 1: the stream went through the serial kernel."""
+    return _last_pieces
+
+
+def flush_points(buf):
+    """The occurrences of the byte-aligned empty stored block's LEN / NLEN words (00 00 FF FF: what Z_SYNC_FLUSH, Z_FULL_FLUSH and this
+    package's encoder leave behind) in a host bytes-like.  Its only use is the readers' choice of a route: the split decoder can cut a
+    stream at no other place."""
+    if isinstance(buf, np.ndarray):
+        buf = np.ascontiguousarray(buf).reshape(-1).view(np.uint8).tobytes()       # (bytes.count is a memchr-speed search)
+    elif not isinstance(buf, (bytes, bytearray)):
+        buf = bytes(buf)
+    return buf.count(FLUSH_MARKER)
+
+
+def inflate_segments(buf, offsets, sizes, out_sizes, out_stride=None, out=None, split=False):
     """(out, status, produced): the zlib streams buf[offsets[i] : offsets[i] + sizes[i]] decoded on the device, stream i into
     out[i * out_stride : i * out_stride + out_sizes[i]].  buf: a C-contiguous NumPy array or device tensor (taken as bytes); out is a
     uint8 array / tensor of the same kind of len(sizes) * out_stride bytes (out_stride: max(out_sizes) rounded up to 16 when None),
     status an int32 and produced an int64 array / tensor.  status[i] is one of RDR_INFL_*: 0 exactly when zlib.decompress accepts the
     stream and its output fits the slot.  `out`: an existing buffer to decode into - slot bytes a stream does not reach keep their value
-    (a new buffer is zeroed).  One transfer each way for NumPy, none for tensors."""
+    (a new buffer is zeroed).  One transfer each way for NumPy, none for tensors.
+    split: long streams are cut at their flush points and decoded by many waves (rdr_inflate_decode_split); out, status and produced are
+    byte for byte those of split=False, last_pieces() tells how many pieces each stream was decoded in, and the call synchronises."""
+    global _last_pieces
     so = np.ascontiguousarray(offsets, dtype=np.int64).ravel()
     sb = np.ascontiguousarray(sizes, dtype=np.int64).ravel()
     cap = np.ascontiguousarray(out_sizes, dtype=np.int64).ravel()
@@ -199,6 +221,12 @@ def inflate_segments(buf, offsets, sizes, out_sizes, out_stride=None, out=None):
         raise TypeError(f'inflate_segments: out must be a {kind} of {n} slots of {out_stride} bytes')
     status = r.new(n, np.int32, fill=-1)
     produced = r.new(n, np.int64, fill=0)
+    if split:
+        pieces = np.zeros(n, dtype=np.int64)
+        L.check(r.ctx.lib.rdr_inflate_decode_split(r.ctx.handle, L.ptr(r.bytes), r.nbytes, L.ptr(so), L.ptr(sb), n, L.ptr(cap), L.ptr(out), out_stride, L.ptr(status),
+                                                   L.ptr(produced), L.ptr(pieces), r.loc), r.ctx.handle)
+        _last_pieces = pieces
+        return out, status, produced
     L.check(r.ctx.lib.rdr_inflate_decode(r.ctx.handle, L.ptr(r.bytes), r.nbytes, L.ptr(so), L.ptr(sb), n, L.ptr(cap), L.ptr(out), out_stride, L.ptr(status),
                                          L.ptr(produced), r.loc), r.ctx.handle)
     return out, status, produced

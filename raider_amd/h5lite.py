@@ -46,6 +46,14 @@ class UnsupportedHDF5Feature(NotImplementedError):
 # profiles/r24_inflate.json) on 20 x 1000 x 1000 cubes: float32 in 16 chunks 665 ms on the device against 253 ms through zlib, in 64
 # chunks 178 ms against 252 ms; float64 in 16 chunks 319 ms against 394 ms, in 64 chunks 94 ms against 390 ms.
 _INFLATE_MIN_CHUNKS = 64
+# Fewer chunks, but long ones that the split decoder cuts at their flush points: chunks + flush points from which the device route is
+# taken.  Measured (tools/bench_inflate_split.py, profiles/r28_inflate_split.json): a 20 x 150 x 150 float32 cube in nine device-written
+# chunks (63 units) 31.5 ms on the device against 6.3 ms through zlib - not ahead, two passes over one 32 KiB piece on one lane are a
+# floor of about 30 ms; 20 x 1000 x 1000 cubes in 16 chunks (2400 - 4700 units) 86 against 437 ms (float32), 54 against 767 ms
+# (float64).  Between them the crossing is the rasters' (tifflite._INFLATE_MIN_PIECES: not ahead at 264 units, ahead from 528), the same
+# kernels on the same kind of stream.  One chunk alone stays on the host.  Chunks whose flush points keep the history (Z_SYNC_FLUSH) are
+# not told apart before the measure pass and are slower on this route (72 units: 31.4 against 6.5 ms); the HDF5 library writes none.
+_INFLATE_MIN_PIECES = 512
 
 
 def _u(b, off, n):
@@ -281,13 +289,14 @@ class Dataset:
         return out
 
     def read_device(self, device=None, inflate='auto'):
-        """The dataset as a device tensor in native byte order, its chunks inflated (rdr_inflate_decode) and put together
+        """The dataset as a device tensor in native byte order, its chunks inflated (rdr_inflate_decode_split) and put together
         (rdr_h5_unchunk) on the GPU - or None when the dataset is not a candidate, and the caller takes read().  Candidates: a chunked
         layout whose index _chunks() reads, a float or integer type of 1 / 2 / 4 / 8 bytes, the filter pipeline [shuffle,] deflate
         [, fletcher32] in that order, every chunk filtered (filter mask 0).  inflate: 'device', 'host' (always None) or 'auto' (the
-        device from _INFLATE_MIN_CHUNKS chunks on).  A chunk the device does not accept is inflated by zlib on the host and patched
+        device from _INFLATE_MIN_CHUNKS chunks on, or from two chunks on when they and the flush points inside them, deflate.flush_points,
+        together reach _INFLATE_MIN_PIECES).  A chunk the device does not accept is inflated by zlib on the host and patched
         in: a damaged chunk raises what read() raises.  The fletcher32 checksum is dropped unverified, as read() drops it."""
-        from .deflate import inflate_mode, inflate_segments, h5_unchunk
+        from .deflate import inflate_mode, inflate_segments, flush_points, h5_unchunk
         inflate = inflate_mode(inflate)
         if inflate == 'host' or self.dtype is None or self.dtype.kind not in 'fiu' or self.dtype.itemsize not in (1, 2, 4, 8):
             return None
@@ -304,8 +313,6 @@ class Dataset:
             return None
         if not entries or any(mask != 0 or not filtered for _, _, mask, _, filtered in entries):
             return None
-        if inflate == 'auto' and len(entries) < _INFLATE_MIN_CHUNKS:
-            return None
         import torch
         if not hasattr(torch, self.dtype.newbyteorder('=').name):
             return None                                               # (an unsigned type this torch build has no tensor for)
@@ -319,6 +326,14 @@ class Dataset:
         buf = np.frombuffer(f.buf, dtype=np.uint8)
         if np.any(sizes <= 0) or np.any(offsets < 0) or np.any(offsets + sizes > buf.size):
             return None                                               # (read() says what is wrong with the file)
+        if inflate == 'auto' and len(entries) < _INFLATE_MIN_CHUNKS:
+            # a long chunk is decoded in as many pieces as it has flush points (rdr_inflate_decode_split): they count as chunks do.  One
+            # chunk alone stays on the host (measured, not ahead), and without a visible GPU the caller's read() serves the file
+            if len(entries) < 2 or not torch.cuda.is_available():
+                return None
+            marks = sum(flush_points(bytes(buf[o:o + n])) for o, n in zip(offsets, sizes))
+            if len(entries) + marks < _INFLATE_MIN_PIECES:
+                return None
         plain = int(np.prod(chunk)) * es
         stride = (plain + 15) // 16 * 16
         device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
@@ -328,7 +343,7 @@ class Dataset:
         with warnings.catch_warnings():
             warnings.simplefilter('ignore')                           # (a read-only mapping: it is only read)
             src = torch.from_numpy(buf[lo:hi]).to(device)
-        segs, status, produced = inflate_segments(src, offsets - lo, sizes, np.full(len(entries), plain, dtype=np.int64), out_stride=stride)
+        segs, status, produced = inflate_segments(src, offsets - lo, sizes, np.full(len(entries), plain, dtype=np.int64), out_stride=stride, split=True)
         bad = (status != 0) | (produced != plain)
         for k in np.nonzero(bad.cpu().numpy())[0]:
             k = int(k)

@@ -391,11 +391,28 @@ def _gpu_device(device):
 # 4000 x 4000 int16 DEM read to a device tensor in 64 segments takes 119 ms on the device route against 71 ms through zlib, in 256
 # segments 32 ms against 80 ms - one wave decodes one segment, so the route pays only once a few hundred waves run side by side.
 _INFLATE_MIN_SEGMENTS = 256
+# Fewer segments, but long ones that the split decoder cuts at their flush points: segments + flush points (_inflate_units) from which the
+# device route is taken.  Measured (tools/bench_inflate_split.py, profiles/r28_inflate_split.json) on float32 rasters in 8 or 16
+# device-written strips: 264 units 26.7 ms on the device against 21.7 ms through zlib (not ahead: two passes over one 32 KiB piece on one
+# lane are a floor of about 30 ms), 528 units 37.2 against 43.7 ms, 1024 units 60.7 against 85.5 ms, 1984 units 93.8 against 170.3 ms.
+# One segment alone stays on the host whatever it holds (32 MB in 683 pieces: 57.0 against 58.8 ms, inside the spans).  Not told apart
+# before the measure pass, and slower on this route: segments whose flush points keep the history (Z_SYNC_FLUSH), which collapse to one
+# piece each and then run the serial kernel - libtiff and GDAL write none; inflate='host' is the way round them.
+_INFLATE_MIN_PIECES = 512
 
 
-def _read_device(info, band, device, inflate='host'):
+def _inflate_units(info, whole=None):
+    """What the device route decodes side by side: the segments and the flush points inside them, at which rdr_inflate_decode_split
+    cuts a long segment into pieces (deflate.flush_points).  whole: the file's bytes as a uint8 array, when they have been read."""
+    from .deflate import flush_points
+    if whole is None:
+        whole = np.fromfile(info.path, dtype=np.uint8)
+    return len(info.offsets) + sum(flush_points(whole[int(o):int(o) + int(c)]) for o, c in zip(info.offsets, info.bytecounts))
+
+
+def _read_device(info, band, device, inflate='host', whole=None):
     """The decode through the two kernels; a uint8 tensor holding the raster's bytes, and its shape.  inflate: where deflate segments
-    are decoded, 'host' or 'device'."""
+    are decoded, 'host' or 'device'.  whole: the file's bytes as a uint8 array when the caller has read them already."""
     import torch
     nseg = len(info.offsets)
     full = info.tile_h * info.tile_w * info.spp_seg * info.dtype.itemsize
@@ -416,10 +433,11 @@ def _read_device(info, band, device, inflate='host'):
         # the file's bytes go up, rdr_inflate_decode writes the (zeroed) slots; a segment it does not accept is decoded again on the
         # host and patched in, so that the host route's result - a truncated over-long stream - or its exception stands
         from . import deflate
-        whole = np.fromfile(info.path, dtype=np.uint8)
+        if whole is None:
+            whole = np.fromfile(info.path, dtype=np.uint8)
         src = torch.from_numpy(whole).to(device)
         need = np.array([info.seg_bytes(k) for k in range(nseg)], dtype=np.int64)
-        segs, status, _ = deflate.inflate_segments(src, info.offsets, info.bytecounts, need, out_stride=stride)
+        segs, status, _ = deflate.inflate_segments(src, info.offsets, info.bytecounts, need, out_stride=stride, split=True)
         for k in np.nonzero(status.cpu().numpy())[0]:
             k = int(k)
             o = int(info.offsets[k])
@@ -427,11 +445,17 @@ def _read_device(info, band, device, inflate='host'):
             segs[k * stride:k * stride + len(d)] = torch.from_numpy(np.frombuffer(d, dtype=np.uint8).copy()).to(device)
     else:
         buf = np.zeros(nseg * stride, dtype=np.uint8)
-        with open(info.path, 'rb') as f:
+        if whole is not None:                                    # (read by the caller to choose the route: not read again)
             for k in range(nseg):
-                f.seek(int(info.offsets[k]))
-                d = _host_segment(info, f.read(int(info.bytecounts[k])), k)
+                o = int(info.offsets[k])
+                d = _host_segment(info, whole[o:o + int(info.bytecounts[k])].tobytes(), k)
                 buf[k * stride:k * stride + len(d)] = np.frombuffer(d, dtype=np.uint8)
+        else:
+            with open(info.path, 'rb') as f:
+                for k in range(nseg):
+                    f.seek(int(info.offsets[k]))
+                    d = _host_segment(info, f.read(int(info.bytecounts[k])), k)
+                    buf[k * stride:k * stride + len(d)] = np.frombuffer(d, dtype=np.uint8)
         segs = torch.from_numpy(buf).to(device)
     return assemble_device(segs, stride, info.height, info.width, info.tile_h, info.tile_w, info.predictor, info.swap, info.dtype, info.planar, info.count, band)
 
@@ -440,8 +464,9 @@ def read(path, band=None, device=None, inflate='auto'):
     """(array, profile) of the first image of a GeoTIFF.  band: 1-based, None = every band ((H, W) for a one-band file, else (bands, H, W)).
     device: a torch GPU device - the array is a tensor there and the decoded raster never exists on the host; None - a NumPy array
     (LZW files still pass through the GPU, which decodes them; all others are read without one).  inflate: where deflate segments
-    are decoded - 'host' (zlib), 'device' (rdr_inflate_decode; with device=None the result is downloaded) or 'auto' (the device when
-    `device` is given and the file has at least _INFLATE_MIN_SEGMENTS segments).  Both routes give the same pixels and errors."""
+    are decoded - 'host' (zlib), 'device' (rdr_inflate_decode_split; with device=None the result is downloaded) or 'auto' (the device when
+    `device` is given and the file has _INFLATE_MIN_SEGMENTS segments, or more than one and, with the flush points inside them,
+    _INFLATE_MIN_PIECES).  Both routes give the same pixels and errors."""
     from .deflate import inflate_mode
     inflate = inflate_mode(inflate)
     info = TiffInfo(path)
@@ -449,10 +474,21 @@ def read(path, band=None, device=None, inflate='auto'):
         raise IndexError(f'{path}: band {band} of {info.count}')
     b0 = None if band is None else int(band) - 1
     deflated = info.compression in (8, 32946)
+    whole = None
     if inflate == 'auto':
-        inflate = 'device' if deflated and device is not None and len(info.offsets) >= _INFLATE_MIN_SEGMENTS else 'host'
+        inflate = 'host'
+        if deflated and device is not None:
+            nseg = len(info.offsets)
+            if nseg >= _INFLATE_MIN_SEGMENTS:
+                inflate = 'device'
+            elif nseg > 1:
+                # fewer segments, but long ones may be cut at their flush points: the file is read once, here, and the chosen route
+                # decodes from these bytes.  A file of ONE segment stays on the host: measured, not ahead (see _INFLATE_MIN_PIECES)
+                whole = np.fromfile(info.path, dtype=np.uint8)
+                if _inflate_units(info, whole) >= _INFLATE_MIN_PIECES:
+                    inflate = 'device'
     if device is not None or info.compression == 5 or (deflated and inflate == 'device'):
-        raw, shape = _read_device(info, b0, _gpu_device(device), inflate)
+        raw, shape = _read_device(info, b0, _gpu_device(device), inflate, whole)
         if device is not None:
             arr = raw.view(_torch_dtype(info.dtype)).reshape(shape)
         else:
