@@ -752,6 +752,43 @@ int rdr_grid_stats(rdr_ctx* ctx, const double* values, int64_t n, int nd, const 
                    double* st_median, double* st_stdev, int64_t* nstations, double* mean_of_means, double* mean_of_medians, double* mean_of_stdevs,
                    int64_t* cell_nobs, double* abs_mean, double* abs_median, double* abs_stdev, int loc);
 
+/* rdr_seasonal_fit: the seasonal sinusoids of raiderStats (cli/statsPlot.py _amplitude_and_phase, :2311-2479, and the cell means behind
+ * the grid_seasonal_* maps, :1796-2309; csrc/seasonal_kernels.h).  Per station the exact least-squares fit of
+ *     y ~ A sin(w t + p) + c      (linear in a = A cos p_c, b = A sin p_c, c at a given w; tau = t - t_ref, t_ref the middle of the axis)
+ * to its values, at omega[0] (scan = 0: the reference's fixed period, k must be 1) or at the frequency of the band omega[0 .. k) where
+ * the residual sum R(w) is smallest (scan = 1): k* = argmin over the grid (the lowest index on ties), then a golden-section search of R
+ * inside [omega[k* - 1], omega[k* + 1]] (clipped to the band) until the bracket is below 1e-10 of omega[1] - omega[0], R is flat to
+ * round-off, or 64 steps; the best frequency evaluated wins.  The reference's Levenberg-Marquardt run from one FFT bin ends in this
+ * minimum often, not always; where it does not, this fit has the lower residual.
+ *   t [nd]            HOST, whatever loc: POSIX seconds of the dates, finite, in any order.
+ *   values [nd][n]    at loc: one row per date, NaN = no row; station-contiguous rows as for rdr_grid_stats.
+ *   omega [k]         HOST: angular frequencies in rad / s, finite, > 0, ascending (scan: an evenly spaced grid is what makes sense).
+ *   min_span, min_frac  the reference's eligibility (:2346-2347), evaluated on the device: a station is fitted when
+ *                     span = (max t - min t of its rows) / 31556952 >= min_span, rows / (span * 365.25) >= min_frac and rows >= P + 1,
+ *                     P = 3 parameters (scan = 0) or 4 (scan = 1).  (The reference accepts rows = P, with an infinite covariance.)
+ *   cell_start [ncells + 1], cells   at loc, both or neither: the stations sorted by cell as for rdr_grid_stats.
+ *   station [16][n]   at loc, doubles: 0 rows, 1 span in years, 2 fitted (0 / 1), 3 at_edge (k* is the first or last grid index),
+ *                     4 A = hypot(a, b), 5 p in (-pi, pi] (for t in POSIX seconds), 6 c, 7 w, 8 R, 9 rmse = sqrt(R / (rows - 2)),
+ *                     10 .. 13 the sigmas of A, w (NaN for scan = 0), p, c: square roots of the diagonal of R / (rows - P) (J^T J)^-1 with
+ *                     the analytic Jacobian at the solution (formed with tau centred and in years, then carried to t), 14 k* (NaN for
+ *                     scan = 0), 15 the golden-section steps taken.  A station that is not fitted - not eligible, a singular system,
+ *                     a non-finite result - has 0 in rows 2 and 3 and NaN in rows 4 .. 15.
+ *   cells [14][ncells]  per cell, over its fitted stations in station order: rows 0 .. 6 the plain means of the reference's columns
+ *                     phsfit = 182.625 sin(p), ampfit, periodfit = 1 / (w / 2 pi * 31556952) years, phsfit_c, ampfit_c, periodfit_c,
+ *                     seasonalfit_rmse, rows 7 .. 13 their means weighted by the stations' row counts (the reference's groupby over the
+ *                     long table); NaN for a cell without a fitted station.  The three *_c columns carry the reference's labels
+ *                     (:2424-2426: ampfit_c, periodfit_c, phsfit_c = sqrt of pcov[0,0], [1,1], [2,2]): for scan = 1 the sigmas of A, w, p,
+ *                     for scan = 0 - parameters (A, p, c) - periodfit_c is the sigma of p and phsfit_c the sigma of c.
+ * sin / cos of omega[k] tau[d] are computed once per (k, d); a lane owns a station and adds every sum in date order, f64, without any
+ * floating-point atomic: two calls, host or device arrays, and any order of the stations give the same bytes per station.
+ * A call with host outputs synchronises.  RDR_ERR_INVALID, before the device is touched: a NULL ctx, t, values, omega or station, a wrong
+ * loc, n outside 1 .. 2^20, nd outside 1 .. 4096, k outside 1 .. 4096, scan not 0 / 1, scan = 0 with k != 1, min_span negative or not
+ * finite, min_frac not finite, an omega that is not finite, not > 0 or not ascending, a t that is not finite, cell_start without cells or
+ * the reverse, ncells outside 1 .. 2^20; and, after cell_start was read back from the device where it lives there: cell_start not
+ * starting at 0, not ending at n or not ascending. */
+int rdr_seasonal_fit(rdr_ctx* ctx, const double* t, const double* values, int64_t n, int nd, const double* omega, int k, int scan, double min_span,
+                     double min_frac, const int64_t* cell_start, int ncells, double* station, double* cells, int loc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,3 +15,4 @@ from .time_interp import (DatetimeFailed, NoWeatherModelData, WrongNumberOfFiles
 from .variogram import (GridVariograms, PairVariogram, StationGrid, deramp, fit_variogram, grid_variograms, pair_variogram, station_grid,  # noqa: F401
                         station_variograms, utm_common_center)
 from .station_stats import (GridStatistics, grid_statistics, load_gridfile, read_station_csv, save_gridfile, station_table)  # noqa: F401
+from .seasonal import GridSeasonal, SeasonalFits, grid_seasonal, seasonal_fits  # noqa: F401

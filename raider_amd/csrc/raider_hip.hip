@@ -421,6 +421,7 @@ static auto by_dtype(const rdr_cube* q, F&& f) -> decltype(f(float2())) {
 #include "variogram_kernels.h"
 #include "cell_variogram_kernels.h"
 #include "grid_stats_kernels.h"
+#include "seasonal_kernels.h"
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -4160,6 +4161,87 @@ int rdr_grid_stats(rdr_ctx* c, const double* values, int64_t n, int nd, const in
     if (of_any || ab_any) hipLaunchKernelGGL(grid_stats_cell_kernel, dim3((unsigned)ncells), dim3(GS_TILE), 0, c->stream, A);
     HIPCHECK(c, hipGetLastError());
     for (Out& o : outs) { rc = finish_out(c, o.host, o.dev, o.bytes, loc); if (rc) return rc; }
+    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return RDR_OK;
+}
+
+// ---- seasonal sinusoids (seasonal_kernels.h; raider_amd/seasonal.py: seasonal_fits, grid_seasonal) -------------------------------------
+int rdr_seasonal_fit(rdr_ctx* c, const double* t, const double* values, int64_t n, int nd, const double* omega, int k, int scan, double min_span,
+                     double min_frac, const int64_t* cell_start, int ncells, double* station, double* cells, int loc) {
+    const std::string w("rdr_seasonal_fit");
+    if (!c || !t || !values || !omega || !station) return fail(c, RDR_ERR_INVALID, w + ": NULL argument");
+    if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, w + ": loc must be RDR_HOST or RDR_DEVICE");
+    if (n < 1 || n > ((int64_t)1 << 20)) return fail(c, RDR_ERR_INVALID, w + ": n must be 1 .. 2^20 stations (got " + std::to_string(n) + ")");
+    if (nd < 1 || nd > 4096) return fail(c, RDR_ERR_INVALID, w + ": nd must be 1 .. 4096 dates (got " + std::to_string(nd) + ")");
+    if (k < 1 || k > 4096) return fail(c, RDR_ERR_INVALID, w + ": k must be 1 .. 4096 frequencies (got " + std::to_string(k) + ")");
+    if (scan != 0 && scan != 1) return fail(c, RDR_ERR_INVALID, w + ": scan must be 0 or 1");
+    if (!scan && k != 1) return fail(c, RDR_ERR_INVALID, w + ": the fixed mode (scan = 0) takes one frequency (got k = " + std::to_string(k) + ")");
+    if (!(min_span >= 0.0) || !std::isfinite(min_span)) return fail(c, RDR_ERR_INVALID, w + ": min_span must be finite and >= 0");
+    if (!std::isfinite(min_frac)) return fail(c, RDR_ERR_INVALID, w + ": min_frac must be finite");
+    for (int i = 0; i < k; ++i) {
+        if (!std::isfinite(omega[i]) || !(omega[i] > 0.0)) return fail(c, RDR_ERR_INVALID, w + ": omega[" + std::to_string(i) + "] must be finite and > 0");
+        if (i && !(omega[i] > omega[i - 1])) return fail(c, RDR_ERR_INVALID, w + ": omega must ascend (index " + std::to_string(i) + ")");
+    }
+    double tmin = t[0], tmax = t[0];
+    for (int d = 0; d < nd; ++d) {
+        if (!std::isfinite(t[d])) return fail(c, RDR_ERR_INVALID, w + ": t[" + std::to_string(d) + "] is not finite");
+        tmin = std::min(tmin, t[d]); tmax = std::max(tmax, t[d]);
+    }
+    if ((cell_start == nullptr) != (cells == nullptr)) return fail(c, RDR_ERR_INVALID, w + ": cell_start and cells come together or not at all");
+    if (cells && (ncells < 1 || ncells > (1 << 20))) return fail(c, RDR_ERR_INVALID, w + ": ncells must be 1 .. 2^20 cells (got " + std::to_string(ncells) + ")");
+    HIPCHECK(c, hipSetDevice(c->device));
+    if (cells) {                                  // cell_start is checked on the host (an array on the device is read back)
+        std::vector<int64_t> back_cs;
+        const int64_t* hcs = cell_start;
+        if (loc == RDR_DEVICE) {
+            back_cs.resize((size_t)ncells + 1);
+            HIPCHECK(c, hipMemcpyAsync(back_cs.data(), cell_start, ((size_t)ncells + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHECK(c, hipStreamSynchronize(c->stream));
+            hcs = back_cs.data();
+        }
+        if (hcs[0] != 0) return fail(c, RDR_ERR_INVALID, w + ": cell_start[0] must be 0 (got " + std::to_string(hcs[0]) + ")");
+        if (hcs[ncells] != n) return fail(c, RDR_ERR_INVALID, w + ": cell_start[ncells] must be n = " + std::to_string(n) + " (got " + std::to_string(hcs[ncells]) + ")");
+        for (int g = 0; g < ncells; ++g)
+            if (hcs[g + 1] < hcs[g]) return fail(c, RDR_ERR_INVALID, w + ": cell_start is not ascending at index " + std::to_string(g + 1));
+    }
+    SeasonalArgs A{};
+    A.n = n; A.nd = nd; A.k = k; A.scan = scan; A.ncells = cells ? ncells : 0;
+    A.min_span = min_span; A.min_frac = min_frac; A.t_ref = 0.5 * (tmin + tmax);
+    A.ntiles = (k + SF_KT - 1) / SF_KT;
+    const unsigned nblk = (unsigned)((n + 63) / 64);
+    // enough waves to fill the device: the frequency tiles are cut into segments, which changes no result
+    A.nseg = scan ? std::max(1, std::min(A.ntiles, (int)((8192 + nblk - 1) / nblk))) : 0;
+    A.tiles_per_seg = scan ? (A.ntiles + A.nseg - 1) / A.nseg : 0;
+    if (scan) A.nseg = (A.ntiles + A.tiles_per_seg - 1) / A.tiles_per_seg;
+    std::vector<double> small((size_t)nd + k);
+    for (int d = 0; d < nd; ++d) small[d] = t[d] - A.t_ref;
+    for (int i = 0; i < k; ++i) small[(size_t)nd + i] = omega[i];
+    const void* d;
+    int rc = stage_in(c, SLOT_IN0, values, (size_t)nd * n * 8, loc, &d); if (rc) return rc; A.values = (const double*)d;
+    rc = stage_in(c, SLOT_IN1, cell_start, ((size_t)ncells + 1) * 8, loc, &d); if (rc) return rc; A.cell_start = (const long long*)d;
+    rc = stage_in(c, SLOT_IN2, small.data(), small.size() * 8, RDR_HOST, &d); if (rc) return rc;
+    A.tau = (const double*)d; A.omega = A.tau + nd;
+    const size_t tab_b = scan ? (size_t)A.ntiles * nd * SF_KT * sizeof(double2) : 0, prep_b = (size_t)5 * n * 8, best_b = (size_t)A.nseg * 2 * n * 8;
+    void* aux; rc = ensure(c, SLOT_AUX, tab_b + prep_b + best_b, &aux); if (rc) return rc;
+    A.table = (double2*)aux; A.prep = (double*)(static_cast<char*>(aux) + tab_b); A.best = (double*)(static_cast<char*>(aux) + tab_b + prep_b);
+    const size_t sb = (size_t)SF_NCOL * n * 8, cb = cells ? (size_t)2 * SF_NREF * ncells * 8 : 0;
+    void* ds = station; void* dc = cells;
+    if (loc == RDR_HOST) {
+        void* base; rc = ensure(c, SLOT_OUT0, sb + cb, &base); if (rc) return rc;
+        ds = base; dc = cells ? static_cast<char*>(base) + sb : nullptr;
+    }
+    A.station = (double*)ds; A.cells = (double*)dc;
+    hipLaunchKernelGGL(seasonal_prep_kernel, dim3(nblk), dim3(64), 0, c->stream, A);
+    if (scan) {
+        const long long total = (long long)A.ntiles * nd * SF_KT;
+        hipLaunchKernelGGL(seasonal_table_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, A);
+        hipLaunchKernelGGL(seasonal_scan_kernel, dim3(nblk, (unsigned)A.nseg), dim3(64), 0, c->stream, A);
+    }
+    hipLaunchKernelGGL(seasonal_fit_kernel, dim3(nblk), dim3(64), 0, c->stream, A);
+    if (cells) hipLaunchKernelGGL(seasonal_cell_kernel, dim3((unsigned)(((long long)ncells * SF_NREF + 255) / 256)), dim3(256), 0, c->stream, A);
+    HIPCHECK(c, hipGetLastError());
+    rc = finish_out(c, station, ds, sb, loc); if (rc) return rc;
+    rc = finish_out(c, cells, dc, cb, loc); if (rc) return rc;
     if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
     return RDR_OK;
 }

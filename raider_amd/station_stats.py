@@ -10,7 +10,7 @@ mean, median and standard deviation:
   read_station_csv  - the reference's CSV layout -> station_table, through the standard library's csv
   save_gridfile / load_gridfile - the GeoTIFF files of `--grid_to_raster` (:436-541), through tifflite
 
-Not here: the seasonal fits, the `seasonalinterval` filter, the plots.
+The seasonal fits and their maps are in seasonal.py.  Not here: the `seasonalinterval` filter, the per-station debug plots, the plots.
 """
 import csv
 import os
