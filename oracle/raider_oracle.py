@@ -423,7 +423,9 @@ def stere_forward(lat, lon, lat_0=90.0, lat_ts=None, k_0=1.0, lon_0=0.0, x_0=0.0
 
 def _tm_setup(a, es, lat_0, lon_0, k_0):
     f = 1 - np.sqrt(1 - es); n = f / (2 - f)
-    A = a / (1 + n) * (1 + n ** 2 / 4 + n ** 4 / 64 + n ** 6 / 256)
+    # k_0 A multiplied out from the left, k_0 a / (1 + n) (...), the order of tm_setup (csrc/proj_kernels.h): k_0 (a / (1 + n) (...))
+    # rounds ONE ulp away on WGS 84 and Airy, and at 1e-6 degrees from a pole one ulp of xi = (y - y_0) / kA is 4e-7 degrees of longitude
+    kA = k_0 * a / (1 + n) * (1 + n ** 2 / 4 + n ** 4 / 64 + n ** 6 / 256)
     al = [n / 2 - 2 * n ** 2 / 3 + 5 * n ** 3 / 16 + 41 * n ** 4 / 180 - 127 * n ** 5 / 288 + 7891 * n ** 6 / 37800,
           13 * n ** 2 / 48 - 3 * n ** 3 / 5 + 557 * n ** 4 / 1440 + 281 * n ** 5 / 630 - 1983433 * n ** 6 / 1935360,
           61 * n ** 3 / 240 - 103 * n ** 4 / 140 + 15061 * n ** 5 / 26880 + 167603 * n ** 6 / 181440,
@@ -434,7 +436,7 @@ def _tm_setup(a, es, lat_0, lon_0, k_0):
           17 * n ** 3 / 480 - 37 * n ** 4 / 840 - 209 * n ** 5 / 4480 + 5569 * n ** 6 / 90720,
           4397 * n ** 4 / 161280 - 11 * n ** 5 / 504 - 830251 * n ** 6 / 7257600,
           4583 * n ** 5 / 161280 - 108847 * n ** 6 / 3991680, 20648693 * n ** 6 / 638668800]
-    return np.sqrt(es), k_0 * A, al, be
+    return np.sqrt(es), kA, al, be
 
 
 def _tm_conformal(e, phi, lam):
@@ -447,9 +449,14 @@ def _tm_conformal(e, phi, lam):
 def tm_forward(lat, lon, lat_0=0.0, lon_0=0.0, k_0=0.9996, x_0=500000.0, y_0=0.0, a=6378137.0, es=0.0066943799901413165):
     """Geodetic -> transverse Mercator (UTM: lat_0 = 0, k_0 = 0.9996, x_0 = 500 000, y_0 = 0 / 10 000 000, lon_0 = 6 zone - 183):
     what pyproj does in transformPoints (delay.py:404-436) for a UTM output grid.  Krueger's series in the third flattening to
-    n^6 (Karney 2011, eqs. 7-11, 35) = the formulation of PROJ's `etmerc` / `utm`; PARITY WITH PROJ ITSELF IS UNPINNED (pyproj is
-    absent), pinned instead on Snyder's UTM example (PP 1395 p. 269: Clarke 1866, (40.5 N, 73.5 W), lon_0 = 75 W -> x = 127 106.5 m,
-    y = 4 484 124.4 m) and the OSGB example of IOGP Guidance Note 7-2 (E 577 274.99, N 69 740.50).  Returns (x, y)."""
+    n^6 (Karney 2011, eqs. 7-11, 35) = the formulation of PROJ's `etmerc` / `utm`.  pyproj is absent, so what it is pinned on is not
+    PROJ but the EXACT mapping: the meridian distance continued analytically in the isometric latitude, solved in 40 digits without a
+    series (tests/projection_exact.py, tests/test_geodesy_exact.py) - within 1e-8 m (measured 6.7e-9 m) up to 35 degrees from the central
+    meridian at every latitude, the poles included, on six parameter sets; beyond that the n^6 truncation shows, 2.1e-8 m at 45 degrees
+    and 1.2e-5 m at 60 degrees.  Also on Snyder's UTM example (PP 1395 p. 269: Clarke 1866, (40.5 N, 73.5 W), lon_0 = 75 W -> x =
+    127 106.5 m, y = 4 484 124.4 m) and the OSGB example of IOGP Guidance Note 7-2 (E 577 274.99, N 69 740.50), which carry the
+    centimetres of the truncated series they were printed from (the exact values: 127 106.467, 4 484 124.427; 577 274.984, 69 740.492).
+    Returns (x, y)."""
     e, kA, al, _ = _tm_setup(a, es, lat_0, lon_0, k_0)
     xi0p, eta0p = _tm_conformal(e, np.radians(lat_0), 0.0)
     xi0 = xi0p + sum(al[j] * np.sin(2 * (j + 1) * xi0p) * np.cosh(2 * (j + 1) * eta0p) for j in range(6))
@@ -462,7 +469,8 @@ def tm_forward(lat, lon, lat_0=0.0, lon_0=0.0, k_0=0.9996, x_0=500000.0, y_0=0.0
 
 
 def tm_inverse(x, y, lat_0=0.0, lon_0=0.0, k_0=0.9996, x_0=500000.0, y_0=0.0, a=6378137.0, es=0.0066943799901413165):
-    """Transverse Mercator -> geodetic (Karney 2011 eqs. 11, 36 and the Newton step 19-21).  Returns (lat, lon) in degrees."""
+    """Transverse Mercator -> geodetic (Karney 2011 eqs. 11, 36 and the Newton step 19-21).  Pinned as tm_forward is: its (lat, lon) go
+    back through the exact forward within 1e-8 m of the input (measured 5.2e-9 m).  Returns (lat, lon) in degrees."""
     e, kA, al, be = _tm_setup(a, es, lat_0, lon_0, k_0)
     xi0p, eta0p = _tm_conformal(e, np.radians(lat_0), 0.0)
     xi0 = xi0p + sum(al[j] * np.sin(2 * (j + 1) * xi0p) * np.cosh(2 * (j + 1) * eta0p) for j in range(6))

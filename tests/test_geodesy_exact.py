@@ -6,6 +6,8 @@ adds what those examples cannot: the defining equations themselves, solved to 40
 uses (heights -500 m ... 85 km, every latitude).  Findings it asserts:
 
   * geodetic -> ECEF and the conic projections: the restatements are exact to rounding (< 5e-9 m / 2e-8 m);
+  * transverse Mercator: Krueger's series to n^6 is exact to rounding (< 1e-8 m) within 35 degrees of the central meridian, poles
+    included; its truncation is 2e-8 m at 45 degrees and 1.2e-5 m at 60 degrees (the exact mapping: tests/projection_exact.py);
   * ECEF -> geodetic: PROJ's published inverse is ONE Bowring step, whose truncation grows with height squared - 1e-8 m at 1 km,
     1e-6 m at 10 km, 1.6e-5 m at 40 km, 7e-5 m at 85 km in height (6e-10 degrees in latitude).  The restatement reproduces
     that formula (it is the parity target: the reference calls PROJ); this test bounds how far formula and exact ellipsoid are
@@ -17,6 +19,8 @@ import pytest
 from oracle import raider_oracle as O
 
 mp = pytest.importorskip('mpmath')
+
+from tests import projection_exact as P                   # noqa: E402  (needs mpmath)
 
 A = mp.mpf(6378137)
 F = 1 / mp.mpf('298.257223563')
@@ -69,31 +73,7 @@ def test_conic_projections_against_40_digit_arithmetic():
     """lcc_forward / stere_forward and their inverses: Snyder's closed forms evaluated in 40 digits (the formulas ARE the definition
     of the projection; PROJ implements the same ones) - bounds the double-precision rounding of the restatement, metres at 1e-8."""
     mp.mp.dps = 40
-
-    def tsfn(phi, e):
-        s = mp.sin(phi)
-        return mp.tan((mp.pi / 2 - phi) / 2) / ((1 - e * s) / (1 + e * s)) ** (e / 2)
-
-    def msfn(phi, es):
-        return mp.cos(phi) / mp.sqrt(1 - es * mp.sin(phi) ** 2)
-
-    def lcc(lat, lon, lat_1, lat_2, lat_0, lon_0, a, es, x_0=0.0, y_0=0.0):
-        a, es = mp.mpf(a), mp.mpf(es); e = mp.sqrt(es)
-        p1, p2, p0 = (mp.radians(mp.mpf(v)) for v in (lat_1, lat_2, lat_0))
-        n = mp.log(msfn(p1, es) / msfn(p2, es)) / mp.log(tsfn(p1, e) / tsfn(p2, e)) if abs(p1 - p2) > mp.mpf('1e-10') else mp.sin(p1)
-        Fc = msfn(p1, es) * tsfn(p1, e) ** (-n) / n
-        rho0 = a * Fc * tsfn(p0, e) ** n
-        rho = a * Fc * tsfn(mp.radians(mp.mpf(lat)), e) ** n
-        th = n * mp.radians(mp.mpf(lon) - mp.mpf(lon_0))
-        return mp.mpf(x_0) + rho * mp.sin(th), mp.mpf(y_0) + rho0 - rho * mp.cos(th)
-
-    def stere_north(lat, lon, lat_ts, lon_0, a, es):
-        a, es = mp.mpf(a), mp.mpf(es); e = mp.sqrt(es)
-        pc = mp.radians(mp.mpf(lat_ts))
-        rho = a * msfn(pc, es) * tsfn(mp.radians(mp.mpf(lat)), e) / tsfn(pc, e)
-        dl = mp.radians(mp.mpf(lon) - mp.mpf(lon_0))
-        return rho * mp.sin(dl), -rho * mp.cos(dl)
-
+    lcc, stere = P.lcc_exact, P.stere_exact
     rng = np.random.default_rng(1)
     cases = [dict(lat_1=38.5, lat_2=38.5, lat_0=38.5, lon_0=-97.5, a=6371229.0, es=0.0),                       # HRRR
              dict(lat_1=33.0, lat_2=45.0, lat_0=23.0, lon_0=-96.0, a=6378206.4, es=0.00676866)]                # Snyder's ellipsoidal case
@@ -111,8 +91,52 @@ def test_conic_projections_against_40_digit_arithmetic():
         la = rng.uniform(45, 89.5, 40); lo = rng.uniform(-180, 180, 40)
         x, y = O.stere_forward(la, lo, **kw)
         for k in range(la.size):
-            ex, ey = stere_north(float(la[k]), float(lo[k]), kw['lat_ts'], kw['lon_0'], kw['a'], kw['es'])
+            ex, ey = stere(float(la[k]), float(lo[k]), **kw)
             assert abs(float(mp.mpf(float(x[k])) - ex)) < 2e-8 and abs(float(mp.mpf(float(y[k])) - ey)) < 2e-8
+
+
+def test_transverse_mercator_against_40_digit_arithmetic():
+    """tm_forward / tm_inverse (Krueger's series to n^6, twelve typed rational coefficients) against the EXACT mapping - the analytic
+    continuation of the meridian distance in the isometric latitude, solved in 40 digits without any series (tests/projection_exact.py) -
+    on six parameter sets (three UTM zones, OSGB on Airy with lat_0 = 49, Snyder's Clarke 1866 case, a sphere with lat_0 = -30): 65
+    points per set within 35 degrees of the central meridian at latitudes up to +-89.999999, the poles, the antimeridian wrap.  Forward:
+    within 1e-8 m (5 ulp of 1e7 m; measured 6.7e-9 m).  Inverse: the exact (x, y) rounded to the millimetre come back, through the exact
+    forward, within 1e-8 m (measured 5.2e-9 m).  What a typed coefficient does here: 61/240 -> 61/241 in al[2] gives 8.0e-4 m forward,
+    17/480 -> 17/481 in be[2] 5.6e-5 m back (either also breaks the 1e-11 degree closure of tests/test_oracle_golden.py); n^3 / 1000 added
+    to BOTH, a slip the two series share, 7.6e-4 m and 7.7e-4 m - and closure and the printed examples stay green.
+    Beyond 35 degrees the assertion is the series' own TRUNCATION, measured on this reference, not rounding: 2.1e-8 m at 45 degrees from
+    the meridian (bound 1e-7 m), 1.2e-5 m at 60 degrees (bound 1e-4 m); the inverse closes within 4.6e-9 m / 5.4e-7 m there."""
+    rec = P.tm_measure(lambda la, lo, p: O.tm_forward(la, lo, **p), lambda x, y, p: O.tm_inverse(x, y, **p))
+    for r in rec:
+        print(f"{r['group']:6s} {r['name']:14s} forward {r['fwd'].max():.3e} m   inverse {r['inv'].max():.3e} {'deg' if r['group'] == 'pole' else 'm'}")
+        assert np.isfinite(r['x']).all() and np.isfinite(r['y']).all() and np.isfinite(r['lat']).all() and np.isfinite(r['lon']).all()
+        assert r['lon'].min() >= -180.0 and r['lon'].max() <= 180.0
+    for group in ('in', 'anti'):
+        assert P.worst(rec, 'fwd', group=group) < 1e-8 and P.worst(rec, 'inv', group=group) < 1e-8, group
+    # the poles: x = x_0 and the exact northing k_0 (+-M(pi/2) - M(lat_0)); the inverse of that point is the pole
+    assert P.worst(rec, 'fwd', group='pole') < 1e-8 and P.worst(rec, 'inv', group='pole') < 1e-9
+    assert P.worst(rec, 'fwd', group='out45') < 1e-7 and P.worst(rec, 'inv', group='out45') < 1e-7
+    assert P.worst(rec, 'fwd', group='out60') < 1e-4 and P.worst(rec, 'inv', group='out60') < 1e-4
+    assert P.worst(rec, 'fwd', group='out60') > 1e-6            # (what is recorded is the truncation: it must be visible in that group)
+
+
+def test_cones_near_the_pole_and_the_cut_meridian_against_40_digit_arithmetic():
+    """The point sets of the device test (tests/projection_exact.py: cone_sets) on the oracle: HRRR, Snyder's ellipsoidal cone, a
+    SOUTHERN cone with false origin, HRRR-AK, EPSG:3413's parameters, a south-polar lat_ts = -71 case and the k_0 = 0.994 variant, 20
+    points each with two within 1e-6 degrees of the projection's pole and two within 0.1 degrees of the cut meridian.  Within 2e-8 m,
+    forward and (millimetre-rounded (x, y) -> inverse -> exact forward) back, with ONE exception, which is the number format and not the
+    formulas: next to the pole of a Lambert cone rho ~ colat^n (n ~ 0.6) is tens of metres at a colatitude of 1e-6 degrees, which a double
+    near 90 degrees / pi/2 resolves to 1e-8 of itself only.  Forward (pi/2 - phi is formed in doubles): measured 8e-8 .. 5e-7 m.  Inverse:
+    ONE ulp of the returned latitude is 5e-7 .. 1.5e-6 m (projection_exact.lcc_pole_quantum); four are allowed."""
+    rec = P.cone_measure(O.project_forward, O.project_inverse)
+    for k, r in enumerate(rec):
+        near = r['near'] & (P.cone_sets()[k][1]['proj'] == 'lcc')
+        print(f"{r['name']:10s} forward {r['fwd'][~near].max():.3e} m   inverse {r['inv'][~near].max():.3e} m   next to an LCC pole: {r['fwd'][near]} {r['inv'][near]}")
+        assert r['fwd'][~near].max() < 2e-8 and r['inv'][~near].max() < 2e-8, r['name']
+        assert r['lon'].min() >= -180.0 and r['lon'].max() <= 180.0
+        if near.any():
+            q = P.lcc_pole_quantum(k)[near]
+            assert (r['fwd'][near] < 4 * q).all() and (r['inv'][near] < 4 * q).all(), (r['name'], q)
 
 
 ERFA_PY = '/opt/conda/bin/python3.9'          # an Anaconda interpreter in the image carries pyerfa (the IAU SOFA routines, with astropy)

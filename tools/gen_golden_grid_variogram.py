@@ -56,6 +56,8 @@ def scene():
         lo = rng.uniform(W + ix + 0.06, W + ix + 0.94, k); la = rng.uniform(S + iy + 0.06, S + iy + 0.94, k)
         x, y = O.tm_forward(la, lo, lon_0=-117.0)
         la2, lo2 = O.tm_inverse(np.round(x), np.round(y), lon_0=-117.0)                 # integer-metre lattice nodes of zone 11
+        # (the committed g21 was made when the oracle rounded k_0 A one ulp differently - k_0 (a / (1 + n) (...)): a regeneration may move
+        # lon / lat, and with them everything recorded, by an ulp; stage 1, the device's metres of the NEW lon / lat, has to be redone too)
         lon.append(lo2); lat.append(la2)
     lon, lat = np.concatenate(lon), np.concatenate(lat)
     perm = rng.permutation(lon.size)                                                    # stations do not come sorted by cell
