@@ -789,6 +789,42 @@ int rdr_grid_stats(rdr_ctx* ctx, const double* values, int64_t n, int nd, const 
 int rdr_seasonal_fit(rdr_ctx* ctx, const double* t, const double* values, int64_t n, int nd, const double* omega, int k, int scan, double min_span,
                      double min_frac, const int64_t* cell_start, int ncells, double* station, double* cells, int loc);
 
+/* rdr_variogram_fit: exponential variogram models (cli/statsPlot.py _fit_vario with __exponential__, nugget=False, :661-713;
+ * csrc/variogram_fit_kernels.h) as EXACT BOUNDED MINIMA of the reference's own objective over the reference's own box - not the point at
+ * which scipy's trust-region run happens to stop.  One fit per row f of h [nfits][m], gamma [nfits][m] (f64); a column where either is
+ * NaN is absent; n is the number of columns present.
+ *   model      b (1 - exp(-h / a)): range a, sill b.  The reference's third parameter never enters a model without nugget.
+ *   bounds     0 <= a <= ub_a, 0 <= b <= ub_b: from ub [nfits][3] when given, else the reference's defaults
+ *              0.8 * (max h, max gamma, max gamma) over the row's present columns.
+ *   objective  scipy's cost for loss='soft_l1', f_scale = s:  C(a, b) = s^2 sum_i (sqrt(1 + z_i) - 1),  z_i = (r_i (1 / s))^2,
+ *              r_i = b e_i - gamma_i,  e_i = 1 - exp(-h_i / a); each term evaluated as z_i / (sqrt(1 + z_i) + 1), which keeps its digits at
+ *              z ~ 1e-6 (delays in metres), where the textbook form loses six.
+ *   sill       for a given range C is convex in b and D(b) = sum e_i r_i / sqrt(1 + z_i) non-decreasing: D(0) >= 0 gives b = 0,
+ *              D(ub_b) <= 0 gives b = ub_b, else bisection of [0, ub_b] (D > 0: the upper half is dropped) until the bracket is at most
+ *              2^-52 ub_b wide or 64 halvings; b is the middle of the bracket.
+ *   range      a_floor = h_pos / 38, h_pos the smallest positive present lag (exp(-38) < 2^-54: below it every e_i of a positive lag is
+ *              exactly 1 and the model no longer depends on a).  k_scan candidates a_k = a_floor exp(k ln(ub_a / a_floor) / (k_scan - 1)),
+ *              the first exactly a_floor, the last exactly ub_a (ub_a <= a_floor: the single candidate ub_a, no refinement); the
+ *              candidate of lowest C, each at its own best sill, the lowest index on ties; then 8 rounds of 64 candidates spaced the same
+ *              way over [a_(k-1), a_(k+1)] of the round before (clipped to its grid, end points included), each round centred on its
+ *              own best.  The best candidate evaluated anywhere wins; a tie stays with the earlier round, then the lower index.
+ *   outputs    params [nfits][3] = (a, b, ub_c / 2): the third is the reference's untouched nugget start; cost [nfits] = C(a, b);
+ *              rmse [nfits] = sqrt(mean r_i^2), the reference's sqrt(nanmean(fun^2)); n [nfits] (int64);
+ *              status [nfits] (int32), decided in this order: 1 no column present; 2 a negative lag or an infinity among the present
+ *              values; 3 no positive lag (every e_i is 0); 2 ub_a or ub_b not finite or <= 0 (max gamma <= 0, where scipy raises);
+ *              0 fitted.  A row with status != 0 holds NaN in params, cost and rmse and 0 in flags;
+ *              flags [nfits] (int32) bits: 1 range at a_floor, 2 range at ub_a (within 2^-40 of the bound: the last round's candidates
+ *              lie a few ulp apart), 4 sill 0, 8 sill ub_b (by the two tests on D).
+ * One wave per row.  n <= 64: lanes are range candidates, e_i is kept per (point, lane) in LDS for the bisection, a lane adds its sums in
+ * column order.  n > 64: lanes stride over the columns, candidates run one after the other, a sum is the lanes' partial sums folded by a
+ * fixed butterfly.  The two may differ in round-off from each other; each is deterministic: a row's bytes depend on nothing but the row,
+ * not on the batch, its position in it, the place of the arrays, or the run.  No floating-point atomic.
+ * Every array lives at `loc`; a call with host outputs synchronises.  RDR_ERR_INVALID, before the device is touched: a NULL ctx, h,
+ * gamma or output, a wrong loc, nfits outside 1 .. 2^22 (an empty batch is an error), m outside 1 .. 65536, nfits x m beyond 2^30,
+ * f_scale not finite or <= 0, k_scan not a multiple of 64 in 64 .. 4096. */
+int rdr_variogram_fit(rdr_ctx* ctx, const double* h, const double* gamma, int64_t nfits, int m, const double* ub, double f_scale, int k_scan,
+                      double* params, double* cost, double* rmse, int64_t* n, int32_t* status, int32_t* flags, int loc);
+
 #ifdef __cplusplus
 }
 #endif

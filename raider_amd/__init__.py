@@ -12,7 +12,7 @@ from .engine import (Cube, Rays, grid_geodetic, interp_project_epochs, nparts_fr
 from .llreader import AOI, BoundingBox, GeocodedFile, Geocube, RasterRDR, StationFile, bounds_from_csv, bounds_from_latlon_rasters  # noqa: F401
 from .time_interp import (DatetimeFailed, NoWeatherModelData, WrongNumberOfFiles, combine_weather_files, get_dt, get_nearest_wmtimes,  # noqa: F401
                           get_weights_time_interp, getWeatherFile, round_date, round_time, tropo_delay_interp, tropo_delay_interp_series)
-from .variogram import (GridVariograms, PairVariogram, StationGrid, deramp, fit_variogram, grid_variograms, pair_variogram, station_grid,  # noqa: F401
+from .variogram import (GridVariograms, PairVariogram, StationGrid, VariogramFits, deramp, fit_variogram, fit_variograms, grid_variograms, pair_variogram, station_grid,  # noqa: F401
                         station_variograms, utm_common_center)
 from .station_stats import (GridStatistics, grid_statistics, load_gridfile, read_station_csv, save_gridfile, station_table)  # noqa: F401
 from .seasonal import GridSeasonal, SeasonalFits, grid_seasonal, seasonal_fits  # noqa: F401

@@ -167,6 +167,7 @@ SYMBOLS = [
     ('rdr_cell_variogram', C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int] + [_VP] * 11 + [C.c_int]),
     ('rdr_grid_stats', C.c_int, [_VP, _VP, C.c_int64, C.c_int, _VP, C.c_int] + [_VP] * 12 + [C.c_int]),
     ('rdr_seasonal_fit', C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, _VP, C.c_int, C.c_int, C.c_double, C.c_double, _VP, C.c_int, _VP, _VP, C.c_int]),
+    ('rdr_variogram_fit', C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, _VP, C.c_double, C.c_int] + [_VP] * 6 + [C.c_int]),
 ]
 
 

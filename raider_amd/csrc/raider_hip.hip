@@ -422,6 +422,7 @@ static auto by_dtype(const rdr_cube* q, F&& f) -> decltype(f(float2())) {
 #include "cell_variogram_kernels.h"
 #include "grid_stats_kernels.h"
 #include "seasonal_kernels.h"
+#include "variogram_fit_kernels.h"
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -4242,6 +4243,50 @@ int rdr_seasonal_fit(rdr_ctx* c, const double* t, const double* values, int64_t 
     HIPCHECK(c, hipGetLastError());
     rc = finish_out(c, station, ds, sb, loc); if (rc) return rc;
     rc = finish_out(c, cells, dc, cb, loc); if (rc) return rc;
+    if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return RDR_OK;
+}
+
+// ---- exponential variogram models (variogram_fit_kernels.h; raider_amd/variogram.py: fit_variograms) -----------------------------------
+int rdr_variogram_fit(rdr_ctx* c, const double* h, const double* gamma, int64_t nfits, int m, const double* ub, double f_scale, int k_scan,
+                      double* params, double* cost, double* rmse, int64_t* n, int32_t* status, int32_t* flags, int loc) {
+    const std::string w("rdr_variogram_fit");
+    if (!c || !h || !gamma || !params || !cost || !rmse || !n || !status || !flags) return fail(c, RDR_ERR_INVALID, w + ": NULL argument");
+    if (loc != RDR_HOST && loc != RDR_DEVICE) return fail(c, RDR_ERR_INVALID, w + ": loc must be RDR_HOST or RDR_DEVICE");
+    if (nfits < 1 || nfits > ((int64_t)1 << 22)) return fail(c, RDR_ERR_INVALID, w + ": nfits must be 1 .. 2^22 rows (got " + std::to_string(nfits) + ")");
+    if (m < 1 || m > 65536) return fail(c, RDR_ERR_INVALID, w + ": m must be 1 .. 65536 columns (got " + std::to_string(m) + ")");
+    if (nfits * m > ((int64_t)1 << 30)) return fail(c, RDR_ERR_INVALID, w + ": nfits x m must not exceed 2^30 values (got " + std::to_string(nfits * m) + ")");
+    if (!std::isfinite(f_scale) || !(f_scale > 0.0)) return fail(c, RDR_ERR_INVALID, w + ": f_scale must be finite and > 0");
+    if (k_scan < 64 || k_scan > 4096 || k_scan % 64) return fail(c, RDR_ERR_INVALID, w + ": k_scan must be a multiple of 64 in 64 .. 4096 (got " + std::to_string(k_scan) + ")");
+    HIPCHECK(c, hipSetDevice(c->device));
+    VarioFitArgs A{};
+    const void* d;
+    const size_t vb = (size_t)nfits * m * 8;
+    int rc = stage_in(c, SLOT_IN0, h, vb, loc, &d); if (rc) return rc; A.h = (const double*)d;
+    rc = stage_in(c, SLOT_IN1, gamma, vb, loc, &d); if (rc) return rc; A.gamma = (const double*)d;
+    rc = stage_in(c, SLOT_IN2, ub, (size_t)nfits * 24, loc, &d); if (rc) return rc; A.ub = (const double*)d;
+    // the outputs: where they are (loc = device), or back to back in one slot from which they are downloaded (loc = host)
+    struct Out { void* host; size_t bytes; void* dev; };
+    const size_t fb = (size_t)nfits * 8;
+    Out outs[6] = {{params, 3 * fb, nullptr}, {cost, fb, nullptr}, {rmse, fb, nullptr}, {n, fb, nullptr}, {status, fb / 2, nullptr}, {flags, fb / 2, nullptr}};
+    if (loc == RDR_DEVICE) {
+        for (Out& o : outs) o.dev = o.host;
+    } else {
+        size_t total = 0;
+        for (Out& o : outs) total += (o.bytes + 15) & ~(size_t)15;
+        void* base; rc = ensure(c, SLOT_OUT0, total, &base); if (rc) return rc;
+        size_t off = 0;
+        for (Out& o : outs) { o.dev = static_cast<char*>(base) + off; off += (o.bytes + 15) & ~(size_t)15; }
+    }
+    A.nfits = nfits; A.m = m; A.k_scan = k_scan; A.f_scale = f_scale;
+    A.params = (double*)outs[0].dev; A.cost = (double*)outs[1].dev; A.rmse = (double*)outs[2].dev; A.n = (long long*)outs[3].dev;
+    A.status = (int*)outs[4].dev; A.flags = (int*)outs[5].dev;
+    // one wave per row in each launch; a row is fitted by the instantiation its number of present columns selects
+    const size_t lds = (size_t)(128 + 64 * std::min(m, 64)) * 8;
+    hipLaunchKernelGGL(variogram_fit_kernel<false>, dim3((unsigned)nfits), dim3(64), lds, c->stream, A);
+    if (m > 64) hipLaunchKernelGGL(variogram_fit_kernel<true>, dim3((unsigned)nfits), dim3(64), 0, c->stream, A);
+    HIPCHECK(c, hipGetLastError());
+    for (Out& o : outs) { rc = finish_out(c, o.host, o.dev, o.bytes, loc); if (rc) return rc; }
     if (loc == RDR_HOST) HIPCHECK(c, hipStreamSynchronize(c->stream));
     return RDR_OK;
 }

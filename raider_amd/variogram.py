@@ -9,6 +9,8 @@ for every date of a [D, N] series in one call, the distance of a pair shared by 
   deramp              - the plane removal of `_emp_vario` (:620-624), per date over its valid points (host, N x 3 least squares)
   utm_common_center   - WGS84_to_UTM(common_center=True) (:621): metres in the UTM zone of the median lon / lat
   fit_variogram       - `_fit_vario` with Nparm=3 (:661-701) through scipy.optimize.least_squares (host)
+  fit_variograms      - exponential models of MANY binned variograms in one device call (csrc/variogram_fit_kernels.h: rdr_variogram_fit),
+                        each the exact minimum of _fit_vario's own objective over its own bounds; `fitter='device'` of the two drivers
   station_variograms  - the chain _emp_vario + _binned_vario + _fit_vario for every date of a series, on all pairs
 
 With no more than 1000 pairs (N <= 45) the reference keeps every pair too and both give the same binned variogram.
@@ -242,15 +244,121 @@ def fit_variogram(h, gamma, model='exponential', ub=None):
     return VariogramFit(res.x, d_test, fn(res.x, d_test), res)
 
 
+# ---- exponential models as exact bounded minima, every row in one device call ---------------------------------------------------------
+MAX_FIT_COLUMNS = 65536
+MAX_FITS = 1 << 22
+AT_FLOOR, AT_UB_A, SILL_ZERO, SILL_UB = 1, 2, 4, 8         # bits of VariogramFits.flags
+
+
+class VariogramFits(namedtuple('VariogramFits', 'params cost rmse n status flags')):
+    """What fit_variograms returns, per row [F] (NumPy arrays or GPU tensors, as the inputs were): params [F, 3] = (range, sill, the
+    reference's untouched nugget start ub_c / 2), cost (scipy's soft_l1 cost at the minimum), rmse = sqrt(mean r^2), n (int64: the
+    columns present), status (int32: 0 fitted, 1 no column present, 2 unusable bounds or values, 3 no positive lag; NaN in params, cost,
+    rmse unless 0) and flags (int32 bits: AT_FLOOR = 1 range at h_pos / 38, AT_UB_A = 2 range at its upper bound, SILL_ZERO = 4,
+    SILL_UB = 8).  hmax [F] (an attribute, not a field): the row's largest lag, for curve()."""
+
+    def __new__(cls, params, cost, rmse, n, status, flags, hmax=None):
+        self = super().__new__(cls, params, cost, rmse, n, status, flags)
+        self.hmax = hmax
+        return self
+
+    def curve(self, f, npts=100):
+        """(d_test, v_test) of row f as `_fit_vario` returns them: the model on linspace(0, the row's largest lag, npts).  Host arrays."""
+        host = lambda a: a.detach().cpu().numpy() if _is_tensor(a) else np.asarray(a)
+        d_test = np.linspace(0, float(host(self.hmax[f])), npts)
+        return d_test, exponential(host(self.params[f]), d_test)
+
+
+def fit_variograms(h, gamma, ub=None, f_scale=0.1, k_scan=512, ctx=None):
+    """The exponential model b (1 - exp(-h / a)) of every row of h, gamma ([M] or [F, M]; NaN in either = column absent) in ONE device call
+    (rdr_variogram_fit) -> VariogramFits over F rows (F = 1 for [M]).  Each fit is the exact minimum of `_fit_vario`'s objective - scipy's
+    soft_l1 cost with f_scale - over `_fit_vario`'s box 0 .. ub: ub [3] or [F, 3] (range, sill, nugget), None for the reference's
+    0.8 * (max h, max gamma, max gamma) per row.  The range is found by a scan of k_scan (a multiple of 64 in 64 .. 4096) geometrically
+    spaced candidates and eight refinement rounds, each candidate at its own best sill; include/raider_hip.h states the contract.
+    scipy's trust-region run (fit_variogram) stops short of this minimum on delays in metres: its gradient tolerance is absolute.
+    h, gamma (and ub) are all NumPy arrays or all GPU tensors; the outputs are of the same kind.  There is no CPU fallback."""
+    tensors = [_is_tensor(a) for a in (h, gamma)]
+    if any(tensors) and not all(tensors):
+        raise TypeError('h and gamma must be both NumPy arrays or both GPU tensors')
+    on_device = all(tensors)
+    if on_device:
+        import torch
+        if not (h.is_cuda and gamma.is_cuda):
+            raise TypeError('tensors must live on the GPU')
+        h = h.to(torch.float64); g = gamma.to(torch.float64)
+        h = (h if h.ndim == 2 else h[None]).contiguous(); g = (g if g.ndim == 2 else g[None]).contiguous()
+    else:
+        h = np.asarray(h, dtype=np.float64); g = np.asarray(gamma, dtype=np.float64)
+        h = np.ascontiguousarray(h if h.ndim == 2 else h[None]); g = np.ascontiguousarray(g if g.ndim == 2 else g[None])
+    if h.ndim != 2 or tuple(h.shape) != tuple(g.shape):
+        raise ValueError(f'h and gamma must be [M] or [F, M] and of the same shape (got {tuple(h.shape)} and {tuple(g.shape)})')
+    nf, m = int(h.shape[0]), int(h.shape[1])
+    if not 1 <= nf <= MAX_FITS:
+        raise ValueError(f'1 .. {MAX_FITS} rows (got {nf})')
+    if not 1 <= m <= MAX_FIT_COLUMNS:
+        raise ValueError(f'1 .. {MAX_FIT_COLUMNS} columns (got {m})')
+    k_scan = int(k_scan); f_scale = float(f_scale)
+    if not 64 <= k_scan <= 4096 or k_scan % 64:
+        raise ValueError(f'k_scan must be a multiple of 64 in 64 .. 4096 (got {k_scan})')
+    if not (np.isfinite(f_scale) and f_scale > 0):
+        raise ValueError(f'f_scale must be finite and > 0 (got {f_scale})')
+    if ub is not None:
+        shape = tuple(ub.shape) if hasattr(ub, 'shape') else np.shape(ub)
+        if shape not in ((3,), (1, 3), (nf, 3)):
+            raise ValueError(f'ub must hold three upper bounds (range, sill, nugget), [3] or [F, 3] (got shape {shape})')
+        if on_device:
+            ub = ub.to(device=h.device, dtype=torch.float64) if _is_tensor(ub) else torch.from_numpy(np.asarray(ub, dtype=np.float64)).to(h.device)
+            ub = ub.reshape(-1, 3).expand(nf, 3).contiguous()
+        else:
+            ub = np.asarray(ub.detach().cpu().numpy() if _is_tensor(ub) else ub, dtype=np.float64)
+            ub = np.ascontiguousarray(np.broadcast_to(ub.reshape(-1, 3), (nf, 3)))
+    ctx = ctx or Context.default()
+    if on_device:
+        ctx.adopt_torch_stream(h)
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=h.device)
+        f64, i64, i32 = torch.float64, torch.int64, torch.int32
+        hmax = torch.where(torch.isnan(h), torch.full_like(h, -np.inf), h).amax(dim=1)
+        hmax = torch.where(torch.isinf(hmax) & (hmax < 0), torch.full_like(hmax, np.nan), hmax)
+    else:
+        new = lambda shape, dtype: np.empty(shape, dtype=dtype)
+        f64, i64, i32 = np.float64, np.int64, np.int32
+        hmax = np.where(np.isnan(h), -np.inf, h).max(axis=1)
+        hmax = np.where(np.isneginf(hmax), np.nan, hmax)
+    o = VariogramFits(new((nf, 3), f64), new((nf,), f64), new((nf,), f64), new((nf,), i64), new((nf,), i32), new((nf,), i32), hmax)
+    check(ctx.lib.rdr_variogram_fit(ctx.handle, ptr(h), ptr(g), nf, m, ptr(ub), f_scale, k_scan, ptr(o.params), ptr(o.cost), ptr(o.rmse), ptr(o.n),
+                                    ptr(o.status), ptr(o.flags), L.RDR_DEVICE if on_device else L.RDR_HOST), ctx.handle)
+    return o
+
+
+def _mean_rows(total, count):
+    """total / count per bin, NaN where count is 0 - elementwise where the sums live (NumPy arrays or GPU tensors)"""
+    if _is_tensor(total):
+        import torch
+        return torch.where(count > 0, total / count, torch.full_like(total, np.nan))
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return np.where(count > 0, total / count, np.nan)
+
+
+def _check_fitter(fitter, model):
+    if fitter not in ('scipy', 'device'):
+        raise ValueError(f"fitter must be 'scipy' or 'device' (got {fitter!r})")
+    if fitter == 'device' and model != 'exponential':
+        raise ValueError(f"fitter='device' fits the exponential model only (got model={model!r}): the Gaussian model carries a live nugget and stays on the host")
+
+
 StationVariograms = namedtuple('StationVariograms', 'variogram binned fits x y')
 
 
-def station_variograms(lon, lat, values, deramp=True, edges=None, nbins=19, model='exponential', density_threshold=10, fit=True, ctx=None):
+def station_variograms(lon, lat, values, deramp=True, edges=None, nbins=19, model='exponential', density_threshold=10, fit=True, ctx=None,
+                       fitter='scipy'):
     """_emp_vario + _binned_vario + _fit_vario (:611-701, as _append_variogram chains them) for every date of `values` [D, N] at
     stations lon / lat [deg], over ALL pairs of the stations valid on the date.  One UTM zone serves every date: that of the medians
     over all stations (the reference takes the medians of each date's valid stations).  A date with fewer than `density_threshold` valid
     stations gives empty binned arrays and no fit, as the reference's empty sample does.
-    -> StationVariograms(variogram = PairVariogram, binned = [(hExp, expVario)] per date, fits = [VariogramFit or None], x, y)."""
+    -> StationVariograms(variogram = PairVariogram, binned = [(hExp, expVario)] per date, fits = [VariogramFit or None], x, y).
+    fitter='device': all dates are fitted in one fit_variograms call and `fits` is its VariogramFits over the D dates (status 1 for a date
+    without a binned value); the exponential model only."""
+    _check_fitter(fitter, model)
     v = np.asarray(values, dtype=np.float64)
     v = np.array(v[None, :] if v.ndim == 1 else v)
     x, y = utm_common_center(np.asarray(lon, dtype=np.float64).reshape(-1), np.asarray(lat, dtype=np.float64).reshape(-1))
@@ -263,7 +371,10 @@ def station_variograms(lon, lat, values, deramp=True, edges=None, nbins=19, mode
     for d in range(v.shape[0]):
         h, g = pv.binned(d)
         binned.append((h, g))
-        fits.append(fit_variogram(h, g, model) if (fit and h.size) else None)
+        if fitter == 'scipy':
+            fits.append(fit_variogram(h, g, model) if (fit and h.size) else None)
+    if fitter == 'device':
+        fits = fit_variograms(_mean_rows(pv.lag_sum, pv.count), _mean_rows(pv.gamma_sum, pv.count), ctx=ctx) if fit else None
     return StationVariograms(pv, binned, fits, x, y)
 
 
@@ -330,7 +441,8 @@ class GridVariograms:
     (range, sill, nugget of the total fit) and rmse [G], NaN for a cell without a good date; sparse_grids: the cells that hold stations
     but no good date; skipped_slices: (cell, date index) of the slices that hold data but fewer than density_threshold stations;
     grid_range, grid_variance, grid_variogram_rmse [ny, nx]: the maps, row 0 in the north (cli/statsPlot.py:3302-3337);
-    date_fits: {(cell, date index): VariogramFit} when per_date_fits was asked for, else None; x, y: the sorted stations' metres."""
+    date_fits: {(cell, date index): VariogramFit} when per_date_fits was asked for (fitter='device': a VariogramFits over [G * D] rows), else
+    None; x, y: the sorted stations' metres."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -375,7 +487,7 @@ def _cell_call(ctx, x, y, start, v, deramp, min_valid, edges, nbins, residuals, 
 
 
 def grid_variograms(lon, lat, values, spacing=1.0, bbox=None, density_threshold=10, deramp=True, nbins=19, binned=False, model='exponential',
-                    errlimit=np.inf, fit=True, per_date_fits=False, ctx=None):
+                    errlimit=np.inf, fit=True, per_date_fits=False, ctx=None, fitter='scipy'):
     """`raiderStats --variogramplot` up to its three maps (VariogramAnalysis.create_variograms / _append_variogram, cli/statsPlot.py:721-883,
     and stats_analyses :3300-3339) for stations lon / lat [N] (degrees) and values [D, N] (NaN = missing), over ALL pairs of every cell
     -> GridVariograms.  lon, lat, values are all NumPy arrays or all GPU tensors (values then never visits the host; lon and lat do, for
@@ -393,7 +505,12 @@ def grid_variograms(lon, lat, values, spacing=1.0, bbox=None, density_threshold=
       6. per cell with a good date: fit_variogram (host, scipy.optimize.least_squares, as the reference) of the total binned variogram
          - of the concatenated per-date binned arrays with binned=True (:796-798); rmse = sqrt(nanmean(fun^2)), NaN above errlimit.
          fit=False leaves params and rmse NaN.  per_date_fits=True also fits every good slice: one host scipy fit per slice, G x D of
-         them - off by default, the maps do not need them."""
+         them - off by default, the maps do not need them.
+         fitter='device' (the exponential model only): the fits are fit_variograms' exact bounded minima instead.  The rows lag_sum / count
+         (NaN for an empty bin) are formed where the sums live; ALL total fits are one device call - with binned=True on the rows
+         [G, D * nbins] of the per-date bins, NaN for a date that is not good -, and with per_date_fits=True all G x D slices are a second
+         one: date_fits is then a VariogramFits over [G * D] rows (row c * D + d; a slice that is not good has status 1), not a dict."""
+    _check_fitter(fitter, model)
     tensors = [_is_tensor(a) for a in (lon, lat, values)]
     if any(tensors) and not all(tensors):
         raise TypeError('lon, lat and values must be all NumPy arrays or all GPU tensors')
@@ -477,6 +594,29 @@ def grid_variograms(lon, lat, values, spacing=1.0, bbox=None, density_threshold=
                          edges=o['edges'], total_count=t['total_count'], total_lag=t['total_lag'], total_gamma=t['total_gamma'],
                          total_edges=dev(total_edges), residuals=resid, params=params, rmse=rmse, sparse_grids=sparse, skipped_slices=skipped,
                          date_fits=None, x=x, y=y)
+    if fitter == 'device':
+        if on_device:
+            gd = dev(good)
+            mask = lambda a, keep: torch.where(keep, a, torch.full_like(a, np.nan))
+        else:
+            gd = good
+            mask = lambda a, keep: np.where(keep, a, np.nan)
+        if fit or per_date_fits:
+            ph = mask(_mean_rows(o['lag_sum'], o['count']), gd[:, :, None]); pg = mask(_mean_rows(o['gamma_sum'], o['count']), gd[:, :, None])
+        if fit:
+            if binned:
+                th, tg = ph.reshape(ng, nd * nbins), pg.reshape(ng, nd * nbins)
+            else:
+                th, tg = _mean_rows(t['total_lag'], t['total_count']), _mean_rows(t['total_gamma'], t['total_count'])
+                th = mask(th, dev(has_good)[:, None]); tg = mask(tg, dev(has_good)[:, None])
+            f = fit_variograms(th, tg, ctx=ctx)
+            params[:] = host(f.params)
+            e = host(f.rmse)
+            with np.errstate(invalid='ignore'):
+                rmse[:] = np.where(e <= errlimit, e, np.nan)
+        if per_date_fits:
+            res.date_fits = fit_variograms(ph.reshape(ng * nd, nbins), pg.reshape(ng * nd, nbins), ctx=ctx)
+        fit = per_date_fits = False            # (done; the maps below)
     if fit or per_date_fits:
         cnt = host(o['count']); lag = host(o['lag_sum']); gam = host(o['gamma_sum'])
         per = lambda c, d: (lag[c, d][cnt[c, d] > 0] / cnt[c, d][cnt[c, d] > 0], gam[c, d][cnt[c, d] > 0] / cnt[c, d][cnt[c, d] > 0])
