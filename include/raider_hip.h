@@ -169,6 +169,12 @@ int64_t rdr_generic_ray_count(rdr_ctx* ctx);
 /* diagnostics: 64-ray waves of the last rdr_ray_prepass that left the per-level length loop of pass 1 out because their length bounds
  * could not raise any level maximum of the slice (0 with RAIDER_HIP_PASS1_SKIP=0; results never depend on it); -1 for a NULL ctx */
 int64_t rdr_skipped_wave_count(rdr_ctx* ctx);
+/* diagnostics: rdr_raytrace calls of this ctx that fitted and marched their rays in ONE kernel on a probed partition (one f32 lon/lat cube on
+ * exactly uniform axes, one slice of GRID rays with per-pixel look vectors in device arrays, 2 < K <= 128; RAIDER_HIP_ONE_PASS=0: none),
+ * and how many of those found the probed partition - or a ray - to need the two classic passes after all, which then ran behind it on the
+ * device (as of the last partition this ctx read back: no synchronisation of its own).  Results never depend on the route; -1 for a NULL ctx */
+int64_t rdr_one_pass_count(rdr_ctx* ctx);
+int64_t rdr_one_pass_redo_count(rdr_ctx* ctx);
 
 /* ---- weather cube ----------------------------------------------------------------------------
  * Replaces getInterpolators (tools/RAiDER/delayFcns.py:23-58): the two fields of one processed weather

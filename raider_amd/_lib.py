@@ -74,6 +74,8 @@ SYMBOLS = [
     ('rdr_trim', C.c_int, [_VP, C.c_int64, c_lp]),
     ('rdr_generic_ray_count', C.c_int64, [_VP]),
     ('rdr_skipped_wave_count', C.c_int64, [_VP]),
+    ('rdr_one_pass_count', C.c_int64, [_VP]),
+    ('rdr_one_pass_redo_count', C.c_int64, [_VP]),
     ('rdr_profile_get', C.c_int, [_VP, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     ('rdr_clock_sample_begin', C.c_int, [_VP, C.c_double]),
     ('rdr_clock_sample_end', C.c_int, [_VP, c_dp]),
@@ -371,6 +373,14 @@ class Context:
     def skipped_wave_count(self):
         """64-ray waves of the last ray_prepass that skipped pass 1's per-level length loop (diagnostics; RAIDER_HIP_PASS1_SKIP)."""
         return int(self.lib.rdr_skipped_wave_count(self.handle))
+
+    def one_pass_count(self):
+        """raytrace() calls of this context that fitted and marched their rays in one kernel (diagnostics; RAIDER_HIP_ONE_PASS)."""
+        return int(self.lib.rdr_one_pass_count(self.handle))
+
+    def one_pass_redo_count(self):
+        """... of which the two classic passes ran behind after all, as of the last partition read back (want_nparts=True)."""
+        return int(self.lib.rdr_one_pass_redo_count(self.handle))
 
     def clock_sample(self, ms):
         """Start sampling the shader clock for `ms` milliseconds of wall time (one sleeping wave on the copy stream); returns a

@@ -71,6 +71,13 @@ struct rdr_ctx {
     int64_t side_cap = 0;                     // columns of `side` in the current layout
     DevBuf lev;                               // level table of pass 2: [nslices][nz + 1] LevelRec (level_table_kernel)
     int* d_sidectr = nullptr;                 // [1] next free column
+    // the one-kernel ray route (trace_one_pass)
+    int* d_onepass = nullptr;                 // [OP_WORDS] its device state (RayParams::one_pass)
+    DevBuf probe;                             // tile list of its probe, kept while the scene's tiling and the stream stay what they were
+    struct { int tiles_x = 0; int64_t tiles_y = 0; hipStream_t stream = nullptr; int64_t count = 0; } probe_key;
+    DevBuf gridtrig;                          // sines / cosines of the batch's latitudes and longitudes (grid_trig_kernel)
+    int64_t one_pass_calls = 0;               // calls that took the route
+    int64_t one_pass_redos = 0;               // ... whose classic passes ran, as of the last partition the host read back
     int* h_word = nullptr;                    // [16] page-locked host words: flags read back WITHOUT stalling the host before the final sync
     // Small host inputs (axes, level lists, a cube's three axes) go up through a ring of page-locked buffers: the caller's array is consumed by a
     // memcpy before the call returns and the device copy is REALLY asynchronous (from pageable memory hipMemcpyAsync first waits for everything
@@ -473,6 +480,8 @@ int rdr_create(int device, rdr_ctx** out) {
         HIPCHECK(nullptr, hipMalloc((void**)&c->d_tilectr, 32 * sizeof(int)));
         HIPCHECK(nullptr, hipMalloc((void**)&c->d_sidectr, sizeof(int)));
         HIPCHECK(nullptr, hipMemset(c->d_sidectr, 0, sizeof(int)));
+        HIPCHECK(nullptr, hipMalloc((void**)&c->d_onepass, OP_WORDS * sizeof(int)));
+        HIPCHECK(nullptr, hipMemset(c->d_onepass, 0, OP_WORDS * sizeof(int)));
         HIPCHECK(nullptr, hipHostMalloc((void**)&c->h_word, 16 * sizeof(int), hipHostMallocDefault));
         HIPCHECK(nullptr, hipHostMalloc((void**)&c->nan_words, rdr_ctx::NAN_SLOTS * sizeof(int), hipHostMallocDefault));
         HIPCHECK(nullptr, hipMemset(c->d_nslow, 0, 2 * sizeof(int)));
@@ -500,6 +509,9 @@ void rdr_destroy(rdr_ctx* c) {
     if (c->side.p) (void)hipFree(c->side.p);
     if (c->lev.p) (void)hipFree(c->lev.p);
     if (c->d_sidectr) (void)hipFree(c->d_sidectr);
+    if (c->d_onepass) (void)hipFree(c->d_onepass);
+    if (c->probe.p) (void)hipFree(c->probe.p);
+    if (c->gridtrig.p) (void)hipFree(c->gridtrig.p);
     if (c->h_word) (void)hipHostFree(c->h_word);
     if (c->nan_words) (void)hipHostFree(c->nan_words);
     for (auto& ps : c->pin) { if (ps.ev) (void)hipEventDestroy(ps.ev); if (ps.p) (void)hipHostFree(ps.p); }
@@ -641,6 +653,8 @@ int rdr_set_side_capacity(rdr_ctx* c, int64_t columns) {
 
 int64_t rdr_generic_ray_count(rdr_ctx* c) { return c ? c->last_nslow : -1; }
 int64_t rdr_skipped_wave_count(rdr_ctx* c) { return c ? c->last_nskip : -1; }
+int64_t rdr_one_pass_count(rdr_ctx* c) { return c ? c->one_pass_calls : -1; }
+int64_t rdr_one_pass_redo_count(rdr_ctx* c) { return c ? c->one_pass_redos : -1; }
 
 int rdr_set_profiling(rdr_ctx* c, int on) {
     if (!c) return fail(nullptr, RDR_ERR_INVALID, "ctx is NULL");
@@ -2304,6 +2318,84 @@ int rdr_ray_kernel_attributes(rdr_ctx* c, const rdr_cube* q, int which, int32_t*
     return RDR_OK;
 }
 
+// ---- the one-kernel route (trace_kernel, raider_kernels.h) -----------------------------------------------------------------------------
+// RAIDER_HIP_ONE_PASS=0: every call takes the two passes (the A/B switch of the route; read once per process, like RAIDER_HIP_PASS1_SKIP)
+static bool one_pass_on() {
+    static const int on = []() { const char* e = std::getenv("RAIDER_HIP_ONE_PASS"); return e ? std::atoi(e) : 1; }();
+    return on != 0;
+}
+
+// LDS of a trace_kernel launch: the common layout, pass 1's two skip tables and the park behind them
+static size_t trace_smem(const rdr_cube* q) { return ray_smem(q) + skip_smem_bytes(q->nz) + trace_park_bytes(); }
+
+// May this pass 1 + pass 2 over ONE slice of `per` tiles go through trace_kernel?  One f32 lon/lat cube on exactly uniform axes (march_kernel's
+// REGULAR), GRID origins with per-pixel look vectors (the one input form trace_kernel is built for: the sincos of an incidence / heading batch
+// puts it into scratch), no per-ray heights, a partition to be reduced, device arrays, 2 < K <= 128 (the limits of the wave bound), records
+// that fit one group - they are still reserved, for the classic passes behind - and the kernel's LDS.
+static bool one_pass_eligible(rdr_ctx* c, const rdr_cube* q, const RayParams& P, int K, int64_t per, int64_t nslices, int64_t fit, bool device_rays) {
+    return one_pass_on() && device_rays && q->dtype == RDR_F32 && q->proj.kind == 0 && march_grid(q, false) == 1 &&
+           P.origin_mode == RDR_ORIGIN_GRID && P.los_mode == RDR_LOS_VEC && !P.ht_ray && !P.hts && nslices == 1 && P.nslices == 1 &&
+           P.maxlen_bits != nullptr && !P.nparts_override && K > 2 && K <= 128 && per <= fit && per < ((int64_t)1 << 31) &&
+           ray_lds_total(q) + skip_smem_bytes(q->nz) + trace_park_bytes() <= c->lds_max;
+}
+
+// The probe's tiles of a scene of tiles_x x tiles_y tiles: its four border rows and columns - the edges of a swath hold its longest rays -
+// and every eighth tile of every eighth row inside: 2 / tiles_x + 2 / tiles_y + 1 / 64 of the scene, 3 % of the headline one.
+static std::vector<int> probe_tiles(int tiles_x, int64_t tiles_y) {
+    std::vector<int> v;
+    for (int64_t ty = 0; ty < tiles_y; ++ty) {
+        const bool edge_row = ty == 0 || ty == tiles_y - 1;
+        for (int tx = 0; tx < tiles_x; ++tx)
+            if (edge_row || tx == 0 || tx == tiles_x - 1 || (ty % 8 == 4 && tx % 8 == 4)) v.push_back((int)(ty * tiles_x + tx));
+    }
+    return v;
+}
+
+// One slice of `per` tiles (P: records reserved, outputs set) through the route.  Everything is enqueued, nothing is waited for:
+//   grid_trig_kernel, the probe (crossings_kernel, reduce only, over probe_tiles)                      profiling scope 0
+//   level_table_kernel, partition_check_kernel<false>, trace_kernel, partition_check_kernel<true>       profiling scope 1
+//   the classic launch_crossings + launch_level_table + launch_march with RayParams::one_pass set: they return at their top unless
+//   the check - or trace_kernel itself - raised OP_NEED, and overwrite every output when they run.
+static int trace_one_pass(rdr_ctx* c, const rdr_cube* q, const RayParams& P, int K, int64_t per) {
+    int rc = grow(c, c->gridtrig, (size_t)(P.ny + P.nx) * 2 * sizeof(double)); if (rc) return rc;
+    if (c->probe_key.tiles_x != P.tiles_x || c->probe_key.tiles_y != per / P.tiles_x || c->probe_key.stream != c->stream) {
+        const std::vector<int> list = probe_tiles(P.tiles_x, per / P.tiles_x);
+        rc = grow(c, c->probe, list.size() * sizeof(int)); if (rc) return rc;
+        rc = upload(c, c->probe.p, list.data(), list.size() * sizeof(int)); if (rc) return rc;
+        c->probe_key.tiles_x = P.tiles_x; c->probe_key.tiles_y = per / P.tiles_x; c->probe_key.stream = c->stream; c->probe_key.count = (int64_t)list.size();
+    }
+    RayParams Pp = P;                                      // the probe: pass 1 as the chunked schedule launches it, over the list
+    Pp.ws = nullptr; Pp.one_pass = nullptr; Pp.tile_list = (const int*)c->probe.p;
+    {
+        KTimer t(c, 0);
+        hipLaunchKernelGGL(grid_trig_kernel, dim3((unsigned)std::min<int64_t>(64, (P.ny + P.nx + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, P, (double*)c->gridtrig.p);
+    }
+    HIPCHECK(c, hipGetLastError());
+    rc = launch_crossings(c, q, Pp, 0, c->probe_key.count); if (rc) return rc;
+    RayParams Pt = P;                                      // trace_kernel on the probed partition
+    Pt.ws = nullptr; Pt.tile_list = nullptr; Pt.one_pass = nullptr; Pt.grid_trig = (const double*)c->gridtrig.p;
+    rc = launch_level_table(c, q, Pt, 0, 1); if (rc) return rc;
+    Pt.one_pass = c->d_onepass;
+    Pt.tile_begin = 0; Pt.tile_count = per; Pt.nslots = 0; Pt.skip_levels = pass1_skip_on() ? 1 : 0;
+    HIPCHECK(c, hipMemsetAsync(c->d_tilectr + 16, 0, 8 * sizeof(int), c->stream));
+    Pt.tile_ctr = c->d_tilectr + 16;
+    hipError_t e;
+    {
+        KTimer t(c, 1);
+        hipLaunchKernelGGL(partition_check_kernel<false>, dim3(1), dim3(BLOCK), 0, c->stream, Pt, K);
+        e = launch_lds(trace_kernel<float2, 1, 1>, dim3(ray_grid(c, per, 8)), dim3(BLOCK), trace_smem(q), c->stream, make_view<float2>(q), Pt, q->proj);
+        hipLaunchKernelGGL(partition_check_kernel<true>, dim3(1), dim3(BLOCK), 0, c->stream, Pt, K);
+    }
+    if (e != hipSuccess) return fail(c, RDR_ERR_HIP, std::string("trace_kernel launch: ") + hipGetErrorString(e));
+    HIPCHECK(c, hipGetLastError());
+    ++c->one_pass_calls;
+    RayParams Pc = P;                                      // the two classic passes, conditional on OP_NEED
+    Pc.one_pass = c->d_onepass;
+    rc = launch_crossings(c, q, Pc, 0, per); if (rc) return rc;
+    rc = launch_level_table(c, q, Pc, 0, 1); if (rc) return rc;
+    return launch_march(c, q, Pc, 0, per);
+}
+
 // The workspace schedule of pass 1 + pass 2 over `nslices` slices of `per` tiles each (tiles numbered slice-major), `fit` tiles of
 // ray records at a time (ws_chunk_tiles).  Whole slices fit: groups of up to `max_group` slices, each one pass 1 that stores the
 // records and one pass 2 on them, then after_group(first slice, slices).  Otherwise, per slice: pass 1 reduction only, then chunked
@@ -2311,8 +2403,15 @@ int rdr_ray_kernel_attributes(rdr_ctx* c, const rdr_cube* q, int which, int32_t*
 // stores.  `march` is pass 2 (NULL: launch_march on q).
 static int ray_passes(rdr_ctx* c, const rdr_cube* q, const RayParams& P, int K, int64_t per, int64_t nslices, int64_t fit, int64_t max_group,
                       bool reduce, const std::function<int(const RayParams&, int64_t, int64_t)>& march = nullptr,
-                      const std::function<int(int64_t, int64_t)>& after_group = nullptr) {
+                      const std::function<int(int64_t, int64_t)>& after_group = nullptr, bool device_rays = false) {
     const auto pass2 = [&](const RayParams& Pm, int64_t tb, int64_t tc) { return march ? march(Pm, tb, tc) : launch_march(c, q, Pm, tb, tc); };
+    // one slice of one cube whose rays may be fitted and marched in one kernel (one_pass_eligible): trace_one_pass; device_rays: the batch's
+    // arrays are device arrays
+    if (reduce && !march && !after_group && one_pass_eligible(c, q, P, K, per, nslices, fit, device_rays)) {
+        RayParams Pg = P;
+        const int rc = ws_reserve(c, per, K, Pg); if (rc) return rc;      // (as the two passes reserve them: the classic launches behind write them)
+        return trace_one_pass(c, q, Pg, K, per);
+    }
     if (per <= fit) {
         const int64_t g = std::min<int64_t>(max_group, std::max<int64_t>(1, fit / per));
         for (int64_t s0 = 0; s0 < nslices; s0 += g) {
@@ -2414,12 +2513,14 @@ static int march_on_records(rdr_ctx* c, const rdr_cube* q, RayCall& R, bool reus
 // slow-ray counter - and the skipped-wave counter behind it for `nskip` - copied in that order, ONE wait, last_nslow (last_nskip) set.
 static int partition_read(rdr_ctx* c, double* maxlen, size_t nmax, int* flags, size_t nflags, bool nskip, void* more = nullptr, const void* d_more = nullptr,
                           size_t more_bytes = 0) {
-    int ctr[2] = {0, 0};
+    int ctr[2] = {0, 0}, redo = 0;
     HIPCHECK(c, hipMemcpyAsync(maxlen, c->d_maxlen, nmax * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipMemcpyAsync(flags, c->d_flags, nflags * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     if (more_bytes) HIPCHECK(c, hipMemcpyAsync(more, d_more, more_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipMemcpyAsync(ctr, c->d_nslow, (nskip ? 2 : 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (c->one_pass_calls > 0) HIPCHECK(c, hipMemcpyAsync(&redo, c->d_onepass + OP_REDO, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
+    if (c->one_pass_calls > 0) c->one_pass_redos = redo;
     c->last_nslow = ctr[0];
     if (nskip) c->last_nskip = ctr[1];
     return RDR_OK;
@@ -2632,7 +2733,7 @@ static int raytrace_impl(rdr_ctx* c, const char* who, const rdr_cube* const* qs,
         // one slice: pass 1 reduces AND stores the ray records when they all fit, pass 2 streams them back; else chunked
         std::function<int(const RayParams&, int64_t, int64_t)> march;      // (one epoch: ray_passes' own launch_march)
         if (D > 1) march = [&](const RayParams& Pm, int64_t tb, int64_t tc) { return launch_march_epochs(c, qs, D, Pm, tb, tc, (int64_t)r->n); };
-        rc = ray_passes(c, q, P, K, P.ntiles, 1, ws_chunk_tiles(c, K), 1, true, march); if (rc) return rc;
+        rc = ray_passes(c, q, P, K, P.ntiles, 1, ws_chunk_tiles(c, K), 1, true, march, nullptr, D == 1 && r->loc == RDR_DEVICE); if (rc) return rc;
         rc = finish_out(c, wet, dw, bytes, r->loc); if (rc) return rc;
         rc = finish_out(c, hydro, dh, bytes, r->loc); if (rc) return rc;
     }

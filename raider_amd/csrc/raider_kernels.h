@@ -9,6 +9,11 @@
 //   march_slice_levels /       pass 2: the two level loops of the light rays over E cubes on one ray geometry, called by
 //   march_ray_height_levels    march_kernel (E = 1) and by march_epochs_kernel (epoch_kernels.h, E epochs of a date series)
 //   march_kernel               pass 2: the trapezoid of _build_cube_ray [delay.py:285-323]
+//   trace_kernel               both in one kernel, for one slice of GRID rays with look vectors on an f32 lon/lat cube with exactly
+//                              uniform axes: pass 1's tile body (pass1_tiles, written once for both kernels) folds the exact maxima and
+//                              marches the tile from registers on a PROBED partition (crossings_kernel over RayParams::tile_list,
+//                              level_table_kernel, partition_check_kernel<false>); partition_check_kernel<true> then proves the partition
+//                              from the exact maxima or sends the call through the two passes enqueued behind (RayParams::one_pass)
 //
 // Design notes (MI355X):
 //   * one ray per lane, 64-lane wavefronts, 256-thread workgroups = one 16x16 pixel tile of the scene: neighbouring rays
@@ -506,7 +511,16 @@ struct RayParams {
     int stage_f64;                     // light march on f64 cubes: stage every level's footprint of a wave in LDS (0: the direct gathers)
     int skip_levels;                   // pass 1, lon/lat slice kernels: a wave whose length bounds cannot raise any level maximum leaves the per-level loop
                                        // out (0: never; != 0 only on a launch that allocated skip_smem_bytes); such waves are counted in nslow[1]
+    // the one-kernel route (trace_kernel; nullptr on every other call)
+    const double* grid_trig;           // (sin, cos) of ypts[ny], then of xpts[nx], in degrees (grid_trig_kernel)
+    const int* tile_list;              // pass 1 over a LIST of tiles: walk position lt stands for tile tile_list[lt] of the batch (the probe; reduce only)
+    int* one_pass;                     // [OP_WORDS] state of the route (OP_*): trace_kernel reads the snapshot of the probed partition and raises OP_NEED;
+                                       // the classic kernels enqueued behind it return at once while OP_NEED is 0
 };
+// RayParams::one_pass: OP_NEED != 0: the two classic passes must run (a generic ray, a non-finite ray, a partition the probe missed); OP_BITS: what
+// fill_partition derives from the PROBED partition (1 poison, 2 clamp_lo, 4 clamp_hi); OP_REDO: calls whose classic passes ran, counted on the
+// device; OP_NPARTS: the probed nParts[k]
+constexpr int OP_NEED = 0, OP_BITS = 1, OP_REDO = 2, OP_NPARTS = 8, OP_WORDS = OP_NPARTS + MAX_LEVELS;
 
 // The argument block of the two ray kernels as the kernarg segment holds it.  The light instantiations read their uniform parameters from
 // there AT THE POINT OF USE, through the constant address space (scalar loads) and a pointer made opaque per site (ray_args): a field
@@ -668,6 +682,10 @@ inline size_t ray_smem_bytes(int64_t ny, int64_t nx, int64_t nz, int exact_y, in
 __device__ __forceinline__ double* skip_dabs(const RaySmem& m) { return reinterpret_cast<double*>(m.K + 4); }
 __device__ __forceinline__ unsigned long long* skip_floor(const RaySmem& m, int nz) { return reinterpret_cast<unsigned long long*>(m.K + 4) + 7 * nz; }
 inline size_t skip_smem_bytes(int64_t nz) { return (size_t)nz * 8 * 8; }
+// trace_kernel's park BEHIND those two: [PN][BLOCK] doubles, a lane's longitude polynomial while pass 1's folds run (the fit and the folds are the
+// register-hungriest stretch, and the march needs the polynomial after them: parked here it is not parked in scratch).  Its launch allocates all three.
+__device__ __forceinline__ double* trace_park(const RaySmem& m, int nz) { return reinterpret_cast<double*>(m.K + 4) + 8 * nz; }
+inline size_t trace_park_bytes() { return (size_t)PN * BLOCK * 8; }
 
 
 // Axis tables: once per workgroup.
@@ -773,9 +791,22 @@ __device__ __forceinline__ float float_above_abs(double x) { return (float)(fabs
 //   1: GRID origins + per-pixel look vectors;  2: GRID origins + incidence / heading (arrays or scalars) or zenith;  0: any.
 // PR (light kernel only): per-ray origin heights (P.ht_ray) - a separate instantiation so that the slice kernels carry none of it; the
 // generic kernel looks at P.ht_ray at run time.
-template <typename T2, bool SLOW, bool LCC = false, int OM = 0, bool PR = false>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 : 4, SLOW ? 8 : 4))) void crossings_kernel(CubeView<T2> c, RayParams P, LccParams proj) {
+// (pass 2's pieces the TRACE body calls; defined with pass 2 below)
+template <typename T2, int E, bool NC>
+__device__ __forceinline__ void march_slice_levels(const CubeView<T2>& c, const EpochCubes<T2, E>& ev, const RaySmem& m, const RayPoly& q, const double (&xc)[PX],
+                                                   const LevelRec* lev, double u0, double u1, int K, bool clamp_lo, bool clamp_hi, unsigned long long live,
+                                                   double* acc_w, double* acc_h);
+__device__ __forceinline__ bool lane_nocheck(double u0r, double u1r, bool active, bool mine, RayPoly& q, double (&xc)[PX], int ny, int nx);
+template <typename RP>
+__device__ __forceinline__ void tile_ray(const RP& P, int64_t t, int tl, int64_t& i, bool& active);
+// TRACE (trace_kernel; lon/lat f32 slice rays on a REGULAR cube): the tile's rays are marched where they were fitted, from registers, on the
+// PROBED partition - pass 1 as it stands (same set-up, same fit, same folds: the body is written once, so the bits of q, xc, u0, u1 and scale
+// cannot differ from the records' of the two-pass route), then march_slice_levels as march_kernel calls it.  No record is written or read.
+template <typename T2, bool SLOW, bool LCC, int OM, bool PR, bool TRACE>
+__device__ __forceinline__ void pass1_tiles(const CubeView<T2>& c, const RayParams& P, const LccParams& proj) {
     static_assert(!SLOW || (OM == 0 && !PR), "the generic kernel takes every input form");
+    static_assert(!TRACE || (!SLOW && !LCC && !PR && OM != 0), "the one-kernel route: light lon/lat slice rays of a GRID batch");
+    if (!TRACE && P.one_pass != nullptr && P.one_pass[OP_NEED] == 0) return;       // (enqueued behind trace_kernel, which needed no second opinion)
     const bool per_ray = PR || (SLOW && P.ht_ray != nullptr);
     if (SLOW && *P.nslow == 0) return;
     // The uniform parameters as the tile loop reads them: the light instantiations through the kernarg segment, afresh at every site
@@ -785,6 +816,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
     auto Jk = [&]() -> decltype(auto) { if constexpr (SLOW) return (proj); else return (ray_args<T2>()->proj); };
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const RaySmem m = carve_smem(smem_raw, c.ny, c.nx, c.nz, c.exact_y, c.exact_x);
+    // TRACE: the cube view of the march (march_kernel's REGULAR), and what the probed partition decides for every ray (OP_BITS)
+    CubeView<T2> cm = c;
+    if (TRACE) { cm.exact_y = 1; cm.exact_x = 1; cm.small = 1; }
+    double poison = 0.0;
+    bool clamp_lo = false, clamp_hi = false;
     // The instantiations whose waves may skip the per-level length loop (below): not the per-ray-height ones (their loop starts per lane), and
     // not on conic cubes (those spill around the fit already, and the decision added 8 to 16 B of scratch to them).
     constexpr bool SKIPPABLE = !SLOW && !PR && !LCC;
@@ -824,7 +860,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
         const auto& pa = Pk();                             // (this site: the tile's place in the batch and its rays)
         const int origin_mode = OM != 0 ? 0 : pa.origin_mode;
         const int los_mode = OM == 1 ? 0 : pa.los_mode;
-        const int64_t tg = pa.tile_begin + lt;             // tile of the batch; t: tile within its slice
+        const int64_t tg = pa.tile_list ? (int64_t)pa.tile_list[lt] : pa.tile_begin + lt;   // tile of the batch; t: tile within its slice
         const int sl = (int)(tg / pa.tiles_per_slice);
         const int64_t t = tg - (int64_t)sl * pa.tiles_per_slice;
         if (sl != slice) {                                 // (workgroup-uniform) first tile, or the walk has reached the next slice
@@ -834,6 +870,14 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
             K = fill_levels(Ck().nz, m, ht, pa.zref);
             int tz = threadIdx.x;
             asm volatile("" : "+v"(tz));
+            if constexpr (TRACE) {
+                // the columns start from the PROBED maxima (column 0; any value the device table has held is a maximum of the slice): the floor
+                // of the skip decisions below then stands near the final maxima from the first tile on, and almost every wave takes level 1 only
+                for (int k = tz; k < K * MXCOLS; k += BLOCK)
+                    m.mxcol[k] = (k & (MXCOLS - 1)) == 0 ? pa.maxlen_bits[(int64_t)sl * MAX_LEVELS + (k / MXCOLS)] : 0ULL;
+                const int bits = pa.one_pass[OP_BITS];
+                poison = (bits & 1) ? qnan() : 0.0; clamp_lo = (bits & 2) != 0; clamp_hi = (bits & 4) != 0;
+            } else
             if (reduce_on()) for (int k = tz; k < K * MXCOLS; k += BLOCK) m.mxcol[k] = 0ULL;
             if (skip_on()) {
                 double* const dabs = skip_dabs(m);
@@ -887,6 +931,17 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
         if (PR || SLOW) { if (per_ray && active) hti = pa.ht_ray[i]; }
         RayBase base;
         if (!SLOW && origin_mode == 0) {
+            if constexpr (TRACE) {
+                if (active) { lat = pa.ypts[row]; lon = pa.xpts[col]; }
+                base.lat0 = lat; base.lon0 = lon;
+                // the same sines / cosines, from the table grid_trig_kernel filled with the same call (RayParams::grid_trig): with sincos in
+                // this kernel its constants are hoisted out of the tile loop, 20 registers the march does not have
+                base.s0 = 0.0; base.c0 = 1.0; base.sl0 = 0.0; base.cl0 = 1.0;
+                if (active) {
+                    const double* const gy = pa.grid_trig + 2 * row; const double* const gx = pa.grid_trig + 2 * (pa.ny + col);
+                    base.s0 = gy[0]; base.c0 = gy[1]; base.sl0 = gx[0]; base.cl0 = gx[1];
+                }
+            } else {
             // a tile has 16 distinct latitudes and 16 distinct longitudes: 32 lanes take the sines / cosines for everybody
             // (the previous tile's readers are past the barriers of walk.next())
             if (tl < 32) {
@@ -900,6 +955,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
             base.lat0 = lat; base.lon0 = lon;
             base.s0 = active ? m.trig[2 * (tl >> 4)] : 0.0; base.c0 = active ? m.trig[2 * (tl >> 4) + 1] : 1.0;
             base.sl0 = active ? m.trig[32 + 2 * (tl & 15)] : 0.0; base.cl0 = active ? m.trig[33 + 2 * (tl & 15)] : 1.0;
+            }
             if (active) {                                          // lla2ecef (geodesy.h) with the shared sines / cosines
                 const double N = WGS84_A / sqrt(1.0 - WGS84_ES * base.s0 * base.s0);
                 ox = (N + hti) * base.c0 * base.cl0;
@@ -973,6 +1029,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
         if (!SLOW) {
             const unsigned long long slow_mask = __ballot(!fast_ok);
             if (slow_mask && (tl & 63) == 0) atomicAdd(Pk().nslow, (int)__popcll(slow_mask));
+            if constexpr (TRACE) { if (slow_mask && (tl & 63) == 0) atomicOr(Pk().one_pass + OP_NEED, 1); }   // a ray for the generic kernels
         }
         const bool mine = SLOW ? !fast_ok : fast_ok;      // lanes this instantiation is responsible for
         if (SLOW && !__any(mine)) continue;               // (wave-uniform) nothing to mop up in this wave
@@ -1067,8 +1124,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
             const double scale = nl * half;                           // ray length per unit of u
             // The record's stores (TileRecords), at each of the three places they stand; the base is formed afresh each time.
             auto records = [&]() { const auto& a = Pk(); return TileRecords(a.ws, a.nslots, lt, tl); };
-            auto has_ws = [&]() { return Pk().ws != nullptr; };
-            if (has_ws() && mine) {
+            auto has_ws = [&]() { if constexpr (TRACE) return false; else return Pk().ws != nullptr; };
+            if (TRACE || (has_ws() && mine)) {
                 // exact-uniform axes: hand pass 2 the INDEX-space coordinate (v - g0) * (n-1)/(g[n-1]-g0) directly (cell_xy<true>)
                 const auto& ca = Ck();
                 if (ca.exact_y) {
@@ -1083,19 +1140,26 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
 #pragma unroll
                     for (int n = 1; n < PN; ++n) q.lon[n] *= inv_dx;
                 }
-                const TileRecords w = records();
-                TileRecords::Run r = w.run(WS_POLY_H);
+                if constexpr (TRACE) {
+                    double* const park = trace_park(m, ca.nz) + tl;
 #pragma unroll
-                for (int n = 0; n < PN; ++n) r.next() = q.h[n];
+                    for (int n = 0; n < PN; ++n) park[n * BLOCK] = q.lon[n];
+                } else {
+                    const TileRecords w = records();
+                    TileRecords::Run r = w.run(WS_POLY_H);
 #pragma unroll
-                for (int n = 0; n < PN; ++n) r.next() = q.lat[n];
+                    for (int n = 0; n < PN; ++n) r.next() = q.h[n];
 #pragma unroll
-                for (int n = 0; n < PN; ++n) r.next() = q.lon[n];
-                w[WS_SCALE] = scale;
+                    for (int n = 0; n < PN; ++n) r.next() = q.lat[n];
+#pragma unroll
+                    for (int n = 0; n < PN; ++n) r.next() = q.lon[n];
+                    w[WS_SCALE] = scale;
+                }
             }
             // getTopOfAtmosphere carried on u: u0 = u(h); u += (h - H(u)) * su / factor   (losreader.py:724-731)
             // Level 0 (ten plain Newton steps per end, losreader.py:770-777) sets the gain of every later level.
             double u_hi = 0.0, gain = su;
+            double u_first = 0.0;       // (TRACE: the bottom crossing of the first level, field WS_U0 of a record)
             double last_len = 0.0;      // a light ray's lengths are NaN for every level or for none (they all stem from one polynomial)
             if (PR ? (k0 < K) : (K > 0)) {
                 const double lo = PR ? lo_first : m.lo[0], hi = PR ? m.hi[k0] : m.hi[0];
@@ -1111,6 +1175,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
                 last_len = L;
                 gain = su * (L / (hi - lo));                                                   // su / cos_factor, losreader.py:824-825
                 if (has_ws() && mine) { TileRecords::Run r = records().run(WS_U0); r.next() = u_lo; r.next() = u_hi; }
+                if constexpr (TRACE) u_first = u_lo;
                 if (reduce_on()) {
                     atomicMax(&mxc[PR ? k0 * MXCOLS : 0], (unsigned long long)__double_as_longlong((cnt && L > 0.0) ? L : 0.0));
                     if (cnt && !(poly5(q.h, u_lo) < Ck().z_lo)) my_flags |= 4;                    // first sample of the ray
@@ -1135,7 +1200,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
                 // The metres-per-unit-u scale is folded into the polynomial once (8 multiplications), so a level costs 7 FMAs, one
                 // subtraction and the v_max.
                 const double mscale = cnt ? scale : 0.0;
-                const double u_end = (PR ? (k0 + 1 < K) : (K > 1)) ? poly7(xc, m.xv[K - 1]) : u_hi;   // the ray's last crossing (flags below)
+                // the ray's last crossing (flags below); TRACE keeps xc for the march and takes it behind the loops, one value less across them
+                auto last_crossing = [&]() { return (PR ? (k0 + 1 < K) : (K > 1)) ? poly7(xc, m.xv[K - 1]) : u_hi; };
+                double u_end = 0.0;
+                if constexpr (!TRACE) u_end = last_crossing();
                 double xm[PX];
 #pragma unroll
                 for (int n = 0; n < PX; ++n) xm[n] = xc[n] * mscale;
@@ -1177,6 +1245,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
                         for (int n = 1; n < PX; ++n) S += fabs(xm[n]);
                         if (!cnt) S = 0.0;
                         const bool finite = !__any(!(S < __builtin_inf()));
+                        if constexpr (TRACE) { if (!finite && (tl & 63) == 0) atomicOr(Pk().one_pass + OP_NEED, 1); }   // a NaN or infinite ray
                         const float a0 = wave_max_nonneg(finite ? float_above_abs(S) : 0.0f);
                         if (finite && a0 == 0.0f) skip = true;                                 // nothing but lanes that do not count
                         else if (finite) {
@@ -1189,6 +1258,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
                                 Ba = fma(an, dabs[(n - 1) * nz + ka], Ba);
                                 if (K > 64) Bb = fma(an, dabs[(n - 1) * nz + kb], Bb);
                             }
+                            // (TRACE holds the lat / lon polynomials through this stretch.  Left alone, the two sums are sunk into the branch of
+                            // the lanes that compare them, and the seven maxima and table entries wait there side by side - in scratch)
+                            if constexpr (TRACE) asm volatile("" : "+v"(Ba), "+v"(Bb));
                             const double margin = fma((double)a0, 0x1p-44, 0x1p-120);
                             Ba = fma(Ba, 1.0 + 0x1p-30, margin);
                             Bb = fma(Bb, 1.0 + 0x1p-30, margin);
@@ -1218,10 +1290,43 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
                     s_hi = st;
                     atomicMax(&mxc[k * MXCOLS], (unsigned long long)__double_as_longlong(fmax(fabs(L), 0.0)));
                 }
+                if constexpr (TRACE) u_end = last_crossing();
                 if (PR ? (k0 + 1 < K) : (K > 1)) last_len = u_end * scale;                    // (only its NaN-ness is used)
                 if (K > 0 && cnt && !(poly5(q.h, u_end) > Ck().z_hi)) my_flags |= 8;         // last sample of the ray
             }
             if (reduce && cnt && K > 0) my_flags |= (last_len != last_len) ? 1 : 2;
+            if constexpr (TRACE) {
+                // the lanes' flags as ONE wave-uniform word from here on (flush ORs the lanes' words: the same result), so that no lane
+                // carries them through the march
+                int wave_flags = 0;
+#pragma unroll
+                for (int b = 1; b <= 8; b <<= 1) if (__any(my_flags & b)) wave_flags |= b;
+                my_flags = wave_flags;
+                // ---- the march of march_kernel<T2, false, 1>, on the values a record would have carried
+                {
+                    asm volatile("" ::: "memory");             // (the parked polynomial is read back HERE, not forwarded past the folds in registers)
+                    int tp = threadIdx.x;
+                    asm volatile("" : "+v"(tp));
+                    const double* const park = trace_park(m, cm.nz) + tp;
+#pragma unroll
+                    for (int n = 0; n < PN; ++n) q.lon[n] = park[n * BLOCK];
+                }
+                double acc_w = 0.0, acc_h = 0.0;
+                const double u0r = active ? u_first : 0.0, u1r = active ? u_hi : 0.0;
+                const EpochCubes<T2, 1> one{{cm.v}};
+                const unsigned long long live = __builtin_amdgcn_ballot_w64(active && mine);
+                const LevelRec* const lev = Pk().lev + (int64_t)__builtin_amdgcn_readfirstlane(sl) * (cm.nz + 1);
+                const bool lane_safe = lane_nocheck(u0r, u1r, active, mine, q, xc, cm.ny, cm.nx);
+                if (__all(lane_safe)) march_slice_levels<T2, 1, true>(cm, one, m, q, xc, lev, u0r, u1r, K, clamp_lo, clamp_hi, live, &acc_w, &acc_h);
+                else march_slice_levels<T2, 1, false>(cm, one, m, q, xc, lev, u0r, u1r, K, clamp_lo, clamp_hi, live, &acc_w, &acc_h);
+                acc_w *= scale; acc_h *= scale;
+                // (the ray's place in the output derived afresh behind the loop - tile_ray, as march_kernel has it - not carried across it)
+                int to = threadIdx.x;
+                asm volatile("" : "+v"(to));
+                int64_t io; bool there;
+                tile_ray(Pk(), t, to, io, there);
+                if (there && mine) { const auto& oa = Pk(); const int64_t o = (int64_t)sl * oa.n + io; oa.wet[o] = acc_w + poison; oa.hyd[o] = acc_h + poison; }
+            }
         }
     }
     flush();
@@ -1229,6 +1334,29 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 
         __syncthreads();
         if (threadIdx.x == 0 && m.K[3] > 0) atomicAdd(Pk().nslow + 1, m.K[3]);
     }
+}
+
+template <typename T2, bool SLOW, bool LCC = false, int OM = 0, bool PR = false>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 : 4, SLOW ? 8 : 4))) void crossings_kernel(CubeView<T2> c, RayParams P, LccParams proj) {
+    pass1_tiles<T2, SLOW, LCC, OM, PR, false>(c, P, proj);
+}
+
+// ---- the one-kernel route: fit and march a tile's slice rays in ONE kernel, on a partition that was probed and is then proven ----------
+// Only one fact forces two passes over the rays: nParts[k] = ceil(max over the slice of the level's length / max_seg) + 1 needs every ray,
+// but only through a maximum - and a maximum is monotone.  The host (trace_one_pass) runs crossings_kernel reduce-only over a small list of
+// tiles (the border of the scene and a coarse lattice: RayParams::tile_list), level_table_kernel on what that found, and
+// partition_check_kernel<false>, which notes the probed nParts and what fill_partition derives from the flags (OP_NPARTS, OP_BITS).  Then
+// this kernel: pass 1's tile body as it stands - every ray folds into the real maxima and flags, seeded with the probed ones so that the
+// wave bound skips nearly every level loop - and, from the registers the records would have been written from, pass 2's slice loop on the
+// PROBED level records.  partition_check_kernel<true> recomputes nParts and the derived flags from the final maxima; when they equal the
+// probed ones (integers and three bits: equality is a proof) the delays are, bit for bit, what the two passes give - same fit, same
+// partition, same loop.  Anything else raises OP_NEED: a differing partition, a ray for the generic kernels, a non-finite ray.  The classic
+// kernels are enqueued behind in every case, return at their top while OP_NEED is 0, and overwrite every output when it is not.
+// GRID: march_kernel's (1: REGULAR, the only one built); OM: crossings_kernel's (1 or 2: a GRID batch).
+template <typename T2, int GRID, int OM>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) void trace_kernel(CubeView<T2> c, RayParams P, LccParams proj) {
+    static_assert(GRID == 1 && sizeof(T2) == 8, "built for f32 cubes on exactly uniform axes");
+    pass1_tiles<T2, false, false, OM, false, true>(c, P, proj);
 }
 
 // ---- pass 2: the parts march_kernel and march_epochs_kernel (epoch_kernels.h) share ---------------------------------
@@ -1307,6 +1435,7 @@ __device__ __forceinline__ LevelRec make_level_rec(const RaySmem& m, int nz, int
 // Launched with ray_smem_bytes(0, 0, nz, 1, 1) of LDS (the z table and the level arrays; no horizontal axis).
 template <typename T2>
 __global__ __launch_bounds__(BLOCK) void level_table_kernel(CubeView<T2> c, RayParams P, int first_slice, LevelRec* table) {
+    if (P.one_pass != nullptr && P.one_pass[OP_NEED] == 0) return;                // (enqueued behind trace_kernel: pass1_tiles)
     c.exact_y = 1; c.exact_x = 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const RaySmem m = carve_smem(smem_raw, c.ny, c.nx, c.nz, 1, 1);
@@ -1330,6 +1459,45 @@ __global__ __launch_bounds__(BLOCK) void level_table_kernel(CubeView<T2> c, RayP
             r.npkz = 0; r.pad[0] = r.pad[1] = r.pad[2] = 0;
         }
         out[k] = r;
+    }
+}
+
+// The sines and cosines of a GRID batch's ny latitudes and nx longitudes for trace_kernel (RayParams::grid_trig): what tile_trig computes per
+// tile in pass 1, by the same sincos on the same argument - the same bits.
+__global__ __launch_bounds__(BLOCK) void grid_trig_kernel(RayParams P, double* trig) {
+    for (int64_t j = (int64_t)blockIdx.x * BLOCK + threadIdx.x; j < P.ny + P.nx; j += (int64_t)gridDim.x * BLOCK) {
+        double sv, cv;
+        sincos((j < P.ny ? P.ypts[j] : P.xpts[j - P.ny]) * DEG_TO_RAD, &sv, &cv);
+        trig[2 * j] = sv; trig[2 * j + 1] = cv;
+    }
+}
+
+// The one-kernel route's two looks at the partition of slice 0 (one workgroup; K levels): nParts[k] as level_table_kernel derives them and the
+// three things fill_partition derives from the flags.  VERIFY false, after the probe: noted in P.one_pass, OP_NEED cleared.  VERIFY true, after
+// trace_kernel has folded every ray: compared with the note - any difference raises OP_NEED - and RDR_FLAG_DIVERGED set as fill_partition sets
+// it (the classic march behind, which would, may not run).
+template <bool VERIFY>
+__global__ __launch_bounds__(BLOCK) void partition_check_kernel(RayParams P, int K) {
+    __shared__ int s_diverged, s_differs;
+    if (threadIdx.x == 0) { s_diverged = 0; s_differs = 0; }
+    __syncthreads();
+    int* const op = P.one_pass;
+    for (int k = threadIdx.x; k < K; k += BLOCK) {
+        bool diverged;
+        const int np = level_nparts(P, 0, k, diverged);
+        if (diverged) s_diverged = 1;
+        if (VERIFY) { if (op[OP_NPARTS + k] != np) s_differs = 1; }
+        else op[OP_NPARTS + k] = np;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int f = P.flags[0];
+        const int bits = ((s_diverged || (f & (1 | 32))) ? 1 : 0) | ((f & 4) ? 0 : 2) | ((f & 8) ? 0 : 4);      // poison, clamp_lo, clamp_hi
+        if (VERIFY) {
+            if (s_diverged) atomicOr(P.flags, 16);
+            if (s_differs || bits != op[OP_BITS]) op[OP_NEED] = 1;
+            if (op[OP_NEED] != 0) op[OP_REDO] += 1;
+        } else { op[OP_BITS] = bits; op[OP_NEED] = 0; }
     }
 }
 
@@ -1598,6 +1766,7 @@ template <typename T2, bool SLOW, int GRID = 0, bool PR = false>
 // it, 6.8 against 11.4 ms per 16 M rays; the per-ray-height instantiation, 24 B of scratch at four waves, is better off as it is: 5.7 against 6.4 ms)
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(SLOW ? 1 : (sizeof(T2) == 16 ? 3 : 4), SLOW ? 8 : (sizeof(T2) == 16 ? 3 : 4)))) void march_kernel(CubeView<T2> c_in, RayParams P, LccParams proj) {
     static_assert(!SLOW || !PR, "the generic kernel looks at P.ht_ray at run time");
+    if (P.one_pass != nullptr && P.one_pass[OP_NEED] == 0) return;                // (enqueued behind trace_kernel: pass1_tiles)
     if (SLOW && *P.nslow == 0) return;
     const bool per_ray = PR || (SLOW && P.ht_ray != nullptr);
     // (the uniform parameters of the tile body: crossings_kernel.  The cube view stays by value: the level loops read it as SGPR operands)
